@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json metric: queries/sec (+ achieved HBM GB/s) of flat
 cosine top-10 search, N=10M, d=768, single query in flight, on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows N] [--dim D]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--rows N] [--dim D] [--full] [--dump-outputs DIR]
 
 A step = one `flat_search` call (one query scanned against the whole corpus)
 through the C ABI of libvettore_hip.so: query H2D, scan + fused top-k kernel,
@@ -11,8 +11,10 @@ merge kernel, result D2H.  The corpus is resident in HBM before timing starts.
 Setup ends with a pause (r06, --release-wait, 2.5 s): the build hands its 30-GB source tensor back to the driver, and for
 ~1.2 s after such a release every scan of the card runs 2.5 % slower -- the driver's 20 steps (0.1 s) used to sit inside
 that stretch (tools/ramp_probe.py, profiles/r06/ramp_probe.jsonl).  Then W warm-up steps and EXACTLY K timed steps
-between barrier + synchronize, as the contract says.
-At N = 8 the line also carries BASELINE configs[3] (L2, rows over eight GPUs) as `side.config4`.
+between barrier + synchronize, as the contract says.  That is all a plain run does: setup, warm-up, the K steps, the
+outputs of the last step if --dump-outputs names a directory, the JSON line.  The roofline, `long_run`, the side legs,
+the CPU baseline and the summary come with --full.
+With --full at N = 8 the line also carries BASELINE configs[3] (L2, rows over eight GPUs) as `side.config4`.
 
 N > 1: the SAME 10M-row corpus is sharded across N GPUs (strong scaling); every
 query runs on every shard and the per-shard top-k lists meet in one all-gather
@@ -26,7 +28,7 @@ to get there, same library underneath:
     its own one-device index, torch.distributed (nccl = RCCL) carries the
     all-gather (vettore_amd/sharded.py); `rccl_ranks` = dist.get_world_size().
 
-At N = 1 the JSON line also carries `side`: short legs of the other BASELINE
+With --full at N = 1 the JSON line also carries `side`: short legs of the other BASELINE
 configs on the same box (config 2: N=1M single query; config 3: dot, batches of
 256 on the FP32 matrix cores; config 5: quantized search; funnel search), each
 with its own roofline figure, and `callers`: 8 and 64 threads searching the
@@ -108,6 +110,13 @@ def parse():
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # (the supervised measurement itself)
     ap.add_argument("--child-timeout", type=float, default=480.0, help="seconds a supervised measurement may take")
     ap.add_argument("--exchange-note", default=None, help=argparse.SUPPRESS)  # (why this child runs over the host exchange)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the HIP-event pass and its roofline, long_run, the side legs, the CPU "
+                         "baseline, the other exchange, side.config4 at N = 8 and the summary (a plain run times the K steps "
+                         "and nothing else)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (the top-k list of one query) to "
+                         "DIR/hit_ids.npy (float64: the i of \"doc-<i>\") and DIR/hit_scores.npy (float32), in rank order")
     return ap.parse_args()
 
 
@@ -305,6 +314,14 @@ def verify_against_oracle(nifs, dim, order_code, limit=10):
         return {"checker": "oracle/ (CPU restatement of flat.rs / search.rs / distances.rs)", "side_index_rows": n, "equal_bit_for_bit": out}
     finally:
         oracle.set_reduce_order(oracle.DEFAULT_ORDER)
+
+
+def dump_outputs(path, hits):
+    """--dump-outputs DIR: the [(id, score)] list the last timed step returned, as two arrays in rank order."""
+    os.makedirs(path, exist_ok=True)
+    ids = np.array([float(int(h[0].rpartition(b"-")[2])) for h in hits], dtype=np.float64)
+    np.save(os.path.join(path, "hit_ids.npy"), ids)
+    np.save(os.path.join(path, "hit_scores.npy"), np.array([h[1] for h in hits], dtype=np.float32))
 
 
 def hits_of(L, handle_ptr):
@@ -1269,6 +1286,8 @@ def main():
 
 
 def measure(a):
+    if a.dump_outputs and a.mode != "single":
+        sys.exit("--dump-outputs: the headline's single-query mode only")
     steps_default = a.steps is None
     a.steps = 1000 if a.steps is None else a.steps
     a.warmup = 50 if a.warmup is None else a.warmup
@@ -1392,7 +1411,7 @@ def measure(a):
         np.random.default_rng(SEED_QUERY).uniform(-1, 1, size=(nq, a.dim)).astype(np.float32)
     hp = C.c_void_p()
 
-    def search_c(q):
+    def search_c(q, keep=False):
         # the step is the C-ABI call itself (the hit list is freed, not unpacked into Python
         # objects -- a NIF would build BEAM terms here)
         st = L.vt_flat_search(ref.handle, q.ctypes.data_as(C.POINTER(C.c_float)), a.dim, a.limit, C.byref(hp))
@@ -1400,11 +1419,14 @@ def measure(a):
             # (a wedged exchange arrives here as "RCCL exchange timed out on shard s ...": say so and
             # leave with a non-zero status -- a fresh process is the only retry)
             sys.exit("bench.py: flat_search failed with status %d: %s" % (st, (L.vt_last_error() or b"").decode()))
+        if keep:   # (--dump-outputs, the last timed step: the list is kept and unpacked once the clock has stopped)
+            return C.c_void_p(hp.value)
         n_hits = L.vt_hits_len(hp)
         L.vt_hits_free(hp)
         return range(n_hits)
 
-    search = (lambda q: sharded.search(q, a.limit)) if (sharded is not None and use_dist) else search_c  # noqa: E731
+    on_ranks = sharded is not None and use_dist
+    search = (lambda q, keep=False: sharded.search(q, a.limit)) if on_ranks else search_c  # noqa: E731
     # first search also settles the id ranks -- setup, not a step
     search(qs[0])
     t_build = time.perf_counter() - t_build
@@ -1422,8 +1444,9 @@ def measure(a):
             torch.cuda.synchronize(dv)
         torch.cuda.synchronize()
 
-    def timed_run(profiling, steps=None):
+    def timed_run(profiling, steps=None, keep_last=False):
         steps = a.steps if steps is None else steps
+        last = a.warmup + steps - 1
         for i in range(a.warmup):
             search(qs[i])
         nifs.flat_set_profiling(ref, profiling)
@@ -1431,34 +1454,40 @@ def measure(a):
         sync()
         t0 = time.perf_counter()
         for i in range(a.warmup, a.warmup + steps):
-            hits = search(qs[i])
+            hits = search(qs[i], keep_last and i == last)
         sync()
         dt = time.perf_counter() - t0
         prof = nifs.flat_get_profile(ref, reset=True)
         nifs.flat_set_profiling(ref, False)
+        if keep_last and not on_ranks:
+            hits = nifs._take_hits(hits)
         assert len(hits) == min(a.limit, total_rows)
         if launched:
             t = torch.tensor([dt], dtype=torch.float64, device=torch.device("cpu") if host_exchange else device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        return dt, prof
+        return dt, prof, hits
 
-    # The K timed steps twice, like every side leg: first WITH the library's
+    # With --full the K timed steps run twice, like every side leg: first WITH the library's
     # HIP-event bookkeeping -- the dominant kernel's own duration, measured live on the stream it is
     # launched on: the roofline figure --, then WITHOUT it -- two event records per call are two
-    # barrier packets in a chain of three launches -- end to end: `value` and `ms_per_step`.
+    # barrier packets in a chain of three launches -- end to end: `value` and `ms_per_step`.  A plain run
+    # times the second pass alone.
     #
     # r06 -- the build's last act is to hand its 30-GB source tensor back to the driver, and for ~1.2 s after such a release
     # every scan runs 2.5 % slower (release_wait above): rounds 1-5 timed the driver's 20 steps inside that stretch.
-    dt_events, prof = timed_run(True)
-    dt, _ = timed_run(False)
+    if a.full:
+        dt_events, prof, _ = timed_run(True)
+    dt, _, last_hits = timed_run(False, keep_last=bool(a.dump_outputs))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_hits)
 
     # A timed region of a fraction of a second (the driver's --steps 20 is 0.09 s of scans) is one number without a
     # spread: the same step is then timed once more for >= 1.2 s -- same barrier + synchronize bracket, same maximum
     # over the ranks, the queries taken round and round -- and reported beside it as `long_run`; `steps` / `warmup` /
     # `value` / `ms_per_step` keep the driver's semantics.  (Every rank derives the count from the reduced dt.)
     long_run = None
-    if dt < 1.0 and a.steps > 0:
+    if a.full and dt < 1.0 and a.steps > 0:
         long_steps = int(math.ceil(1.2 / (dt / a.steps)))
         each = np.empty(long_steps)
         sync()
@@ -1483,9 +1512,6 @@ def measure(a):
     out = None
     if rank == 0:
         qps = a.steps / dt
-        scan_ms = prof["scan_ms"] / max(1, prof["scan_launches"])
-        bytes_per_launch = prof["scan_bytes"] / max(1, prof["scan_launches"])
-        achieved = bytes_per_launch / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
         out = {
             "metric": "queries/sec, flat %s top-%d, N=%d d=%d (achieved HBM GB/s in roofline)" % (a.metric, a.limit, total_rows, a.dim),
             "value": qps,
@@ -1494,8 +1520,11 @@ def measure(a):
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": dt / a.steps * 1e3,
-            "ms_per_step_with_event_timing": dt_events / a.steps * 1e3,
-            "long_run": long_run,
+        }
+        if a.full:
+            out["ms_per_step_with_event_timing"] = dt_events / a.steps * 1e3
+            out["long_run"] = long_run
+        out.update({
             "higher_is_better": True,
             "scaling": a.scaling,
             "vs_baseline": None,
@@ -1511,7 +1540,12 @@ def measure(a):
                 "setup_s": round(t_build, 1),
                 "release_wait_s": a.release_wait,
             },
-            "roofline": {
+        })
+        if a.full:
+            scan_ms = prof["scan_ms"] / max(1, prof["scan_launches"])
+            bytes_per_launch = prof["scan_bytes"] / max(1, prof["scan_launches"])
+            achieved = bytes_per_launch / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+            out["roofline"] = {
                 "bound": "hbm",
                 "kernel": "scan_topk_kernel",
                 "achieved": achieved,
@@ -1524,9 +1558,8 @@ def measure(a):
                 "avg_launch_ms": scan_ms,
                 "measured_read_peak": measured_read_peak(devices[0]),
                 "frac_of_measured_read_peak": (achieved / measured_read_peak(devices[0])) if measured_read_peak(devices[0]) else None,
-            },
-        }
-        if shards_in_process > 1 or force_sharded or launched:
+            }
+        if a.full and (shards_in_process > 1 or force_sharded or launched):
             # one line must be enough to read a bad scaling curve: the scan a shard does per query
             # (HIP events, averaged over shards and steps) and everything else of a step -- query
             # upload, select, worker hand-off, the exchange itself, D2H, host merge
@@ -1537,19 +1570,19 @@ def measure(a):
             out["config"]["devices"] = devices
         if a.exchange_note:
             out["config"]["exchange_note"] = (out["config"].get("exchange_note", "") + "; " if out["config"].get("exchange_note") else "") + a.exchange_note
-            if len(set(devices)) < len(devices):
+            if a.full and len(set(devices)) < len(devices):
                 # several shards on one GPU: their scans overlap, a launch sees a share of the card
                 out["roofline"]["note"] = "shards share a device: per-launch figures are one overlapping scan's share"
                 out["roofline"]["whole_job_GBps"] = total_rows * a.dim * 4 / (dt / a.steps) / 1e9 / len(set(devices))
-        if (shards_in_process > 1 or force_sharded) and rccl_ranks:
+        if a.full and (shards_in_process > 1 or force_sharded) and rccl_ranks:
             # the same steps over the other exchange, for comparison (not the headline)
             assert nifs.flat_set_exchange(ref, _lib.EXCHANGE_HOST) == "ok"
-            dt2, _ = timed_run(False)
+            dt2, _, _ = timed_run(False)
             out["config"]["host_exchange_ms_per_step"] = dt2 / a.steps * 1e3
             assert nifs.flat_set_exchange(ref, _lib.EXCHANGE_RCCL) == "ok"
-        if a.gpus == 1 and not launched and not a.no_side and not force_sharded and a.metric == "cosine":
+        if a.full and a.gpus == 1 and not launched and not a.no_side and not force_sharded and a.metric == "cosine":
             out["side"] = side_legs(a, torch, nifs, L, device, ref)
-        if a.gpus == 1 and not launched and not a.no_cpu and a.cpu_seconds > 0:
+        if a.full and a.gpus == 1 and not launched and not a.no_cpu and a.cpu_seconds > 0:
             cb = cpu_baseline(a.dim, a.limit, a.cpu_seconds)
             out["cpu_baseline"] = {
                 "value": cb["rows_per_s_T"] / a.rows,
@@ -1567,7 +1600,7 @@ def measure(a):
                               "value": v["rows_per_s"] / a.rows, "effective_GBps": v["effective_GBps"]} for v in cb["variants"]],
             }
     # BASELINE configs[3] beside the headline -- at the width of the node, and only there (every rank takes part)
-    if (a.gpus == 8 or a.config4_anyway) and not a.no_side:
+    if a.full and (a.gpus == 8 or a.config4_anyway) and not a.no_side:
         # (a failure of the side leg must not take the headline with it: every rank runs the same code on the same seeds,
         # so what raises on one raises on all of them, at the same place)
         try:
@@ -1578,7 +1611,7 @@ def measure(a):
             out.setdefault("side", {})["config4"] = leg4
     if use_dist:
         dist.destroy_process_group()
-    if rank == 0:
+    if rank == 0 and a.full:
         # The handful of numbers a reader of a TRUNCATED record needs (VERDICT r5 #4b: the driver keeps `config` whole
         # and the last 2 000 bytes of the line): once inside `config`, once as the line's LAST key.
         side = out.get("side") or {}
@@ -1607,6 +1640,7 @@ def measure(a):
             summary["config4_verified"] = at("config4", "verified")
         out["config"]["summary"] = summary
         out["summary"] = summary
+    if rank == 0:
         # RCCL's version banner sits in libc's stdout buffer: flush it first so
         # that the JSON line is the last line of output
         C.CDLL(None).fflush(None)

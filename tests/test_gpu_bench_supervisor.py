@@ -24,6 +24,7 @@ def bench(args, timeout=600, launcher=None, **env):
                 "--master-port", "29713"]
     if "--release-wait" not in args:
         args = list(args) + ["--release-wait", "0"]      # (setup's pause is for measurements; these runs check behaviour)
+    args = list(args) + ["--full"]   # (the lines' roofline, exchange figures, side.config4 and summary come with --full)
     r = subprocess.run(cmd + [BENCH] + args, env=e, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     return r, (json.loads(lines[-1]) if lines else None)

@@ -490,7 +490,7 @@ def test_bench_runs_as_the_driver_invokes_it_for_two_gpus():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--devices", "0,0", "--rows", "200000",
-                          "--dim", "64", "--steps", "20", "--warmup", "3", "--no-cpu"], capture_output=True, text=True,
+                          "--dim", "64", "--steps", "20", "--warmup", "3", "--no-cpu", "--full"], capture_output=True, text=True,
                          env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])

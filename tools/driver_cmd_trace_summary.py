@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/driver_cmd_trace_summary.py [<dir with p_kernel_trace.csv> [<the run's JSON line>]] -- what rocprofv3's kernel trace of
-LITERALLY the driver's command (`rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5`,
+the driver's command (`rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`, --full for the roofline,
 tools/refresh_profiles.sh: driver_cmd) says about the headline kernel: the dispatches over the 10 M-row corpus in the order
 they ran, by the time since the first of them, beside the line's own figures.  (Through round 5 the first ~1.2 s of scanning
 -- the stretch after bench.py handed its 30-GB source tensor back to the driver -- ran 2.5 % slower per kernel, and the driver's
@@ -25,7 +25,7 @@ t0 = big[0][0]
 big = [((t - t0) / 1e9, ms) for t, ms in big]
 line = json.loads(open(line_path).read().strip().splitlines()[-1])
 
-print("command: rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5   (literally the driver's command)")
+print("command: rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full   (the driver's command + --full)")
 print("the JSON line of that run:")
 print("  config.release_wait_s: %s" % line.get("config", {}).get("release_wait_s"))
 print("  value (W warm-up + %d timed steps): %.2f queries/s, %.4f ms per step; long_run %.2f queries/s over %d steps" % (

@@ -2,7 +2,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/prof3
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -o p -- python3 $R/bench.py > $OUT/default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/default -o p -- python3 $R/bench.py --full > $OUT/default.log 2>&1
 grep -a "^{\"" $OUT/default.log | tail -1 > $OUT/default.json
 cd $R
 python3 - <<'PY'

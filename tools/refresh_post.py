@@ -41,7 +41,7 @@ write, n2 = per_launch(out + '/single_write/p_counter_collection.csv', 'scan_top
 stat = [r for r in csv.DictReader(open(out + '/single/p_kernel_stats.csv')) if 'scan_topk_kernel' in r['Name']][0]
 json.dump({
     "round": int(RND[1:]),
-    "command": "python3 bench.py --no-side  (N=10M, d=768, cosine, limit 10; PMC passes: --steps 20 --warmup 2 --no-cpu --no-side)",
+    "command": "python3 bench.py --full --no-side  (N=10M, d=768, cosine, limit 10; PMC passes: --steps 20 --warmup 2 --no-cpu --no-side)",
     "rows": 10000000, "dim": 768, "kernel": stat['Name'],
     "rocprof_avg_ns": float(stat['AverageNs']), "rocprof_calls": int(stat['Calls']),
     "FETCH_SIZE_KB_per_launch": fetch, "WRITE_SIZE_KB_per_launch": write,

@@ -16,9 +16,9 @@ pmc() {  # name, counter, bench args...
   rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $OUT/$name -o p -- python3 $R/bench.py "$@" > $OUT/$name.log 2>&1
 }
 export RND=${RND:-r06}
-stats single --no-side          # the headline alone: the scan kernel's average is the bench line's avg_launch_ms
-stats default                   # no flags (1 000 timed steps): headline + side legs (config 2 shares the scan kernel: 1 100 launches at N=1M)
-stats driver_cmd --gpus 1 --steps 20 --warmup 5   # LITERALLY the driver's command under the profiler (VERDICT r5 #4a): the line's avg_launch_ms beside rocprofv3's own average
+stats single --full --no-side   # the headline alone: the scan kernel's average is the bench line's avg_launch_ms
+stats default --full            # 1 000 timed steps: headline + side legs (config 2 shares the scan kernel: 1 100 launches at N=1M)
+stats driver_cmd --gpus 1 --steps 20 --warmup 5 --full   # the driver's command (+ --full for the roofline) under the profiler (VERDICT r5 #4a): the line's avg_launch_ms beside rocprofv3's own average
 pmc single_fetch FETCH_SIZE --steps 20 --warmup 2 --no-cpu --no-side
 pmc single_write WRITE_SIZE --steps 20 --warmup 2 --no-cpu --no-side
 stats batch --mode batch --nominate f32 --steps 6 --warmup 1 --no-cpu          # K2: FP32 matrix cores
@@ -62,8 +62,8 @@ python3 $R/tools/pattern_funnel_probe.py 2>/dev/null | grep "^{" > $OUT/${RND}_p
 cd $R
 # the 8-GPU operating points priced on one GPU (a shard of 10 M / 8 and of 40 M / 8 rows through worker + RCCL exchange + merge)
 cd /tmp
-python3 $R/bench.py --gpus 1 --exchange rccl --rows 1250000 --no-cpu > $OUT/${RND}_shard_10m_of_8.json 2> $OUT/shard_a.log
-python3 $R/bench.py --gpus 1 --exchange rccl --metric l2 --rows 5000000 --no-cpu > $OUT/${RND}_shard_40m_of_8.json 2> $OUT/shard_b.log
+python3 $R/bench.py --gpus 1 --exchange rccl --rows 1250000 --no-cpu --full > $OUT/${RND}_shard_10m_of_8.json 2> $OUT/shard_a.log
+python3 $R/bench.py --gpus 1 --exchange rccl --metric l2 --rows 5000000 --no-cpu --full > $OUT/${RND}_shard_40m_of_8.json 2> $OUT/shard_b.log
 python3 $R/bench.py --gpus 1 --exchange rccl --mode batch --metric l2 --rows 5000000 --steps 60 --warmup 5 --no-cpu > $OUT/${RND}_shard_40m_of_8_batch.json 2> $OUT/shard_c.log
 python3 $R/bench.py --gpus 1 --exchange rccl --mode batch --metric l2 --rows 5000000 --batch 4096 --steps 6 --warmup 1 --no-cpu > $OUT/${RND}_shard_40m_of_8_batch16.json 2> $OUT/shard_d.log
 cd $R
