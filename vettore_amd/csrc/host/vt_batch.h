@@ -134,11 +134,11 @@ int batch_group_queue(Shard *ix, Ctx &c, BatchGroupRun &run, const float *querie
   a.nq_pad = nq_pad;
   a.n_total = n;
   const bool l2_family = ix->metric == VT_L2 || ix->metric == VT_L2_SQUARED;
-  a.xnorm2 = l2_family ? ix->dXnorm2.p : nullptr;
+  a.xnorm2 = l2_family ? ix->norms.buf.p : nullptr;
   if (bf16) {
     a.Qimage = c.dBQimage.p;
     if (shadow) {
-      a.Xshadow = ix->dShadow.p;
+      a.Xshadow = ix->shadow.buf.p;
       VT_HIP(vt::launch_batch_q_image16(c.dBQ.p, ld, nq_pad, c.dBQimage.p, c.stream));
     } else {
       VT_HIP(vt::launch_batch_q_image(c.dBQ.p, ld, nq_pad, c.dBQimage.p, c.stream));
@@ -499,7 +499,7 @@ int pattern_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vecto
   uint32_t sweeps = 0;
   for (size_t g0 = 0; g0 < nq; g0 += vt::kPatternMultiMax, ++sweeps) {
     vt::PatternMultiArgs a{};
-    a.bits = ix->dNzBits.p;
+    a.bits = ix->nz_bits.buf.p;
     a.qbits = reinterpret_cast<const uint64_t *>(c.dBQ.p) + g0 * q_words;
     a.id_rank = ix->dRank.p;
     a.n = n;

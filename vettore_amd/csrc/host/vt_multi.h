@@ -111,7 +111,7 @@ int shard_delete(Shard *ix, const char *id, size_t id_len, bool *began) {
     ix->ids.pop_back();
     ix->rank_host.pop_back();
     ix->n -= 1;
-    if (r != last) index_touch_row(ix, r);  // row r now holds what was the last row
+    if (r != last) ix->touch_rows(&r, 1);  // row r now holds what was the last row
   }
   if (ix->n == 0) {
     ix->dim = -1;

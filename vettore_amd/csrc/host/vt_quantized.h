@@ -36,7 +36,7 @@ int hamming_hist_collect(Shard *ix, Ctx &c, uint32_t k1, bool *timed) {
   }
   c.ham_dirty = true;  // until this query's collect pass has been queued
   vt::HammingHistArgs h{};
-  h.bits = ix->dBits.p;
+  h.bits = ix->bits.buf.p;
   h.qbits = c.dQbits;
   h.n = ix->n;
   h.words = words;
@@ -86,7 +86,7 @@ int hamming_stage_dev(Shard *ix, Ctx &c, uint32_t k1, bool use_hist, ResultBlock
   VT_TRY(c.dPartKeys.ensure((size_t)waves * k1));
   VT_TRY(c.dPartPay.ensure((size_t)waves * k1));
   vt::HammingArgs h{};
-  h.bits = ix->dBits.p;
+  h.bits = ix->bits.buf.p;
   h.qbits = c.dQbits;
   h.id_rank = ix->dRank.p;
   h.n = ix->n;
@@ -156,7 +156,7 @@ int quantized_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t cand
   } else {
     // stage 1: binary_top_k (search.rs:76-92), candidate rows via the host
     std::vector<vt::Entry> cand;
-    VT_TRY(run_hamming(c, ix->dBits.p, c.dQbits, ix->dRank.p, ix->n, d, candidates, cand, true));
+    VT_TRY(run_hamming(c, ix->bits.buf.p, c.dQbits, ix->dRank.p, ix->n, d, candidates, cand, true));
     if (local) first = cand;
     std::vector<uint32_t> rows(cand.size());
     for (size_t i = 0; i < cand.size(); ++i) rows[i] = cand[i].row;
@@ -333,7 +333,7 @@ int quantized_group(Shard *ix, Ctx &c, const float *queries, const std::vector<s
   VT_HIP(hipMemsetAsync(c.dHamHist.p, 0, (size_t)nq * hist_stride * sizeof(uint32_t), c.stream));
   c.ham_dirty = true;  // (the single-query path's two alternating histograms live in the same buffer)
   vt::HammingMultiArgs h{};
-  h.bits = ix->dBits.p;
+  h.bits = ix->bits.buf.p;
   h.qbits = dbits;
   h.n = n;
   h.words = words;

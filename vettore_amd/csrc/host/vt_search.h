@@ -33,7 +33,7 @@ bool pattern_metric(int metric) {
   return metric == VT_HAMMING || metric == VT_JACCARD;
 }
 bool pattern_search_applies(const Shard *ix, size_t limit) {
-  return pattern_metric(ix->metric) && !ix->nz_refused && ix->n >= kPatternMinRows &&
+  return pattern_metric(ix->metric) && !ix->nz_bits.refused && ix->n >= kPatternMinRows &&
          std::min<size_t>(limit, ix->n) + 1 <= kPatternMaxWant;
 }
 
@@ -44,13 +44,26 @@ bool shadow_metric(int metric) {
          metric == VT_L2_SQUARED;
 }
 bool shadow_wanted(const Shard *ix) {
-  return ix->shadow_mode == VT_SHADOW_AUTO && !ix->sh_refused && ix->nominate == VT_NOMINATE_BF16 && shadow_metric(ix->metric) &&
+  return ix->shadow_mode == VT_SHADOW_AUTO && !ix->shadow.refused && ix->nominate == VT_NOMINATE_BF16 && shadow_metric(ix->metric) &&
          ix->n > 0 && ix->dim > 0;
 }
-size_t shadow_rows(const Shard *ix) { return std::max<size_t>(ix->cap, ix->n); }
-bool shadow_current(const Shard *ix) {
-  return ix->sh_valid && ix->sh_dirty.empty() && ix->dShadow.p != nullptr &&
-         ix->dShadow.count >= vt::shadow_elems((uint32_t)shadow_rows(ix), ix->ld);
+size_t shadow_elems(const Shard *ix) { return vt::shadow_elems((uint32_t)std::max<size_t>(ix->cap, ix->n), ix->ld); }
+bool shadow_current(const Shard *ix) { return ix->shadow.current(shadow_elems(ix)); }
+
+// The derived columns a reader with `need` / `limit` wants current, as the elements each must hold (0: not wanted).
+// shard_stale and shard_prepare both go by this one answer.  (A shard with rows.)
+struct ColumnsWanted {
+  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0;
+};
+ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
+  ColumnsWanted w;
+  const size_t rows = std::max<size_t>(ix->cap, ix->n);
+  const size_t bwords = vt::hamming_matrix_words((uint32_t)rows, ((uint32_t)ix->dim + 63) / 64);
+  if (need & NEED_BITS) w.bits = bwords;
+  if ((need & NEED_NZBITS) && pattern_search_applies(ix, limit)) w.nz_bits = bwords;
+  if (need & NEED_NORMS) w.norms = rows;
+  if ((need & NEED_NORMS) && shadow_wanted(ix)) w.shadow = shadow_elems(ix);
+  return w;
 }
 
 bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
@@ -60,22 +73,14 @@ bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
     if ((need & NEED_STRICT_RANKS) || !lazy_ranks_ok(ix, limit)) return true;
     if (!ix->rank_dirty.empty() || ix->rank_dirty_all || ix->dRank.count < rows) return true;
   }
-  if (need & NEED_BITS) {
-    const size_t bwords = vt::hamming_matrix_words((uint32_t)rows, ((uint32_t)ix->dim + 63) / 64);
-    if (!ix->bits_valid || !ix->bits_dirty.empty() || ix->dBits.count < bwords) return true;
-  }
-  if ((need & NEED_NZBITS) && pattern_search_applies(ix, limit)) {
-    const size_t bwords = vt::hamming_matrix_words((uint32_t)rows, ((uint32_t)ix->dim + 63) / 64);
-    if (!ix->nz_valid || !ix->nz_dirty.empty() || ix->dNzBits.count < bwords) return true;
-  }
-  if ((need & NEED_NORMS) && (ix->max_sqnorm < 0.0 || !ix->norm_dirty.empty() || ix->dXnorm2.count < rows)) return true;
-  if ((need & NEED_NORMS) && shadow_wanted(ix) && !shadow_current(ix)) return true;
-  return false;
+  const ColumnsWanted w = columns_wanted(ix, need, limit);
+  return (w.bits && !ix->bits.current(w.bits)) || (w.nz_bits && !ix->nz_bits.current(w.nz_bits)) ||
+         (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow));
 }
 
-int index_ensure_bits(Shard *ix, bool nonzero = false);
-int index_ensure_norms(Shard *ix);
-int index_ensure_shadow(Shard *ix);
+int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords);
+int index_ensure_norms(Shard *ix, size_t rows);
+int index_ensure_shadow(Shard *ix, size_t elems);
 
 // Brings the derived columns a reader needs up to date (exclusive access; primary context).
 int shard_prepare(Shard *ix, unsigned need, size_t limit) {
@@ -84,10 +89,11 @@ int shard_prepare(Shard *ix, unsigned need, size_t limit) {
     if (!(need & NEED_STRICT_RANKS) && lazy_ranks_ok(ix, limit)) VT_TRY(index_lazy_ranks(ix));
     else VT_TRY(index_sync_ranks(ix, false));
   }
-  if (need & NEED_BITS) VT_TRY(index_ensure_bits(ix));
-  if ((need & NEED_NZBITS) && pattern_search_applies(ix, limit)) VT_TRY(index_ensure_bits(ix, true));
-  if (need & NEED_NORMS) VT_TRY(index_ensure_norms(ix));
-  if ((need & NEED_NORMS) && shadow_wanted(ix)) VT_TRY(index_ensure_shadow(ix));
+  const ColumnsWanted w = columns_wanted(ix, need, limit);
+  if (w.bits) VT_TRY(index_ensure_bits(ix, false, w.bits));
+  if (w.nz_bits) VT_TRY(index_ensure_bits(ix, true, w.nz_bits));
+  if (w.norms) VT_TRY(index_ensure_norms(ix, w.norms));
+  if (w.shadow) VT_TRY(index_ensure_shadow(ix, w.shadow));
   return VT_OK;
 }
 
@@ -98,7 +104,7 @@ int batch_group(Shard *ix, Ctx &c, const float *queries, size_t nq, size_t limit
 // batch path wants is current already -- a reader under the shared lock never waits for a build.
 bool single_nominate_applies(const Shard *ix, size_t limit) {
   return ix->single_nominate && ix->ranks_clean && limit >= 1 && limit <= (size_t)vt::kMaxFusedK && ix->n >= 4096 &&
-         shadow_wanted(ix) && shadow_current(ix) && !shard_stale(ix, NEED_NORMS, limit);
+         shadow_wanted(ix) && !shard_stale(ix, NEED_NORMS, limit);
 }
 
 // flat.rs:96-124 on a shard whose rank column shard_prepare has brought up to date --
@@ -138,7 +144,7 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
   std::vector<vt::Entry> entries;
   auto best_rows = [&](size_t want) -> int {
     if (by_pattern)
-      return run_hamming(c, ix->dNzBits.p, c.dQbits, ix->dRank.p, ix->n, j.d, want, entries, true, ix->metric == VT_JACCARD);
+      return run_hamming(c, ix->nz_bits.buf.p, c.dQbits, ix->dRank.p, ix->n, j.d, want, entries, true, ix->metric == VT_JACCARD);
     return run_scan(c, j, want, entries, true);
   };
   if (lazy) {
@@ -314,7 +320,7 @@ int funnel_stage(Shard *ix, Ctx &c, const float *query, uint32_t d, const std::v
     return collect_from_keys(c, c.dCandKeys.p, c.dCandPay.p, (uint32_t)rows.size(), want, out);
   }
   if (all_rows && pattern_stage_applies(ix, c, want))
-    return run_hamming(c, ix->dNzBits.p, c.dQbits, ix->dRank.p, ix->n, d, want, out, true, ix->metric == VT_JACCARD,
+    return run_hamming(c, ix->nz_bits.buf.p, c.dQbits, ix->dRank.p, ix->n, d, want, out, true, ix->metric == VT_JACCARD,
                        (((uint32_t)ix->dim + 63) / 64 + 1) / 2);
   ScanJob j{};
   j.X = ix->dX;
@@ -347,7 +353,7 @@ int scan_stage_dev(Shard *ix, Ctx &c, uint32_t d, const ResultBlock *src, uint32
     VT_TRY(c.dPartKeys.ensure((size_t)hlists * want));
     VT_TRY(c.dPartPay.ensure((size_t)hlists * want));
     vt::HammingArgs h{};
-    h.bits = ix->dNzBits.p;
+    h.bits = ix->nz_bits.buf.p;
     h.qbits = c.dQbits;
     h.id_rank = ix->dRank.p;
     h.n = ix->n;
@@ -500,53 +506,47 @@ int funnel_rows(Shard *ix, Ctx &c, const float *query, const size_t *stages, siz
   return VT_OK;
 }
 
-// Sign bits of every stored row in K4's layout, built on first use (`nonzero`: the column of
-// non-zero bits that flat_search under float hamming / jaccard reads instead of the rows).
-int index_ensure_bits(Shard *ix, bool nonzero) {
+// Sign bits of every stored row in K4's layout -- compress_sign_bits (collection.ex:926) kept in HBM, `bwords` words --
+// built on first use (`nonzero`: the column of non-zero bits that flat_search under float hamming / jaccard reads
+// instead of the rows).
+int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords) {
   Ctx &c = ix->ctx;
-  const uint32_t d = (uint32_t)ix->dim, words = (d + 63) / 64;
-  DevBuf<uint64_t> &col = nonzero ? ix->dNzBits : ix->dBits;
-  bool &valid = nonzero ? ix->nz_valid : ix->bits_valid;
-  std::vector<uint32_t> &dirty = nonzero ? ix->nz_dirty : ix->bits_dirty;
-  // compress_sign_bits of every stored row (collection.ex:926): kept in HBM
-  const size_t bwords = vt::hamming_matrix_words(std::max<uint32_t>(ix->cap, ix->n), words);
-  if (valid && col.count >= bwords) {
+  const uint32_t d = (uint32_t)ix->dim;
+  DerivedColumn<uint64_t> &col = nonzero ? ix->nz_bits : ix->bits;
+  if (col.current(bwords)) return VT_OK;
+  if (col.patchable(bwords)) {
     // only the rows mutated since the last use
     uint32_t count = 0;
-    VT_TRY(upload_row_list(ix, dirty, &count));
-    VT_HIP(vt::launch_sign_pack_rows(ix->dX, ix->ld, c.dRankPairs.p, count, d, col.p, c.stream, nonzero ? 1 : 0));
+    VT_TRY(upload_row_list(ix, col.dirty, &count));
+    VT_HIP(vt::launch_sign_pack_rows(ix->dX, ix->ld, c.dRankPairs.p, count, d, col.buf.p, c.stream, nonzero ? 1 : 0));
     if (count) VT_HIP(hipStreamSynchronize(c.stream));  // the pinned list is reused by the next caller
-    dirty.clear();
+    col.mark_current();
     return VT_OK;
   }
-  dirty.clear();
+  col.forget();
   if (nonzero) {
     // (an accelerator, not a requirement: on a card too full for d / 8 more bytes per row the
     // searches keep reading the rows)
-    valid = false;
-    bool refused = col.ensure(bwords) != VT_OK;
+    bool refused = col.buf.ensure(bwords) != VT_OK;
 #ifdef VT_TEST_HOOKS
     // (libvettore_hip_hooks.so only: the allocation "fails", tests/test_gpu_parity.py checks what follows)
-    if (vt::env::on(vt::env::TEST_REFUSE_NZBITS)) {
-      col.release();
-      refused = true;
-    }
+    refused = refused || vt::env::on(vt::env::TEST_REFUSE_NZBITS);
 #endif
     if (refused) {
-      ix->nz_refused = true;
+      col.refuse();
       return VT_OK;
     }
   } else {
-    VT_TRY(col.ensure(bwords));
+    VT_TRY(col.buf.ensure(bwords));
   }
-  VT_HIP(hipMemsetAsync(col.p, 0, bwords * sizeof(uint64_t), c.stream));
-  VT_HIP(vt::launch_sign_pack(ix->dX, ix->ld, ix->n, d, col.p, 1, c.stream, nonzero ? 1 : 0));
+  VT_HIP(hipMemsetAsync(col.buf.p, 0, bwords * sizeof(uint64_t), c.stream));
+  VT_HIP(vt::launch_sign_pack(ix->dX, ix->ld, ix->n, d, col.buf.p, 1, c.stream, nonzero ? 1 : 0));
   // The column counts as current from here on, for readers on OTHER streams too (leased contexts
   // under the shared lock): the build must have finished before the exclusive lock can drop, also on
   // the paths that return without touching this stream again (limit == 0, a query that fails
   // validation) -- ADVICE r3.
   VT_HIP(hipStreamSynchronize(c.stream));
-  valid = true;
+  col.mark_current();
   return VT_OK;
 }
 
@@ -555,24 +555,23 @@ int index_ensure_bits(Shard *ix, bool nonzero) {
 // than kMaxDerivedDirty mutations rebuild the whole image (one pass over the rows: ~10 ms per
 // 30 GB).  An accelerator, not a requirement: without room for it -- after the allocation at least
 // a quarter of the card must still be free, the rows will want to grow -- the shard is marked
-// `sh_refused` and its batches keep streaming the f32 rows (until the index is emptied).
-int index_ensure_shadow(Shard *ix) {
+// refused and its batches keep streaming the f32 rows (until the index is emptied).
+int index_ensure_shadow(Shard *ix, size_t elems) {
   Ctx &c = ix->ctx;
-  const uint32_t rows = (uint32_t)shadow_rows(ix);
-  const size_t elems = vt::shadow_elems(rows, ix->ld);
-  if (ix->sh_valid && ix->dShadow.p && ix->dShadow.count >= elems) {
+  DerivedColumn<uint16_t> &col = ix->shadow;
+  if (col.current(elems)) return VT_OK;
+  if (col.patchable(elems)) {
     uint32_t count = 0;
-    VT_TRY(upload_row_list(ix, ix->sh_dirty, &count));
-    VT_HIP(vt::launch_shadow_rows(ix->dX, ix->ld, c.dRankPairs.p, count, ix->ld, ix->dShadow.p, c.stream));
+    VT_TRY(upload_row_list(ix, col.dirty, &count));
+    VT_HIP(vt::launch_shadow_rows(ix->dX, ix->ld, c.dRankPairs.p, count, ix->ld, col.buf.p, c.stream));
     if (count) VT_HIP(hipStreamSynchronize(c.stream));  // the pinned list is reused by the next caller; readers on other streams follow
     c.prof.shadow_patched_rows += count;
-    ix->sh_dirty.clear();
+    col.mark_current();
     return VT_OK;
   }
-  ix->sh_valid = false;
-  ix->sh_dirty.clear();
-  if (ix->dShadow.count < elems) {
-    ix->dShadow.release();
+  col.forget();
+  if (col.buf.count < elems) {
+    col.buf.release();
     size_t free_b = 0, total_b = 0;
     VT_HIP(hipMemGetInfo(&free_b, &total_b));
     bool refused = free_b < elems * sizeof(uint16_t) || free_b - elems * sizeof(uint16_t) < total_b / 4;
@@ -581,23 +580,21 @@ int index_ensure_shadow(Shard *ix) {
     if (!refused) {
       const size_t roomy = elems + elems / 4;
       if (free_b >= roomy * sizeof(uint16_t) && free_b - roomy * sizeof(uint16_t) >= total_b / 4) want = roomy;
-      refused = ix->dShadow.ensure(want) != VT_OK;
+      refused = col.buf.ensure(want) != VT_OK;
     }
 #ifdef VT_TEST_HOOKS
     // (libvettore_hip_hooks.so only: the allocation "fails", tests/test_gpu_shadow.py checks what follows)
-    if (vt::env::on(vt::env::TEST_REFUSE_SHADOW)) {
-      ix->dShadow.release();
-      refused = true;
-    }
+    refused = refused || vt::env::on(vt::env::TEST_REFUSE_SHADOW);
 #endif
     if (refused) {
-      ix->sh_refused = true;
+      col.refuse();
       return VT_OK;
     }
   }
-  const uint32_t rows_img = (uint32_t)(vt::shadow_elems(rows, ix->ld) / ix->ld);
+  // (the slab's rows [0, cap) -> the whole image)
+  const uint32_t rows_img = (uint32_t)(elems / ix->ld);
   if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
-  VT_HIP(vt::launch_shadow_build(ix->dX, ix->ld, std::min<uint32_t>(rows, ix->cap), rows_img, ix->ld, ix->dShadow.p, c.stream));
+  VT_HIP(vt::launch_shadow_build(ix->dX, ix->ld, ix->cap, rows_img, ix->ld, col.buf.p, c.stream));
   if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
   // current from here on, for readers on other streams too: the build has finished before the
   // exclusive lock can drop
@@ -608,7 +605,7 @@ int index_ensure_shadow(Shard *ix) {
     c.prof.shadow_builds += 1;
     c.prof.shadow_build_ms += ms;
   }
-  ix->sh_valid = true;
+  col.mark_current();
   return VT_OK;
 }
 
@@ -618,7 +615,7 @@ int quantized_rows(Shard *ix, Ctx &c, size_t candidates, std::vector<uint32_t> &
   std::vector<vt::Entry> local;
   std::vector<vt::Entry> &cand = entries ? *entries : local;
   cand.clear();
-  VT_TRY(run_hamming(c, ix->dBits.p, c.dQbits, ix->dRank.p, ix->n, d, candidates, cand, false));
+  VT_TRY(run_hamming(c, ix->bits.buf.p, c.dQbits, ix->dRank.p, ix->n, d, candidates, cand, false));
   rows.resize(cand.size());
   for (size_t i = 0; i < cand.size(); ++i) rows[i] = cand[i].row;
   return VT_OK;
@@ -626,37 +623,32 @@ int quantized_rows(Shard *ix, Ctx &c, size_t candidates, std::vector<uint32_t> &
 
 // Per-row squared norms and their maximum (the error margin of the batched path), brought
 // up to date: all rows on first use, afterwards only the rows mutated since.
-int index_ensure_norms(Shard *ix) {
+int index_ensure_norms(Shard *ix, size_t rows) {
   Ctx &c = ix->ctx;
   const uint32_t d = (uint32_t)ix->dim, n = ix->n;
+  DerivedColumn<float> &col = ix->norms;
+  if (col.current(rows)) return VT_OK;
   VT_TRY(c.dBNorm.ensure(1));
-  if (ix->max_sqnorm >= 0.0 && ix->dXnorm2.count >= std::max<uint32_t>(ix->cap, n) && !ix->norm_dirty.empty()) {
+  unsigned long long bits = 0;
+  if (col.patchable(rows)) {
     // norms of the rows mutated since the last batch; the maximum can only be kept or raised
     // (a stale larger bound only widens the acceptance margin)
     uint32_t count = 0;
-    VT_TRY(upload_row_list(ix, ix->norm_dirty, &count));
-    unsigned long long bits = 0;
+    VT_TRY(upload_row_list(ix, col.dirty, &count));
     std::memcpy(&bits, &ix->max_sqnorm, sizeof(double));
     VT_HIP(hipMemcpyAsync(c.dBNorm.p, &bits, sizeof(bits), hipMemcpyHostToDevice, c.stream));
-    VT_HIP(vt::launch_row_sqnorms_rows(ix->dX, ix->ld, c.dRankPairs.p, count, d, ix->dXnorm2.p, c.dBNorm.p, c.stream));
-    VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
-    VT_HIP(hipStreamSynchronize(c.stream));
-    std::memcpy(&ix->max_sqnorm, &bits, sizeof(double));
-    ix->norm_dirty.clear();
-  } else if (ix->max_sqnorm >= 0.0 && ix->dXnorm2.count < std::max<uint32_t>(ix->cap, n)) {
-    ix->max_sqnorm = -1.0;  // the slab grew past the norm column
-  }
-  if (ix->max_sqnorm < 0.0) {
-    ix->norm_dirty.clear();
-    unsigned long long bits = 0;
-    VT_TRY(ix->dXnorm2.ensure(std::max<uint32_t>(ix->cap, n)));
+    VT_HIP(vt::launch_row_sqnorms_rows(ix->dX, ix->ld, c.dRankPairs.p, count, d, col.buf.p, c.dBNorm.p, c.stream));
+  } else {
+    // all rows: a first use, more than kMaxDerivedDirty mutations since, or a slab that grew past the column
+    col.forget();
+    VT_TRY(col.buf.ensure(rows));
     VT_HIP(hipMemsetAsync(c.dBNorm.p, 0, sizeof(unsigned long long), c.stream));
-    VT_HIP(vt::launch_row_sqnorms(ix->dX, ix->ld, n, d, ix->dXnorm2.p, c.dBNorm.p, c.stream));
-    VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
-    VT_HIP(hipStreamSynchronize(c.stream));
-    std::memcpy(&ix->max_sqnorm, &bits, sizeof(double));
+    VT_HIP(vt::launch_row_sqnorms(ix->dX, ix->ld, n, d, col.buf.p, c.dBNorm.p, c.stream));
   }
-
+  VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
+  VT_HIP(hipStreamSynchronize(c.stream));
+  std::memcpy(&ix->max_sqnorm, &bits, sizeof(double));
+  col.mark_current();
   return VT_OK;
 }
 

@@ -11,12 +11,9 @@ int index_reserve_once(Shard *ix, uint32_t want_rows);
 // of the batch pass, half the slab's size), the shadow goes and the growth is tried once more.
 int index_reserve(Shard *ix, uint32_t want_rows) {
   int st = index_reserve_once(ix, want_rows);
-  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->dShadow.p) {
+  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->shadow.buf.p) {
     (void)hipStreamSynchronize(ix->ctx.stream);
-    ix->dShadow.release();
-    ix->sh_valid = false;
-    ix->sh_refused = true;
-    ix->sh_dirty.clear();
+    ix->shadow.refuse();
     st = index_reserve_once(ix, want_rows);
   }
   return st;
@@ -83,17 +80,7 @@ int index_set_dim(Shard *ix, size_t d) {
     return fail(VT_ERR_UNSUPPORTED, "dimension " + std::to_string(d) + " exceeds what the scan kernel stages in LDS");
   const uint32_t ld = vt::padded_dim((uint32_t)d);
   ix->for_each_ctx([](Ctx &c) { c.ham_dirty = true; });  // K4h's histograms are cleared for d + 1 bins only: a new dimension starts clean
-  ix->bits_valid = false;    // derived per-row data belongs to the old rows
-  ix->nz_valid = false;
-  ix->nz_refused = false;
-  ix->max_sqnorm = -1.0;
-  ix->bits_dirty.clear();
-  ix->nz_dirty.clear();
-  ix->norm_dirty.clear();
-  ix->sh_valid = false;
-  ix->sh_refused = false;
-  ix->sh_dirty.clear();
-  ix->dShadow.release();  // (an emptied index gives the room back; the next batch builds anew)
+  ix->reset_derived();
   if (ld != ix->ld) {
     VT_HIP(hipStreamSynchronize(ix->ctx.stream));
     ix->slab.release();
@@ -320,40 +307,6 @@ struct RowSource {
   // the copy to the device (index_store_bulk_host) -- anything else must be handed validated rows
   bool unvalidated = false;
 };
-
-constexpr size_t kMaxDerivedDirty = 65536;  // more mutated rows than this: rebuild instead of patching
-
-// Row `r` changed: its sign bits, non-zero bits and norm are stale.
-inline void index_touch_row(Shard *ix, uint32_t r) {
-  if (ix->bits_valid) {
-    ix->bits_dirty.push_back(r);
-    if (ix->bits_dirty.size() > kMaxDerivedDirty) {
-      ix->bits_valid = false;
-      ix->bits_dirty.clear();
-    }
-  }
-  if (ix->nz_valid) {
-    ix->nz_dirty.push_back(r);
-    if (ix->nz_dirty.size() > kMaxDerivedDirty) {
-      ix->nz_valid = false;
-      ix->nz_dirty.clear();
-    }
-  }
-  if (ix->max_sqnorm >= 0.0) {
-    ix->norm_dirty.push_back(r);
-    if (ix->norm_dirty.size() > kMaxDerivedDirty) {
-      ix->max_sqnorm = -1.0;
-      ix->norm_dirty.clear();
-    }
-  }
-  if (ix->sh_valid) {
-    ix->sh_dirty.push_back(r);
-    if (ix->sh_dirty.size() > kMaxDerivedDirty) {
-      ix->sh_valid = false;
-      ix->sh_dirty.clear();
-    }
-  }
-}
 
 // Uploads a row list (rows still < n) for the patch kernels; returns its length.
 int upload_row_list(Shard *ix, std::vector<uint32_t> &list, uint32_t *count) {
@@ -729,18 +682,7 @@ int index_store_bulk_host(Shard *ix, size_t count, const char *ids, const size_t
     return kRetryGeneral;
   }
   // derived columns: everything behind n_before is new
-  if (count > kMaxDerivedDirty) {
-    ix->bits_valid = false;
-    ix->nz_valid = false;
-    ix->max_sqnorm = -1.0;
-    ix->bits_dirty.clear();
-    ix->nz_dirty.clear();
-    ix->norm_dirty.clear();
-    ix->sh_valid = false;
-    ix->sh_dirty.clear();
-  } else {
-    for (size_t i = 0; i < count; ++i) index_touch_row(ix, target[i]);
-  }
+  ix->touch_rows(target.data(), count);
   // the rank column on the device
   if (ranked_here || ix->ranks_clean) {
     // (ids that arrived in order extend the ranks in place: only the new ones travel, unless the column has to be regrown)
@@ -827,18 +769,7 @@ int index_store_rows(Shard *ix, size_t count, const char *ids, const size_t *id_
   // tests/test_gpu_multishard.py checks that the handle is poisoned from then on)
   if (vt::env::on(vt::env::TEST_FAIL_AFTER_ID_UPDATE)) return fail(VT_ERR_DEVICE, "injected failure after the id table changed");
 #endif
-  if (count > kMaxDerivedDirty) {
-    ix->bits_valid = false;
-    ix->nz_valid = false;
-    ix->max_sqnorm = -1.0;
-    ix->bits_dirty.clear();
-    ix->nz_dirty.clear();
-    ix->norm_dirty.clear();
-    ix->sh_valid = false;
-    ix->sh_dirty.clear();
-  } else {
-    for (size_t i = 0; i < count; ++i) index_touch_row(ix, target[i]);
-  }
+  ix->touch_rows(target.data(), count);
   const uint32_t ld = ix->ld;
   bool pending = false;
   unsigned char *land_buf = nullptr;  // a trickle's slot of the landing ring (host and device view), the event behind it,

@@ -135,6 +135,55 @@ struct Ctx {
   }
 };
 
+constexpr size_t kMaxDerivedDirty = 65536;  // more mutated rows than this: rebuild instead of patching
+
+// A per-row column computed from a shard's rows and kept across searches (Shard: sign bits, non-zero bits, squared
+// norms, bf16 shadow), so that a search after a mutation need not pass over all the rows again.  One policy for all:
+//  - a mutated row joins `dirty` while the column is valid; past kMaxDerivedDirty of them the column is forgotten, and
+//    the next reader rebuilds it from scratch instead of patching row by row;
+//  - a reader that wants `elems` elements may use it under the shared lock only while it is current(elems); otherwise
+//    the column is patched or rebuilt first, under the exclusive lock (vt_search.h, shard_prepare).  A buffer smaller
+//    than `elems` (the slab grew) means a rebuild;
+//  - a new dimension or an emptied index resets it;
+//  - an optional column (non-zero bits, shadow) that cannot get memory is `refused`: readers go without it until the
+//    next reset (the shadow also until vt_flat_set_batch_shadow asks for it again).
+template <typename T>
+struct DerivedColumn {
+  DevBuf<T> buf;
+  bool valid = false;            // buf describes every row but those in `dirty`
+  bool refused = false;
+  std::vector<uint32_t> dirty;   // rows mutated since the column was last brought up to date
+
+  void touch(uint32_t row) {
+    if (!valid) return;
+    dirty.push_back(row);
+    if (dirty.size() > kMaxDerivedDirty) forget();
+  }
+  void forget() {
+    valid = false;
+    dirty.clear();
+  }
+  void reset() {
+    forget();
+    refused = false;
+  }
+  void release() {  // the room goes back; the next use builds anew
+    forget();
+    buf.release();
+  }
+  void refuse() {
+    release();
+    refused = true;
+  }
+  void mark_current() {  // built, or its dirty rows patched
+    valid = true;
+    dirty.clear();
+  }
+  // valid and large enough: the dirty rows are all it lacks
+  bool patchable(size_t elems) const { return valid && buf.p != nullptr && buf.count >= elems; }
+  bool current(size_t elems) const { return patchable(elems) && dirty.empty(); }
+};
+
 }  // namespace
 
 struct Shard;
@@ -192,31 +241,25 @@ struct Shard {
   Slab slab;
   float *dX = nullptr;  // == slab.p
   DevBuf<uint32_t> dRank;
-  DevBuf<uint64_t> dBits;
-  bool bits_valid = false;
-  // Rows mutated since the bit matrix / the norms were last brought up to date; patched in
-  // place at the next use (a full rebuild is a pass over the whole corpus).
-  std::vector<uint32_t> bits_dirty, norm_dirty;
-  // The same for float hamming / jaccard collections: one bit per coordinate, set iff it is
-  // non-zero -- all those two metrics look at (distances.rs:319-347) -- in K4's layout; flat_search
-  // reads these 1/32 of the row bytes instead of the rows (vt_search.h, pattern_search_applies).
-  DevBuf<uint64_t> dNzBits;
-  bool nz_valid = false;
-  bool nz_refused = false;  // the card had no room for the column: searches keep reading the rows (until the index is emptied)
-  std::vector<uint32_t> nz_dirty;
+  // The derived columns (DerivedColumn states how they are kept):
+  // sign bits of every row in K4's layout (quantized search, funnel stages)
+  DerivedColumn<uint64_t> bits;
+  // Float hamming / jaccard collections: one bit per coordinate, set iff it is non-zero -- all those two metrics look
+  // at (distances.rs:319-347) -- in K4's layout; flat_search reads these 1/32 of the row bytes instead of the rows
+  // (vt_search.h, pattern_search_applies).  Optional: when it is refused, searches keep reading the rows.
+  DerivedColumn<uint64_t> nz_bits;
+  // per-row squared norms (the batched path's L2 term) and their maximum max_i sum_j x_ij^2 (its error margin; a
+  // value only while the column is valid)
+  DerivedColumn<float> norms;
+  double max_sqnorm = 0.0;
   // K2s: the rows once more, rounded to bf16, in the order the matrix cores take their operands in
   // (vt_device.h shadow_index) -- what the bf16 nomination pass reads instead of the f32 rows when
-  // the card has room for it (vt_search.h, index_ensure_shadow).  Kept like the bit columns: built
-  // by the first batch that wants it, patched per mutated row, given back when the slab needs the room.
-  DevBuf<uint16_t> dShadow;
+  // the card has room for it (vt_search.h, index_ensure_shadow).  Optional: when there is no room, or the slab takes
+  // the room back (index_reserve), it is refused and batches stream the f32 rows.
+  DerivedColumn<uint16_t> shadow;
   int shadow_mode = default_shadow();  // VT_SHADOW_*
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
-  bool sh_valid = false;
-  bool sh_refused = false;  // no room (or the slab took the room back): batches stream the f32 rows until the index is emptied
-  std::vector<uint32_t> sh_dirty;
-  double max_sqnorm = -1.0;  // max_i sum_j x_ij^2, < 0 = stale (error margin of the batched path)
-  DevBuf<float> dXnorm2;     // per-row squared norms, valid with max_sqnorm
   // ids
   std::vector<std::string> ids;  // by row
   vt_host::IdTable row_of{&ids};  // id bytes -> row (the bytes themselves stay in `ids`)
@@ -264,6 +307,33 @@ struct Shard {
   void for_each_ctx(F f) {
     f(ctx);
     for (auto &e : extra) f(*e);
+  }
+
+  // Rows changed (stored, or moved by a delete): each derived column notes them.  More than kMaxDerivedDirty at once
+  // would only overflow every list: forget all.
+  void touch_rows(const uint32_t *rows, size_t count) {
+    if (count > kMaxDerivedDirty) return forget_derived();
+    for (size_t i = 0; i < count; ++i) {
+      bits.touch(rows[i]);
+      nz_bits.touch(rows[i]);
+      norms.touch(rows[i]);
+      shadow.touch(rows[i]);
+    }
+  }
+  void forget_derived() {
+    bits.forget();
+    nz_bits.forget();
+    norms.forget();
+    shadow.forget();
+  }
+  // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
+  // shadow gives its room back.
+  void reset_derived() {
+    bits.reset();
+    nz_bits.reset();
+    norms.reset();
+    shadow.reset();
+    shadow.buf.release();
   }
 };
 

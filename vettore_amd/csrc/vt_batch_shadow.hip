@@ -6,7 +6,7 @@
 // alone 6.7 TB/s, MFMA alone 3.2 ms per 10 M rows, together 5.3 ms).  Here the rounding has been
 // done once, when the rows arrived: beside the f32 slab the shard keeps -- when the card has
 // room -- an image of the same rows in bf16, already in the order the matrix cores take their
-// operands in (Shard::dShadow, built by shadow_build_kernel, patched per mutated row like the
+// operands in (Shard::shadow, built by shadow_build_kernel, patched per mutated row like the
 // sign bits).  The pass reads N * ld * 2 bytes instead of N * ld * 4, converts nothing, and both
 // operands reach LDS as whole fragments.  Same rounding (v_cvt_pk_bf16_f32, round to nearest
 // even) => the same nominations as K2b's, the same bound in batch_group; nothing this kernel

@@ -430,11 +430,9 @@ int vt_flat_set_batch_shadow(vt_flat *h, int mode) {
     if (mode == VT_SHADOW_OFF) {  // the room goes back at once
       (void)hipSetDevice(s->ctx.device);
       (void)hipStreamSynchronize(s->ctx.stream);
-      s->dShadow.release();
-      s->sh_valid = false;
-      s->sh_dirty.clear();
+      s->shadow.release();
     } else {
-      s->sh_refused = false;  // asked for again: the next batch looks at the free memory anew
+      s->shadow.refused = false;  // asked for again: the next batch looks at the free memory anew
     }
   }
   return VT_OK;
@@ -454,8 +452,8 @@ int vt_flat_batch_shadow(const vt_flat *h) {
   std::shared_lock<std::shared_mutex> rl(h->rw);
   const Shard *ix = h->shards[0].get();
   if (ix->shadow_mode == VT_SHADOW_OFF) return VT_SHADOW_STATE_OFF;
-  if (ix->sh_refused) return VT_SHADOW_STATE_REFUSED;
-  if (!ix->dShadow.p || !ix->sh_valid) return VT_SHADOW_STATE_NONE;
+  if (ix->shadow.refused) return VT_SHADOW_STATE_REFUSED;
+  if (!ix->shadow.buf.p || !ix->shadow.valid) return VT_SHADOW_STATE_NONE;
   return shadow_current(ix) ? VT_SHADOW_STATE_CURRENT : VT_SHADOW_STATE_STALE;
 }
 
