@@ -68,6 +68,8 @@ enum {
   VT_ERR_PREFIX = 6,         /* "invalid prefix dimensions"           search.rs:47 */
   VT_ERR_DIMS_POSITIVE = 7,  /* "dimensions must be positive"         distances.rs:463 */
   VT_ERR_POISONED = 8,       /* "flat lock poisoned"                  nifs.rs:269: an earlier mutation died half-way */
+  VT_ERR_EMPTY_VECTORS = 9,  /* "vectors must not be empty"           multi_vector.rs:57, :141 */
+  VT_ERR_SCORE_OVERFLOW = 10, /* "score overflow"                     multi_vector.rs:84 */
   /* statuses the reference cannot produce */
   VT_ERR_NOMEM = 16,
   VT_ERR_DEVICE = 17,        /* HIP error / no gfx950 device; see vt_last_error() */
@@ -382,6 +384,26 @@ int vt_normalize_l2(int device, size_t count, size_t d, const float *in,
  * out has count * ((d + 63) / 64) words. */
 int vt_compress_sign_bits(int device, size_t count, size_t d, const float *in,
                           uint64_t *out);
+
+/* ------------------------------------------------- MaxSim (late interaction)
+ * Vectors are ragged: vector j of a list is values[value_off[j] .. value_off[j + 1]), and a
+ * length that differs from the query's is the reference's "dimension mismatch".  Validation
+ * follows the reference exactly: the metric code, then the query vectors on their own (first
+ * non-empty, equal lengths, finite), then the documents in order -- with no query vectors every
+ * document is validated on its own and scores 0.0, a document without vectors scores 0.0 -- and
+ * the first error (a scoring error of an earlier document included) is the call's status.
+ * Scores: per query vector the best similarity_value over the document's vectors, summed in f32
+ * in query order (bit-identical to the reference for the lane order of vt_set_default_reduce_order).
+ * No CPU fallback: a valid call without a device returns VT_ERR_DEVICE. */
+/* multi_vector_score/3, nifs.rs:177-187 -> multi_vector.rs:40-88 */
+int vt_multi_vector_score(int device, const float *query, const size_t *query_off, size_t nquery,
+                          const float *doc, const size_t *doc_off, size_t ndoc, int metric_code, float *out);
+/* multi_vector_top_k/4, nifs.rs:188-198 -> multi_vector.rs:90-132: the `limit` best documents by
+ * descending score (f32::total_cmp), ties by ascending id bytes; vt_hits_raw is the score. */
+int vt_multi_vector_top_k(int device, size_t count, const char *ids, const size_t *id_off,
+                          const size_t *doc_vec_off, /* count + 1: document i owns vectors [doc_vec_off[i], doc_vec_off[i + 1]) */
+                          const float *values, const size_t *value_off, const float *query, const size_t *query_off,
+                          size_t nquery, int metric_code, size_t limit, vt_hits **out);
 
 /* ------------------------------------------------------------ profiling
  * Device-side timing of the dominant kernels with HIP events on the stream the

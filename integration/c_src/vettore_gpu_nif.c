@@ -598,6 +598,125 @@ static ERL_NIF_TERM binary_top_k(ErlNifEnv *env, int argc, const ERL_NIF_TERM ar
   return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
 }
 
+/* [[float]] -> values + value_off (ragged: every vector keeps its own length) */
+static int get_vectors(ErlNifEnv *env, ERL_NIF_TERM list, float **vals, size_t **off, size_t *count) {
+  unsigned len;
+  *vals = NULL;
+  *off = NULL;
+  if (!enif_get_list_length(env, list, &len)) return 0;
+  *off = (size_t *)calloc((size_t)len + 1, sizeof(size_t));
+  size_t cap = 64;
+  *vals = (float *)malloc(cap * sizeof(float));
+  if (!*off || !*vals) return 0;
+  ERL_NIF_TERM head, tail = list;
+  for (unsigned i = 0; i < len; ++i) {
+    float *v = NULL;
+    size_t n = 0;
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !get_f32_list(env, head, &v, &n)) return 0;
+    if ((*off)[i] + n > cap) {
+      cap = ((*off)[i] + n) * 2 + 64;
+      float *grown = (float *)realloc(*vals, cap * sizeof(float));
+      if (!grown) { free(v); return 0; }
+      *vals = grown;
+    }
+    memcpy(*vals + (*off)[i], v, n * sizeof(float));
+    (*off)[i + 1] = (*off)[i] + n;
+    free(v);
+  }
+  *count = len;
+  return 1;
+}
+
+/* metric_code: u8 in the reference */
+static int get_metric_code(ErlNifEnv *env, ERL_NIF_TERM t, int *code) {
+  return enif_get_int(env, t, code) && *code >= 0 && *code <= 255;
+}
+
+/* multi_vector_score([[float]], [[float]], metric_code)                    nifs.rs:177-187 */
+static ERL_NIF_TERM multi_vector_score(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  float *q = NULL, *dv = NULL;
+  size_t *qoff = NULL, *doff = NULL, nq = 0, nd = 0;
+  int code;
+  (void)argc;
+  if (!get_vectors(env, argv[0], &q, &qoff, &nq) || !get_vectors(env, argv[1], &dv, &doff, &nd) ||
+      !get_metric_code(env, argv[2], &code)) {
+    free(q); free(qoff); free(dv); free(doff);
+    return enif_make_badarg(env);
+  }
+  float score = 0.0f;
+  int st = vt_multi_vector_score(0, q, qoff, nq, dv, doff, nd, code, &score);
+  free(q); free(qoff); free(dv); free(doff);
+  return st == VT_OK ? enif_make_tuple2(env, mk_atom(env, "ok"), enif_make_double(env, (double)score)) : mk_error(env, st);
+}
+
+/* multi_vector_top_k([{id, [[float]]}], [[float]], metric_code, limit)     nifs.rs:188-198 */
+static ERL_NIF_TERM multi_vector_top_k(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  unsigned count;
+  char *ids = NULL;
+  size_t *id_off = NULL, *doc_vec_off = NULL, *val_off = NULL, *qoff = NULL, nq = 0, limit;
+  float *vals = NULL, *q = NULL;
+  int code, ok = enif_get_list_length(env, argv[0], &count);
+  size_t nvec = 0, ids_cap = 64, vals_cap = 64, vecs_cap = 64;
+  (void)argc;
+  if (ok) {
+    id_off = (size_t *)calloc((size_t)count + 1, sizeof(size_t));
+    doc_vec_off = (size_t *)calloc((size_t)count + 1, sizeof(size_t));
+    val_off = (size_t *)calloc(vecs_cap + 1, sizeof(size_t));
+    ids = (char *)malloc(ids_cap);
+    vals = (float *)malloc(vals_cap * sizeof(float));
+    ok = id_off && doc_vec_off && val_off && ids && vals;
+  }
+  ERL_NIF_TERM head, tail = argv[0];
+  for (unsigned i = 0; ok && i < count; ++i) {
+    const ERL_NIF_TERM *pair;
+    int arity;
+    ErlNifBinary id;
+    float *dv = NULL;
+    size_t *doff = NULL, nd = 0;
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !enif_get_tuple(env, head, &arity, &pair) || arity != 2 ||
+        !enif_inspect_binary(env, pair[0], &id) || !get_vectors(env, pair[1], &dv, &doff, &nd)) {
+      free(dv); free(doff);
+      ok = 0;
+      break;
+    }
+    if (id_off[i] + id.size > ids_cap) {
+      ids_cap = (id_off[i] + id.size) * 2 + 64;
+      char *g = (char *)realloc(ids, ids_cap);
+      if (g) ids = g; else ok = 0;
+    }
+    if (ok && val_off[nvec] + doff[nd] > vals_cap) {
+      vals_cap = (val_off[nvec] + doff[nd]) * 2 + 64;
+      float *g = (float *)realloc(vals, vals_cap * sizeof(float));
+      if (g) vals = g; else ok = 0;
+    }
+    if (ok && nvec + nd > vecs_cap) {
+      vecs_cap = (nvec + nd) * 2 + 64;
+      size_t *g = (size_t *)realloc(val_off, (vecs_cap + 1) * sizeof(size_t));
+      if (g) val_off = g; else ok = 0;
+    }
+    if (ok) {
+      memcpy(ids + id_off[i], id.data, id.size);
+      id_off[i + 1] = id_off[i] + id.size;
+      memcpy(vals + val_off[nvec], dv, doff[nd] * sizeof(float));
+      for (size_t j = 0; j < nd; ++j) val_off[nvec + j + 1] = val_off[nvec] + doff[j + 1];
+      nvec += nd;
+      doc_vec_off[i + 1] = nvec;
+    }
+    free(dv); free(doff);
+  }
+  ok = ok && get_vectors(env, argv[1], &q, &qoff, &nq) && get_metric_code(env, argv[2], &code) && get_size(env, argv[3], &limit);
+  ERL_NIF_TERM res;
+  if (!ok) {
+    res = enif_make_badarg(env);
+  } else {
+    vt_hits *h;
+    int st = vt_multi_vector_top_k(0, count, ids, id_off, doc_vec_off, vals, val_off, q, qoff, nq, code, limit, &h);
+    res = st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
+  }
+  free(ids); free(id_off); free(doc_vec_off); free(val_off); free(vals); free(q); free(qoff);
+  return res;
+}
+
 static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   (void)priv; (void)info;
   /* a libvettore_hip.so built from another header would be handed structs of the wrong size */
@@ -623,6 +742,8 @@ static ErlNifFunc funcs[] = {
   {"compress_sign_bits", 1, compress_sign_bits, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"vector_top_k", 5, vector_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"binary_top_k", 4, binary_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"multi_vector_score", 3, multi_vector_score, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"multi_vector_top_k", 4, multi_vector_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(Elixir.Vettore.Gpu.Nifs, funcs, load, NULL, NULL, NULL)

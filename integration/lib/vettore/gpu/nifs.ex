@@ -45,4 +45,6 @@ defmodule Vettore.Gpu.Nifs do
   def compress_sign_bits(_vector), do: :erlang.nif_error(:nif_not_loaded)
   def vector_top_k(_vectors, _query, _metric_code, _dimensions, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def binary_top_k(_vectors, _query, _dimensions, _limit), do: :erlang.nif_error(:nif_not_loaded)
+  def multi_vector_score(_query_vectors, _document_vectors, _metric_code), do: :erlang.nif_error(:nif_not_loaded)
+  def multi_vector_top_k(_documents, _query_vectors, _metric_code, _limit), do: :erlang.nif_error(:nif_not_loaded)
 end

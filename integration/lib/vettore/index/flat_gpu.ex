@@ -173,6 +173,9 @@ defmodule Vettore.Index.FlatGpu do
   defdelegate compress_sign_bits(vector), to: Nifs
   defdelegate vector_top_k(vectors, query, metric_code, dimensions, limit), to: Nifs
   defdelegate binary_top_k(vectors, query, dimensions, limit), to: Nifs
+  # MaxSim (late interaction) on the device: Vettore.Nifs.multi_vector_score/3 and multi_vector_top_k/4
+  defdelegate multi_vector_score(query_vectors, document_vectors, metric_code), to: Nifs
+  defdelegate multi_vector_top_k(documents, query_vectors, metric_code, limit), to: Nifs
 
   # collection.ex:510 / :547
   defp max_candidates(limit) when is_integer(limit), do: max(limit * 10, limit)

@@ -32,6 +32,7 @@ SYMBOLS = [
     "vt_flat_load_matrix", "vt_flat_load_device_matrix", "vt_flat_quantized_search", "vt_flat_quantized_search_batch", "vt_flat_funnel_search", "vt_flat_funnel_search_batch", "vt_flat_hybrid_search",
     "vt_rank_ids", "vt_flat_set_id_ranks", "vt_flat_stream", "vt_flat_search_begin", "vt_flat_merge_gathered",
     "vt_vector_top_k", "vt_binary_top_k", "vt_normalize_l2", "vt_compress_sign_bits",
+    "vt_multi_vector_score", "vt_multi_vector_top_k",
     "vt_flat_set_profiling", "vt_flat_get_profile", "vt_flat_get_profile_sized",
     "vt_flat_set_batch_shadow", "vt_flat_batch_shadow", "vt_flat_set_single_nominate", "vt_flat_single_nominate",
 ]
@@ -151,6 +152,9 @@ def load() -> C.CDLL:
                                   C.c_size_t, C.POINTER(vp)]
     L.vt_normalize_l2.argtypes = [C.c_int, C.c_size_t, C.c_size_t, f32p, f32p]
     L.vt_compress_sign_bits.argtypes = [C.c_int, C.c_size_t, C.c_size_t, f32p, u64p]
+    L.vt_multi_vector_score.argtypes = [C.c_int, f32p, szp, C.c_size_t, f32p, szp, C.c_size_t, C.c_int, f32p]
+    L.vt_multi_vector_top_k.argtypes = [C.c_int, C.c_size_t, C.c_char_p, szp, szp, f32p, szp, f32p, szp, C.c_size_t,
+                                        C.c_int, C.c_size_t, C.POINTER(vp)]
     L.vt_flat_set_profiling.argtypes = [vp, C.c_int]
     L.vt_flat_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
     L.vt_flat_get_profile_sized.argtypes = [vp, vp, C.c_size_t, C.c_int]

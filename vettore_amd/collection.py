@@ -29,6 +29,7 @@ class Embedding:
     vector: Any = None
     binary_vector: Optional[List[int]] = None
     metadata: Any = None
+    vectors: Optional[List[List[float]]] = None   # multi-vector (late-interaction) form; `vector` is then their mean
 
 
 def _finite_f32(v) -> bool:  # collection.ex:1264-1270
@@ -114,25 +115,53 @@ class Collection:
             return ("error", "invalid_vector")
         return ("ok", res[1])
 
-    # -- collection.ex:921-937 ----------------------------------------------
+    # -- collection.ex:963-991: every vector validated and normalized; anything but a non-empty list is refused
+    def _prepare_vectors(self, vectors):
+        if not isinstance(vectors, (list, tuple)) or len(vectors) == 0:
+            return ("error", "invalid_multi_vector")
+        out = []
+        for v in vectors:
+            ok = _validate_vector(v, self.dimensions)
+            if ok != "ok":
+                return ok
+            n = self._normalize(v)
+            if n[0] != "ok":
+                return n
+            out.append(n[1])
+        return ("ok", out)
+
+    # -- collection.ex:921-937, :993-1017 -------------------------------------
     def _prepare_embedding(self, emb):
         if isinstance(emb, dict):
             emb = Embedding(id=emb.get("id"), value=emb.get("value"), vector=emb.get("vector"),
-                            metadata=emb.get("metadata"))
+                            metadata=emb.get("metadata"), vectors=emb.get("vectors"))
         if not isinstance(emb, Embedding):
             return ("error", "invalid_embedding")
         if not isinstance(emb.id, (str, bytes)) or len(emb.id) == 0:
             return ("error", "missing_id")
-        ok = _validate_vector(emb.vector, self.dimensions)
-        if ok != "ok":
-            return ok
-        vec = self._normalize(emb.vector)
+        vectors = None
+        if emb.vectors is not None:
+            pv = self._prepare_vectors(emb.vectors)
+            if pv[0] != "ok":
+                return pv
+            vectors = pv[1]
+        if emb.vector is None and vectors is not None:
+            # mean_vector: an f64 sum in order, divided by the count, then the collection's normalization
+            acc = [0.0] * self.dimensions
+            for v in vectors:
+                acc = [a + float(x) for a, x in zip(acc, v)]
+            vec = self._normalize([a / len(vectors) for a in acc])
+        else:
+            ok = _validate_vector(emb.vector, self.dimensions)
+            if ok != "ok":
+                return ok
+            vec = self._normalize(emb.vector)
         if vec[0] != "ok":
             return vec
         bits = nifs.compress_sign_bits(vec[1])                  # collection.ex:926, :941-946
         idb = nifs._bytes(emb.id)
         return ("ok", Embedding(id=idb, value=emb.value if emb.value is not None else idb, vector=vec[1],
-                                binary_vector=bits, metadata=emb.metadata))
+                                binary_vector=bits, metadata=emb.metadata, vectors=vectors))
 
     # -- collection.ex:168-189, :459-479 -------------------------------------
     def put(self, emb):
@@ -219,6 +248,44 @@ class Collection:
 
     def hybrid_search(self, query, opts=None):
         return self._staged("hybrid_search", ("limit", "generators", "rerank"), query, opts)                 # :59
+
+    # -- collection.ex:298-323 ------------------------------------------------
+    def multi_vector_search(self, query_vectors, opts=None):
+        """MaxSim over every stored embedding (its `vectors`, or its one `vector`): Results carry the score."""
+        opts = {} if opts is None else opts
+        if not isinstance(opts, dict):
+            return ("error", "invalid_options")
+        bad = [k for k in opts if k not in ("limit", "metric")]
+        if bad:
+            return ("error", ("unsupported_option", bad[0]))
+        limit = opts.get("limit", 10)
+        if not (isinstance(limit, int) and not isinstance(limit, bool) and 0 < limit <= MAX_NIF_USIZE):
+            return ("error", "invalid_limit")
+        metric = METRIC_ALIASES.get(opts.get("metric", self.metric), opts.get("metric", self.metric))
+        if metric not in METRICS:
+            return ("error", "invalid_metric")
+        qv = self._prepare_vectors(query_vectors)
+        if qv[0] != "ok":
+            return qv
+        return self._multi_vector_results(qv[1], list(self.store.values()), metric, limit)
+
+    # -- collection.ex:742-806: the documents, one native call, errors as atoms, Results with score only
+    def _multi_vector_results(self, query_vectors, embeddings, metric, limit):
+        documents = []
+        for e in embeddings:
+            vectors = e.vectors if e.vectors else [e.vector]
+            for v in vectors:
+                ok = _validate_vector(v, self.dimensions)
+                if ok != "ok":
+                    return ok
+            documents.append((e.id, vectors))
+        res = nifs.multi_vector_top_k(documents, query_vectors, nifs.METRIC_CODE[metric], limit)
+        if res[0] != "ok":
+            return ("error", {"score overflow": "score_overflow", "dimension mismatch": "dimension_mismatch",
+                              "vector contains a non-finite value": "invalid_multi_vector"}.get(res[1], res[1]))
+        by_id = {e.id: e for e in embeddings}
+        return ("ok", [Result(id=i, value=by_id[i].value, score=float(score), distance=None, metric=metric,
+                              metadata=by_id[i].metadata) for i, score in res[1] if i in by_id])
 
     # (extensions of the adapter: lists of queries, one call)
     def search_batch(self, queries, opts=None):

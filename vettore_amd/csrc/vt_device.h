@@ -515,6 +515,46 @@ hipError_t launch_read_peak(const void *buf, size_t bytes, float *sink, uint32_t
 size_t read_peak_bytes(size_t bytes);
 hipError_t launch_peak_fill(void *buf, size_t bytes, hipStream_t s);
 
+// K9: MaxSim / ColBERT scoring (multi_vector.rs:65-88) of a chunk of documents, for multi_vector_top_k / _score.
+// The documents' vectors are one row-major matrix X (`stride` floats apart); document i owns rows
+// [doc_off[i], doc_off[i + 1]).  A wave takes one document at a time, a lane one of its vectors, and walks
+// the query vectors of the launch's panel -- staged in LDS -- eight at a time: every (query vector,
+// document vector) pair is one lane's own chain in the reference's order (distances.rs:42-68 for eight
+// metrics, :160-185 for cosine), the maximum over the document's vectors a wave reduction, the sum over the
+// query vectors one sequential f32 chain in query order.  Query vectors that do not fit in one panel go in
+// several launches over the same documents (panel_q0 > 0): the running sum and status live in
+// total / status between them.  The launch that holds the last query vector writes one key per document:
+// (~total_cmp(score) << 32) | id rank -- the smallest key is the best hit (collect_from_keys) --, and on an
+// error kEmptyKey and (row << 8 | status) into *first_error (atomicMin: the earliest document wins).
+constexpr int kErrScoreOverflow = 10;  // VT_ERR_SCORE_OVERFLOW
+struct MaxSimArgs {
+  const float *X;           // document vectors; unused when nq == 0
+  size_t stride;            // floats between rows (>= d)
+  const uint32_t *doc_off;  // [ndoc + 1] rows of each document (relative to X); unused when nq == 0
+  uint32_t ndoc;
+  const float *Q;           // [nq][q_stride] query vectors (device), zero-padded, q_stride % 8 == 0
+  uint32_t q_stride;
+  uint32_t nq;              // query vectors of the call (0: every document scores 0.0)
+  uint32_t panel_q0, panel_qn;  // this launch's query vectors [panel_q0, panel_q0 + panel_qn)
+  uint32_t d;
+  int metric, order;
+  const double *qnorm;      // cosine: [nq] sqrt(f64 q.q)  (launch_maxsim_norms)
+  const double *tnorm;      // cosine: per row of X  sqrt(f64 t.t)
+  float *total;             // [ndoc] running sum between panel launches (unused with one panel)
+  int *status;              // [ndoc] 0, kErrOverflow or kErrScoreOverflow between panel launches
+  const uint32_t *id_rank;  // [ndoc]
+  uint32_t row0;            // the chunk's first document within the call (payload row = row0 + i)
+  uint64_t *keys;           // [ndoc]
+  Payload *pay;             // [ndoc] {row0 + i, score}
+  unsigned long long *first_error;  // (row << 8 | status), ~0 when none
+};
+// Query vectors per panel for dimension d (0: a single query vector does not fit in LDS) and the LDS bytes of a panel.
+uint32_t maxsim_panel_rows(uint32_t d, uint32_t *q_stride);
+size_t maxsim_lds_bytes(uint32_t panel_qn, uint32_t q_stride);
+hipError_t launch_maxsim(const MaxSimArgs &a, uint32_t blocks, hipStream_t s);
+// norms[i] = sqrt(f64 sum of x[i][j]^2, j in order) for n rows `stride` floats apart (distances.rs:166-167)
+hipError_t launch_maxsim_norms(const float *X, size_t stride, uint32_t n, uint32_t d, double *norms, hipStream_t s);
+
 // normalize_l2 (distances.rs:350-361) on rows: out = (x / sqrt(f64 sum x^2)) as f32.
 hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *out, hipStream_t s);
 

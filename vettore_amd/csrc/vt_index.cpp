@@ -43,6 +43,7 @@
 #include "host/vt_quantized.h"
 #include "host/vt_funnel.h"
 #include "host/vt_hybrid.h"
+#include "host/vt_maxsim.h"
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
 
@@ -60,6 +61,8 @@ const char *vt_strerror(int status) {
     case VT_ERR_PREFIX: return "invalid prefix dimensions";
     case VT_ERR_DIMS_POSITIVE: return "dimensions must be positive";
     case VT_ERR_POISONED: return "flat lock poisoned";
+    case VT_ERR_EMPTY_VECTORS: return "vectors must not be empty";
+    case VT_ERR_SCORE_OVERFLOW: return "score overflow";
     case VT_ERR_NOMEM: return "out of memory";
     case VT_ERR_DEVICE: return "device error";
     case VT_ERR_UNSUPPORTED: return "unsupported on device";
@@ -836,6 +839,35 @@ int vt_vector_top_k(int device, size_t count, const char *ids, const size_t *id_
   }
   if (first_error != VT_OK) return first_error;
   return hits_from_batch(ids, id_off, entries, out);
+  });
+}
+
+int vt_multi_vector_top_k(int device, size_t count, const char *ids, const size_t *id_off, const size_t *doc_vec_off,
+                          const float *values, const size_t *value_off, const float *query, const size_t *query_off,
+                          size_t nquery, int metric_code, size_t limit, vt_hits **out) {
+  return guarded([&]() -> int {
+  if (!out || (count && (!id_off || !doc_vec_off || !value_off)) || (nquery && !query_off)) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  std::vector<vt::Entry> entries;
+  VT_TRY(maxsim_top_k(device, count, ids, id_off, doc_vec_off, values, value_off, query, query_off, nquery, metric_code,
+                      limit, entries));
+  return hits_from_batch(ids, id_off, entries, out);
+  });
+}
+
+int vt_multi_vector_score(int device, const float *query, const size_t *query_off, size_t nquery, const float *doc,
+                          const size_t *doc_off, size_t ndoc, int metric_code, float *out) {
+  return guarded([&]() -> int {
+  if (!out || (nquery && !query_off) || (ndoc && !doc_off)) return VT_ERR_ARGUMENT;
+  // multi_vector.rs:40-63 score() is top_k's walk over one document
+  const size_t id_off[2] = {0, 0}, doc_vec_off[2] = {0, ndoc};
+  const size_t none[1] = {0};
+  std::vector<vt::Entry> entries;
+  VT_TRY(maxsim_top_k(device, 1, "", id_off, doc_vec_off, doc, ndoc ? doc_off : none, query, query_off, nquery,
+                      metric_code, 1, entries));
+  if (entries.size() != 1) return fail(VT_ERR_DEVICE, "MaxSim: the document's score did not come back");
+  *out = entries[0].raw;
+  return VT_OK;
   });
 }
 

@@ -158,6 +158,16 @@ __device__ __forceinline__ float chunk_sum(int op_rt, int order_rt, float p0, fl
   return comb<OP>(op_rt, e, dpp_xor1(e));
 }
 
+// The same four lane orders when ONE lane holds the whole chunk l0..l7 (MaxSim: one lane per vector pair).
+template <int OP, int ORDER>
+__device__ __forceinline__ float chunk_sum1(const float (&l)[8]) {
+  auto c = [](float a, float b) { return comb<OP>(0, a, b); };
+  if (ORDER == 1) return c(c(c(l[0], l[4]), c(l[2], l[6])), c(c(l[1], l[5]), c(l[3], l[7])));  // AVX
+  if (ORDER == 2) return c(c(c(c(l[0], l[1]), l[2]), l[3]), c(c(c(l[4], l[5]), l[6]), l[7]));  // SEQ
+  if (ORDER == 3) return c(c(c(l[0], l[2]), c(l[1], l[3])), c(c(l[4], l[6]), c(l[5], l[7])));  // SSE2
+  return c(c(c(l[0], l[1]), c(l[2], l[3])), c(c(l[4], l[5]), c(l[6], l[7])));                  // PAIR
+}
+
 // distances.rs:70-90 recover_metric_overflow (+ the f64 branch of l2(),
 // distances.rs:140-147), run by the one lane whose f32 result was non-finite.
 // The recovered value comes back BY VALUE -- NaN where there is none (a recovered value is finite by

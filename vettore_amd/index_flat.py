@@ -271,10 +271,49 @@ class FlatGpu:
                 spec.append((nifs.GEN_FUNNEL, cand, st[1]))
             else:
                 spec.append((nifs.GEN_QUANTIZED if name == "quantized" else nifs.GEN_SEARCH, cand, []))
-        if opts.get("rerank", "exact") != "exact":
-            return ("error", ("invalid_rerank", opts.get("rerank")))           # (multi-vector rerank: not on the flat path)
-        res = nifs.flat_hybrid_search(collection.index_state, q[1], spec, limit)
-        return res if res[0] != "ok" else ("ok", _hydrate(collection, res[1]))
+        rerank = opts.get("rerank", "exact")
+        if rerank == "exact":
+            res = nifs.flat_hybrid_search(collection.index_state, q[1], spec, limit)
+            return res if res[0] != "ok" else ("ok", _hydrate(collection, res[1]))
+        if not (isinstance(rerank, tuple) and len(rerank) in (2, 3) and rerank[0] == "multi_vector"
+                and (len(rerank) == 2 or isinstance(rerank[2], dict))):
+            return ("error", ("invalid_rerank", rerank))                       # collection.ex:646-647
+        return FlatGpu._multi_vector_rerank(collection, q[1], spec, rerank, limit)
+
+    @staticmethod
+    def _multi_vector_rerank(collection, query, spec, rerank, limit):
+        """hybrid_rerank {:multi_vector, qv[, opts]} (collection.ex:633-658): MaxSim over the candidates' stored vectors.
+        The candidate union comes first.  The exact rerank of a generator's candidates keeps ALL of them when its limit
+        is the candidate count, and reranking reorders a set without changing it: so the set a generator feeds the
+        rerank is exactly what the existing call returns with limit = candidates (flat_funnel_search,
+        flat_quantized_search, flat_search)."""
+        ropts = rerank[2] if len(rerank) == 3 else {}
+        bad = [k for k in ropts if k != "metric"]
+        if bad:
+            return ("error", ("unsupported_option", bad[0]))
+        metric = ropts.get("metric", collection.metric)
+        metric = {"euclidean": "l2", "dot": "inner_product", "dot_product": "inner_product"}.get(metric, metric)
+        if metric not in nifs.METRICS:
+            return ("error", "invalid_metric")
+        qv = collection._prepare_vectors(rerank[1])
+        if qv[0] != "ok":
+            return qv
+        seen, candidates = set(), []
+        for kind, cand, stages in spec:
+            if kind == nifs.GEN_FUNNEL:
+                res = nifs.flat_funnel_search(collection.index_state, query, stages, cand, cand)
+            elif kind == nifs.GEN_QUANTIZED:
+                res = nifs.flat_quantized_search(collection.index_state, query, cand, cand)
+            else:
+                res = nifs.flat_search(collection.index_state, query, cand)
+            if res[0] != "ok":
+                return res
+            for id_, _ in res[1]:
+                got = collection.get(id_)
+                if id_ not in seen and got[0] == "ok":
+                    seen.add(id_)
+                    candidates.append(got[1])
+        return collection._multi_vector_results(qv[1], candidates, metric, limit)
 
 
 def _valid_size(v):

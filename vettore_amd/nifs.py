@@ -385,6 +385,43 @@ def vector_top_k(vectors, query, metric_code: int, dimensions: int, limit: int):
     return ("ok", _take_hits(h)) if st == 0 else _err(st)
 
 
+def _vector_list(vectors) -> Tuple[np.ndarray, np.ndarray]:
+    """Vec<Vec<f32>>: ragged, every vector carries its own length."""
+    return _pack_ragged([_f32_list(v) for v in vectors], np.float32)
+
+
+def multi_vector_score(query_vectors, document_vectors, metric_code: int):
+    """nifs.rs:177-187: ("ok", score) or ("error", reason)."""
+    if not isinstance(metric_code, int) or not 0 <= metric_code <= 255:
+        raise TypeError("badarg: metric_code is a u8")
+    qv, qoff = _vector_list(query_vectors)
+    dv, doff = _vector_list(document_vectors)
+    out = C.c_float()
+    st = _lib.load().vt_multi_vector_score(DEVICE, _fp(qv), _szp(qoff), qoff.size - 1, _fp(dv), _szp(doff),
+                                           doff.size - 1, metric_code, C.byref(out))
+    return ("ok", float(out.value)) if st == 0 else _err(st)
+
+
+def multi_vector_top_k(documents, query_vectors, metric_code: int, limit: int):
+    """nifs.rs:188-198: documents are [(id, [[float]])]; ("ok", [(id, score)]) best first."""
+    if not isinstance(metric_code, int) or not 0 <= metric_code <= 255:
+        raise TypeError("badarg: metric_code is a u8")
+    if not isinstance(limit, int) or not 0 <= limit <= USIZE_MAX:
+        raise TypeError("badarg: limit is a usize")
+    ids, ioff = _pack_ids(i for i, _ in documents)
+    per_doc = [[_f32_list(v) for v in vecs] for _, vecs in documents]
+    doc_vec_off = np.zeros(len(per_doc) + 1, dtype=np.uintp)
+    if per_doc:
+        doc_vec_off[1:] = np.cumsum([len(v) for v in per_doc])
+    vals, voff = _pack_ragged([v for vecs in per_doc for v in vecs], np.float32)
+    qv, qoff = _vector_list(query_vectors)
+    h = C.c_void_p()
+    st = _lib.load().vt_multi_vector_top_k(DEVICE, len(documents), ids, _szp(ioff), _szp(doc_vec_off), _fp(vals),
+                                           _szp(voff), _fp(qv), _szp(qoff), qoff.size - 1, metric_code, limit,
+                                           C.byref(h))
+    return ("ok", _take_hits(h)) if st == 0 else _err(st)
+
+
 def binary_top_k(vectors, query, dimensions: int, limit: int):
     """nifs.rs:164-175."""
     ids, ioff = _pack_ids(i for i, _ in vectors)
