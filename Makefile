@@ -22,7 +22,7 @@ HIPFLAGS += -DVT_EXPERIMENTS -DVT_BATCH_TIMING_EXPERIMENTS -DVT_MULTI_TIMING_EXP
 CHECK_SCRATCH := @true
 endif
 
-DEVSRC  := vt_kernels vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_multi vt_prefix_multi vt_maxsim
+DEVSRC  := vt_kernels vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_multi vt_prefix_multi vt_maxsim vt_sketch
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -59,6 +59,11 @@ $(LIBDIR)/vt_maxsim.o: $(CSRC)/vt_maxsim.hip $(DEVHDR)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_maxsim.resources
 	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_maxsim.resources maxsim_kernel
+# K1q (the int8 sketch pass): its register ring must stay in registers
+$(LIBDIR)/vt_sketch.o: $(CSRC)/vt_sketch.hip $(DEVHDR)
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_sketch.resources
+	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_sketch.resources sketch_scan_kernel
 $(LIBDIR)/vt_batch_shadow.o: $(CSRC)/vt_batch_shadow.hip $(DEVHDR)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_batch_shadow.resources

@@ -443,6 +443,14 @@ typedef struct vt_profile {
   double shadow_build_ms;
   uint64_t shadow_patched_rows;      /* rows re-rounded in place after mutations */
   uint64_t sweep_queries;            /* plain searches of a batch served by K1p sweeps (their sweeps count as scan_launches) */
+  /* K1q: lone searches nominated from the int8 sketch (its passes count as scan_launches / scan_ms / scan_bytes too) */
+  uint64_t sketch_launches;          /* passes over the sketch */
+  double sketch_ms;
+  uint64_t sketch_bytes;             /* what the passes read: whole tiles of int8 rows and their metadata */
+  uint64_t sketch_candidates;        /* rows handed to the exact rescoring, summed over passes */
+  uint64_t sketch_fallbacks;         /* passes the bound could not certify (the search then scanned the f32 rows) */
+  uint64_t sketch_builds;            /* whole builds of the sketch */
+  uint64_t sketch_patched_rows;      /* rows re-quantised in place after mutations */
 } vt_profile;
 int vt_flat_set_profiling(vt_flat *index, int enabled);
 int vt_flat_get_profile(vt_flat *index, vt_profile *out, int reset);

@@ -55,6 +55,9 @@ class Profile(C.Structure):
         ("prefix_queries", C.c_uint64),
         ("nominate_shadow_launches", C.c_uint64), ("shadow_builds", C.c_uint64), ("shadow_build_ms", C.c_double),
         ("shadow_patched_rows", C.c_uint64), ("sweep_queries", C.c_uint64),
+        ("sketch_launches", C.c_uint64), ("sketch_ms", C.c_double), ("sketch_bytes", C.c_uint64),
+        ("sketch_candidates", C.c_uint64), ("sketch_fallbacks", C.c_uint64), ("sketch_builds", C.c_uint64),
+        ("sketch_patched_rows", C.c_uint64),
     ]
 
 

@@ -6,7 +6,7 @@
 namespace {
 
 // ---- what a reader needs up to date before it may run under the shared lock ----------
-enum : unsigned { NEED_RANKS = 1, NEED_STRICT_RANKS = 2, NEED_BITS = 4, NEED_NORMS = 8, NEED_NZBITS = 16 };
+enum : unsigned { NEED_RANKS = 1, NEED_STRICT_RANKS = 2, NEED_BITS = 4, NEED_NORMS = 8, NEED_NZBITS = 16, NEED_SKETCH = 32 };
 // Internal: only the true id order can decide (a tie at the boundary of a lazy search).
 constexpr int kEscalate = -101;
 
@@ -50,10 +50,28 @@ bool shadow_wanted(const Shard *ix) {
 size_t shadow_elems(const Shard *ix) { return vt::shadow_elems((uint32_t)std::max<size_t>(ix->cap, ix->n), ix->ld); }
 bool shadow_current(const Shard *ix) { return ix->shadow.current(shadow_elems(ix)); }
 
+// K1q (vt_sketch.hip): a lone cosine / inner-product search over rows of at least kSketchMinBytes reads the
+// int8 sketch -- a quarter of the bytes -- and the exact K1 rescores the rows it cannot rule out.  Only on strictly
+// ranked shards (lazy searches after trickle inserts keep K1), and only while each block's list of k' = max(2k, k + 16)
+// fits one wave buffer.  NEED_SKETCH asks for the column and means nothing where this says no.
+constexpr double kSketchMinBytes = 256.0 * (1 << 20);  // f32 rows below this: the pass's two extra launches cost more than it saves
+constexpr uint32_t kSketchCandCap = 4096;              // candidates the gathered K1 rescores at most (more: not certified)
+constexpr uint32_t kSketchRescoreBlocks = 32;
+inline uint32_t sketch_list_k(size_t limit) { return (uint32_t)std::max<size_t>(2 * limit, limit + 16); }
+bool sketch_metric(int metric) { return metric == VT_COSINE || metric == VT_INNER_PRODUCT || metric == VT_NEG_INNER_PRODUCT; }
+bool sketch_wanted(const Shard *ix, size_t limit) {
+  if (!vt::env::on(vt::env::SKETCH) || ix->sketch.refused || !sketch_metric(ix->metric) || ix->single_nominate) return false;
+  if (!ix->ranks_clean || ix->n == 0 || ix->dim <= 0 || (uint32_t)ix->dim > vt::kSketchMaxDim) return false;
+  if (limit == 0 || sketch_list_k(limit) > (size_t)vt::kMaxFusedK || vt::sketch_scan_lds_bytes((uint32_t)ix->dim, sketch_list_k(limit)) == 0)
+    return false;
+  return vt::env::on(vt::env::FORCE_SKETCH) || (double)ix->n * ix->ld * 4.0 >= kSketchMinBytes;
+}
+size_t sketch_elems(const Shard *ix) { return vt::sketch_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
+
 // The derived columns a reader with `need` / `limit` wants current, as the elements each must hold (0: not wanted).
 // shard_stale and shard_prepare both go by this one answer.  (A shard with rows.)
 struct ColumnsWanted {
-  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0;
+  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0;
 };
 ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   ColumnsWanted w;
@@ -63,6 +81,7 @@ ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   if ((need & NEED_NZBITS) && pattern_search_applies(ix, limit)) w.nz_bits = bwords;
   if (need & NEED_NORMS) w.norms = rows;
   if ((need & NEED_NORMS) && shadow_wanted(ix)) w.shadow = shadow_elems(ix);
+  if ((need & NEED_SKETCH) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
   return w;
 }
 
@@ -75,12 +94,14 @@ bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
   }
   const ColumnsWanted w = columns_wanted(ix, need, limit);
   return (w.bits && !ix->bits.current(w.bits)) || (w.nz_bits && !ix->nz_bits.current(w.nz_bits)) ||
-         (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow));
+         (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow)) ||
+         (w.sketch && !ix->sketch.current(w.sketch));
 }
 
 int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords);
 int index_ensure_norms(Shard *ix, size_t rows);
 int index_ensure_shadow(Shard *ix, size_t elems);
+int index_ensure_sketch(Shard *ix, size_t bytes);
 
 // Brings the derived columns a reader needs up to date (exclusive access; primary context).
 int shard_prepare(Shard *ix, unsigned need, size_t limit) {
@@ -94,6 +115,7 @@ int shard_prepare(Shard *ix, unsigned need, size_t limit) {
   if (w.nz_bits) VT_TRY(index_ensure_bits(ix, true, w.nz_bits));
   if (w.norms) VT_TRY(index_ensure_norms(ix, w.norms));
   if (w.shadow) VT_TRY(index_ensure_shadow(ix, w.shadow));
+  if (w.sketch) VT_TRY(index_ensure_sketch(ix, w.sketch));
   return VT_OK;
 }
 
@@ -107,12 +129,145 @@ bool single_nominate_applies(const Shard *ix, size_t limit) {
          shadow_wanted(ix) && !shard_stale(ix, NEED_NORMS, limit);
 }
 
+// K1q, its certification and the gathered K1 on the candidates, one host wait.  *done: the hits in *out
+// are the exact top `limit`; otherwise the caller scans the f32 rows -- the bound could not certify (counted), or it
+// declined before any launch because a dot of these rows could reach the f32 overflow K1 must see for itself.
+int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
+  *done = false;
+  const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d), nch = ld8 / 16;
+  // the query in two int8 levels: q = t1 Q1 + t2 Q2 + eta, with ||q|| and ||eta|| from f64 sums rounded up
+  float m1 = 0.0f;
+  double qq = 0.0;
+  for (uint32_t i = 0; i < d; ++i) {
+    m1 = std::max(m1, std::fabs(query[i]));
+    qq += (double)query[i] * (double)query[i];
+  }
+  const double up = 1.0 + 0x1p-30;
+  const double qn = std::sqrt(qq) * up;
+  if (!(qn * ix->sketch_max_norm * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
+  const size_t total = (size_t)ld + 2 * (size_t)ld8 / 4;
+  VT_TRY(c.dQ.ensure(total));
+  VT_TRY(c.hQ.ensure(total));
+  std::memcpy(c.hQ.p, query, (size_t)d * sizeof(float));
+  for (uint32_t i = d; i < ld; ++i) c.hQ.p[i] = 0.0f;
+  int8_t *q1 = reinterpret_cast<int8_t *>(c.hQ.p + ld), *q2 = q1 + ld8;
+  std::memset(q1, 0, 2 * (size_t)ld8);
+  float t1 = m1 / 127.0f, t2 = 0.0f;
+  if (!(t1 > 0.0f) || !std::isfinite(127.0f / m1)) t1 = 0.0f;
+  std::vector<double> r(d);
+  double m2 = 0.0;
+  for (uint32_t i = 0; i < d; ++i) {
+    int v = 0;
+    if (t1 > 0.0f) v = std::max(-127, std::min(127, (int)std::nearbyint((double)query[i] / (double)t1)));
+    q1[i] = (int8_t)v;
+    r[i] = (double)query[i] - (double)t1 * v;  // exact in f64
+    m2 = std::max(m2, std::fabs(r[i]));
+  }
+  t2 = (float)(m2 / 127.0);
+  if (!(t2 > 0.0f) || !std::isfinite(127.0 / (double)t2)) t2 = 0.0f;
+  double ee = 0.0;
+  for (uint32_t i = 0; i < d; ++i) {
+    int v = 0;
+    if (t2 > 0.0f) v = std::max(-127, std::min(127, (int)std::nearbyint(r[i] / (double)t2)));
+    q2[i] = (int8_t)v;
+    const double e = r[i] - (double)t2 * v;
+    ee += e * e;
+  }
+  c.qbits_kind = 0;
+  c.qsrc = c.dQ.p;
+  VT_HIP(hipMemcpyAsync(c.dQ.p, c.hQ.p, total * sizeof(float), hipMemcpyHostToDevice, c.stream));
+
+  const uint32_t kp = sketch_list_k(limit), k = (uint32_t)limit;
+  const uint32_t blocks = (uint32_t)c.num_cus * (kp <= (uint32_t)vt::kSmallK ? 4u : 2u);
+  VT_TRY(c.dSkKeys.ensure((size_t)blocks * kp));
+  VT_TRY(c.dSkPay.ensure((size_t)blocks * kp));
+  VT_TRY(c.dSkRows.ensure(kSketchCandCap));
+  VT_TRY(c.dSkCount.ensure(1));
+  VT_TRY(c.hSkInfo.ensure(4));
+  VT_TRY(c.dPartKeys.ensure((size_t)kSketchRescoreBlocks * k));
+  VT_TRY(c.dPartPay.ensure((size_t)kSketchRescoreBlocks * k));
+  uint32_t *info = c.hSkInfo.mapped();
+  if (!info) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch status)");
+  vt::SketchScanArgs a{};
+  a.img = ix->sketch.buf.p;
+  a.id_rank = ix->dRank.p;
+  a.qimg = reinterpret_cast<const int8_t *>(c.dQ.p + ld);
+  a.n = ix->n;
+  a.d = d;
+  a.nch = nch;
+  a.metric = ix->metric;
+  a.t1 = t1;
+  a.t2 = t2;
+  a.qn = qn;
+  a.eta = std::sqrt(ee) * up;
+  a.kerr = 8.0 * d * 0x1p-24;  // K1's summation error per unit of ||q|| ||x_r|| (DESIGN_APPENDIX A.5)
+  a.k = kp;
+  a.part_keys = c.dSkKeys.p;
+  a.part_pay = c.dSkPay.p;
+  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_HIP(vt::launch_sketch_scan(a, blocks, c.stream));
+  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_HIP(vt::launch_sketch_certify(c.dSkKeys.p, c.dSkPay.p, blocks, kp, k, kSketchCandCap, c.dSkRows.p, c.dSkCount.p, info,
+                                   c.stream));
+  // the candidates through K1 itself (GENERAL, the count read on the device), then its select into the pinned block
+  vt::ScanArgs sa{};
+  sa.X = ix->dX;
+  sa.stride = ld;
+  sa.q = c.qsrc;
+  sa.id_rank = ix->dRank.p;
+  sa.gather = c.dSkRows.p;
+  sa.gather_stride = 1;
+  sa.n = kSketchCandCap;
+  sa.d = d;
+  sa.metric = ix->metric;
+  sa.order = ix->order;
+  sa.k = k;
+  sa.part_keys = c.dPartKeys.p;
+  sa.part_pay = c.dPartPay.p;
+  sa.status = c.dStatus.p;
+  sa.batch_counts = c.dSkCount.p;
+  sa.batch_cap = kSketchCandCap;
+  VT_HIP(vt::launch_scan_batch(sa, kSketchRescoreBlocks, 1, c.stream));
+  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, kSketchRescoreBlocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
+                           c.dSelKeys.p, c.dSelPay.p, c.stream));
+  VT_HIP(hipStreamSynchronize(c.stream));
+  const bool certified = c.hSkInfo.p[0] == 1u && c.hRes.p->status == 0;
+  if (c.profiling) {
+    float ms = 0.f;
+    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+    const uint64_t bytes = (uint64_t)vt::sketch_bytes(ix->n, d);
+    c.prof.sketch_launches += 1;
+    c.prof.sketch_ms += ms;
+    c.prof.sketch_bytes += bytes;
+    c.prof.sketch_candidates += c.hSkInfo.p[1];
+    c.prof.scan_launches += 1;
+    c.prof.scan_ms += ms;
+    c.prof.scan_rows += ix->n;
+    c.prof.scan_bytes += bytes;
+  }
+  if (!certified) {
+    c.prof.sketch_fallbacks += 1;
+    return VT_OK;
+  }
+  std::vector<vt::Entry> entries(c.hRes.p->e, c.hRes.p->e + c.hRes.p->count);
+  VT_TRY(make_hits(ix, entries, out));
+  *done = true;
+  return VT_OK;
+}
+
 // flat.rs:96-124 on a shard whose rank column shard_prepare has brought up to date --
 // strictly (ranks_clean) or lazily (newcomers share kUnranked).  Read-only on the shard.
-int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, vt_hits **out) {
+// `lone`: a search on its own (flat_search), which takes K1q when the sketch is current; the single searches a batch
+// leaves over do not.
+int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, vt_hits **out, bool lone = false) {
   if (limit == 0) return empty_hits(out);
   VT_TRY(validate_vector(query, n, ix->dim));
   if (ix->n == 0) return empty_hits(out);
+  if (lone && sketch_wanted(ix, limit) && ix->sketch.current(sketch_elems(ix))) {
+    bool done = false;
+    VT_TRY(sketch_search(ix, c, query, limit, &done, out));
+    if (done) return VT_OK;
+  }
   if (single_nominate_applies(ix, limit)) {
     std::vector<char> done(1, 0);
     vt_hits *one = nullptr;
@@ -172,11 +327,12 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
 // The same for a caller that owns the shard outright (a shard worker, or any caller under
 // the exclusive lock): prepare, run on the primary context, settle a boundary tie.
 int search_owner(Shard *ix, const float *query, size_t n, size_t limit, vt_hits **out) {
-  if (shard_stale(ix, NEED_RANKS | NEED_NZBITS, limit)) VT_TRY(shard_prepare(ix, NEED_RANKS | NEED_NZBITS, limit));
-  int st = search_ready(ix, ix->ctx, query, n, limit, out);
+  const unsigned need = NEED_RANKS | NEED_NZBITS | NEED_SKETCH;
+  if (shard_stale(ix, need, limit)) VT_TRY(shard_prepare(ix, need, limit));
+  int st = search_ready(ix, ix->ctx, query, n, limit, out, true);
   if (st == kEscalate) {
     VT_TRY(shard_prepare(ix, NEED_STRICT_RANKS, limit));
-    st = search_ready(ix, ix->ctx, query, n, limit, out);
+    st = search_ready(ix, ix->ctx, query, n, limit, out, true);
   }
   return st;
 }
@@ -605,6 +761,62 @@ int index_ensure_shadow(Shard *ix, size_t elems) {
     c.prof.shadow_builds += 1;
     c.prof.shadow_build_ms += ms;
   }
+  col.mark_current();
+  return VT_OK;
+}
+
+// The int8 sketch brought up to date (exclusive access; primary context), on the shadow's terms: the rows mutated since
+// its last use are re-quantised in place; a first use, a slab that outgrew it or more than kMaxDerivedDirty mutations
+// rebuild it (one pass over the rows); without room for it -- a quarter of the card must stay free -- it is refused and
+// lone searches keep scanning the f32 rows.  The bound on every row's norm comes back with it (the overflow guard).
+int index_ensure_sketch(Shard *ix, size_t bytes) {
+  Ctx &c = ix->ctx;
+  DerivedColumn<unsigned char> &col = ix->sketch;
+  if (col.current(bytes)) return VT_OK;
+  const uint32_t d = (uint32_t)ix->dim;
+  const size_t tile_bytes = vt::sketch_bytes(vt::kSketchTileRows, d);
+  VT_TRY(c.dBNorm.ensure(1));
+  unsigned long long bits = 0;
+  if (col.patchable(bytes)) {
+    uint32_t count = 0;
+    VT_TRY(upload_row_list(ix, col.dirty, &count));
+    std::memcpy(&bits, &ix->sketch_max_norm, sizeof(double));
+    VT_HIP(hipMemcpyAsync(c.dBNorm.p, &bits, sizeof(bits), hipMemcpyHostToDevice, c.stream));
+    const uint32_t rows_img = (uint32_t)(col.buf.count / tile_bytes * vt::kSketchTileRows);
+    VT_HIP(vt::launch_sketch_rows(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    c.prof.sketch_patched_rows += count;
+  } else {
+    col.forget();
+    if (col.buf.count < bytes) {
+      col.buf.release();
+      size_t free_b = 0, total_b = 0;
+      VT_HIP(hipMemGetInfo(&free_b, &total_b));
+      bool refused = free_b < bytes || free_b - bytes < total_b / 4;
+      // (geometric head room, as the shadow keeps: a corpus that arrives in appends would otherwise rebuild at every growth)
+      size_t want = bytes;
+      if (!refused) {
+        const size_t roomy = (bytes + bytes / 4 + tile_bytes - 1) / tile_bytes * tile_bytes;
+        if (free_b >= roomy && free_b - roomy >= total_b / 4) want = roomy;
+        refused = col.buf.ensure(want) != VT_OK;
+      }
+#ifdef VT_TEST_HOOKS
+      // (libvettore_hip_hooks.so only: the allocation "fails", tests/test_gpu_sketch.py checks what follows)
+      refused = refused || vt::env::on(vt::env::TEST_REFUSE_SKETCH);
+#endif
+      if (refused) {
+        col.refuse();
+        return VT_OK;
+      }
+    }
+    const uint32_t rows_img = (uint32_t)(bytes / tile_bytes * vt::kSketchTileRows);
+    VT_HIP(hipMemsetAsync(c.dBNorm.p, 0, sizeof(unsigned long long), c.stream));
+    VT_HIP(vt::launch_sketch_build(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    c.prof.sketch_builds += 1;
+  }
+  VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
+  // current from here on, for readers on other streams too: the build has finished before the exclusive lock can drop
+  VT_HIP(hipStreamSynchronize(c.stream));
+  std::memcpy(&ix->sketch_max_norm, &bits, sizeof(double));
   col.mark_current();
   return VT_OK;
 }

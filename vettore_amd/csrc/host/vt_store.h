@@ -8,12 +8,18 @@ namespace {
 // ------------------------------------------------------------------ index ops
 int index_reserve_once(Shard *ix, uint32_t want_rows);
 // The rows come first: when the slab cannot grow and the shard keeps a bf16 shadow (an accelerator
-// of the batch pass, half the slab's size), the shadow goes and the growth is tried once more.
+// of the batch pass, half the slab's size), the shadow goes and the growth is tried once more; then
+// the int8 sketch of lone searches.
 int index_reserve(Shard *ix, uint32_t want_rows) {
   int st = index_reserve_once(ix, want_rows);
   if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->shadow.buf.p) {
     (void)hipStreamSynchronize(ix->ctx.stream);
     ix->shadow.refuse();
+    st = index_reserve_once(ix, want_rows);
+  }
+  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch.buf.p) {  // (then the int8 sketch, a quarter of it)
+    (void)hipStreamSynchronize(ix->ctx.stream);
+    ix->sketch.refuse();
     st = index_reserve_once(ix, want_rows);
   }
   return st;

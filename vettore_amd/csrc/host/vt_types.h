@@ -47,6 +47,12 @@ struct Ctx {
   DevBuf<vt::Entry> dBOut;
   DevBuf<unsigned long long> dBNorm;
   DevBuf<unsigned char> dBQimage;  // K2b: the batch's queries in bf16, fragment order
+  // K1q (vt_search.h, sketch_search): the pass's block lists, the certified candidate rows and their count, and
+  // {certified, candidates, Kt, 0} written by the certify kernel through the host mapping
+  DevBuf<uint64_t> dSkKeys;
+  DevBuf<vt::Payload> dSkPay;
+  DevBuf<uint32_t> dSkRows, dSkCount;
+  PinnedBuf<uint32_t> hSkInfo;
   // grouped quantized searches: one stage-1 block per query
   DevBuf<ResultBlock> dStageB;
   PinnedBuf<float> hBQ, hBTau;
@@ -138,7 +144,7 @@ struct Ctx {
 constexpr size_t kMaxDerivedDirty = 65536;  // more mutated rows than this: rebuild instead of patching
 
 // A per-row column computed from a shard's rows and kept across searches (Shard: sign bits, non-zero bits, squared
-// norms, bf16 shadow), so that a search after a mutation need not pass over all the rows again.  One policy for all:
+// norms, bf16 shadow, int8 sketch), so that a search after a mutation need not pass over all the rows again.  One policy for all:
 //  - a mutated row joins `dirty` while the column is valid; past kMaxDerivedDirty of them the column is forgotten, and
 //    the next reader rebuilds it from scratch instead of patching row by row;
 //  - a reader that wants `elems` elements may use it under the shared lock only while it is current(elems); otherwise
@@ -258,6 +264,12 @@ struct Shard {
   // the room back (index_reserve), it is refused and batches stream the f32 rows.
   DerivedColumn<uint16_t> shadow;
   int shadow_mode = default_shadow();  // VT_SHADOW_*
+  // K1q: the rows once more in int8 with a per-row scale and error bounds (vt_device.h, SketchScanArgs) -- a quarter of
+  // the bytes a lone cosine / dot search reads (vt_search.h, sketch_search).  Optional, like the shadow: refused when the
+  // card has no room, given back when the slab needs it (index_reserve) and when the index is emptied.
+  // sketch_max_norm: an upper bound of every row's norm (a value only while the column is valid; patches only raise it).
+  DerivedColumn<unsigned char> sketch;
+  double sketch_max_norm = 0.0;
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
   // ids
@@ -318,6 +330,7 @@ struct Shard {
       nz_bits.touch(rows[i]);
       norms.touch(rows[i]);
       shadow.touch(rows[i]);
+      sketch.touch(rows[i]);
     }
   }
   void forget_derived() {
@@ -325,6 +338,7 @@ struct Shard {
     nz_bits.forget();
     norms.forget();
     shadow.forget();
+    sketch.forget();
   }
   // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
   // shadow gives its room back.
@@ -334,6 +348,8 @@ struct Shard {
     norms.reset();
     shadow.reset();
     shadow.buf.release();
+    sketch.reset();
+    sketch.buf.release();
   }
 };
 

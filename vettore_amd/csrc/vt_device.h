@@ -558,4 +558,51 @@ hipError_t launch_maxsim_norms(const float *X, size_t stride, uint32_t n, uint32
 // normalize_l2 (distances.rs:350-361) on rows: out = (x / sqrt(f64 sum x^2)) as f32.
 hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *out, hipStream_t s);
 
+// ---- K1q (vt_sketch.hip): a lone dot-family search over an int8 sketch of the rows -----------------------------------
+// Row r is kept as X_r = round(x_r / s_r) in int8 with s_r = max_i |x_ri| / 127, beside two f32 bounds rounded up:
+// rho_r >= ||x_r - s_r X_r|| (the residual, summed in f64) and nu_r >= s_r ||X_r||.  Layout, per tile of 64 rows: the
+// rows' 16-byte chunk c is one 1-KiB run ((tile * (nch + 1) + c) * 1024 + (r % 64) * 16), c < nch = ld8 / 16, and the
+// tile ends with one more run of {s, rho, nu, 0} per row -- a wave streams a tile, metadata included, in whole 1-KiB loads.
+constexpr uint32_t kSketchTileRows = 64;
+constexpr uint32_t kSketchMaxDim = 32768;  // (the query image sits in LDS; and d * 127^2 stays far below 2^31)
+__host__ __device__ inline uint32_t sketch_ld8(uint32_t d) { return (d + 127) / 128 * 128; }
+__host__ __device__ inline size_t sketch_offset(uint32_t row, uint32_t chunk, uint32_t nch) {
+  return ((size_t)(row / kSketchTileRows) * (nch + 1) + chunk) * 1024 + (size_t)(row % kSketchTileRows) * 16;
+}
+// bytes of a sketch covering `rows` rows (whole tiles)
+inline size_t sketch_bytes(uint32_t rows, uint32_t d) {
+  const size_t tiles = ((size_t)rows + kSketchTileRows - 1) / kSketchTileRows;
+  return tiles * ((size_t)sketch_ld8(d) / 16 + 1) * 1024;
+}
+// Rows [0, rows_img) of the image (rows at or past n_src are zero rows); *max_norm (the bits of a non-negative f64,
+// atomicMax'ed) is raised to the largest nu + rho, an upper bound of every row's norm.
+hipError_t launch_sketch_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                               unsigned long long *max_norm, hipStream_t s);
+// the same for the rows of a list
+hipError_t launch_sketch_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                              void *img, unsigned long long *max_norm, hipStream_t s);
+
+struct SketchScanArgs {
+  const void *img;
+  const uint32_t *id_rank;
+  const int8_t *qimg;       // [2][ld8]: the query's two int8 levels, q ~ t1 Q1 + t2 Q2
+  uint32_t n, d, nch;       // nch = ld8 / 16
+  int metric;               // VT_COSINE / VT_INNER_PRODUCT / VT_NEG_INNER_PRODUCT
+  float t1, t2;
+  double qn;                // >= ||q||
+  double eta;               // >= ||q - t1 Q1 - t2 Q2||
+  double kerr;              // K1's summation error per unit of ||q|| ||x_r||
+  uint32_t k;               // entries per block list (k' of DESIGN 4.10)
+  uint64_t *part_keys;      // [blocks][k]: orderable(key(hi_r)) << 32 | id rank
+  Payload *part_pay;        // [blocks][k]: row, key(lo_r) as a float
+};
+size_t sketch_scan_lds_bytes(uint32_t d, uint32_t k);  // 0: not supported
+hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStream_t s);
+
+// One block over the lists of launch_sketch_scan: Kt = the k-th smallest key(lo) retained; every retained row whose
+// key(hi) <= Kt goes to rows[0..cap); certified iff that fits and every full list's largest key(hi) is > Kt.  *count
+// receives the candidates when certified, else 0; info = {certified, candidates, Kt bits, 0} (host-mapped).
+hipError_t launch_sketch_certify(const uint64_t *keys, const Payload *pay, uint32_t lists, uint32_t kp, uint32_t k, uint32_t cap,
+                                 uint32_t *rows, uint32_t *count, uint32_t *info, hipStream_t s);
+
 }  // namespace vt

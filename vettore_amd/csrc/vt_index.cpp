@@ -1007,6 +1007,13 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.shadow_build_ms += p.shadow_build_ms;
       t.shadow_patched_rows += p.shadow_patched_rows;
       t.sweep_queries += p.sweep_queries;
+      t.sketch_launches += p.sketch_launches;
+      t.sketch_ms += p.sketch_ms;
+      t.sketch_bytes += p.sketch_bytes;
+      t.sketch_candidates += p.sketch_candidates;
+      t.sketch_fallbacks += p.sketch_fallbacks;
+      t.sketch_builds += p.sketch_builds;
+      t.sketch_patched_rows += p.sketch_patched_rows;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};
