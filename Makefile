@@ -59,11 +59,13 @@ $(LIBDIR)/vt_maxsim.o: $(CSRC)/vt_maxsim.hip $(DEVHDR)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_maxsim.resources
 	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_maxsim.resources maxsim_kernel
-# K1q (the int8 sketch pass): its register ring must stay in registers
+# K1q (the int8 sketch pass): its register ring must stay in registers; its tail (one block behind every pass) likewise
+# carries no scratch segment
 $(LIBDIR)/vt_sketch.o: $(CSRC)/vt_sketch.hip $(DEVHDR)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_sketch.resources
 	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_sketch.resources sketch_scan_kernel
+	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_sketch.resources sketch_tail_kernel
 $(LIBDIR)/vt_batch_shadow.o: $(CSRC)/vt_batch_shadow.hip $(DEVHDR)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_batch_shadow.resources

@@ -451,6 +451,7 @@ typedef struct vt_profile {
   uint64_t sketch_fallbacks;         /* passes the bound could not certify (the search then scanned the f32 rows) */
   uint64_t sketch_builds;            /* whole builds of the sketch */
   uint64_t sketch_patched_rows;      /* rows re-quantised in place after mutations */
+  uint64_t sketch_tail_rescored;     /* certified passes whose candidates the certifying block rescored itself (no gathered K1) */
 } vt_profile;
 int vt_flat_set_profiling(vt_flat *index, int enabled);
 int vt_flat_get_profile(vt_flat *index, vt_profile *out, int reset);

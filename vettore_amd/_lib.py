@@ -58,6 +58,7 @@ class Profile(C.Structure):
         ("sketch_launches", C.c_uint64), ("sketch_ms", C.c_double), ("sketch_bytes", C.c_uint64),
         ("sketch_candidates", C.c_uint64), ("sketch_fallbacks", C.c_uint64), ("sketch_builds", C.c_uint64),
         ("sketch_patched_rows", C.c_uint64),
+        ("sketch_tail_rescored", C.c_uint64),
     ]
 
 

@@ -54,7 +54,9 @@ bool shadow_current(const Shard *ix) { return ix->shadow.current(shadow_elems(ix
 // int8 sketch -- a quarter of the bytes -- and the exact K1 rescores the rows it cannot rule out.  Only on strictly
 // ranked shards (lazy searches after trickle inserts keep K1), and only while each block's list of k' = max(2k, k + 16)
 // fits one wave buffer.  NEED_SKETCH asks for the column and means nothing where this says no.
-constexpr double kSketchMinBytes = 256.0 * (1 << 20);  // f32 rows below this: the pass's two extra launches cost more than it saves
+// f32 rows below this take K1.  (With the pass's tail in one kernel the two paths meet near 130 MB of f32 rows, DESIGN 5;
+// the cut stays where the suite's launch counters on mid-size corpora were written against it.)
+constexpr double kSketchMinBytes = 256.0 * (1 << 20);
 constexpr uint32_t kSketchCandCap = 4096;              // candidates the gathered K1 rescores at most (more: not certified)
 constexpr uint32_t kSketchRescoreBlocks = 32;
 inline uint32_t sketch_list_k(size_t limit) { return (uint32_t)std::max<size_t>(2 * limit, limit + 16); }
@@ -129,13 +131,56 @@ bool single_nominate_applies(const Shard *ix, size_t limit) {
          shadow_wanted(ix) && !shard_stale(ix, NEED_NORMS, limit);
 }
 
-// K1q, its certification and the gathered K1 on the candidates, one host wait.  *done: the hits in *out
-// are the exact top `limit`; otherwise the caller scans the f32 rows -- the bound could not certify (counted), or it
-// declined before any launch because a dot of these rows could reach the f32 overflow K1 must see for itself.
+// The query in two int8 levels behind its f32 copy in c.hQ: q = t1 Q1 + t2 Q2 + eta.  The integers are chosen with
+// a reciprocal; the residuals r = q - t1 Q1 and eta = r - t2 Q2 are then formed from the chosen integers in f64
+// (t Q has at most 31 significant bits: exact), so the bound holds for any |Q| <= 127 and only its tightness depends on
+// the rounding.  *ee = sum eta_i^2.
+void sketch_query_image(Ctx &c, const float *query, uint32_t d, uint32_t ld, uint32_t ld8, float m1, float *t1_out, float *t2_out,
+                        double *ee_out) {
+  float *hq = c.hQ.p;
+  std::memcpy(hq, query, (size_t)d * sizeof(float));
+  for (uint32_t i = d; i < ld; ++i) hq[i] = 0.0f;
+  int8_t *q1 = reinterpret_cast<int8_t *>(hq + ld), *q2 = q1 + ld8;
+  std::memset(q1 + d, 0, ld8 - d);
+  std::memset(q2 + d, 0, ld8 - d);
+  float t1 = m1 / 127.0f, t2 = 0.0f;
+  if (!(t1 > 0.0f) || !std::isfinite(127.0f / m1)) t1 = 0.0f;
+  double *r = c.hSkResid.data();
+  constexpr double kRound = 0x1.8p52;  // (v + kRound) - kRound: v to the nearest integer, |v| < 2^51, no library call
+  const double t1d = (double)t1, inv1 = t1 > 0.0f ? 1.0 / t1d : 0.0;
+  double m2 = 0.0;
+  for (uint32_t i = 0; i < d; ++i) {
+    const double x = (double)query[i];
+    const int v = (int)std::max(-127.0, std::min(127.0, (x * inv1 + kRound) - kRound));
+    q1[i] = (int8_t)v;
+    r[i] = x - t1d * v;
+    m2 = std::max(m2, std::fabs(r[i]));
+  }
+  t2 = (float)(m2 / 127.0);
+  if (!(t2 > 0.0f) || !std::isfinite(127.0 / (double)t2)) t2 = 0.0f;
+  const double t2d = (double)t2, inv2 = t2 > 0.0f ? 1.0 / t2d : 0.0;
+  double ee = 0.0;
+  for (uint32_t i = 0; i < d; ++i) {
+    const int v = (int)std::max(-127.0, std::min(127.0, (r[i] * inv2 + kRound) - kRound));
+    q2[i] = (int8_t)v;
+    const double e = r[i] - t2d * v;
+    ee += e * e;
+  }
+  *t1_out = t1;
+  *t2_out = t2;
+  *ee_out = ee;
+}
+
+// K1q and its tail, one host wait: the pass, then one block that certifies and -- the usual case, a few
+// dozen candidates -- rescores them with K1's arithmetic and fills the pinned result block.  A candidate list too long
+// for that block (up to kSketchCandCap) goes through the gathered K1 and its select after a second wait.  *done: the
+// hits in *out are the exact top `limit`; otherwise the caller scans the f32 rows -- the bound could not certify
+// (counted), or it declined before any launch because a dot of these rows could reach the f32 overflow K1 must see for
+// itself.
 int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
   *done = false;
   const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d), nch = ld8 / 16;
-  // the query in two int8 levels: q = t1 Q1 + t2 Q2 + eta, with ||q|| and ||eta|| from f64 sums rounded up
+  // ||q|| and ||eta|| from f64 sums rounded up
   float m1 = 0.0f;
   double qq = 0.0;
   for (uint32_t i = 0; i < d; ++i) {
@@ -148,31 +193,10 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   const size_t total = (size_t)ld + 2 * (size_t)ld8 / 4;
   VT_TRY(c.dQ.ensure(total));
   VT_TRY(c.hQ.ensure(total));
-  std::memcpy(c.hQ.p, query, (size_t)d * sizeof(float));
-  for (uint32_t i = d; i < ld; ++i) c.hQ.p[i] = 0.0f;
-  int8_t *q1 = reinterpret_cast<int8_t *>(c.hQ.p + ld), *q2 = q1 + ld8;
-  std::memset(q1, 0, 2 * (size_t)ld8);
-  float t1 = m1 / 127.0f, t2 = 0.0f;
-  if (!(t1 > 0.0f) || !std::isfinite(127.0f / m1)) t1 = 0.0f;
-  std::vector<double> r(d);
-  double m2 = 0.0;
-  for (uint32_t i = 0; i < d; ++i) {
-    int v = 0;
-    if (t1 > 0.0f) v = std::max(-127, std::min(127, (int)std::nearbyint((double)query[i] / (double)t1)));
-    q1[i] = (int8_t)v;
-    r[i] = (double)query[i] - (double)t1 * v;  // exact in f64
-    m2 = std::max(m2, std::fabs(r[i]));
-  }
-  t2 = (float)(m2 / 127.0);
-  if (!(t2 > 0.0f) || !std::isfinite(127.0 / (double)t2)) t2 = 0.0f;
+  if (c.hSkResid.size() < d) c.hSkResid.resize(d);
+  float t1 = 0.0f, t2 = 0.0f;
   double ee = 0.0;
-  for (uint32_t i = 0; i < d; ++i) {
-    int v = 0;
-    if (t2 > 0.0f) v = std::max(-127, std::min(127, (int)std::nearbyint(r[i] / (double)t2)));
-    q2[i] = (int8_t)v;
-    const double e = r[i] - (double)t2 * v;
-    ee += e * e;
-  }
+  sketch_query_image(c, query, d, ld, ld8, m1, &t1, &t2, &ee);
   c.qbits_kind = 0;
   c.qsrc = c.dQ.p;
   VT_HIP(hipMemcpyAsync(c.dQ.p, c.hQ.p, total * sizeof(float), hipMemcpyHostToDevice, c.stream));
@@ -184,8 +208,6 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   VT_TRY(c.dSkRows.ensure(kSketchCandCap));
   VT_TRY(c.dSkCount.ensure(1));
   VT_TRY(c.hSkInfo.ensure(4));
-  VT_TRY(c.dPartKeys.ensure((size_t)kSketchRescoreBlocks * k));
-  VT_TRY(c.dPartPay.ensure((size_t)kSketchRescoreBlocks * k));
   uint32_t *info = c.hSkInfo.mapped();
   if (!info) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch status)");
   vt::SketchScanArgs a{};
@@ -207,31 +229,54 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
   VT_HIP(vt::launch_sketch_scan(a, blocks, c.stream));
   if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
-  VT_HIP(vt::launch_sketch_certify(c.dSkKeys.p, c.dSkPay.p, blocks, kp, k, kSketchCandCap, c.dSkRows.p, c.dSkCount.p, info,
-                                   c.stream));
-  // the candidates through K1 itself (GENERAL, the count read on the device), then its select into the pinned block
-  vt::ScanArgs sa{};
-  sa.X = ix->dX;
-  sa.stride = ld;
-  sa.q = c.qsrc;
-  sa.id_rank = ix->dRank.p;
-  sa.gather = c.dSkRows.p;
-  sa.gather_stride = 1;
-  sa.n = kSketchCandCap;
-  sa.d = d;
-  sa.metric = ix->metric;
-  sa.order = ix->order;
-  sa.k = k;
-  sa.part_keys = c.dPartKeys.p;
-  sa.part_pay = c.dPartPay.p;
-  sa.status = c.dStatus.p;
-  sa.batch_counts = c.dSkCount.p;
-  sa.batch_cap = kSketchCandCap;
-  VT_HIP(vt::launch_scan_batch(sa, kSketchRescoreBlocks, 1, c.stream));
-  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, kSketchRescoreBlocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
-                           c.dSelKeys.p, c.dSelPay.p, c.stream));
+  vt::SketchTailArgs ta{};
+  ta.keys = c.dSkKeys.p;
+  ta.pay = c.dSkPay.p;
+  ta.lists = blocks;
+  ta.kp = kp;
+  ta.k = k;
+  ta.cap = kSketchCandCap;
+  ta.rows = c.dSkRows.p;
+  ta.count = c.dSkCount.p;
+  ta.info = info;
+  ta.X = ix->dX;
+  ta.stride = ld;
+  ta.q = c.qsrc;
+  ta.id_rank = ix->dRank.p;
+  ta.d = d;
+  ta.metric = ix->metric;
+  ta.order = ix->order;
+  ta.status = c.dStatus.p;
+  ta.out = c.dResMapped;
+  VT_HIP(vt::launch_sketch_tail(ta, c.stream));
   VT_HIP(hipStreamSynchronize(c.stream));
-  const bool certified = c.hSkInfo.p[0] == 1u && c.hRes.p->status == 0;
+  if (c.hSkInfo.p[0] == 2u) {
+    // more candidates than the tail's block takes: K1 itself (GENERAL, the count read on the device), then its select
+    VT_TRY(c.dPartKeys.ensure((size_t)kSketchRescoreBlocks * k));
+    VT_TRY(c.dPartPay.ensure((size_t)kSketchRescoreBlocks * k));
+    vt::ScanArgs sa{};
+    sa.X = ix->dX;
+    sa.stride = ld;
+    sa.q = c.qsrc;
+    sa.id_rank = ix->dRank.p;
+    sa.gather = c.dSkRows.p;
+    sa.gather_stride = 1;
+    sa.n = kSketchCandCap;
+    sa.d = d;
+    sa.metric = ix->metric;
+    sa.order = ix->order;
+    sa.k = k;
+    sa.part_keys = c.dPartKeys.p;
+    sa.part_pay = c.dPartPay.p;
+    sa.status = c.dStatus.p;
+    sa.batch_counts = c.dSkCount.p;
+    sa.batch_cap = kSketchCandCap;
+    VT_HIP(vt::launch_scan_batch(sa, kSketchRescoreBlocks, 1, c.stream));
+    VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, kSketchRescoreBlocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
+                             c.dSelKeys.p, c.dSelPay.p, c.stream));
+    VT_HIP(hipStreamSynchronize(c.stream));
+  }
+  const bool certified = c.hSkInfo.p[0] != 0u && c.hRes.p->status == 0;
   if (c.profiling) {
     float ms = 0.f;
     VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
@@ -240,6 +285,7 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
     c.prof.sketch_ms += ms;
     c.prof.sketch_bytes += bytes;
     c.prof.sketch_candidates += c.hSkInfo.p[1];
+    c.prof.sketch_tail_rescored += c.hSkInfo.p[0] == 1u ? 1 : 0;
     c.prof.scan_launches += 1;
     c.prof.scan_ms += ms;
     c.prof.scan_rows += ix->n;

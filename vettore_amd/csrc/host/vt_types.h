@@ -47,12 +47,14 @@ struct Ctx {
   DevBuf<vt::Entry> dBOut;
   DevBuf<unsigned long long> dBNorm;
   DevBuf<unsigned char> dBQimage;  // K2b: the batch's queries in bf16, fragment order
-  // K1q (vt_search.h, sketch_search): the pass's block lists, the certified candidate rows and their count, and
-  // {certified, candidates, Kt, 0} written by the certify kernel through the host mapping
+  // K1q (vt_search.h, sketch_search): the pass's block lists, the certified candidate rows and their count,
+  // {outcome, candidates, Kt, 0} written by the tail kernel through the host mapping, and the host's scratch for the
+  // query's first-level residual (grows, never shrinks: no allocation per search)
   DevBuf<uint64_t> dSkKeys;
   DevBuf<vt::Payload> dSkPay;
   DevBuf<uint32_t> dSkRows, dSkCount;
   PinnedBuf<uint32_t> hSkInfo;
+  std::vector<double> hSkResid;
   // grouped quantized searches: one stage-1 block per query
   DevBuf<ResultBlock> dStageB;
   PinnedBuf<float> hBQ, hBTau;

@@ -600,9 +600,30 @@ size_t sketch_scan_lds_bytes(uint32_t d, uint32_t k);  // 0: not supported
 hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStream_t s);
 
 // One block over the lists of launch_sketch_scan: Kt = the k-th smallest key(lo) retained; every retained row whose
-// key(hi) <= Kt goes to rows[0..cap); certified iff that fits and every full list's largest key(hi) is > Kt.  *count
-// receives the candidates when certified, else 0; info = {certified, candidates, Kt bits, 0} (host-mapped).
-hipError_t launch_sketch_certify(const uint64_t *keys, const Payload *pay, uint32_t lists, uint32_t kp, uint32_t k, uint32_t cap,
-                                 uint32_t *rows, uint32_t *count, uint32_t *info, hipStream_t s);
+// key(hi) <= Kt is a candidate; certified iff they number at most `cap` and no list consists of candidates alone (a
+// full list whose largest key(hi) is <= Kt).  info = {outcome, candidates, Kt bits, 0} (host-mapped), outcome
+//   1: certified, and the block rescored the candidates itself with K1's arithmetic (X, q, order, metric; *status
+//      raised like K1's) and wrote the k best, sorted, with the status word into *out like launch_select -- taken when
+//      they are few enough for its LDS (at most 256);
+//   2: certified, rows[0..*count) hold the candidates for a gathered K1;
+//   0: not certified (*count = 0).
+struct SketchTailArgs {
+  const uint64_t *keys;     // [lists][kp], launch_sketch_scan's part_keys
+  const Payload *pay;       // [lists][kp]
+  uint32_t lists, kp, k, cap;
+  uint32_t *rows;           // [cap]
+  uint32_t *count;
+  uint32_t *info;           // [4]
+  const float *X;           // the f32 rows, `stride` floats apart
+  size_t stride;
+  const float *q;           // the query padded with zeros to padded_dim(d) floats (device)
+  const uint32_t *id_rank;  // per row; null => row index
+  uint32_t d;
+  int metric, order;
+  int *status;
+  ResultBlock *out;
+  uint32_t ld, ss, lds_words;  // set by the launcher
+};
+hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s);
 
 }  // namespace vt

@@ -1014,6 +1014,7 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch_fallbacks += p.sketch_fallbacks;
       t.sketch_builds += p.sketch_builds;
       t.sketch_patched_rows += p.sketch_patched_rows;
+      t.sketch_tail_rescored += p.sketch_tail_rescored;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

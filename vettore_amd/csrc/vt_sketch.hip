@@ -7,9 +7,11 @@
 //     [a_r - e_r, a_r + e_r] is rounded outwards to f32;
 //   * the rank function of the three metrics is monotone non-increasing in the dot, so key(hi_r) <= key_r <= key(lo_r):
 //     every block keeps its k' smallest (key(hi_r), id rank) keys (WaveTopK, K1's list layout) with key(lo_r) beside them.
-// sketch_certify_kernel then proves that the retained rows with key(hi) <= Kt hold the exact top k, and the gathered K1
-// (exact arithmetic) rescores only those.
+// sketch_tail_kernel then proves that the retained rows with key(hi) <= Kt hold the exact top k and rescores those few
+// with K1's exact arithmetic itself; a longer candidate list goes through the gathered K1.
 #include "vt_scan.cuh"
+
+#include <algorithm>
 
 namespace vt {
 
@@ -224,90 +226,313 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch_scan_kernel(cons
   if (wib == 0) tk.store(a.part_keys + (size_t)blockIdx.x * a.k, a.part_pay + (size_t)blockIdx.x * a.k, lane);
 }
 
-// ---- certification ------------------------------------------------------------------------------
-constexpr int kCertThreads = 1024;
-__global__ __launch_bounds__(kCertThreads) void sketch_certify_kernel(const uint64_t *__restrict__ keys, const Payload *__restrict__ pay,
-                                                                      uint32_t lists, uint32_t kp, uint32_t k, uint32_t cap,
-                                                                      uint32_t *__restrict__ rows, uint32_t *count, uint32_t *info) {
+// ---- the tail: certification and, for a short candidate list, the exact rescoring and the final select ---------------
+// One block.  Kt is the k-th smallest retained key(lo), exactly DESIGN 4.10's threshold.  One sweep of independent
+// loads stages the key(lo) words in LDS when lists * k' of them fit (104 KB at the headline; otherwise later sweeps read
+// global memory again) and leaves every thread the smallest of its own; an empty slot counts as 0xffffffff.  The k-th
+// smallest of those 1 024 minima is located to its top 16 bits by two 8-bit radix passes over one word per thread; U is
+// that bin's upper end.  k distinct entries are <= U, so the entries <= U hold the k smallest of all: they are filed (at
+// most 1 024, else the pass is not certified) and Kt is their k-th smallest by counting.  With k or fewer live entries
+// Kt is the maximum.  The collect is one more sweep of independent loads over the 64-bit keys; a list is refused when
+// every one of its k' slots is a candidate (it is full and its largest key(hi) is <= Kt: it may have dropped a row that
+// matters).
+// Up to kTailFuseMax candidates whose chunk sums fit the same LDS are then rescored here with K1's arithmetic: a wave
+// per row, a lane pair per 8-float chunk (elem4 / chunk_sum of vt_scan.cuh in the index's reduce order), the sums to an
+// LDS row, and one thread per candidate walks its row's sums in order -- the reference's sequential chain -- then the
+// scalar tail, K1's finiteness check, f64 recovery and status word.  The k best by (rank key, id rank) go sorted into
+// the pinned result block like select_topk_kernel's short-list path.  Longer candidate lists are left in rows[] for the
+// gathered K1 (info[0] = 2).
+constexpr int kTailThreads = 1024;
+constexpr uint32_t kTailFuseMax = 256;
+constexpr uint32_t kTailSurvivors = 1024;  // entries <= U the exact choice of Kt takes (one per thread)
+
+// hist[bin] += 1 for the lanes with `on`; called by whole waves.  The top digits of the retained keys are nearly all
+// equal, and 64 LDS atomics on one address run one after the other: the first two distinct bins of a wave are counted
+// by ballot and added once each, whatever is left goes lane by lane.
+__device__ __forceinline__ void hist_add(uint32_t *hist, bool on, uint32_t bin, int lane) {
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const uint64_t act = __ballot(on);
+    if (!act) return;
+    const int leader = __ffsll((long long)act) - 1;
+    const uint32_t lb = (uint32_t)__shfl((int)bin, leader, kWave);
+    const uint64_t same = __ballot(on && bin == lb);
+    if (lane == leader) atomicAdd(&hist[lb], (uint32_t)__popcll(same));
+    on = on && bin != lb;
+  }
+  if (on) atomicAdd(&hist[bin], 1u);
+}
+
+__global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchTailArgs a) {
+  extern __shared__ __align__(16) uint32_t dyn[];  // the key(lo) words; once Kt is known: per-list counts, chunk sums
   __shared__ uint32_t hist[256];
-  __shared__ uint32_t s_prefix, s_remaining, s_total, s_count, s_fail;
-  const uint32_t m = lists * kp;
-  const int tid = threadIdx.x;
+  __shared__ uint32_t s_prefix, s_remaining, s_total, s_count, s_fail, s_live, s_nsv, s_kt;
+  __shared__ uint32_t sv[kTailSurvivors];
+  __shared__ uint32_t c_row[kTailFuseMax];
+  __shared__ uint64_t c_key[kTailFuseMax];
+  const uint32_t m = a.lists * a.kp;
+  const uint32_t tid = threadIdx.x;
+  const int lane = tid & (kWave - 1), w = tid / kWave;
+  const bool in_lds = m <= a.lds_words;
   if (tid == 0) {
     s_prefix = 0;
-    s_remaining = k;
+    s_remaining = a.k;
     s_total = 0;
     s_count = 0;
     s_fail = 0;
+    s_live = 0;
+    s_nsv = 0;
+    s_kt = 0xffffffffu;
   }
-  // Kt: the k-th smallest key(lo) of the retained entries, 8 bits per pass
+  __syncthreads();
+  constexpr uint32_t kUnroll = 8;
+  uint32_t mine = 0xffffffffu;  // the smallest key(lo) word among this thread's entries
+  {
+    uint32_t live = 0;
+    for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
+      uint64_t key[kUnroll];
+      float raw[kUnroll];
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+        key[u] = i < m ? a.keys[i] : kEmptyKey;
+        raw[u] = i < m ? a.pay[i].raw : 0.0f;  // (an empty slot's payload was never written: loaded, not used)
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+        const uint32_t v = key[u] == kEmptyKey ? 0xffffffffu : orderable(raw[u]);
+        live += key[u] != kEmptyKey ? 1u : 0u;
+        mine = v < mine ? v : mine;
+        if (i < m && in_lds) dyn[i] = v;
+      }
+    }
+    live = wave_sum_u(live);
+    if (lane == 0 && live) atomicAdd(&s_total, live);
+  }
+  // U = the upper end of the 16-bit bin that holds the k-th smallest of the 1 024 threads' minima (k <= 256): k distinct
+  // entries are <= U, so Kt <= U, and the entries <= U -- a few more than k unless hundreds tie -- hold the k smallest
+  // of all.  Two radix passes over one word per thread, in place of four over all lists * k' words.
   uint32_t mask = 0;
-  for (int pass = 0; pass < 4; ++pass) {
+  for (int pass = 0; pass < 2; ++pass) {
     const int shift = 24 - 8 * pass;
-    for (int i = tid; i < 256; i += kCertThreads) hist[i] = 0;
+    if (tid < 256) hist[tid] = 0;
     __syncthreads();
     const uint32_t prefix = s_prefix;
-    for (uint32_t i = tid; i < m; i += kCertThreads) {
-      if (keys[i] == kEmptyKey) continue;
-      const uint32_t v = orderable(pay[i].raw);
-      if ((v & mask) == prefix) atomicAdd(&hist[(v >> shift) & 255u], 1u);
-    }
+    hist_add(hist, (mine & mask) == prefix, (mine >> shift) & 255u, lane);
     __syncthreads();
-    if (tid == 0) {
-      uint32_t cum = 0, b = 0;
-      if (pass == 0)
-        for (uint32_t j = 0; j < 256; ++j) s_total += hist[j];
-      for (; b < 255; ++b) {
-        if (cum + hist[b] >= s_remaining) break;
-        cum += hist[b];
+    if (w == 0) {  // the bin that holds the s_remaining-th smallest of this digit: four bins per lane, one wave scan
+      const uint32_t krem = s_remaining;
+      const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+      const uint32_t sum = h0 + h1 + h2 + h3;
+      uint32_t incl = sum;
+#pragma unroll
+      for (int o = 1; o < kWave; o <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, o, kWave);
+        if (lane >= o) incl += t;
       }
-      s_remaining -= cum;
-      s_prefix = prefix | (b << shift);
+      uint32_t cum = incl - sum;
+      if (cum < krem && krem <= incl) {
+        uint32_t b = 0;
+        if (cum + h0 < krem) {
+          cum += h0;
+          b = 1;
+          if (cum + h1 < krem) {
+            cum += h1;
+            b = 2;
+            if (cum + h2 < krem) {
+              cum += h2;
+              b = 3;
+            }
+          }
+        }
+        s_remaining = krem - cum;
+        s_prefix = prefix | ((4u * (uint32_t)lane + b) << shift);
+      }
     }
     mask |= 255u << shift;
     __syncthreads();
   }
-  const uint32_t kt = s_total <= k ? 0xffffffffu : s_prefix;  // (k or fewer entries in all: every one is a candidate)
-  // collect, and check that no full list can have dropped a row with key(hi) <= Kt
-  const int lane = tid & (kWave - 1), w = tid / kWave;
-  for (uint32_t l = w; l < lists; l += kCertThreads / kWave) {
-    bool full = true;
-    uint32_t mx = 0;
-    for (uint32_t j0 = 0; j0 < kp; j0 += kWave) {
-      const uint32_t j = j0 + lane;
-      bool empty = true;
-      uint32_t lo = 0;
-      if (j < kp) {
-        const uint64_t key = keys[(size_t)l * kp + j];
-        empty = key == kEmptyKey;
-        lo = (uint32_t)(key >> 32);
-        if (!empty) {
-          mx = mx > lo ? mx : lo;
-          if (lo <= kt) {
-            const uint32_t pos = atomicAdd(&s_count, 1u);
-            if (pos < cap) rows[pos] = pay[(size_t)l * kp + j].row;
+  // the entries <= U into sv[]; Kt = their k-th smallest, every survivor's place found by counting
+  uint32_t kt = 0xffffffffu;  // (k or fewer entries in all: every one is a candidate)
+  if (s_total > a.k) {
+    const uint32_t ub = s_prefix | 0xffffu;
+    for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
+      uint32_t v[kUnroll];
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+        v[u] = 0xffffffffu;
+        if (i < m) v[u] = in_lds ? dyn[i] : (a.keys[i] == kEmptyKey ? 0xffffffffu : orderable(a.pay[i].raw));
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        if (b + u * kTailThreads < m && v[u] <= ub) {
+          const uint32_t pos = atomicAdd(&s_nsv, 1u);
+          if (pos < kTailSurvivors) sv[pos] = v[u];
+        }
+      }
+    }
+    __syncthreads();
+    const uint32_t nsv = s_nsv;
+    if (nsv > kTailSurvivors) {  // (a thousand entries tie around the k-th: nothing the candidate cap would take)
+      if (tid == 0) {
+        *a.count = 0u;
+        a.info[0] = 0u;
+        a.info[1] = nsv;
+        a.info[2] = ub;
+        a.info[3] = 0u;
+      }
+      return;
+    }
+    if (tid < nsv) {
+      const uint32_t v = sv[tid];
+      uint32_t lt = 0, le = 0;
+      for (uint32_t x = 0; x < nsv; ++x) {
+        const uint32_t o = sv[x];
+        lt += o < v ? 1u : 0u;
+        le += o <= v ? 1u : 0u;
+      }
+      if (lt < a.k && a.k <= le) s_kt = v;  // (every thread that gets here writes the same word)
+    }
+    __syncthreads();
+    kt = s_kt;
+  }
+
+  // collect; dyn[0..lists): candidates per list
+  const uint32_t lists4 = (a.lists + 3u) & ~3u;
+  for (uint32_t l = tid; l < a.lists; l += kTailThreads) dyn[l] = 0;
+  __syncthreads();
+  for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
+    uint64_t key[kUnroll];
+#pragma unroll
+    for (uint32_t u = 0; u < kUnroll; ++u) {
+      const uint32_t i = b + u * kTailThreads;
+      key[u] = i < m ? a.keys[i] : kEmptyKey;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kUnroll; ++u) {
+      const uint32_t i = b + u * kTailThreads;
+      if (key[u] != kEmptyKey && (uint32_t)(key[u] >> 32) <= kt) {
+        const uint32_t row = a.pay[i].row;
+        const uint32_t pos = atomicAdd(&s_count, 1u);
+        if (pos < a.cap) a.rows[pos] = row;
+        if (pos < kTailFuseMax) c_row[pos] = row;
+        atomicAdd(&dyn[i / a.kp], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  for (uint32_t l = tid; l < a.lists; l += kTailThreads)
+    if (dyn[l] == a.kp) s_fail = 1;
+  __syncthreads();
+  const uint32_t cnt = s_count;
+  const bool ok = !s_fail && cnt <= a.cap;
+  const bool fused = ok && cnt <= kTailFuseMax && lists4 + cnt * a.ss <= a.lds_words;
+  if (!fused) {
+    if (tid == 0) {
+      *a.count = ok ? cnt : 0u;
+      a.info[0] = ok ? 2u : 0u;
+      a.info[1] = cnt;
+      a.info[2] = kt;
+      a.info[3] = 0u;
+    }
+    return;
+  }
+
+  // K1 on the candidates: wave w takes candidates w, w + 16, ...; lane l the floats [256 s + 4 l, + 4) of segment s
+  float *S = reinterpret_cast<float *>(dyn + lists4);  // [cnt][ss]
+  const int odd = lane & 1;
+  const uint32_t cfull = a.d / 8, tail = a.d % 8, tail_base = a.ss - 12;
+  for (uint32_t c = (uint32_t)w; c < cnt; c += kTailThreads / kWave) {
+    const float *x = a.X + (size_t)c_row[c] * a.stride;
+    float *Srow = S + (size_t)c * a.ss;
+    for (uint32_t s0 = 0; s0 < a.ld; s0 += 4 * 256) {
+      f32x4 xv[4], qv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t col = s0 + u * 256 + (uint32_t)lane * 4;
+        const bool in = col < a.ld;
+        xv[u] = in ? *reinterpret_cast<const f32x4 *>(x + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+        qv[u] = in ? *reinterpret_cast<const f32x4 *>(a.q + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t col = s0 + u * 256 + (uint32_t)lane * 4;
+        const f32x4 pr = elem4<OP_DOT>(OP_DOT, qv[u], xv[u]);
+        const float sum = chunk_sum<OP_DOT, -1>(OP_DOT, a.order, pr.x, pr.y, pr.z, pr.w, odd);
+        const uint32_t ch = col >> 3;
+        if (col < a.ld) {
+          if (ch < cfull) {
+            if (!odd) Srow[ch] = sum;
+          } else if (ch == cfull) {  // the tail chunk: the reference adds these products one by one
+            *reinterpret_cast<f32x4 *>(Srow + tail_base + odd * 4) = pr;
           }
         }
       }
-      if (__ballot(j < kp && empty)) full = false;
     }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-      const uint32_t other = (uint32_t)__shfl_xor((int)mx, o, kWave);
-      mx = mx > other ? mx : other;
-    }
-    if (lane == 0 && full && mx <= kt) s_fail = 1;
   }
   __syncthreads();
+  uint64_t key = kEmptyKey;
+  uint32_t row = 0;
+  float raw = 0.0f;
+  if (tid < cnt) {
+    row = c_row[tid];
+    const float *Sr = S + (size_t)tid * a.ss;
+    float acc = 0.0f;
+    uint32_t c = 0;
+    for (; c + 4 <= cfull; c += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(Sr + c);
+      acc = acc + v.x;
+      acc = acc + v.y;
+      acc = acc + v.z;
+      acc = acc + v.w;
+    }
+    for (; c < cfull; ++c) acc = acc + Sr[c];
+    for (uint32_t j = 0; j < tail; ++j) acc = acc + Sr[tail_base + j];
+    // distances.rs:42-68 compute(): value, finiteness, f64 recovery -- as scan_topk_kernel has them
+    raw = a.metric == M_NIP ? -acc : acc;
+    bool valid = true;
+    if (!finite_f32(raw)) {
+      const float rec = recover_overflow(a.metric, a.q, a.X + (size_t)row * a.stride, a.d);
+      if (rec == rec) {
+        raw = rec;
+      } else {
+        atomicMax(a.status, kErrOverflow);
+        valid = false;
+      }
+    }
+    float rank = raw;
+    if (a.metric == M_COS) rank = 1.0f - raw;
+    else if (a.metric == M_IP) rank = -raw;
+    if (valid) key = ((uint64_t)orderable(rank) << 32) | (a.id_rank ? a.id_rank[row] : row);
+  }
+  if (tid < kTailFuseMax) c_key[tid] = key;
+  const uint64_t votes = __ballot(key != kEmptyKey);
+  if (lane == 0 && votes) atomicAdd(&s_live, (uint32_t)__popcll(votes));
+  __syncthreads();
+  if (key != kEmptyKey) {
+    uint32_t pos = 0;
+    for (uint32_t x = 0; x < cnt; ++x) {
+      const uint64_t kx = c_key[x];
+      pos += (kx < key || (kx == key && x < tid)) ? 1u : 0u;
+    }
+    if (pos < a.k) {
+      Entry e;
+      e.key = key;
+      e.row = row;
+      e.raw = raw;
+      a.out->e[pos] = e;
+    }
+  }
   if (tid == 0) {
-    const uint32_t cnt = s_count;
-    const bool ok = !s_fail && cnt <= cap;
-    *count = ok ? cnt : 0u;
-    info[0] = ok ? 1u : 0u;
-    info[1] = cnt;
-    info[2] = kt;
-    info[3] = 0u;
-    __threadfence_system();
+    a.out->count = s_live < a.k ? s_live : a.k;
+    a.out->status = atomicExch(a.status, 0);  // (every atomicMax above is behind the barrier)
+    *a.count = cnt;
+    a.info[0] = 1u;
+    a.info[1] = cnt;
+    a.info[2] = kt;
+    a.info[3] = 0u;
   }
 }
 
@@ -353,10 +578,25 @@ hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStrea
   return hipGetLastError();
 }
 
-hipError_t launch_sketch_certify(const uint64_t *keys, const Payload *pay, uint32_t lists, uint32_t kp, uint32_t k, uint32_t cap,
-                                 uint32_t *rows, uint32_t *count, uint32_t *info, hipStream_t s) {
-  if (lists == 0 || kp == 0 || k == 0 || k > kp || !rows || !count || !info) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sketch_certify_kernel, dim3(1), dim3(kCertThreads), 0, s, keys, pay, lists, kp, k, cap, rows, count, info);
+size_t sketch_tail_lds_bytes(uint32_t lists, uint32_t kp, uint32_t d) {
+  // the key(lo) words if they fit, and room for a few dozen rows of chunk sums beside the per-list counts
+  const size_t room = 128 * 1024;
+  const size_t want = std::max((size_t)lists * kp, ((size_t)lists + 4) + 64 * (size_t)(padded_dim(d) / 8 + 12)) * 4;
+  return std::max(std::min(want, room), ((size_t)lists + 4) * 4);
+}
+
+hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s) {
+  if (a.lists == 0 || a.kp == 0 || a.k == 0 || a.k > a.kp || a.k > (uint32_t)kMaxFusedK || !a.rows || !a.count || !a.info || !a.out ||
+      !a.status || a.d == 0)
+    return hipErrorInvalidValue;
+  const size_t lds = sketch_tail_lds_bytes(a.lists, a.kp, a.d);
+  if (lds > kMaxLds - 8 * 1024) return hipErrorInvalidValue;
+  a.ld = padded_dim(a.d);
+  a.ss = a.ld / 8 + 12;  // (K1's panel row: 4 * odd dwords, the eight tail products behind the sums)
+  a.lds_words = (uint32_t)(lds / 4);
+  hipError_t e = allow_lds(sketch_tail_kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sketch_tail_kernel, dim3(1), dim3(kTailThreads), lds, s, a);
   return hipGetLastError();
 }
 
