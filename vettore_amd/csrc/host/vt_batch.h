@@ -106,8 +106,7 @@ int batch_group_queue(Shard *ix, Ctx &c, BatchGroupRun &run, const float *querie
   VT_TRY(c.hBCount.ensure(nq_pad));
   VT_TRY(c.hBOut.ensure((size_t)nq_pad * k));
   VT_TRY(c.hBOutCount.ensure(nq_pad + 1));  // (+ the status word: a copy into pageable memory would wait for the stream)
-  VT_TRY(c.dPartKeys.ensure((size_t)nq_pad * kBlocksPerQuery * k));
-  VT_TRY(c.dPartPay.ensure((size_t)nq_pad * kBlocksPerQuery * k));
+  VT_TRY(c.ensure_part_lists((size_t)nq_pad * kBlocksPerQuery * k));
   if (bf16) VT_TRY(c.dBQimage.ensure(std::max(vt::batch_bf16_image_bytes(ld), vt::batch_shadow_image_bytes(ld))));
 
   run.queries = queries;
@@ -185,21 +184,11 @@ int batch_group_queue(Shard *ix, Ctx &c, BatchGroupRun &run, const float *querie
   a.stages = 0;
   if (c.profiling) VT_HIP(hipEventRecord(c.ev3, c.stream));
   // exact rescoring of every query's candidates with the K1 arithmetic
-  vt::ScanArgs sa{};
-  sa.X = ix->dX;
-  sa.stride = ix->ld;
+  vt::ScanArgs sa = scan_args(ix, c, d);
   sa.q = c.dBQ.p;
-  sa.id_rank = ix->dRank.p;
-  sa.gather = &c.dBCand.p->row;
-  sa.gather_stride = sizeof(vt::BatchCand) / sizeof(uint32_t);
-  sa.n = cand_cap;
-  sa.d = d;
-  sa.metric = ix->metric;
-  sa.order = ix->order;
+  set_gather(sa, gather_of(c.dBCand.p), cand_cap);
   sa.k = k;
-  sa.part_keys = c.dPartKeys.p;
-  sa.part_pay = c.dPartPay.p;
-  sa.status = c.dStatus.p;
+  use_part_lists(sa, c);
   sa.batch_counts = c.dBCount.p;
   sa.batch_cap = cand_cap;
   VT_HIP(vt::launch_scan_batch(sa, kBlocksPerQuery, nq_pad, c.stream));
@@ -394,8 +383,7 @@ int multi_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vector<
   const size_t nq_pad = (nq + vt::kMultiMaxQueries - 1) / vt::kMultiMaxQueries * vt::kMultiMaxQueries;
   VT_TRY(c.dBQ.ensure(nq_pad * ld));
   VT_TRY(c.hBQ.ensure(nq_pad * ld));
-  VT_TRY(c.dPartKeys.ensure(nq * blocks * k));
-  VT_TRY(c.dPartPay.ensure(nq * blocks * k));
+  VT_TRY(c.ensure_part_lists(nq * blocks * k));
   // per query a packed result block: 16-byte header + k entries (Entry is 16 bytes)
   const uint32_t out_stride = 16 + k * (uint32_t)sizeof(vt::Entry);
   VT_TRY(c.dBOut.ensure(nq * (k + 1)));
@@ -408,7 +396,7 @@ int multi_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vector<
     for (uint32_t j = 0; j < d; ++j) qnz[i] += q[j] != 0.0f ? 1u : 0u;
   }
   VT_HIP(hipMemcpyAsync(c.dBQ.p, c.hBQ.p, nq_pad * ld * sizeof(float), hipMemcpyHostToDevice, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   uint32_t sweeps = 0;
   for (size_t g0 = 0; g0 < nq; g0 += vt::kMultiMaxQueries, ++sweeps) {
     const uint32_t gn = (uint32_t)std::min<size_t>(vt::kMultiMaxQueries, nq - g0);
@@ -427,26 +415,18 @@ int multi_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vector<
     a.first_query = (uint32_t)g0;
     a.dbg = (uint32_t)vt::env::get(vt::env::MQ_DBG);
     for (uint32_t i = 0; i < gn; ++i) a.q_nonzero[i] = qnz[g0 + i];
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
+    use_part_lists(a, c);
     a.status = c.dStatus.p;
     VT_HIP(vt::launch_scan_multi(a, blocks, c.stream));
   }
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   VT_HIP(vt::launch_select_queries(c.dPartKeys.p, c.dPartPay.p, (uint32_t)nq, blocks * k, k, c.dBOut.p, out_stride, c.stream));
   int status = 0;
   VT_HIP(hipMemcpyAsync(c.hBOut.p, c.dBOut.p, nq * out_stride, hipMemcpyDeviceToHost, c.stream));
   VT_HIP(hipMemcpyAsync(&status, c.dStatus.p, sizeof(int), hipMemcpyDeviceToHost, c.stream));
   VT_HIP(hipMemsetAsync(c.dStatus.p, 0, sizeof(int), c.stream));
   VT_HIP(hipStreamSynchronize(c.stream));
-  if (c.profiling) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    c.prof.scan_launches += sweeps;
-    c.prof.scan_ms += ms;
-    c.prof.scan_rows += (uint64_t)sweeps * n;
-    c.prof.scan_bytes += (uint64_t)sweeps * n * d * 4;
-  }
+  if (c.profiling) VT_TRY(c.book_scan(sweeps, (uint64_t)sweeps * n, (uint64_t)sweeps * n * d * 4));
   // "metric overflow" belongs to one query (flat.rs:105): the single-query path finds out whose
   if (status != 0) return kRetryInternal;
   for (size_t i = 0; i < nq; ++i) {
@@ -481,8 +461,7 @@ int pattern_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vecto
   const size_t up_floats = nq * q_words * 2;
   VT_TRY(c.dBQ.ensure(up_floats));
   VT_TRY(c.hBQ.ensure(up_floats));
-  VT_TRY(c.dPartKeys.ensure(nq * blocks * k));
-  VT_TRY(c.dPartPay.ensure(nq * blocks * k));
+  VT_TRY(c.ensure_part_lists(nq * blocks * k));
   const uint32_t out_stride = 16 + k * (uint32_t)sizeof(vt::Entry);  // per query a packed result block: header + k entries
   VT_TRY(c.dBOut.ensure(nq * (k + 1)));
   VT_TRY(c.hBOut.ensure(nq * (k + 1)));
@@ -495,7 +474,7 @@ int pattern_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vecto
       if (q[j] != 0.0f) w[j / 64] |= 1ull << (j % 64);  // distances.rs:319-347: what the two metrics compare
   }
   VT_HIP(hipMemcpyAsync(c.dBQ.p, c.hBQ.p, nq * q_words * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   uint32_t sweeps = 0;
   for (size_t g0 = 0; g0 < nq; g0 += vt::kPatternMultiMax, ++sweeps) {
     vt::PatternMultiArgs a{};
@@ -510,20 +489,15 @@ int pattern_scan_group(Shard *ix, Ctx &c, const float *queries, const std::vecto
     a.nq = (uint32_t)std::min<size_t>(vt::kPatternMultiMax, nq - g0);
     a.first_query = (uint32_t)g0;
     a.jaccard = ix->metric == VT_JACCARD ? 1 : 0;
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
+    use_part_lists(a, c);
     VT_HIP(vt::launch_pattern_multi(a, blocks, c.stream));
   }
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   VT_HIP(vt::launch_select_queries(c.dPartKeys.p, c.dPartPay.p, (uint32_t)nq, blocks * k, k, c.dBOut.p, out_stride, c.stream));
   VT_HIP(hipMemcpyAsync(c.hBOut.p, c.dBOut.p, nq * out_stride, hipMemcpyDeviceToHost, c.stream));
   VT_HIP(hipStreamSynchronize(c.stream));
   if (c.profiling) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    c.prof.hamming_launches += sweeps;
-    c.prof.hamming_ms += ms;
-    c.prof.hamming_bytes += (uint64_t)sweeps * n * words * 8;
+    VT_TRY(c.book_hamming(sweeps, (uint64_t)sweeps * n * words * 8));
     c.prof.hamming_queries += nq;
   }
   for (size_t i = 0; i < nq; ++i) {

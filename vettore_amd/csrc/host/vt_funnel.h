@@ -146,12 +146,10 @@ int funnel_group_queue(Shard *ix, Ctx &c, FunnelGroupRun &run, const float *quer
   VT_TRY(c.dBSample.ensure((size_t)vt::kCosineMultiMax * sample_rows));
   VT_TRY(c.dBTau.ensure(vt::kCosineMultiMax));
   VT_TRY(c.dBCount.ensure(vt::kCosineMultiMax));
-  VT_TRY(c.dPartKeys.ensure((size_t)nq * kListCap));
-  VT_TRY(c.dPartPay.ensure((size_t)nq * kListCap));
+  VT_TRY(c.ensure_part_lists((size_t)nq * kListCap));
   VT_TRY(c.dStageB.ensure(nq));
   constexpr uint32_t kStageBlocks = 4;  // K1 batch mode: blocks per query over its <= 256 candidates (8-row tiles)
-  VT_TRY(c.dCandKeys.ensure((size_t)nq * k1 * kStageBlocks));
-  VT_TRY(c.dCandPay.ensure((size_t)nq * k1 * kStageBlocks));
+  VT_TRY(c.ensure_cand_lists((size_t)nq * k1 * kStageBlocks));
   // (a list that came out short leaves the tail of its block as it was: rows a later stage may still gather --
   // zeroed, they are row 0)
   VT_HIP(hipMemsetAsync(c.dStageB.p, 0, (size_t)nq * sizeof(ResultBlock), c.stream));
@@ -228,10 +226,10 @@ int funnel_group_queue(Shard *ix, Ctx &c, FunnelGroupRun &run, const float *quer
   a.cand_pay = pa.cand_pay = c.dPartPay.p;
   a.cand_count = pa.cand_count = c.dBCount.p;
   a.cand_cap = pa.cand_cap = kListCap;
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   if (cosine) VT_HIP(vt::launch_cosine_scan_multi(a, c.grid_for(ntiles, lds), c.stream));
   else VT_HIP(vt::launch_prefix_multi(pa, c.grid_for(ntiles, lds, vt::prefix_multi_blocks_per_cu()), c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   VT_HIP(hipMemcpyAsync(hListCount, c.dBCount.p, vt::kCosineMultiMax * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
   VT_HIP(vt::launch_select_lists(c.dPartKeys.p, c.dPartPay.p, nq, kListCap, c.dBCount.p, k1, c.dStageB.p,
                                  (uint32_t)sizeof(ResultBlock), c.stream, /*sixteen blocks per list=*/true));
@@ -242,37 +240,22 @@ int funnel_group_queue(Shard *ix, Ctx &c, FunnelGroupRun &run, const float *quer
                           hipMemcpyDeviceToHost, c.stream));
   // later stages re-score the same candidates on a longer prefix (collection.ex:674-691), then
   // exact_rerank on the full vectors (collection.ex:821-851): the queries on grid.y
-  vt::CosineRerankArgs r{};
-  r.X = ix->dX;
-  r.stride = ix->ld;
+  // (d, and K1's k, are each stage's own: set in the loop below)
+  vt::CosineRerankArgs r = cosine_rerank_args(ix, c, 0);
   r.q = c.dBQ.p;
-  r.id_rank = ix->dRank.p;
-  r.gather = &c.dStageB.p->e[0].row;
-  r.gather_stride = sizeof(vt::Entry) / sizeof(uint32_t);
-  r.n = k1;
-  r.out_keys = c.dCandKeys.p;
-  r.out_pay = c.dCandPay.p;
-  r.status = c.dStatus.p;
+  set_gather(r, gather_of(c.dStageB.p), k1);
   r.q_stride = ld;
-  r.gather_qstride = (uint32_t)(sizeof(ResultBlock) / sizeof(uint32_t));
+  r.gather_qstride = kBlockGatherWords;
   // (the other families: K1 over each query's candidate rows, kStageBlocks lists of `k` per query)
-  vt::ScanArgs sa{};
-  sa.X = ix->dX;
-  sa.stride = ix->ld;
+  vt::ScanArgs sa = scan_args(ix, c, 0);
   sa.q = c.dBQ.p;
-  sa.id_rank = ix->dRank.p;
-  sa.gather = &c.dStageB.p->e[0].row;
-  sa.gather_stride = sizeof(vt::Entry) / sizeof(uint32_t);
-  sa.n = k1;
-  sa.metric = ix->metric;
-  sa.order = ix->order;
+  set_gather(sa, gather_of(c.dStageB.p), k1);
   sa.part_keys = c.dCandKeys.p;
   sa.part_pay = c.dCandPay.p;
-  sa.status = c.dStatus.p;
   sa.batch_counts = dcounts;
   sa.batch_cap = k1;
   sa.batch_qstride = ld;
-  sa.batch_gather_stride = (uint32_t)(sizeof(ResultBlock) / sizeof(uint32_t));
+  sa.batch_gather_stride = kBlockGatherWords;
   static const uint32_t kListsPerQuery = vt::scan_lists(kStageBlocks);
   for (size_t i = 1; i < nstages; ++i) {
     if (cosine) {
@@ -329,18 +312,11 @@ int funnel_group_finish(Shard *ix, Ctx &c, const FunnelGroupRun &run, vt_hits **
   constexpr uint32_t kListCap = 8192;
   VT_HIP(hipStreamSynchronize(c.stream));
   if (c.profiling) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
     if (as_scan) {  // (a batch of plain searches: the sweep is its scan)
-      c.prof.scan_launches += 1;
-      c.prof.scan_ms += ms;
-      c.prof.scan_rows += n;
-      c.prof.scan_bytes += (uint64_t)n * d1 * 4;
+      VT_TRY(c.book_scan(1, n, (uint64_t)n * d1 * 4));
       c.prof.sweep_queries += nq;
     } else {
-      c.prof.prefix_launches += 1;
-      c.prof.prefix_ms += ms;
-      c.prof.prefix_bytes += (uint64_t)n * d1 * 4;
+      VT_TRY(c.book_prefix((uint64_t)n * d1 * 4));
       c.prof.prefix_queries += nq;
     }
   }

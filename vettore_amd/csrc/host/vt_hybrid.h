@@ -43,14 +43,7 @@ int hybrid_ready(Shard *ix, Ctx &c, const float *query, size_t n, const int *kin
     } else {  // the index's own search with limit = candidates (collection.ex:583-592)
       // (flat search ranks cosine by the f32 dot of normalised vectors, not by the f64 cosine
       // a vector_top_k stage would use: the plain scan serves every metric here)
-      ScanJob j{};
-      j.X = ix->dX;
-      j.stride = ix->ld;
-      j.id_rank = ix->dRank.p;
-      j.n = ix->n;
-      j.d = (uint32_t)ix->dim;
-      j.metric = ix->metric;
-      j.order = ix->order;
+      vt::ScanArgs j = scan_args(ix, c, (uint32_t)ix->dim);
       j.q_nonzero = qnz_full;
       VT_TRY(run_scan(c, j, candidates[i], kept, false));
       rows.resize(kept.size());

@@ -139,44 +139,16 @@ int shard_begin(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, v
   VT_TRY(upload_query(c, query, n, &qnz));
   const uint32_t d = (uint32_t)ix->dim, k = (uint32_t)limit;
   if (vt::scan_lds_bytes(d, k) == 0) return fail(VT_ERR_UNSUPPORTED, "dimension/limit exceed the scan kernel's LDS");
-  const uint32_t tile_rows = vt::scan_tile_rows(ix->n, d, c.resident_waves());
-  const uint32_t blocks = c.grid_for((ix->n + tile_rows - 1) / tile_rows, vt::scan_lds_bytes(d, k));
-  VT_TRY(c.dPartKeys.ensure((size_t)blocks * k));
-  VT_TRY(c.dPartPay.ensure((size_t)blocks * k));
-  vt::ScanArgs a{};
-  a.X = ix->dX;
-  a.stride = ix->ld;
-  a.q = c.qsrc;
-  a.id_rank = ix->dRank.p;
-  a.n = ix->n;
-  a.d = d;
-  a.metric = ix->metric;
-  a.order = ix->order;
-  a.k = k;
+  vt::ScanArgs a = scan_args(ix, c, d);
   a.q_nonzero = qnz;
-  a.tile_rows = tile_rows;
-  a.part_keys = c.dPartKeys.p;
-  a.part_pay = c.dPartPay.p;
-  a.status = c.dStatus.p;
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
-  VT_HIP(vt::launch_scan(a, blocks, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
-  c.begin_rows = ix->n;
+  VT_TRY(scan_to_block(c, a, k, c.profiling, c.dStatus.p, static_cast<ResultBlock *>(device_block)));
+  c.begin_rows = ix->n;  // (the span is booked by settle_begin_profile, after the caller's wait)
   c.begin_dim = d;
-  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, blocks * k, k, 0, 0, c.dStatus.p,
-                           static_cast<ResultBlock *>(device_block), c.dSelKeys.p, c.dSelPay.p, c.stream));
   return VT_OK;
 }
 
 int settle_begin_profile(Ctx &c) {
-  if (c.profiling && c.begin_rows) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    c.prof.scan_launches += 1;
-    c.prof.scan_ms += ms;
-    c.prof.scan_rows += c.begin_rows;
-    c.prof.scan_bytes += (uint64_t)c.begin_rows * c.begin_dim * 4;
-  }
+  if (c.profiling && c.begin_rows) VT_TRY(c.book_scan(1, c.begin_rows, (uint64_t)c.begin_rows * c.begin_dim * 4));
   c.begin_rows = 0;
   return VT_OK;
 }
@@ -527,14 +499,7 @@ int multi_stage(vt_flat *h, StageKind kind, uint32_t d, const float *query, size
       return quantized_rows(ix, c, keep, rows, &per[s]);
     }
     if (kind == STAGE_SEARCH) {
-      ScanJob j{};
-      j.X = ix->dX;
-      j.stride = ix->ld;
-      j.id_rank = ix->dRank.p;
-      j.n = ix->n;
-      j.d = (uint32_t)ix->dim;
-      j.metric = ix->metric;
-      j.order = ix->order;
+      vt::ScanArgs j = scan_args(ix, c, (uint32_t)ix->dim);
       j.q_nonzero = qnz_full;
       return run_scan(c, j, keep, per[s], false);
     }

@@ -28,8 +28,7 @@ int hamming_hist_collect(Shard *ix, Ctx &c, uint32_t k1, bool *timed) {
   VT_TRY(c.dDist16.ensure(((size_t)std::max<uint32_t>(ix->cap, ix->n) + 7) / 8 * 8));
   VT_TRY(c.dHamHist.ensure(2 * kHammingHistStride));
   VT_TRY(c.dHamCount.ensure(1));
-  VT_TRY(c.dPartKeys.ensure(kHammingListCap));
-  VT_TRY(c.dPartPay.ensure(kHammingListCap));
+  VT_TRY(c.ensure_part_lists(kHammingListCap));
   if (!c.ham_ready || c.ham_dirty) {
     VT_HIP(hipMemsetAsync(c.dHamHist.p, 0, 2 * kHammingHistStride * sizeof(uint32_t), c.stream));
     c.ham_ready = true;
@@ -46,9 +45,9 @@ int hamming_hist_collect(Shard *ix, Ctx &c, uint32_t k1, bool *timed) {
   h.hist = c.dHamHist.p + c.ham_parity * kHammingHistStride;
   h.list_count = c.dHamCount.p;
   const uint32_t blocks = c.grid_for((ix->n + 63) / 64, vt::hamming_hist_lds_bytes(d), c.hamming_blocks_per_cu);
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   VT_HIP(vt::launch_hamming_dist(h, blocks, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   *timed = c.profiling;
   vt::HammingCollectArgs g{};
   g.dist = c.dDist16.p;
@@ -74,7 +73,6 @@ int hamming_hist_collect(Shard *ix, Ctx &c, uint32_t k1, bool *timed) {
 // gathers by).  use_hist: K4h (stream + histogram + threshold collect), else K4 (fused top-k).
 // No select here takes the status word: a raised flag stays in c.dStatus for the call's last select.
 int hamming_stage_dev(Shard *ix, Ctx &c, uint32_t k1, bool use_hist, ResultBlock *dst, bool *timed) {
-  const uint32_t d = (uint32_t)ix->dim, words = (d + 63) / 64;
   if (use_hist) {
     VT_TRY(hamming_hist_collect(ix, c, k1, timed));
     VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, kHammingListCap, k1, 0, 0, nullptr, dst, c.dSelKeys.p, c.dSelPay.p,
@@ -83,22 +81,13 @@ int hamming_stage_dev(Shard *ix, Ctx &c, uint32_t k1, bool use_hist, ResultBlock
   }
   const uint32_t blocks = c.grid_for((ix->n + 63) / 64, vt::hamming_lds_bytes(k1), c.hamming_blocks_per_cu);
   const uint32_t waves = vt::scan_lists(blocks);
-  VT_TRY(c.dPartKeys.ensure((size_t)waves * k1));
-  VT_TRY(c.dPartPay.ensure((size_t)waves * k1));
-  vt::HammingArgs h{};
-  h.bits = ix->bits.buf.p;
-  h.qbits = c.dQbits;
-  h.id_rank = ix->dRank.p;
-  h.n = ix->n;
-  h.words = words;
-  h.pairs = (words + 1) / 2;
-  h.d = d;
+  VT_TRY(c.ensure_part_lists((size_t)waves * k1));
+  vt::HammingArgs h = hamming_args(ix->bits.buf.p, c, ix, (uint32_t)ix->dim);
   h.k = k1;
-  h.part_keys = c.dPartKeys.p;
-  h.part_pay = c.dPartPay.p;
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  use_part_lists(h, c);
+  VT_TRY(c.mark_begin());
   VT_HIP(vt::launch_hamming(h, blocks, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   *timed = c.profiling;
   VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, waves * k1, k1, 0, 0, nullptr, dst, c.dSelKeys.p, c.dSelPay.p, c.stream));
   return VT_OK;
@@ -123,8 +112,7 @@ int quantized_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t cand
   auto run = [&](bool use_hist) -> int {
   std::vector<vt::Entry> entries, first;
   bool first_in_block = false;
-  const uint32_t *gather = nullptr;
-  uint32_t gather_stride = 1;
+  GatherList gather{};
   bool timed_hamming = false;
   auto copy_first_block = [&]() -> int {  // queued behind the select that fills c.dStage[0]
     if (!local) return VT_OK;
@@ -139,8 +127,7 @@ int quantized_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t cand
     VT_TRY(c.dStage.ensure(1));
     VT_TRY(hamming_stage_dev(ix, c, (uint32_t)ncand, use_hist, c.dStage.p, &timed_hamming));
     VT_TRY(copy_first_block());
-    gather = &c.dStage.p->e[0].row;
-    gather_stride = sizeof(vt::Entry) / sizeof(uint32_t);
+    gather = gather_of(c.dStage.p);
   } else if (use_hist) {
     if (local) return VT_ERR_ARGUMENT;  // callers keep one-round searches to candidates <= kMaxFusedK
     // up to 4 096 candidates (limit * 10 for limit <= 409): the exact candidate SET as a
@@ -151,8 +138,7 @@ int quantized_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t cand
     VT_TRY(c.dListPay.ensure(k1));
     VT_HIP(vt::launch_select_list(c.dPartKeys.p, c.dPartPay.p, kHammingListCap, c.dHamCount.p, k1, c.dListKeys.p, c.dListPay.p,
                                   c.stream));
-    gather = &c.dListPay.p->row;
-    gather_stride = sizeof(vt::Payload) / sizeof(uint32_t);
+    gather = gather_of(c.dListPay.p);
   } else {
     // stage 1: binary_top_k (search.rs:76-92), candidate rows via the host
     std::vector<vt::Entry> cand;
@@ -163,47 +149,22 @@ int quantized_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t cand
     VT_TRY(c.dRows.ensure(rows.size()));
     VT_HIP(hipMemcpyAsync(c.dRows.p, rows.data(), rows.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
     VT_HIP(hipStreamSynchronize(c.stream));  // `rows` is pageable and dies with this scope
-    gather = c.dRows.p;
+    gather = gather_of(c.dRows.p);
   }
   // stage 2: vector_top_k over the candidates (search.rs:38-73)
   if (ix->metric == VT_COSINE) {
-    VT_TRY(c.dCandKeys.ensure(ncand));
-    VT_TRY(c.dCandPay.ensure(ncand));
-    vt::CosineRerankArgs a{};
-    a.X = ix->dX;
-    a.stride = ix->ld;
-    a.q = c.qsrc;
-    a.id_rank = ix->dRank.p;
-    a.gather = gather;
-    a.gather_stride = gather_stride;
-    a.n = (uint32_t)ncand;
-    a.d = d;
-    a.out_keys = c.dCandKeys.p;
-    a.out_pay = c.dCandPay.p;
-    a.status = c.dStatus.p;
+    VT_TRY(c.ensure_cand_lists(ncand));
+    vt::CosineRerankArgs a = cosine_rerank_args(ix, c, d);
+    set_gather(a, gather, (uint32_t)ncand);
     VT_HIP(vt::launch_cosine_rerank(a, c.stream));
     VT_TRY(collect_from_keys(c, c.dCandKeys.p, c.dCandPay.p, (uint32_t)ncand, keep, entries));
   } else {
-    ScanJob j{};
-    j.X = ix->dX;
-    j.stride = ix->ld;
-    j.id_rank = ix->dRank.p;
-    j.gather = gather;
-    j.gather_stride = gather_stride;
-    j.n = (uint32_t)ncand;
-    j.d = d;
-    j.metric = ix->metric;
-    j.order = ix->order;
+    vt::ScanArgs j = scan_args(ix, c, d);
+    set_gather(j, gather, (uint32_t)ncand);
     j.q_nonzero = qnz;
     VT_TRY(run_scan(c, j, keep, entries, false));
   }
-  if (timed_hamming) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    c.prof.hamming_launches += 1;
-    c.prof.hamming_ms += ms;
-    c.prof.hamming_bytes += (uint64_t)ix->n * words * 8;
-  }
+  if (timed_hamming) VT_TRY(c.book_hamming(1, (uint64_t)ix->n * words * 8));
   if (local) {
     if (first_in_block) entries_of_block(c.hFirst.p, first);  // (every path above ends in a stream sync)
     local->gens.assign(1, std::move(first));
@@ -299,8 +260,7 @@ int quantized_group(Shard *ix, Ctx &c, const float *queries, const std::vector<s
   VT_TRY(c.dDist16.ensure((size_t)vt::kHammingMultiMax * dist_stride));  // dist[row][8]
   VT_TRY(c.dHamHist.ensure(std::max<size_t>((size_t)nq * hist_stride, 2 * 8192)));
   VT_TRY(c.dHamCount.ensure(vt::kHammingMultiMax));
-  VT_TRY(c.dPartKeys.ensure((size_t)nq * kListCap));
-  VT_TRY(c.dPartPay.ensure((size_t)nq * kListCap));
+  VT_TRY(c.ensure_part_lists((size_t)nq * kListCap));
   VT_TRY(c.dStageB.ensure(nq));
   // results through the host mapping (no D2H copies): [nq][k2] entries, then nq counts, then the status word
   const size_t res_bytes = (size_t)nslots * gs.res_bytes;
@@ -348,9 +308,9 @@ int quantized_group(Shard *ix, Ctx &c, const float *queries, const std::vector<s
   // (more waves per CU than the single pass keeps: eight queries' scalar loads and popcounts per tile
   // want their latency hidden -- 0.230 ms at 2 blocks per CU, 0.210 at 4, N = 10 M)
   const uint32_t blocks = c.grid_for((n + 63) / 64, vt::hamming_multi_lds_bytes(d, words, nq), std::max(4, c.hamming_blocks_per_cu));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   VT_HIP(vt::launch_hamming_dist_multi(h, blocks, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   vt::HammingCollectArgs g{};
   g.dist = c.dDist16.p;
   g.id_rank = ix->dRank.p;
@@ -370,48 +330,27 @@ int quantized_group(Shard *ix, Ctx &c, const float *queries, const std::vector<s
   VT_HIP(vt::launch_select_lists(c.dPartKeys.p, c.dPartPay.p, nq, kListCap, c.dHamCount.p, k1, c.dStageB.p,
                                  (uint32_t)sizeof(ResultBlock), c.stream));
   // stage 2: vector_top_k over each query's candidates (search.rs:38-73)
-  const uint32_t gather_qstride = (uint32_t)(sizeof(ResultBlock) / sizeof(uint32_t));
   if (ix->metric == VT_COSINE) {
-    VT_TRY(c.dCandKeys.ensure((size_t)nq * k1));
-    VT_TRY(c.dCandPay.ensure((size_t)nq * k1));
-    vt::CosineRerankArgs a{};
-    a.X = ix->dX;
-    a.stride = ix->ld;
+    VT_TRY(c.ensure_cand_lists((size_t)nq * k1));
+    vt::CosineRerankArgs a = cosine_rerank_args(ix, c, d);
     a.q = dq;
-    a.id_rank = ix->dRank.p;
-    a.gather = &c.dStageB.p->e[0].row;
-    a.gather_stride = sizeof(vt::Entry) / sizeof(uint32_t);
-    a.n = k1;
-    a.d = d;
-    a.out_keys = c.dCandKeys.p;
-    a.out_pay = c.dCandPay.p;
-    a.status = c.dStatus.p;
+    set_gather(a, gather_of(c.dStageB.p), k1);
     a.q_stride = ld;
-    a.gather_qstride = gather_qstride;
+    a.gather_qstride = kBlockGatherWords;
     VT_HIP(vt::launch_cosine_rerank_batch(a, nq, c.stream));
     VT_HIP(vt::launch_batch_select(c.dCandKeys.p, c.dCandPay.p, nq, k1, k2, dOut, dOutCount, c.stream));
   } else {
     constexpr uint32_t kBlocksPerQuery = 2;
-    VT_TRY(c.dCandKeys.ensure((size_t)nq * kBlocksPerQuery * k2));
-    VT_TRY(c.dCandPay.ensure((size_t)nq * kBlocksPerQuery * k2));
+    VT_TRY(c.ensure_cand_lists((size_t)nq * kBlocksPerQuery * k2));
     // the stage-1 blocks are 4 112 bytes apart = 257 entries of 16: K1's batch mode walks query y's
     // list at gather + y * batch_cap * gather_stride
     static_assert(sizeof(ResultBlock) == 257 * sizeof(vt::Entry), "stage blocks as K1 batch lists");
-    vt::ScanArgs sa{};
-    sa.X = ix->dX;
-    sa.stride = ix->ld;
+    vt::ScanArgs sa = scan_args(ix, c, d);
     sa.q = dq;
-    sa.id_rank = ix->dRank.p;
-    sa.gather = &c.dStageB.p->e[0].row;
-    sa.gather_stride = sizeof(vt::Entry) / sizeof(uint32_t);
-    sa.n = 257;
-    sa.d = d;
-    sa.metric = ix->metric;
-    sa.order = ix->order;
+    set_gather(sa, gather_of(c.dStageB.p), 257);
     sa.k = k2;
     sa.part_keys = c.dCandKeys.p;
     sa.part_pay = c.dCandPay.p;
-    sa.status = c.dStatus.p;
     sa.batch_counts = dcounts;
     sa.batch_cap = 257;
     // (jaccard needs the query's non-zero count: one value per launch, so those go query by query)
@@ -424,11 +363,7 @@ int quantized_group(Shard *ix, Ctx &c, const float *queries, const std::vector<s
   if (defer) return VT_OK;
   VT_HIP(hipStreamSynchronize(c.stream));
   if (c.profiling) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    c.prof.hamming_launches += 1;
-    c.prof.hamming_ms += ms;
-    c.prof.hamming_bytes += (uint64_t)n * words * 8;
+    VT_TRY(c.book_hamming(1, (uint64_t)n * words * 8));
     c.prof.hamming_queries += nq;
   }
   return quantized_group_finish(ix, c, gs, which, k2, out);

@@ -226,9 +226,9 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   a.k = kp;
   a.part_keys = c.dSkKeys.p;
   a.part_pay = c.dSkPay.p;
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   VT_HIP(vt::launch_sketch_scan(a, blocks, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   vt::SketchTailArgs ta{};
   ta.keys = c.dSkKeys.p;
   ta.pay = c.dSkPay.p;
@@ -252,23 +252,11 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   VT_HIP(hipStreamSynchronize(c.stream));
   if (c.hSkInfo.p[0] == 2u) {
     // more candidates than the tail's block takes: K1 itself (GENERAL, the count read on the device), then its select
-    VT_TRY(c.dPartKeys.ensure((size_t)kSketchRescoreBlocks * k));
-    VT_TRY(c.dPartPay.ensure((size_t)kSketchRescoreBlocks * k));
-    vt::ScanArgs sa{};
-    sa.X = ix->dX;
-    sa.stride = ld;
-    sa.q = c.qsrc;
-    sa.id_rank = ix->dRank.p;
-    sa.gather = c.dSkRows.p;
-    sa.gather_stride = 1;
-    sa.n = kSketchCandCap;
-    sa.d = d;
-    sa.metric = ix->metric;
-    sa.order = ix->order;
+    VT_TRY(c.ensure_part_lists((size_t)kSketchRescoreBlocks * k));
+    vt::ScanArgs sa = scan_args(ix, c, d);
+    set_gather(sa, gather_of(c.dSkRows.p), kSketchCandCap);  // (the list's room: the count is batch_counts[0])
     sa.k = k;
-    sa.part_keys = c.dPartKeys.p;
-    sa.part_pay = c.dPartPay.p;
-    sa.status = c.dStatus.p;
+    use_part_lists(sa, c);
     sa.batch_counts = c.dSkCount.p;
     sa.batch_cap = kSketchCandCap;
     VT_HIP(vt::launch_scan_batch(sa, kSketchRescoreBlocks, 1, c.stream));
@@ -279,17 +267,14 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   const bool certified = c.hSkInfo.p[0] != 0u && c.hRes.p->status == 0;
   if (c.profiling) {
     float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+    VT_TRY(c.span_ms(&ms));
     const uint64_t bytes = (uint64_t)vt::sketch_bytes(ix->n, d);
     c.prof.sketch_launches += 1;
     c.prof.sketch_ms += ms;
     c.prof.sketch_bytes += bytes;
     c.prof.sketch_candidates += c.hSkInfo.p[1];
     c.prof.sketch_tail_rescored += c.hSkInfo.p[0] == 1u ? 1 : 0;
-    c.prof.scan_launches += 1;
-    c.prof.scan_ms += ms;
-    c.prof.scan_rows += ix->n;
-    c.prof.scan_bytes += bytes;
+    VT_TRY(c.book_scan(1, ix->n, bytes));
   }
   if (!certified) {
     c.prof.sketch_fallbacks += 1;
@@ -331,16 +316,7 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
   const bool by_pattern = pattern_search_applies(ix, limit) && !shard_stale(ix, NEED_NZBITS, limit);
   uint32_t qnz = 0;
   VT_TRY(upload_query(c, query, n, &qnz, by_pattern ? 2 : 0));
-  ScanJob j{};
-  j.X = ix->dX;
-  j.stride = ix->ld;
-  j.id_rank = ix->dRank.p;
-  j.gather = nullptr;
-  j.gather_stride = 0;
-  j.n = ix->n;
-  j.d = (uint32_t)ix->dim;
-  j.metric = ix->metric;
-  j.order = ix->order;
+  vt::ScanArgs j = scan_args(ix, c, (uint32_t)ix->dim);
   j.q_nonzero = qnz;
   std::vector<vt::Entry> entries;
   auto best_rows = [&](size_t want) -> int {
@@ -395,81 +371,32 @@ int run_cosine_scan(Ctx &c, Shard *ix, uint32_t d, double qq, size_t want, std::
   if (out.empty() && threshold_applies(total, ix->n, (double)ix->n * vt::padded_dim(d) * 4.0, 90e-6)) {
     const uint32_t k = (uint32_t)total;
     VT_TRY(c.dKeyCol.ensure(((size_t)ix->n + 1) / 2 * 2));
-    VT_TRY(c.dPartKeys.ensure(kThresholdListCap));
-    VT_TRY(c.dPartPay.ensure(kThresholdListCap));
-    vt::CosineScanArgs a{};
-    a.X = ix->dX;
-    a.stride = ix->ld;
-    a.q = c.qsrc;
-    a.qq = qq;
-    a.id_rank = ix->dRank.p;
-    a.n = ix->n;
-    a.d = d;
+    VT_TRY(c.ensure_part_lists(kThresholdListCap));  // (threshold_rows' list: the scan's own lists are shorter)
+    vt::CosineScanArgs a = cosine_scan_args(ix, c, d, qq);
     a.k = 1;
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
-    a.status = c.dStatus.p;
     a.key_out = c.dKeyCol.p;
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
-    VT_HIP(vt::launch_cosine_scan(a, c.grid_for((ix->n + 63) / 64, vt::cosine_scan_lds_bytes(d, 1)), c.stream));
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+    uint32_t blocks = 0;
+    VT_TRY(cosine_scan_all(c, a, &blocks));
     VT_TRY(threshold_rows(c, ix->n, k));
-    VT_TRY(c.dCandKeys.ensure(k));
-    VT_TRY(c.dCandPay.ensure(k));
-    vt::CosineRerankArgs g{};
-    g.X = ix->dX;
-    g.stride = ix->ld;
-    g.q = c.qsrc;
-    g.id_rank = ix->dRank.p;
-    g.gather = &c.dListPay.p->row;
-    g.gather_stride = sizeof(vt::Payload) / sizeof(uint32_t);
-    g.n = k;
-    g.d = d;
-    g.out_keys = c.dCandKeys.p;
-    g.out_pay = c.dCandPay.p;
-    g.status = c.dStatus.p;
+    VT_TRY(c.ensure_cand_lists(k));
+    vt::CosineRerankArgs g = cosine_rerank_args(ix, c, d);
+    set_gather(g, gather_of(c.dListPay.p), k);
     VT_HIP(vt::launch_cosine_rerank(g, c.stream));
     const int rc = collect_sorted_list(c, c.dCandKeys.p, c.dCandPay.p, k, out);
-    if (c.profiling && rc != kRetryInternal) {
-      float ms = 0.0f;
-      VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-      c.prof.prefix_launches += 1;
-      c.prof.prefix_ms += ms;
-      c.prof.prefix_bytes += (uint64_t)ix->n * d * 4;
-    }
+    if (c.profiling && rc != kRetryInternal) VT_TRY(c.book_prefix((uint64_t)ix->n * d * 4));
     if (rc != kRetryInternal) return rc;
     out.clear();
   }
   while (out.size() < total) {
     const uint32_t k = (uint32_t)std::min<size_t>(kmax, total - out.size());
-    const uint32_t blocks = c.grid_for((ix->n + 63) / 64, vt::cosine_scan_lds_bytes(d, k));
-    VT_TRY(c.dPartKeys.ensure((size_t)blocks * k));
-    VT_TRY(c.dPartPay.ensure((size_t)blocks * k));
-    vt::CosineScanArgs a{};
-    a.X = ix->dX;
-    a.stride = ix->ld;
-    a.q = c.qsrc;
-    a.qq = qq;
-    a.id_rank = ix->dRank.p;
-    a.n = ix->n;
-    a.d = d;
+    vt::CosineScanArgs a = cosine_scan_args(ix, c, d, qq);
     a.k = k;
     a.lo_key = lo;
     a.has_lo = has_lo ? 1 : 0;
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
-    a.status = c.dStatus.p;
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
-    VT_HIP(vt::launch_cosine_scan(a, blocks, c.stream));
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+    uint32_t blocks = 0;
+    VT_TRY(cosine_scan_all(c, a, &blocks));
     VT_TRY(select_pass(c, c.dPartKeys.p, c.dPartPay.p, blocks * k, k, 0, false));
-    if (c.profiling) {
-      float ms = 0.0f;
-      VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-      c.prof.prefix_launches += 1;
-      c.prof.prefix_ms += ms;
-      c.prof.prefix_bytes += (uint64_t)ix->n * d * 4;
-    }
+    if (c.profiling) VT_TRY(c.book_prefix((uint64_t)ix->n * d * 4));
     if (c.hRes.p->status == VT_ERR_OVERFLOW) return VT_ERR_OVERFLOW;
     const uint32_t got = c.hRes.p->count;
     for (uint32_t i = 0; i < got; ++i) out.push_back(c.hRes.p->e[i]);
@@ -504,36 +431,17 @@ int funnel_stage(Shard *ix, Ctx &c, const float *query, uint32_t d, const std::v
     double qq = 0.0;  // f64_dot(q, q) over the prefix (distances.rs:179-185)
     for (uint32_t j = 0; j < d; ++j) qq += (double)query[j] * (double)query[j];
     if (all_rows) return run_cosine_scan(c, ix, d, qq, want, out);
-    VT_TRY(c.dCandKeys.ensure(rows.size()));
-    VT_TRY(c.dCandPay.ensure(rows.size()));
-    vt::CosineRerankArgs a{};
-    a.X = ix->dX;
-    a.stride = ix->ld;
-    a.q = c.qsrc;
-    a.id_rank = ix->dRank.p;
-    a.gather = c.dRows.p;
-    a.gather_stride = 1;
-    a.n = (uint32_t)rows.size();
-    a.d = d;
-    a.out_keys = c.dCandKeys.p;
-    a.out_pay = c.dCandPay.p;
-    a.status = c.dStatus.p;
+    VT_TRY(c.ensure_cand_lists(rows.size()));
+    vt::CosineRerankArgs a = cosine_rerank_args(ix, c, d);
+    set_gather(a, gather_of(c.dRows.p), (uint32_t)rows.size());
     VT_HIP(vt::launch_cosine_rerank(a, c.stream));
     return collect_from_keys(c, c.dCandKeys.p, c.dCandPay.p, (uint32_t)rows.size(), want, out);
   }
   if (all_rows && pattern_stage_applies(ix, c, want))
     return run_hamming(c, ix->nz_bits.buf.p, c.dQbits, ix->dRank.p, ix->n, d, want, out, true, ix->metric == VT_JACCARD,
                        (((uint32_t)ix->dim + 63) / 64 + 1) / 2);
-  ScanJob j{};
-  j.X = ix->dX;
-  j.stride = ix->ld;
-  j.id_rank = ix->dRank.p;
-  j.gather = all_rows ? nullptr : c.dRows.p;
-  j.gather_stride = 1;
-  j.n = all_rows ? ix->n : (uint32_t)rows.size();
-  j.d = d;
-  j.metric = ix->metric;
-  j.order = ix->order;
+  vt::ScanArgs j = scan_args(ix, c, d);
+  if (!all_rows) set_gather(j, gather_of(c.dRows.p), (uint32_t)rows.size());
   j.q_nonzero = qnz;
   return run_scan(c, j, want, out, false);
 }
@@ -544,72 +452,28 @@ int funnel_stage(Shard *ix, Ctx &c, const float *query, uint32_t d, const std::v
 // for; an overflow flag stays in c.dStatus until a select with `last` moves it into its block.
 int scan_stage_dev(Shard *ix, Ctx &c, uint32_t d, const ResultBlock *src, uint32_t count, uint32_t want, uint32_t qnz,
                    ResultBlock *dst, bool last) {
-  const uint32_t *gather = src ? &src->e[0].row : nullptr;
-  const uint32_t gstride = sizeof(vt::Entry) / sizeof(uint32_t);
   int *status = last ? c.dStatus.p : nullptr;
   if (!src && pattern_stage_applies(ix, c, want)) {
     // all rows under float hamming / jaccard: the non-zero bits of the prefix (K4) instead of the rows
-    const uint32_t words = (d + 63) / 64;
     const uint32_t hblocks = c.grid_for((ix->n + 63) / 64, vt::hamming_lds_bytes(want), c.hamming_blocks_per_cu);
     const uint32_t hlists = vt::scan_lists(hblocks);
-    VT_TRY(c.dPartKeys.ensure((size_t)hlists * want));
-    VT_TRY(c.dPartPay.ensure((size_t)hlists * want));
-    vt::HammingArgs h{};
-    h.bits = ix->nz_bits.buf.p;
-    h.qbits = c.dQbits;
-    h.id_rank = ix->dRank.p;
-    h.n = ix->n;
-    h.words = words;
-    h.pairs = (words + 1) / 2;
-    h.d = d;
+    VT_TRY(c.ensure_part_lists((size_t)hlists * want));
+    vt::HammingArgs h = pattern_prefix_args(ix, c, d);
     h.k = want;
-    h.part_keys = c.dPartKeys.p;
-    h.part_pay = c.dPartPay.p;
-    h.jaccard = ix->metric == VT_JACCARD ? 1 : 0;
-    h.tile_pairs = (((uint32_t)ix->dim + 63) / 64 + 1) / 2;
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+    use_part_lists(h, c);
+    VT_TRY(c.mark_begin());
     VT_HIP(vt::launch_hamming(h, hblocks, c.stream));
-    if (c.profiling) {
-      VT_HIP(hipEventRecord(c.ev1, c.stream));
-      c.prefix_pending += 1;
-      c.prof.prefix_bytes += (uint64_t)ix->n * words * 8;
-    }
+    VT_TRY(c.mark_end());
+    c.defer_prefix(c.profiling, (uint64_t)ix->n * h.words * 8);
     VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, hlists * want, want, 0, 0, status, dst, c.dSelKeys.p, c.dSelPay.p, c.stream));
     return VT_OK;
   }
-  const uint32_t tile_rows = vt::scan_tile_rows(count, d, c.resident_waves());
-  const uint32_t ntiles = (count + tile_rows - 1) / tile_rows;
-  const uint32_t blocks = c.grid_for(ntiles, vt::scan_lds_bytes(d, want));
-  const uint32_t lists = vt::scan_lists(blocks);
-  VT_TRY(c.dPartKeys.ensure((size_t)lists * want));
-  VT_TRY(c.dPartPay.ensure((size_t)lists * want));
-  vt::ScanArgs a{};
-  a.X = ix->dX;
-  a.stride = ix->ld;
-  a.q = c.qsrc;
-  a.id_rank = ix->dRank.p;
-  a.gather = gather;
-  a.gather_stride = gather ? gstride : 0;
-  a.n = count;
-  a.d = d;
-  a.metric = ix->metric;
-  a.order = ix->order;
-  a.k = want;
+  vt::ScanArgs a = scan_args(ix, c, d);  // (all rows: count == ix->n)
+  if (src) set_gather(a, gather_of(src), count);
   a.q_nonzero = qnz;
-  a.tile_rows = tile_rows;
-  a.part_keys = c.dPartKeys.p;
-  a.part_pay = c.dPartPay.p;
-  a.status = c.dStatus.p;
   const bool timed = c.profiling && !src && d < (uint32_t)ix->dim;  // a sweep of every row's prefix: priced like the cosine one
-  if (timed) VT_HIP(hipEventRecord(c.ev0, c.stream));
-  VT_HIP(vt::launch_scan(a, blocks, c.stream));
-  if (timed) {
-    VT_HIP(hipEventRecord(c.ev1, c.stream));
-    c.prefix_pending += 1;
-    c.prof.prefix_bytes += (uint64_t)ix->n * d * 4;
-  }
-  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, lists * want, want, 0, 0, status, dst, c.dSelKeys.p, c.dSelPay.p,
-                           c.stream));
+  VT_TRY(scan_to_block(c, a, want, timed, status, dst));
+  c.defer_prefix(timed, (uint64_t)ix->n * d * 4);
   return VT_OK;
 }
 
@@ -621,58 +485,26 @@ int scan_stage_dev(Shard *ix, Ctx &c, uint32_t d, const ResultBlock *src, uint32
 int funnel_stage_dev(Shard *ix, Ctx &c, const float *query, uint32_t d, const ResultBlock *src, uint32_t count,
                      uint32_t want, uint32_t qnz, ResultBlock *dst, bool last) {
   if (ix->metric != VT_COSINE) return scan_stage_dev(ix, c, d, src, count, want, qnz, dst, last);
-  const uint32_t *gather = src ? &src->e[0].row : nullptr;
-  const uint32_t gstride = sizeof(vt::Entry) / sizeof(uint32_t);
   int *status = last ? c.dStatus.p : nullptr;
-  {
-    double qq = 0.0;  // f64_dot(q, q) over the prefix (distances.rs:179-185)
-    for (uint32_t j = 0; j < d; ++j) qq += (double)query[j] * (double)query[j];
-    if (!src) {
-      const uint32_t blocks = c.grid_for((ix->n + 63) / 64, vt::cosine_scan_lds_bytes(d, want));
-      VT_TRY(c.dPartKeys.ensure((size_t)blocks * want));
-      VT_TRY(c.dPartPay.ensure((size_t)blocks * want));
-      vt::CosineScanArgs a{};
-      a.X = ix->dX;
-      a.stride = ix->ld;
-      a.q = c.qsrc;
-      a.qq = qq;
-      a.id_rank = ix->dRank.p;
-      a.n = ix->n;
-      a.d = d;
-      a.k = want;
-      a.part_keys = c.dPartKeys.p;
-      a.part_pay = c.dPartPay.p;
-      a.status = c.dStatus.p;
-      if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
-      VT_HIP(vt::launch_cosine_scan(a, blocks, c.stream));
-      if (c.profiling) {
-        VT_HIP(hipEventRecord(c.ev1, c.stream));
-        c.prefix_pending += 1;
-        c.prof.prefix_bytes += (uint64_t)ix->n * d * 4;
-      }
-      VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, blocks * want, want, 0, 0, status, dst, c.dSelKeys.p,
-                               c.dSelPay.p, c.stream));
-      return VT_OK;
-    }
-    VT_TRY(c.dCandKeys.ensure(count));
-    VT_TRY(c.dCandPay.ensure(count));
-    vt::CosineRerankArgs a{};
-    a.X = ix->dX;
-    a.stride = ix->ld;
-    a.q = c.qsrc;
-    a.id_rank = ix->dRank.p;
-    a.gather = gather;
-    a.gather_stride = gstride;
-    a.n = count;
-    a.d = d;
-    a.out_keys = c.dCandKeys.p;
-    a.out_pay = c.dCandPay.p;
-    a.status = c.dStatus.p;
-    VT_HIP(vt::launch_cosine_rerank(a, c.stream));
-    VT_HIP(vt::launch_select(c.dCandKeys.p, c.dCandPay.p, count, want, 0, 0, status, dst, c.dSelKeys.p, c.dSelPay.p,
-                             c.stream));
+  double qq = 0.0;  // f64_dot(q, q) over the prefix (distances.rs:179-185)
+  for (uint32_t j = 0; j < d; ++j) qq += (double)query[j] * (double)query[j];
+  if (!src) {
+    vt::CosineScanArgs a = cosine_scan_args(ix, c, d, qq);
+    a.k = want;
+    uint32_t blocks = 0;
+    VT_TRY(cosine_scan_all(c, a, &blocks));
+    c.defer_prefix(c.profiling, (uint64_t)ix->n * d * 4);
+    VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, blocks * want, want, 0, 0, status, dst, c.dSelKeys.p,
+                             c.dSelPay.p, c.stream));
     return VT_OK;
   }
+  VT_TRY(c.ensure_cand_lists(count));
+  vt::CosineRerankArgs a = cosine_rerank_args(ix, c, d);
+  set_gather(a, gather_of(src), count);
+  VT_HIP(vt::launch_cosine_rerank(a, c.stream));
+  VT_HIP(vt::launch_select(c.dCandKeys.p, c.dCandPay.p, count, want, 0, 0, status, dst, c.dSelKeys.p, c.dSelPay.p,
+                           c.stream));
+  return VT_OK;
 }
 
 // True when every stage of a funnel fits one fused pass on the device.
@@ -795,15 +627,15 @@ int index_ensure_shadow(Shard *ix, size_t elems) {
   }
   // (the slab's rows [0, cap) -> the whole image)
   const uint32_t rows_img = (uint32_t)(elems / ix->ld);
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin());
   VT_HIP(vt::launch_shadow_build(ix->dX, ix->ld, ix->cap, rows_img, ix->ld, col.buf.p, c.stream));
-  if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end());
   // current from here on, for readers on other streams too: the build has finished before the
   // exclusive lock can drop
   VT_HIP(hipStreamSynchronize(c.stream));
   if (c.profiling) {
     float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+    VT_TRY(c.span_ms(&ms));
     c.prof.shadow_builds += 1;
     c.prof.shadow_build_ms += ms;
   }

@@ -71,19 +71,6 @@ int collect_sorted_list(Ctx &c, const uint64_t *keys, const vt::Payload *pay, ui
   return VT_OK;
 }
 
-struct ScanJob {
-  const float *X;
-  size_t stride;
-  const uint32_t *id_rank;
-  const uint32_t *gather;
-  uint32_t gather_stride;
-  uint32_t n;
-  uint32_t d;
-  int metric;
-  int order;
-  uint32_t q_nonzero;
-};
-
 // Limits above kMaxFusedK in ONE scan: the scan has written a key per row into c.dKeyCol;
 // three radix passes + a collect pass + one list select leave the exact `k` best rows,
 // unsorted, in c.dListPay (Payload.row = position in the key column).
@@ -119,19 +106,16 @@ int threshold_big(Ctx &c, const vt::ScanArgs &scan, uint32_t blocks, uint32_t n,
   VT_TRY(c.dPayCol.ensure(n));
   VT_TRY(c.dRadixHist.ensure(6 * vt::kRadixBins));
   VT_TRY(c.dRadixCount.ensure(1));
-  if (!all_rows) {
-    VT_TRY(c.dPartKeys.ensure(cap));
-    VT_TRY(c.dPartPay.ensure(cap));
-  }
+  if (!all_rows) VT_TRY(c.ensure_part_lists(cap));
   VT_TRY(c.hListKeys.ensure(cap));
   VT_TRY(c.hListPay.ensure(cap));
   vt::ScanArgs a = scan;
   a.k = 1;
   a.key_out = c.dKeyCol.p;
   a.pay_out = c.dPayCol.p;
-  if (timed) VT_HIP(hipEventRecord(c.ev0, c.stream));
+  VT_TRY(c.mark_begin(timed));
   VT_HIP(vt::launch_scan(a, blocks, c.stream));
-  if (timed) VT_HIP(hipEventRecord(c.ev1, c.stream));
+  VT_TRY(c.mark_end(timed));
   uint32_t count = 0;
   int status = 0;
   if (!all_rows) {
@@ -156,14 +140,7 @@ int threshold_big(Ctx &c, const vt::ScanArgs &scan, uint32_t blocks, uint32_t n,
   VT_HIP(hipMemcpyAsync(&status, c.dStatus.p, sizeof(status), hipMemcpyDeviceToHost, c.stream));
   VT_HIP(hipMemsetAsync(c.dStatus.p, 0, sizeof(int), c.stream));
   VT_HIP(hipStreamSynchronize(c.stream));
-  if (timed) {
-    float ms = 0.f;
-    VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    c.prof.scan_launches += 1;
-    c.prof.scan_ms += ms;
-    c.prof.scan_rows += n;
-    c.prof.scan_bytes += (uint64_t)n * d * 4;
-  }
+  if (timed) VT_TRY(c.book_scan(1, n, (uint64_t)n * d * 4));
   if (status == VT_ERR_OVERFLOW) return VT_ERR_OVERFLOW;
   if (all_rows) count = n;
   else if (status == vt::kStatusRetry || count > cap) return kRetryInternal;
@@ -192,8 +169,7 @@ int threshold_big(Ctx &c, const vt::ScanArgs &scan, uint32_t blocks, uint32_t n,
 int threshold_rows(Ctx &c, uint32_t n, uint32_t k) {
   VT_TRY(c.dRadixHist.ensure(6 * vt::kRadixBins));
   VT_TRY(c.dRadixCount.ensure(1));
-  VT_TRY(c.dPartKeys.ensure(kThresholdListCap));
-  VT_TRY(c.dPartPay.ensure(kThresholdListCap));
+  VT_TRY(c.ensure_part_lists(kThresholdListCap));
   VT_TRY(c.dListKeys.ensure(k));
   VT_TRY(c.dListPay.ensure(k));
   VT_HIP(hipMemsetAsync(c.dRadixHist.p, 0, 6 * vt::kRadixBins * sizeof(uint32_t), c.stream));
@@ -221,128 +197,73 @@ int threshold_rows(Ctx &c, uint32_t n, uint32_t k) {
 }
 
 // Scan + select passes until `want` hits are collected (ascending by key).
-// The query must already be in c.dQ (padded to padded_dim(d)).
-int run_scan(Ctx &c, const ScanJob &j, size_t want, std::vector<vt::Entry> &out, bool count_profile) {
-  if (vt::scan_lds_bytes(j.d, 1) == 0)
-    return fail(VT_ERR_UNSUPPORTED, "dimension " + std::to_string(j.d) + " exceeds what the scan kernel stages in LDS");
-  const uint32_t tile_rows = vt::scan_tile_rows(j.n, j.d, c.resident_waves());
-  const uint32_t ntiles = (j.n + tile_rows - 1) / tile_rows;
+// `job`: scan_args for the rows plus what the caller adds -- its gather list, q_nonzero; every pass below is a copy of it
+// with its own k, lower bound, tile size, lists and key column.  The query must already be in c.dQ (padded to
+// padded_dim(d)).
+int run_scan(Ctx &c, const vt::ScanArgs &job, size_t want, std::vector<vt::Entry> &out, bool count_profile) {
+  const uint32_t n = job.n, d = job.d;
+  if (vt::scan_lds_bytes(d, 1) == 0)
+    return fail(VT_ERR_UNSUPPORTED, "dimension " + std::to_string(d) + " exceeds what the scan kernel stages in LDS");
+  const uint32_t tile_rows = vt::scan_tile_rows(n, d, c.resident_waves());
+  const uint32_t ntiles = (n + tile_rows - 1) / tile_rows;
   // very wide rows leave no LDS for the large candidate buffer: smaller passes
-  const size_t kmax = vt::scan_lds_bytes(j.d, vt::kMaxFusedK) ? (size_t)vt::kMaxFusedK : (size_t)vt::kSmallK;
+  const size_t kmax = vt::scan_lds_bytes(d, vt::kMaxFusedK) ? (size_t)vt::kMaxFusedK : (size_t)vt::kSmallK;
   uint64_t lo = 0;
   bool has_lo = false;
-  const size_t total = std::min<size_t>(want, j.n);
-  if (!j.gather && out.empty() && total > (size_t)vt::kSelListMax && j.n >= kThresholdMinRows) {
-    vt::ScanArgs a{};
-    a.X = j.X;
-    a.stride = j.stride;
-    a.q = c.qsrc;
-    a.id_rank = j.id_rank;
-    a.n = j.n;
-    a.d = j.d;
-    a.metric = j.metric;
-    a.order = j.order;
-    a.q_nonzero = j.q_nonzero;
-    a.tile_rows = tile_rows;
-    a.part_keys = c.dPartKeys.p;  // (unused in key-column mode)
-    a.part_pay = c.dPartPay.p;
-    a.status = c.dStatus.p;
-    VT_TRY(c.dPartKeys.ensure(kThresholdListCap));
-    VT_TRY(c.dPartPay.ensure(kThresholdListCap));
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
-    const int rc = threshold_big(c, a, c.grid_for(ntiles, vt::scan_lds_bytes(j.d, 1)), j.n, (uint32_t)total,
-                                 c.profiling && count_profile, j.d, out);
+  const size_t total = std::min<size_t>(want, n);
+  const bool timed = c.profiling && count_profile;
+  vt::ScanArgs base = job;
+  base.tile_rows = tile_rows;
+  if (!job.gather && out.empty() && total > (size_t)vt::kSelListMax && n >= kThresholdMinRows) {
+    VT_TRY(c.ensure_part_lists(kThresholdListCap));
+    vt::ScanArgs a = base;
+    use_part_lists(a, c);  // (unused in key-column mode)
+    const int rc = threshold_big(c, a, c.grid_for(ntiles, vt::scan_lds_bytes(d, 1)), n, (uint32_t)total, timed, d, out);
     if (rc != kRetryInternal) return rc;
     out.clear();  // more equal keys at the threshold than the list holds: the pass-per-256 loop below
   }
-  if (!j.gather && out.empty() && threshold_applies(total, j.n, (double)j.n * vt::padded_dim(j.d) * 4.0)) {
+  if (!job.gather && out.empty() && threshold_applies(total, n, (double)n * vt::padded_dim(d) * 4.0)) {
     // one scan in key-column mode, exact threshold on the device, then the winners are
     // re-scored through the gather list for their raw values and sorted
     const uint32_t k = (uint32_t)total;
-    VT_TRY(c.dKeyCol.ensure(((size_t)j.n + 1) / 2 * 2));
-    VT_TRY(c.dPartKeys.ensure(kThresholdListCap));
-    VT_TRY(c.dPartPay.ensure(kThresholdListCap));
-    vt::ScanArgs a{};
-    a.X = j.X;
-    a.stride = j.stride;
-    a.q = c.qsrc;
-    a.id_rank = j.id_rank;
-    a.n = j.n;
-    a.d = j.d;
-    a.metric = j.metric;
-    a.order = j.order;
+    VT_TRY(c.dKeyCol.ensure(((size_t)n + 1) / 2 * 2));
+    VT_TRY(c.ensure_part_lists(kThresholdListCap));
+    vt::ScanArgs a = base;
     a.k = 1;
-    a.q_nonzero = j.q_nonzero;
-    a.tile_rows = tile_rows;
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
-    a.status = c.dStatus.p;
+    use_part_lists(a, c);
     a.key_out = c.dKeyCol.p;
-    const bool timed = c.profiling && count_profile;
-    if (timed) VT_HIP(hipEventRecord(c.ev0, c.stream));
-    VT_HIP(vt::launch_scan(a, c.grid_for(ntiles, vt::scan_lds_bytes(j.d, 1)), c.stream));
-    if (timed) VT_HIP(hipEventRecord(c.ev1, c.stream));
-    VT_TRY(threshold_rows(c, j.n, k));
-    VT_TRY(c.dCandKeys.ensure(k));
-    VT_TRY(c.dCandPay.ensure(k));
+    VT_TRY(c.mark_begin(timed));
+    VT_HIP(vt::launch_scan(a, c.grid_for(ntiles, vt::scan_lds_bytes(d, 1)), c.stream));
+    VT_TRY(c.mark_end(timed));
+    VT_TRY(threshold_rows(c, n, k));
+    VT_TRY(c.ensure_cand_lists(k));
     vt::ScanArgs g = a;
-    g.gather = &c.dListPay.p->row;
-    g.gather_stride = sizeof(vt::Payload) / sizeof(uint32_t);
-    g.n = k;
+    set_gather(g, gather_of(c.dListPay.p), k);
     g.tile_rows = 0;
     g.key_out = c.dCandKeys.p;
     g.pay_out = c.dCandPay.p;
-    VT_HIP(vt::launch_scan(g, c.grid_for((k + vt::kTileRows - 1) / vt::kTileRows, vt::scan_lds_bytes(j.d, 1)), c.stream));
+    VT_HIP(vt::launch_scan(g, c.grid_for((k + vt::kTileRows - 1) / vt::kTileRows, vt::scan_lds_bytes(d, 1)), c.stream));
     const int rc = collect_sorted_list(c, c.dCandKeys.p, c.dCandPay.p, k, out);
-    if (timed && rc != kRetryInternal) {
-      float ms = 0.f;
-      VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-      c.prof.scan_launches += 1;
-      c.prof.scan_ms += ms;
-      c.prof.scan_rows += j.n;
-      c.prof.scan_bytes += (uint64_t)j.n * j.d * 4;
-    }
+    if (timed && rc != kRetryInternal) VT_TRY(c.book_scan(1, n, (uint64_t)n * d * 4));
     if (rc != kRetryInternal) return rc;
     out.clear();  // more equal keys at the threshold than the list holds: the pass-per-256 loop below
   }
   while (out.size() < total) {
     const uint32_t k = (uint32_t)std::min<size_t>(kmax, total - out.size());
-    const uint32_t blocks = c.grid_for(ntiles, vt::scan_lds_bytes(j.d, k));
+    const uint32_t blocks = c.grid_for(ntiles, vt::scan_lds_bytes(d, k));
     const uint32_t waves = vt::scan_lists(blocks);
-    VT_TRY(c.dPartKeys.ensure((size_t)waves * k));
-    VT_TRY(c.dPartPay.ensure((size_t)waves * k));
-    vt::ScanArgs a{};
-    a.X = j.X;
-    a.stride = j.stride;
-    a.q = c.qsrc;
-    a.id_rank = j.id_rank;
-    a.gather = j.gather;
-    a.gather_stride = j.gather_stride;
-    a.n = j.n;
-    a.d = j.d;
-    a.metric = j.metric;
-    a.order = j.order;
+    VT_TRY(c.ensure_part_lists((size_t)waves * k));
+    vt::ScanArgs a = base;
     a.k = k;
     a.lo_key = lo;
     a.has_lo = has_lo ? 1 : 0;
-    a.q_nonzero = j.q_nonzero;
-    a.tile_rows = tile_rows;
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
-    a.status = c.dStatus.p;
-    const bool timed = c.profiling && count_profile;
-    if (timed) VT_HIP(hipEventRecord(c.ev0, c.stream));
+    use_part_lists(a, c);
+    VT_TRY(c.mark_begin(timed));
     VT_HIP(vt::launch_scan(a, blocks, c.stream));
-    if (timed) VT_HIP(hipEventRecord(c.ev1, c.stream));
+    VT_TRY(c.mark_end(timed));
     VT_TRY(select_pass(c, c.dPartKeys.p, c.dPartPay.p, waves * k, k, 0, false));
     if (timed) {
-      float ms = 0.f;
-      VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-      c.prof.scan_launches += 1;
-      c.prof.scan_ms += ms;
-      c.prof.scan_rows += j.n;
-      c.prof.scan_bytes += (uint64_t)j.n * j.d * 4;
+      VT_TRY(c.book_scan(1, n, (uint64_t)n * d * 4));
       c.prof.merge_launches += 1;
     }
     if (c.hRes.p->status == vt::kStatusRetry) return kRetryInternal;
@@ -359,7 +280,6 @@ int run_scan(Ctx &c, const ScanJob &j, size_t want, std::vector<vt::Entry> &out,
 // tile_pairs != 0: `d` is a prefix of rows whose bit tiles hold tile_pairs word pairs (HammingArgs).
 int run_hamming(Ctx &c, const uint64_t *bits, const uint64_t *qbits, const uint32_t *id_rank, uint32_t n, uint32_t d,
                 size_t want, std::vector<vt::Entry> &out, bool count_profile, bool jaccard = false, uint32_t tile_pairs = 0) {
-  const uint32_t words = (d + 63) / 64;
   const uint32_t ntiles = (n + 63) / 64;
   uint64_t lo = 0;
   bool has_lo = false;
@@ -368,34 +288,19 @@ int run_hamming(Ctx &c, const uint64_t *bits, const uint64_t *qbits, const uint3
     const uint32_t k = (uint32_t)std::min<size_t>((size_t)vt::kMaxFusedK, total - out.size());
     const uint32_t blocks = c.grid_for(ntiles, vt::hamming_lds_bytes(k), c.hamming_blocks_per_cu);
     const uint32_t waves = vt::scan_lists(blocks);
-    VT_TRY(c.dPartKeys.ensure((size_t)waves * k));
-    VT_TRY(c.dPartPay.ensure((size_t)waves * k));
-    vt::HammingArgs a{};
-    a.bits = bits;
-    a.qbits = qbits;
-    a.id_rank = id_rank;
-    a.n = n;
-    a.words = words;
-    a.pairs = (words + 1) / 2;
-    a.d = d;
+    VT_TRY(c.ensure_part_lists((size_t)waves * k));
+    vt::HammingArgs a = hamming_args(bits, qbits, id_rank, n, d);
     a.k = k;
     a.lo_key = lo;
     a.has_lo = has_lo ? 1 : 0;
-    a.part_keys = c.dPartKeys.p;
-    a.part_pay = c.dPartPay.p;
+    use_part_lists(a, c);
     a.jaccard = jaccard ? 1 : 0;
     a.tile_pairs = tile_pairs;
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev0, c.stream));
+    VT_TRY(c.mark_begin());
     VT_HIP(vt::launch_hamming(a, blocks, c.stream));
-    if (c.profiling) VT_HIP(hipEventRecord(c.ev1, c.stream));
+    VT_TRY(c.mark_end());
     VT_TRY(select_pass(c, c.dPartKeys.p, c.dPartPay.p, waves * k, k, 0, false));
-    if (c.profiling && count_profile) {
-      float ms = 0.f;
-      VT_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-      c.prof.hamming_launches += 1;
-      c.prof.hamming_ms += ms;
-      c.prof.hamming_bytes += (uint64_t)n * words * 8;
-    }
+    if (c.profiling && count_profile) VT_TRY(c.book_hamming(1, (uint64_t)n * a.words * 8));
     const uint32_t got = c.hRes.p->count;
     for (uint32_t i = 0; i < got; ++i) out.push_back(c.hRes.p->e[i]);
     if (got < k) break;

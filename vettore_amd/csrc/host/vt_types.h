@@ -122,16 +122,68 @@ struct Ctx {
     return VT_OK;
   }
   uint32_t resident_waves() const { return (uint32_t)(num_cus * blocks_per_cu * vt::kWavesPerBlock); }
-  // a prefix scan timed with ev0/ev1 but not yet read back (the chained funnel waits once, at its end)
-  uint32_t prefix_pending = 0;
-  int settle_prefix_profile() {
-    if (!prefix_pending) return VT_OK;
-    float ms = 0.0f;
-    VT_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+  // The two partial-list buffers (one list per block of a scan) are always wanted together; so are the candidate lists.
+  int ensure_part_lists(size_t entries) {
+    VT_TRY(dPartKeys.ensure(entries));
+    return dPartPay.ensure(entries);
+  }
+  int ensure_cand_lists(size_t entries) {
+    VT_TRY(dCandKeys.ensure(entries));
+    return dCandPay.ensure(entries);
+  }
+  // ---- profiling: ev0 / ev1 around a launch (nothing unless profiling, and `on`), and one routine per counter family
+  // that reads the span -- after a wait -- and books it.  A span is settled at once after the caller's wait, or later:
+  // through prefix_pending (below), or through begin_rows (vt_multi.h, settle_begin_profile).
+  int mark_begin(bool on = true) {
+    if (profiling && on) VT_HIP(hipEventRecord(ev0, stream));
+    return VT_OK;
+  }
+  int mark_end(bool on = true) {
+    if (profiling && on) VT_HIP(hipEventRecord(ev1, stream));
+    return VT_OK;
+  }
+  int span_ms(float *ms) {
+    *ms = 0.0f;
+    VT_HIP(hipEventElapsedTime(ms, ev0, ev1));
+    return VT_OK;
+  }
+  int book_scan(uint64_t launches, uint64_t rows, uint64_t bytes) {
+    float ms;
+    VT_TRY(span_ms(&ms));
+    prof.scan_launches += launches;
+    prof.scan_ms += ms;
+    prof.scan_rows += rows;
+    prof.scan_bytes += bytes;
+    return VT_OK;
+  }
+  int book_prefix(uint64_t bytes) {
+    float ms;
+    VT_TRY(span_ms(&ms));
     prof.prefix_launches += 1;
     prof.prefix_ms += ms;
-    prefix_pending = 0;
+    prof.prefix_bytes += bytes;
     return VT_OK;
+  }
+  int book_hamming(uint64_t launches, uint64_t bytes) {
+    float ms;
+    VT_TRY(span_ms(&ms));
+    prof.hamming_launches += launches;
+    prof.hamming_ms += ms;
+    prof.hamming_bytes += bytes;
+    return VT_OK;
+  }
+  // a prefix scan timed with ev0/ev1 but not yet read back (the chained funnel waits once, at its end): its bytes are
+  // booked when it is queued, its span by settle_prefix_profile
+  uint32_t prefix_pending = 0;
+  void defer_prefix(bool timed, uint64_t bytes) {
+    if (!timed) return;
+    prefix_pending += 1;
+    prof.prefix_bytes += bytes;
+  }
+  int settle_prefix_profile() {
+    if (!prefix_pending) return VT_OK;
+    prefix_pending = 0;
+    return book_prefix(0);
   }
   // Tiles are dealt to waves statically, so the grid must be fully resident:
   // blocks per CU = what LDS admits, capped (VT_BLOCKS_PER_CU overrides).

@@ -36,6 +36,7 @@
 #include "host/vt_concurrency.h"
 #include "host/vt_base.h"
 #include "host/vt_types.h"
+#include "host/vt_launch.h"
 #include "host/vt_select.h"
 #include "host/vt_store.h"
 #include "host/vt_search.h"
@@ -803,34 +804,15 @@ int vt_vector_top_k(int device, size_t count, const char *ids, const size_t *id_
     uint32_t qnz = 0;
     VT_TRY(upload_query(c, query, dimensions, &qnz));
     const size_t want = first_error == VT_OK ? limit : (size_t)1;  // only the overflow flag matters then
+    const RowSet rows{dX.p, ld, dRank.p, n, metric_code, default_order()};
     if (metric_code == VT_COSINE) {
-      VT_TRY(c.dCandKeys.ensure(n));
-      VT_TRY(c.dCandPay.ensure(n));
-      vt::CosineRerankArgs a{};
-      a.X = dX.p;
-      a.stride = ld;
-      a.q = c.qsrc;
-      a.id_rank = dRank.p;
-      a.gather = nullptr;
-      a.gather_stride = 0;
-      a.n = n;
-      a.d = d;
-      a.out_keys = c.dCandKeys.p;
-      a.out_pay = c.dCandPay.p;
-      a.status = c.dStatus.p;
-      VT_HIP(vt::launch_cosine_rerank(a, c.stream));
+      VT_TRY(c.ensure_cand_lists(n));
+      VT_HIP(vt::launch_cosine_rerank(cosine_rerank_args(rows, c, d), c.stream));
       // limit == 0 still has to surface "metric overflow": select one
       VT_TRY(collect_from_keys(c, c.dCandKeys.p, c.dCandPay.p, n, std::max<size_t>(want, 1), entries));
       if (limit == 0) entries.clear();
     } else {
-      ScanJob j{};
-      j.X = dX.p;
-      j.stride = ld;
-      j.id_rank = dRank.p;
-      j.n = n;
-      j.d = d;
-      j.metric = metric_code;
-      j.order = default_order();
+      vt::ScanArgs j = scan_args(rows, c, d);
       j.q_nonzero = qnz;
       // limit == 0 still has to surface "metric overflow": scan for one hit
       VT_TRY(run_scan(c, j, std::max<size_t>(want, 1), entries, false));
