@@ -22,54 +22,41 @@ HIPFLAGS += -DVT_EXPERIMENTS -DVT_BATCH_TIMING_EXPERIMENTS -DVT_MULTI_TIMING_EXP
 CHECK_SCRATCH := @true
 endif
 
-DEVSRC  := vt_kernels vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_multi vt_prefix_multi vt_maxsim vt_sketch
+# (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
+# as that unit does once it starts at once; vt_hamming is the next longest at half of it)
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_sketch
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
 all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so oracle
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
+# What a device unit's build checks or adds, per unit:
+#   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
+#   NOSPILL_<unit>    kernels that must not spill (tools/check_scratch.py says why): the build fails if one does
+#   EXTRA_<unit>      compiler flags of that unit alone
 # K1's instantiation units: no scratch at all (r05: the overflow recovery returns its value by value; every launch of a
 # kernel with a scratch segment has it set up)
-$(LIBDIR)/vt_scan_%.o: $(CSRC)/vt_scan_%.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_scan_$*.resources
-	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_scan_$*.resources scan_topk_kernel
-
-# Kernels that must not spill (tools/check_scratch.py says why): the build fails if one does.
-$(LIBDIR)/vt_scan_multi.o: $(CSRC)/vt_scan_multi.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_scan_multi.resources
-	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_scan_multi.resources scan_multi_kernel
-$(LIBDIR)/vt_batch_bf16.o: $(CSRC)/vt_batch_bf16.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_batch_bf16.resources
-	$(CHECK_SCRATCH) $(LIBDIR)/vt_batch_bf16.resources bf16_scores_kernel
+K1_UNITS := vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather
+$(foreach u,$(K1_UNITS),$(eval NOSCRATCH_$(u) := scan_topk_kernel))
+NOSCRATCH_vt_scan_multi   := scan_multi_kernel
+NOSCRATCH_vt_prefix_multi := prefix_multi_kernel
 # (-fno-slp-vectorize: K1p packs two ELEMENTS of a query per instruction by hand; the SLP pass re-packs two QUERIES
 # instead, with a register move per operand pair -- 22-26 % more VALU cycles per chunk, measured)
-$(LIBDIR)/vt_prefix_multi.o: $(CSRC)/vt_prefix_multi.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -fno-slp-vectorize -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_prefix_multi.resources
-	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_prefix_multi.resources prefix_multi_kernel
+EXTRA_vt_prefix_multi     := -fno-slp-vectorize
 # K9 (MaxSim): the overflow recovery returns by value, as in K1 -- no scratch segment behind any launch
-$(LIBDIR)/vt_maxsim.o: $(CSRC)/vt_maxsim.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_maxsim.resources
-	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_maxsim.resources maxsim_kernel
+NOSCRATCH_vt_maxsim       := maxsim_kernel
 # K1q (the int8 sketch pass): its register ring must stay in registers; its tail (one block behind every pass) likewise
 # carries no scratch segment
-$(LIBDIR)/vt_sketch.o: $(CSRC)/vt_sketch.hip $(DEVHDR)
+NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel
+NOSPILL_vt_batch_bf16     := bf16_scores_kernel
+NOSPILL_vt_batch_shadow   := shadow_scores_kernel
+
+# (the compiler's remarks, and with them its warnings and errors, go to <unit>.resources: shown when the compile fails)
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_sketch.resources
-	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_sketch.resources sketch_scan_kernel
-	$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/vt_sketch.resources sketch_tail_kernel
-$(LIBDIR)/vt_batch_shadow.o: $(CSRC)/vt_batch_shadow.hip $(DEVHDR)
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/vt_batch_shadow.resources
-	$(CHECK_SCRATCH) $(LIBDIR)/vt_batch_shadow.resources shadow_scores_kernel
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/$*.resources || { grep -v 'remark:' $(LIBDIR)/$*.resources >&2; exit 1; }
+	$(if $(NOSCRATCH_$*),$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/$*.resources $(NOSCRATCH_$*))
+	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
 
 HOSTHDR := $(wildcard $(CSRC)/host/*.h)
 $(LIBDIR)/vt_index.o: $(CSRC)/vt_index.cpp $(HOSTHDR) $(CSRC)/vt_device.h $(CSRC)/vt_env.h include/vettore_flat.h

@@ -204,7 +204,7 @@ struct HammingArgs {
 };
 hipError_t launch_hamming(const HammingArgs &a, uint32_t blocks, hipStream_t s);
 
-// K4p (vt_kernels.hip): K4's pattern mode (non-zero bits; float hamming / jaccard scores) for up to
+// K4p (vt_hamming.hip): K4's pattern mode (non-zero bits; float hamming / jaccard scores) for up to
 // kPatternMultiMax queries in one sweep of the column; k <= kSmallK; unsorted lists of k per
 // (query, block) at part_keys / part_pay + ((first_query + q) * blocks + block) * k.
 constexpr uint32_t kPatternMultiMax = 8;
@@ -221,7 +221,7 @@ size_t pattern_multi_lds_bytes();
 bool pattern_multi_supports(uint32_t pairs);  // word-pair counts with an unrolled build (d up to 2 048 in steps)
 hipError_t launch_pattern_multi(const PatternMultiArgs &a, uint32_t blocks, hipStream_t s);
 
-// K4h (vt_kernels.hip): distance column + histogram, then threshold collect.
+// K4h (vt_hamming.hip): distance column + histogram, then threshold collect.
 constexpr uint32_t kHammingHistMaxDim = 8191;  // (d + 1) u32 bins must fit comfortably in LDS
 constexpr int kStatusRetry = 100;              // internal: the tie list overflowed, take the K4 path
 struct HammingHistArgs {
@@ -290,7 +290,7 @@ hipError_t launch_pad_rows(const float *src, uint32_t n, uint32_t d, float *dst,
 
 // dst row map[2i + 1] <- src row map[2i] for i < count (map on the device; src rows are d floats,
 // dst rows dst_stride floats, zero padded).
-// A trickle of host rows lands from a pinned slot (layout in vt_kernels.hip: rows, their slab rows, id ranks): one launch.
+// A trickle of host rows lands from a pinned slot (layout in vt_ingest.hip: rows, their slab rows, id ranks): one launch.
 hipError_t launch_land_rows(const float *stage_dev, uint32_t count, uint32_t ld, float *X, uint32_t *rank_col, uint32_t rank_first,
                             uint32_t nranks, hipStream_t s);
 // Swap-delete on the slab: row `last` moves into row r (with its rank when rank_col is given), row `last` is zeroed.

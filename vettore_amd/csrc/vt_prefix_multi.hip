@@ -4,7 +4,7 @@
 // callers at once.
 //
 // A prefix is a narrow thing: 64..256 floats of a 768-float row, i.e. 256-B..1-KiB runs at the rows' 3-KiB stride.
-// The walk is K6b's (vt_kernels.hip, cosine_scan_multi_kernel): a wave parks a 64-row x 64-float panel in its own
+// The walk is K6b's (vt_cosine.hip, cosine_scan_multi_kernel): a wave parks a 64-row x 64-float panel in its own
 // LDS slice -- sixteen 1-KiB loads (4 rows x 256 B each), the next panel's already on their way -- and then lane r
 // walks row r, chunk by chunk.  What differs is the arithmetic, which is K1's to the bit: per 8-float chunk eight
 // separately rounded elements (q*x, (q-x)^2, |q-x|; never an FMA), their horizontal combination in the lane order
