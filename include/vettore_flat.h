@@ -74,7 +74,17 @@ enum {
   VT_ERR_NOMEM = 16,
   VT_ERR_DEVICE = 17,        /* HIP error / no gfx950 device; see vt_last_error() */
   VT_ERR_UNSUPPORTED = 18,   /* shape outside what the device kernels cover; vt_last_error() */
-  VT_ERR_ARGUMENT = 19       /* NULL handle and the like (the shim's badarg) */
+  VT_ERR_ARGUMENT = 19,      /* NULL handle and the like (the shim's badarg) */
+  /* MUVERA (muvera.rs:76-106, :29-42, :164-177): the reference's strings again */
+  VT_ERR_EMPTY_SET = 20,          /* "empty vectors"                               muvera.rs:79 */
+  VT_ERR_MUVERA_DIMENSION = 21,   /* "dimension must be positive"                  muvera.rs:82 */
+  VT_ERR_MUVERA_REPETITIONS = 22, /* "num_repetitions must be positive"            muvera.rs:85 */
+  VT_ERR_MUVERA_SIMHASH = 23,     /* "num_simhash_projections must be < 31"        muvera.rs:88 */
+  VT_ERR_MUVERA_PROJECTION = 24,  /* "projection_dimension must be positive"       muvera.rs:91 */
+  VT_ERR_MUVERA_FINAL = 25,       /* "final_projection_dimension must be positive" muvera.rs:94 */
+  VT_ERR_FDE_OVERFLOW = 26,       /* "fde dimension overflow"                      muvera.rs:34, :38 */
+  VT_ERR_FDE_LIMIT = 27,          /* "fde dimension exceeds safety limit"          muvera.rs:41 */
+  VT_ERR_ENCODING_OVERFLOW = 28   /* "encoding overflow"                           muvera.rs:175, :195 */
 };
 
 /* Lane order of wide::f32x8::reduce_add used for every 8-float chunk
@@ -404,6 +414,30 @@ int vt_multi_vector_top_k(int device, size_t count, const char *ids, const size_
                           const size_t *doc_vec_off, /* count + 1: document i owns vectors [doc_vec_off[i], doc_vec_off[i + 1]) */
                           const float *values, const size_t *value_off, const float *query, const size_t *query_off,
                           size_t nquery, int metric_code, size_t limit, vt_hits **out);
+
+/* ------------------------------------------- MUVERA (fixed-dimensional encoding)
+ * muvera_encode_query/7, muvera_encode_document/7, nifs.rs:430-476 -> muvera.rs:26-74, for `count` sets of
+ * vectors at once.  Set i owns vectors [set_vec_off[i], set_vec_off[i + 1]); vector j is
+ * values[value_off[j] .. value_off[j + 1]).  mode 0 = query (per partition the sum of the projected
+ * vectors), 1 = document (their running average).  final_is_some tells Some(final_projection_dimension)
+ * -- Some(0) included, which is an error -- from None.  `out` is [count][vt_muvera_fde_dimension(...)],
+ * bit-identical to the reference's encode().
+ *
+ * Validation happens on the host before any device call, in the reference's order (muvera.rs:76-106,
+ * then :29-42).  With count == 1 the call is the NIF: the set's error is the returned status.  With more
+ * sets an error of the configuration fails the call, and a set's own error ("empty vectors", "dimension
+ * mismatch", a non-finite value, "encoding overflow") goes to set_status[i] and leaves row i of `out`
+ * zero while the call returns VT_OK; without set_status the first failing set's status is returned.
+ * Encoding a set inside a batch gives the bytes that encoding it alone gives.  No CPU fallback: a valid
+ * call without a device returns VT_ERR_DEVICE; a dimension above 16 384 returns VT_ERR_UNSUPPORTED. */
+int vt_muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off /* count + 1 */,
+                     const float *values, const size_t *value_off /* vectors + 1 */, size_t dimension,
+                     size_t num_repetitions, size_t num_simhash_projections, uint64_t seed,
+                     size_t projection_dimension, size_t final_projection_dimension, int final_is_some,
+                     float *out, int *set_status /* count, may be NULL */);
+/* Length of an encoding under this configuration; 0 when the configuration is not valid. */
+size_t vt_muvera_fde_dimension(size_t num_repetitions, size_t num_simhash_projections, size_t projection_dimension,
+                               size_t final_projection_dimension, int final_is_some);
 
 /* ------------------------------------------------------------ profiling
  * Device-side timing of the dominant kernels with HIP events on the stream the

@@ -717,6 +717,55 @@ static ERL_NIF_TERM multi_vector_top_k(ErlNifEnv *env, int argc, const ERL_NIF_T
   return res;
 }
 
+/* Option<usize> as rustler decodes it: the atom nil is None, an integer that fits is Some(n), anything else does
+ * not decode.  (An atom is an immediate term: one name, one value -- compared as OTP's own NIFs compare theirs.) */
+static int get_option_size(ErlNifEnv *env, ERL_NIF_TERM t, size_t *out, int *is_some) {
+  *out = 0;
+  *is_some = get_size(env, t, out);
+  return *is_some || t == enif_make_atom(env, "nil");
+}
+
+/* muvera_encode_query / muvera_encode_document([[float]], dimension, num_repetitions, num_simhash_projections, seed,
+ * projection_dimension, final_projection_dimension | nil)                 nifs.rs:430-476 -> {:ok, [float]} */
+static ERL_NIF_TERM muvera_encode(ErlNifEnv *env, const ERL_NIF_TERM argv[], int mode) {
+  float *vals = NULL, *fde = NULL;
+  size_t *off = NULL, count = 0, dim, reps, simhash, proj, final_dim;
+  ErlNifUInt64 seed;
+  int final_is_some;
+  if (!get_vectors(env, argv[0], &vals, &off, &count) || !get_size(env, argv[1], &dim) || !get_size(env, argv[2], &reps) ||
+      !get_size(env, argv[3], &simhash) || !enif_get_uint64(env, argv[4], &seed) || !get_size(env, argv[5], &proj) ||
+      !get_option_size(env, argv[6], &final_dim, &final_is_some)) {
+    free(vals); free(off);
+    return enif_make_badarg(env);
+  }
+  const size_t set_off[2] = {0, count};
+  const size_t n = vt_muvera_fde_dimension(reps, simhash, proj, final_dim, final_is_some);
+  ERL_NIF_TERM res;
+  fde = (float *)malloc((n ? n : 1) * sizeof(float)); /* (n == 0: the call below refuses the configuration) */
+  if (!fde) {
+    res = mk_error(env, VT_ERR_NOMEM);
+  } else {
+    int st = vt_muvera_encode(0, mode, 1, set_off, vals, off, dim, reps, simhash, seed, proj, final_dim, final_is_some, fde, NULL);
+    if (st != VT_OK) {
+      res = mk_error(env, st);
+    } else {
+      ERL_NIF_TERM list = enif_make_list(env, 0);
+      for (size_t i = n; i-- > 0;) list = enif_make_list_cell(env, enif_make_double(env, (double)fde[i]), list);
+      res = enif_make_tuple2(env, mk_atom(env, "ok"), list);
+    }
+  }
+  free(vals); free(off); free(fde);
+  return res;
+}
+static ERL_NIF_TERM muvera_encode_query(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return muvera_encode(env, argv, 0);
+}
+static ERL_NIF_TERM muvera_encode_document(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return muvera_encode(env, argv, 1);
+}
+
 static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   (void)priv; (void)info;
   /* a libvettore_hip.so built from another header would be handed structs of the wrong size */
@@ -744,6 +793,8 @@ static ErlNifFunc funcs[] = {
   {"binary_top_k", 4, binary_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"multi_vector_score", 3, multi_vector_score, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"multi_vector_top_k", 4, multi_vector_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"muvera_encode_query", 7, muvera_encode_query, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"muvera_encode_document", 7, muvera_encode_document, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(Elixir.Vettore.Gpu.Nifs, funcs, load, NULL, NULL, NULL)

@@ -47,4 +47,6 @@ defmodule Vettore.Gpu.Nifs do
   def binary_top_k(_vectors, _query, _dimensions, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def multi_vector_score(_query_vectors, _document_vectors, _metric_code), do: :erlang.nif_error(:nif_not_loaded)
   def multi_vector_top_k(_documents, _query_vectors, _metric_code, _limit), do: :erlang.nif_error(:nif_not_loaded)
+  def muvera_encode_query(_vectors, _dimension, _num_repetitions, _num_simhash_projections, _seed, _projection_dimension, _final_projection_dimension), do: :erlang.nif_error(:nif_not_loaded)
+  def muvera_encode_document(_vectors, _dimension, _num_repetitions, _num_simhash_projections, _seed, _projection_dimension, _final_projection_dimension), do: :erlang.nif_error(:nif_not_loaded)
 end

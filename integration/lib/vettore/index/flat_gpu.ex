@@ -177,6 +177,11 @@ defmodule Vettore.Index.FlatGpu do
   defdelegate multi_vector_score(query_vectors, document_vectors, metric_code), to: Nifs
   defdelegate multi_vector_top_k(documents, query_vectors, metric_code, limit), to: Nifs
 
+  # MUVERA fixed-dimensional encodings on the device: Vettore.Nifs.muvera_encode_query/7 and muvera_encode_document/7
+  # (final_projection_dimension is nil or a positive integer, seed any u64) -- what Vettore.Encoding.Muvera calls
+  defdelegate muvera_encode_query(vectors, dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension), to: Nifs
+  defdelegate muvera_encode_document(vectors, dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension), to: Nifs
+
   # collection.ex:510 / :547
   defp max_candidates(limit) when is_integer(limit), do: max(limit * 10, limit)
   defp max_candidates(_), do: 0

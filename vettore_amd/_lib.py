@@ -32,7 +32,7 @@ SYMBOLS = [
     "vt_flat_load_matrix", "vt_flat_load_device_matrix", "vt_flat_quantized_search", "vt_flat_quantized_search_batch", "vt_flat_funnel_search", "vt_flat_funnel_search_batch", "vt_flat_hybrid_search",
     "vt_rank_ids", "vt_flat_set_id_ranks", "vt_flat_stream", "vt_flat_search_begin", "vt_flat_merge_gathered",
     "vt_vector_top_k", "vt_binary_top_k", "vt_normalize_l2", "vt_compress_sign_bits",
-    "vt_multi_vector_score", "vt_multi_vector_top_k",
+    "vt_multi_vector_score", "vt_multi_vector_top_k", "vt_muvera_encode", "vt_muvera_fde_dimension",
     "vt_flat_set_profiling", "vt_flat_get_profile", "vt_flat_get_profile_sized",
     "vt_flat_set_batch_shadow", "vt_flat_batch_shadow", "vt_flat_set_single_nominate", "vt_flat_single_nominate",
 ]
@@ -159,6 +159,10 @@ def load() -> C.CDLL:
     L.vt_multi_vector_score.argtypes = [C.c_int, f32p, szp, C.c_size_t, f32p, szp, C.c_size_t, C.c_int, f32p]
     L.vt_multi_vector_top_k.argtypes = [C.c_int, C.c_size_t, C.c_char_p, szp, szp, f32p, szp, f32p, szp, C.c_size_t,
                                         C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.vt_muvera_encode.argtypes = [C.c_int, C.c_int, C.c_size_t, szp, f32p, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64,
+                                   C.c_size_t, C.c_size_t, C.c_int, f32p, C.POINTER(C.c_int)]
+    L.vt_muvera_fde_dimension.restype = C.c_size_t
+    L.vt_muvera_fde_dimension.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.vt_flat_set_profiling.argtypes = [vp, C.c_int]
     L.vt_flat_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
     L.vt_flat_get_profile_sized.argtypes = [vp, vp, C.c_size_t, C.c_int]
@@ -177,10 +181,10 @@ def load() -> C.CDLL:
 
 
 def error_text(status: int) -> str:
-    """The reference's error string for statuses 1..7, else status + detail."""
+    """The reference's error string for the statuses that carry one, else status + detail."""
     L = load()
     msg = L.vt_strerror(status).decode()
-    if status >= 16:
+    if 16 <= status <= 19:
         detail = L.vt_last_error().decode()
         if detail:
             msg = "%s: %s" % (msg, detail)

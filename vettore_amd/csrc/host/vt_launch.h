@@ -93,6 +93,24 @@ inline vt::HammingArgs pattern_prefix_args(const Shard *ix, Ctx &c, uint32_t d) 
   return a;
 }
 
+// K10 for one configuration (validated: every size fits its field): the shape of a wave's work.  The chunk's buffers
+// (X, set_off, nsets, full, counts, status) and the table are the caller's to name.
+inline vt::MuveraArgs muvera_args(size_t d, size_t R, size_t k, size_t pd, int mode, size_t out_size) {
+  vt::MuveraArgs a{};
+  a.d = (uint32_t)d;
+  a.R = (uint32_t)R;
+  a.k = (uint32_t)k;
+  a.pd = (uint32_t)pd;
+  a.identity = pd == d ? 1 : 0;
+  a.C = (uint32_t)(k + (a.identity ? 0 : pd));
+  a.mode = mode;
+  a.rg = vt::muvera_reps_per_wave(a.R, a.k, a.C, mode);
+  a.groups = (a.R + a.rg - 1) / a.rg;
+  a.rep_size = ((size_t)1 << k) * pd;
+  a.out_size = out_size;
+  return a;
+}
+
 // ------------------------------------------------------------------ gather lists
 // One stage's output as the next stage's gather list: the first row index and the u32 words from one to the next.
 struct GatherList {

@@ -555,6 +555,40 @@ hipError_t launch_maxsim(const MaxSimArgs &a, uint32_t blocks, hipStream_t s);
 // norms[i] = sqrt(f64 sum of x[i][j]^2, j in order) for n rows `stride` floats apart (distances.rs:166-167)
 hipError_t launch_maxsim_norms(const float *X, size_t stride, uint32_t n, uint32_t d, double *norms, hipStream_t s);
 
+// K10: MUVERA fixed-dimensional encoding (muvera.rs:26-74) of a chunk of vector sets, for vt_muvera_encode.
+// The chunk's vectors are one row-major matrix X, d floats apart; set i owns rows [set_off[i], set_off[i + 1]) (a set
+// the host refused owns none and keeps its zero row).  launch_muvera_table writes the call's weights and signs once;
+// launch_muvera_encode runs one wave per (set, group of rg repetitions) over the set's vectors in input order and
+// updates the f32 slots of `full` in place (zeroed by the host); launch_muvera_sketch folds `full` into the final
+// dimension.  "encoding overflow" lands in status[set].
+constexpr int kErrEncodingOverflow = 28;             // VT_ERR_ENCODING_OVERFLOW
+constexpr uint32_t kMuveraLdsPartitions = 4096;      // partition counts a wave keeps in LDS (document mode)
+constexpr uint32_t kMuveraMaxDim = 16384;            // the staged vector: 64 KiB of LDS at most
+struct MuveraArgs {
+  const float *X;           // [rows][d]
+  const uint32_t *set_off;  // [nsets + 1]
+  uint32_t nsets;
+  uint32_t d, R, k, pd;     // dimension, repetitions, SimHash projections, projection dimension
+  uint32_t C;               // table columns per (repetition, coordinate): k, plus pd unless identity
+  int identity;             // pd == d: the coordinates themselves (muvera.rs:141-146)
+  int mode;                 // 0 query (sum), 1 document (running average)
+  const float *table;       // [R][d][C]  (launch_muvera_table); unused when C == 0
+  uint32_t rg, groups;      // repetitions per wave (muvera_reps_per_wave), waves per set = ceil(R / rg)
+  size_t rep_size, out_size;  // 2^k * pd, R * rep_size
+  float *full;              // [nsets][out_size]
+  uint32_t *counts;         // document mode with more than kMuveraLdsPartitions partitions: [nsets][R][2^k], zeroed; else null
+  int *status;              // [nsets], zeroed
+};
+uint64_t muvera_hash4(uint64_t a, uint64_t b, uint64_t c, uint64_t d);  // muvera.rs:219-225 (host: the sketch's slot lists)
+uint32_t muvera_reps_per_wave(uint32_t R, uint32_t k, uint32_t C, int mode);
+size_t muvera_lds_bytes(const MuveraArgs &a);
+hipError_t launch_muvera_table(uint64_t seed, uint32_t R, uint32_t d, uint32_t k, uint32_t C, float *table, hipStream_t s);
+hipError_t launch_muvera_encode(const MuveraArgs &a, hipStream_t s);
+// out[set][s] = the sequential f32-rounded signed sum of full[set][i] over list[off[s] .. off[s + 1]) (low 31 bits: i,
+// increasing; bit 31: sign -1)   muvera.rs:180-200
+hipError_t launch_muvera_sketch(const float *full, size_t out_size, uint32_t nsets, uint32_t final_dim, const uint32_t *off,
+                                const uint32_t *list, float *out, int *status, hipStream_t s);
+
 // normalize_l2 (distances.rs:350-361) on rows: out = (x / sqrt(f64 sum x^2)) as f32.
 hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *out, hipStream_t s);
 

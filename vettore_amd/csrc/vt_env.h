@@ -73,7 +73,8 @@ enum Parse {
   X(FORCE_SKETCH, "force_sketch", P_NONE, 0, "tests: lone cosine / dot searches read the int8 sketch on corpora of a few MB") \
   X(FORCE_THRESHOLD_SELECT, "force_threshold_select", P_NONE, 0, "tests: the key-column threshold path for limits 257..4 096 on small corpora") \
   X(BF16_RANK, "bf16_rank", P_NONE, 0, "tests: K2b / K2s take their threshold from exactly this sample rank (`= limit` leaves no margin: every query takes the second pass)") \
-  X(MAXSIM_CHUNK_BYTES, "maxsim_chunk_bytes", P_NONE, 0, "tests: document-vector bytes per upload chunk of a MaxSim call (default 64 MiB; a few hundred bytes make small calls cross many chunks)")
+  X(MAXSIM_CHUNK_BYTES, "maxsim_chunk_bytes", P_NONE, 0, "tests: document-vector bytes per upload chunk of a MaxSim call (default 64 MiB; a few hundred bytes make small calls cross many chunks)") \
+  X(MUVERA_CHUNK_BYTES, "muvera_chunk_bytes", P_NONE, 0, "tests: bytes of intermediate rows and vectors per chunk of sets of a MUVERA call (default 256 MiB; a few KiB make small calls cross many chunks)")
 
 // Timing experiments (wrong results on purpose: barriers removed, stages skipped) and phase traces of the batch paths:
 // always in the enumeration, but named, read and stored only in builds made with -DVT_EXPERIMENTS (`make experiments`:

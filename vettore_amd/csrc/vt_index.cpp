@@ -45,6 +45,7 @@
 #include "host/vt_funnel.h"
 #include "host/vt_hybrid.h"
 #include "host/vt_maxsim.h"
+#include "host/vt_muvera.h"
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
 
@@ -64,6 +65,15 @@ const char *vt_strerror(int status) {
     case VT_ERR_POISONED: return "flat lock poisoned";
     case VT_ERR_EMPTY_VECTORS: return "vectors must not be empty";
     case VT_ERR_SCORE_OVERFLOW: return "score overflow";
+    case VT_ERR_EMPTY_SET: return "empty vectors";
+    case VT_ERR_MUVERA_DIMENSION: return "dimension must be positive";
+    case VT_ERR_MUVERA_REPETITIONS: return "num_repetitions must be positive";
+    case VT_ERR_MUVERA_SIMHASH: return "num_simhash_projections must be < 31";
+    case VT_ERR_MUVERA_PROJECTION: return "projection_dimension must be positive";
+    case VT_ERR_MUVERA_FINAL: return "final_projection_dimension must be positive";
+    case VT_ERR_FDE_OVERFLOW: return "fde dimension overflow";
+    case VT_ERR_FDE_LIMIT: return "fde dimension exceeds safety limit";
+    case VT_ERR_ENCODING_OVERFLOW: return "encoding overflow";
     case VT_ERR_NOMEM: return "out of memory";
     case VT_ERR_DEVICE: return "device error";
     case VT_ERR_UNSUPPORTED: return "unsupported on device";
@@ -851,6 +861,27 @@ int vt_multi_vector_score(int device, const float *query, const size_t *query_of
   *out = entries[0].raw;
   return VT_OK;
   });
+}
+
+int vt_muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off, const float *values, const size_t *value_off,
+                     size_t dimension, size_t num_repetitions, size_t num_simhash_projections, uint64_t seed,
+                     size_t projection_dimension, size_t final_projection_dimension, int final_is_some, float *out,
+                     int *set_status) {
+  return guarded([&]() -> int {
+  if ((mode != 0 && mode != 1) || (count && (!set_vec_off || !value_off))) return VT_ERR_ARGUMENT;
+  const MuveraConfig m{dimension, num_repetitions, num_simhash_projections, seed, projection_dimension,
+                       final_projection_dimension, final_is_some != 0};
+  return muvera_encode(device, mode, count, set_vec_off, values, value_off, m, out, set_status);
+  });
+}
+
+size_t vt_muvera_fde_dimension(size_t num_repetitions, size_t num_simhash_projections, size_t projection_dimension,
+                               size_t final_projection_dimension, int final_is_some) {
+  const MuveraConfig m{1, num_repetitions, num_simhash_projections, 0, projection_dimension, final_projection_dimension,
+                       final_is_some != 0};
+  size_t out_size = 0, fde = 0;
+  if (muvera_check_config(m) != VT_OK || muvera_check_sizes(m, &out_size, &fde) != VT_OK) return 0;
+  return fde;
 }
 
 int vt_binary_top_k(int device, size_t count, const char *ids, const size_t *id_off, const uint64_t *words,

@@ -422,6 +422,84 @@ def multi_vector_top_k(documents, query_vectors, metric_code: int, limit: int):
     return ("ok", _take_hits(h)) if st == 0 else _err(st)
 
 
+# ------------------------------------------------------------------ MUVERA
+MUVERA_QUERY, MUVERA_DOCUMENT = 0, 1
+U64_MAX = (1 << 64) - 1
+_MUVERA_SET_ERRORS = (2, 3, 20, 28)  # dimension mismatch, non-finite, "empty vectors", "encoding overflow"
+
+
+def _usize(v, what):
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= USIZE_MAX:
+        raise TypeError("badarg: %s is a usize" % what)
+    return v
+
+
+def muvera_fde_dimension(num_repetitions: int, num_simhash_projections: int, projection_dimension: int,
+                         final_projection_dimension) -> int:
+    """Length of an encoding under this configuration (0: the configuration is not valid)."""
+    some = final_projection_dimension is not None
+    return int(_lib.load().vt_muvera_fde_dimension(num_repetitions, num_simhash_projections, projection_dimension,
+                                                   final_projection_dimension if some else 0, 1 if some else 0))
+
+
+def _muvera_call(sets, mode, dimension, num_repetitions, num_simhash_projections, seed, projection_dimension,
+                 final_projection_dimension, want_status):
+    for name, v in (("dimension", dimension), ("num_repetitions", num_repetitions),
+                    ("num_simhash_projections", num_simhash_projections), ("projection_dimension", projection_dimension)):
+        _usize(v, name)
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= U64_MAX:
+        raise TypeError("badarg: seed is a u64")
+    some = final_projection_dimension is not None
+    if some:
+        _usize(final_projection_dimension, "final_projection_dimension")
+    per_set = [[_f32_list(v) for v in vectors] for vectors in sets]
+    set_off = np.zeros(len(per_set) + 1, dtype=np.uintp)
+    if per_set:
+        set_off[1:] = np.cumsum([len(v) for v in per_set])
+    vals, voff = _pack_ragged([v for vectors in per_set for v in vectors], np.float32)
+    fde = muvera_fde_dimension(num_repetitions, num_simhash_projections, projection_dimension, final_projection_dimension)
+    out = np.zeros((len(per_set), fde), dtype=np.float32)
+    status = np.zeros(max(len(per_set), 1), dtype=np.intc)
+    st = _lib.load().vt_muvera_encode(DEVICE, mode, len(per_set), _szp(set_off), _fp(vals), _szp(voff), dimension,
+                                      num_repetitions, num_simhash_projections, seed, projection_dimension,
+                                      final_projection_dimension if some else 0, 1 if some else 0,
+                                      _fp(out.reshape(-1)) if out.size else None,
+                                      status.ctypes.data_as(C.POINTER(C.c_int)) if want_status else None)
+    return st, out, status[:len(per_set)]
+
+
+def _muvera_one(vectors, mode, *config):
+    st, out, _ = _muvera_call([vectors], mode, *config, want_status=False)
+    return ("ok", [float(x) for x in out[0]]) if st == 0 else _err(st)
+
+
+def muvera_encode_query(vectors, dimension: int, num_repetitions: int, num_simhash_projections: int, seed: int,
+                        projection_dimension: int, final_projection_dimension):
+    """nifs.rs:430-451: ("ok", [float]) or ("error", reason); final_projection_dimension is None or an integer."""
+    return _muvera_one(vectors, MUVERA_QUERY, dimension, num_repetitions, num_simhash_projections, seed,
+                       projection_dimension, final_projection_dimension)
+
+
+def muvera_encode_document(vectors, dimension: int, num_repetitions: int, num_simhash_projections: int, seed: int,
+                           projection_dimension: int, final_projection_dimension):
+    """nifs.rs:455-476."""
+    return _muvera_one(vectors, MUVERA_DOCUMENT, dimension, num_repetitions, num_simhash_projections, seed,
+                       projection_dimension, final_projection_dimension)
+
+
+def muvera_encode_batch(sets, mode: int, dimension: int, num_repetitions: int, num_simhash_projections: int, seed: int,
+                        projection_dimension: int, final_projection_dimension):
+    """Extension: every set of `sets` in one call.  ("ok", (matrix [count][fde] float32, [reason or None per set])) --
+    a set with a reason keeps a zero row --, or ("error", reason) when the configuration itself is refused."""
+    st, out, status = _muvera_call(sets, mode, dimension, num_repetitions, num_simhash_projections, seed,
+                                   projection_dimension, final_projection_dimension, want_status=True)
+    if st != 0 and len(status) == 1 and st in _MUVERA_SET_ERRORS:
+        status = [st]   # (one set is the NIF call: its own error is the call's status)
+    elif st != 0:
+        return _err(st)
+    return ("ok", (out, [None if s == 0 else _lib.error_text(int(s)) for s in status]))
+
+
 def binary_top_k(vectors, query, dimensions: int, limit: int):
     """nifs.rs:164-175."""
     ids, ioff = _pack_ids(i for i, _ in vectors)
