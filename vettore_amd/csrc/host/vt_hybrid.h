@@ -1,4 +1,4 @@
-// vt_hybrid.h -- hybrid_search on one shard (collection.ex:325-345) and the stateless helpers' shared pieces
+// vt_hybrid.h -- hybrid_search on one shard (collection.ex:325-345)
 // Part of vt_index.cpp's translation unit (included there, in this order, exactly once): the host
 // side is one TU on purpose -- everything below the C ABI lives in an anonymous namespace.
 #pragma once
@@ -63,49 +63,6 @@ int hybrid_ready(Shard *ix, Ctx &c, const float *query, size_t n, const int *kin
   // hybrid_rerank :exact == exact_rerank (collection.ex:627-630, :821-851)
   VT_TRY(funnel_stage(ix, c, query, (uint32_t)ix->dim, all, false, limit, qnz_full, entries));
   return make_hits(ix, entries, out);
-}
-
-
-// Per-device context for the stateless helpers.
-std::mutex g_ctx_mu;
-std::unordered_map<int, std::unique_ptr<Ctx>> g_ctx;
-int stateless_ctx(int device, Ctx **out) {
-  std::lock_guard<std::mutex> g(g_ctx_mu);
-  auto it = g_ctx.find(device);
-  if (it == g_ctx.end()) {
-    auto c = std::make_unique<Ctx>();
-    VT_TRY(c->init(device));
-    it = g_ctx.emplace(device, std::move(c)).first;
-  }
-  *out = it->second.get();
-  return (*out)->bind();
-}
-
-// id_rank for an ad-hoc batch of ids (ties between equal ids: input order).
-void ranks_for_ids(const char *ids, const size_t *id_off, size_t count, std::vector<uint32_t> &rank) {
-  std::vector<uint32_t> order(count);
-  for (size_t i = 0; i < count; ++i) order[i] = (uint32_t)i;
-  auto view = [&](uint32_t i) { return std::pair<const char *, size_t>(ids + id_off[i], id_off[i + 1] - id_off[i]); };
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    auto x = view(a), y = view(b);
-    const size_t m = std::min(x.second, y.second);
-    const int c = m ? std::memcmp(x.first, y.first, m) : 0;
-    if (c) return c < 0;
-    return x.second < y.second;
-  });
-  rank.resize(count);
-  for (size_t i = 0; i < count; ++i) rank[order[i]] = (uint32_t)i;
-}
-
-int hits_from_batch(const char *ids, const size_t *id_off, const std::vector<vt::Entry> &entries, vt_hits **out) {
-  auto h = std::make_unique<vt_hits>();
-  for (const auto &e : entries) {
-    h->ids.emplace_back(ids + id_off[e.row], id_off[e.row + 1] - id_off[e.row]);
-    h->raw.push_back(e.raw);
-    h->rank_key.push_back(rank_key_of(e.key));
-  }
-  *out = h.release();
-  return VT_OK;
 }
 
 }  // namespace

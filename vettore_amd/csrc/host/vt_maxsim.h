@@ -3,52 +3,14 @@
 // Part of vt_index.cpp's translation unit (included there, in this order, exactly once).
 //
 // A chunk's document vectors are one contiguous run of the caller's `values` (every scored vector has the query's
-// length), copied into one of two pinned staging blocks and uploaded on a copy stream into one of two device
-// buffers while the previous chunk is scored: chunk k + 1's upload overlaps chunk k's kernel, and the host's copy
-// into staging overlaps both.  Keys accumulate over the whole call; one select at the end.
+// length), copied into one of the upload ring's two staging blocks (UploadRing, vt_stateless.h) and uploaded into one
+// of its two device buffers while the previous chunk is scored: chunk k + 1's upload overlaps chunk k's kernel, and
+// the host's copy into staging overlaps both.  Keys accumulate over the whole call; one select at the end.
 #pragma once
 
 namespace {
 
 constexpr size_t kMaxSimChunkBytes = 64u << 20;  // default upload chunk (vt_debug_set maxsim_chunk_bytes)
-
-// The upload pipeline of one device (used under g_ctx_mu, like the stateless context it runs beside).
-struct MaxSimPipe {
-  hipStream_t copy = nullptr;
-  hipEvent_t copied[2] = {nullptr, nullptr}, scored[2] = {nullptr, nullptr};
-  PinnedBuf<float> hX[2];
-  PinnedBuf<uint32_t> hOff[2];
-  DevBuf<float> dX[2];
-  DevBuf<uint32_t> dOff[2];
-  DevBuf<double> dNorm[2];
-  DevBuf<float> dTotal[2];
-  DevBuf<int> dStatus[2];
-  DevBuf<float> dQ;
-  DevBuf<double> dQNorm;
-  DevBuf<uint32_t> dRank;
-  DevBuf<uint64_t> dKeys;
-  DevBuf<vt::Payload> dPay;
-  DevBuf<unsigned long long> dFirst;
-  PinnedBuf<unsigned long long> hFirst;
-
-  int init() {
-    VT_HIP(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-      VT_HIP(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
-      VT_HIP(hipEventCreateWithFlags(&scored[b], hipEventDisableTiming));
-    }
-    return VT_OK;
-  }
-  ~MaxSimPipe() {
-    if (copy) (void)hipStreamSynchronize(copy);
-    for (int b = 0; b < 2; ++b) {
-      if (copied[b]) (void)hipEventDestroy(copied[b]);
-      if (scored[b]) (void)hipEventDestroy(scored[b]);
-    }
-    if (copy) (void)hipStreamDestroy(copy);
-  }
-};
-std::unordered_map<int, std::unique_ptr<MaxSimPipe>> g_maxsim;
 
 // validate_vectors (multi_vector.rs:152-160) over vectors [v0, v1) against `dim`
 int maxsim_validate(const float *values, const size_t *value_off, size_t v0, size_t v1, size_t dim) {
@@ -66,7 +28,7 @@ int maxsim_validate_standalone(const float *values, const size_t *value_off, siz
   return maxsim_validate(values, value_off, v0, v1, dim);
 }
 
-// multi_vector.rs:90-132 top_k: the `limit` best of the documents into `entries` (row = document index).
+// multi_vector.rs:90-132 top_k: the `limit` best of the documents into `entries` (row = document index; no answer on a failure).
 int maxsim_top_k(int device, size_t count, const char *ids, const size_t *id_off, const size_t *doc_vec_off,
                  const float *values, const size_t *value_off, const float *query, const size_t *query_off,
                  size_t nquery, int metric_code, size_t limit, std::vector<vt::Entry> &entries) {
@@ -76,41 +38,24 @@ int maxsim_top_k(int device, size_t count, const char *ids, const size_t *id_off
   const size_t dim = nquery ? query_off[1] - query_off[0] : 0;
   // the reference walks the documents in order and stops at the first error; documents before the first
   // invalid one are scored and may fail first ("metric overflow", "score overflow")
-  // (a pass over every vector: on a large call the longest host step, so it is split over threads by document;
-  // the earliest failing document wins whichever thread finds it)
   auto check_doc = [&](size_t i) {
     const size_t v0 = doc_vec_off[i], v1 = doc_vec_off[i + 1];
     return nquery == 0 ? maxsim_validate_standalone(values, value_off, v0, v1) : maxsim_validate(values, value_off, v0, v1, dim);
   };
-  std::atomic<size_t> first_bad{count};
-  parallel_for(count, 512, [&](size_t lo, size_t hi) {
-    for (size_t i = lo; i < hi && i < first_bad.load(std::memory_order_relaxed); ++i)
-      if (check_doc(i) != VT_OK) {
-        size_t cur = first_bad.load();
-        while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {
-        }
-        break;
-      }
-  });
-  const size_t good = first_bad.load();
-  const int first_error = good < count ? check_doc(good) : VT_OK;
+  int first_error = VT_OK;
+  const size_t good = first_refused(count, check_doc, &first_error);
   if (good == 0) return first_error;
   uint32_t q_stride = 0;
   const uint32_t panel = nquery ? vt::maxsim_panel_rows((uint32_t)std::min<size_t>(dim, 0x7fffffffu), &q_stride) : 1;
   if (dim > 0x7fffffffu || panel == 0)
     return fail(VT_ERR_UNSUPPORTED, "vector dimension exceeds what the MaxSim kernel stages in LDS");
   if (good > 0xFFFFFFF0ull || nquery > 0xFFFFFFF0ull) return fail(VT_ERR_UNSUPPORTED, "more than 2^32-16 documents or query vectors");
-  Ctx *cp = nullptr;
-  VT_TRY(stateless_ctx(device, &cp));
-  Ctx &c = *cp;
-  std::lock_guard<std::mutex> g(g_ctx_mu);
-  auto it = g_maxsim.find(device);
-  if (it == g_maxsim.end()) {
-    auto p = std::make_unique<MaxSimPipe>();
-    VT_TRY(p->init());
-    it = g_maxsim.emplace(device, std::move(p)).first;
-  }
-  MaxSimPipe &P = *it->second;
+  StatelessLease lease;
+  VT_TRY(stateless_lease(device, &lease));
+  Ctx &c = lease.s->ctx;
+  UploadRing &ring = lease.s->ring;
+  MaxSimState &P = lease.s->maxsim;
+  VT_TRY(ring.open());
   const uint32_t n = (uint32_t)good, nq = (uint32_t)nquery, d = (uint32_t)dim;
 
   std::vector<uint32_t> rank;
@@ -135,7 +80,6 @@ int maxsim_top_k(int device, size_t count, const char *ids, const size_t *id_off
   }
 
   vt::MaxSimArgs a{};
-  a.ndoc = 0;
   a.Q = P.dQ.p;
   a.q_stride = q_stride;
   a.nq = nq;
@@ -183,30 +127,23 @@ int maxsim_top_k(int device, size_t count, const char *ids, const size_t *id_off
       const size_t rows = v1 - v0, ndoc = i1 - i0;
       if (rows > 0xFFFFFFF0ull) return fail(VT_ERR_UNSUPPORTED, "more than 2^32-16 vectors in one document");
       const int b = k & 1;
-      if (k >= 2) VT_HIP(hipEventSynchronize(P.copied[b]));  // staging b is free once its last upload is done
-      VT_TRY(P.hX[b].ensure(std::max<size_t>(rows * d, 1)));
-      VT_TRY(P.hOff[b].ensure(ndoc + 1));
-      VT_TRY(P.dX[b].ensure(std::max<size_t>(rows * d, 1)));
-      VT_TRY(P.dOff[b].ensure(ndoc + 1));
+      VT_TRY(ring.reserve(b, rows * d, ndoc + 1));
       const float *src = values + value_off[v0];  // every vector of a scored document has length d: one run
-      float *dst = P.hX[b].p;
+      float *dst = ring.hX[b].p;
       parallel_for(rows * d, (size_t)1 << 20, [&](size_t lo, size_t hi) { std::memcpy(dst + lo, src + lo, (hi - lo) * sizeof(float)); });
-      for (size_t i = 0; i <= ndoc; ++i) P.hOff[b].p[i] = (uint32_t)(doc_vec_off[i0 + i] - v0);
-      if (k >= 2) VT_HIP(hipStreamWaitEvent(P.copy, P.scored[b], 0));  // device buffer b: its last chunk is scored
-      VT_HIP(hipMemcpyAsync(P.dX[b].p, P.hX[b].p, rows * d * sizeof(float), hipMemcpyHostToDevice, P.copy));
-      VT_HIP(hipMemcpyAsync(P.dOff[b].p, P.hOff[b].p, (ndoc + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, P.copy));
-      VT_HIP(hipEventRecord(P.copied[b], P.copy));
-      VT_HIP(hipStreamWaitEvent(c.stream, P.copied[b], 0));
-      a.X = P.dX[b].p;
+      for (size_t i = 0; i <= ndoc; ++i) ring.hOff[b].p[i] = (uint32_t)(doc_vec_off[i0 + i] - v0);
+      VT_TRY(ring.send(b, rows * d, ndoc + 1));
+      VT_TRY(ring.wait_ready(b, c.stream));
+      a.X = ring.dX[b].p;
       a.stride = d;
-      a.doc_off = P.dOff[b].p;
+      a.doc_off = ring.dOff[b].p;
       if (metric_code == VT_COSINE) {
         VT_TRY(P.dNorm[b].ensure(std::max<size_t>(rows, 1)));
         VT_HIP(vt::launch_maxsim_norms(a.X, d, (uint32_t)rows, d, P.dNorm[b].p, c.stream));
         a.tnorm = P.dNorm[b].p;
       }
       VT_TRY(launch_chunk((uint32_t)i0, (uint32_t)ndoc, b));
-      VT_HIP(hipEventRecord(P.scored[b], c.stream));
+      VT_TRY(ring.mark_consumed(b, c.stream));
       i0 = i1;
     }
   }
@@ -216,15 +153,8 @@ int maxsim_top_k(int device, size_t count, const char *ids, const size_t *id_off
   VT_HIP(hipMemcpyAsync(P.hFirst.p, P.dFirst.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
   VT_HIP(hipStreamSynchronize(c.stream));
   const unsigned long long fe = *P.hFirst.p;
-  if (fe != ~0ull) {  // the earliest document that failed on the device comes before the host's first error
-    entries.clear();
-    return (int)(fe & 0xFF);
-  }
-  if (first_error != VT_OK) {
-    entries.clear();
-    return first_error;
-  }
-  return VT_OK;
+  if (fe != ~0ull) return (int)(fe & 0xFF);  // the earliest document that failed on the device: before the host's first error
+  return first_error;
 }
 
 }  // namespace

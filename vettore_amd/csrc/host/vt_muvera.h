@@ -3,8 +3,8 @@
 // sets bounded by a byte budget.
 // Part of vt_index.cpp's translation unit (included there, in this order, exactly once).
 //
-// A chunk's vectors are copied into one of two pinned staging blocks and uploaded on a copy stream into one of two
-// device buffers (every vector of a valid set has the configured length: a set is one run of the caller's `values`);
+// A chunk's vectors are copied into one of the upload ring's two staging blocks (UploadRing, vt_stateless.h) and uploaded
+// into one of its two device buffers (every vector of a valid set has the configured length: a set is one run of `values`);
 // chunk k + 1 is staged and uploaded while chunk k is encoded and its rows come back.  The weights and signs depend
 // on the configuration alone: one table per call, and one list of input indices per count-sketch slot.
 #pragma once
@@ -21,32 +21,6 @@ struct MuveraConfig {
   size_t pd, final_dim;
   bool final_some;  // Some(final_dim), Some(0) included
 };
-
-struct MuveraPipe {
-  hipStream_t copy = nullptr;
-  hipEvent_t copied[2] = {nullptr, nullptr};
-  PinnedBuf<float> hX[2];
-  PinnedBuf<uint32_t> hOff[2];
-  PinnedBuf<int> hStatus;
-  DevBuf<float> dX[2];
-  DevBuf<uint32_t> dOff[2];
-  DevBuf<float> dTable, dFull, dFinal;
-  DevBuf<uint32_t> dCounts, dSlotOff, dSlotList;
-  DevBuf<int> dStatus;
-
-  int init() {
-    VT_HIP(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) VT_HIP(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
-    return VT_OK;
-  }
-  ~MuveraPipe() {
-    if (copy) (void)hipStreamSynchronize(copy);
-    for (int b = 0; b < 2; ++b)
-      if (copied[b]) (void)hipEventDestroy(copied[b]);
-    if (copy) (void)hipStreamDestroy(copy);
-  }
-};
-std::unordered_map<int, std::unique_ptr<MuveraPipe>> g_muvera;
 
 // muvera.rs:81-95: the configuration on its own
 int muvera_check_config(const MuveraConfig &m) {
@@ -121,17 +95,12 @@ int muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off,
   if (count == 0) return VT_OK;
   if (!out) return VT_ERR_ARGUMENT;  // (only now: a refused configuration has no row length to allocate for)
   const bool report_first = !set_status || count == 1;
-  size_t first_bad = count;
-  for (size_t i = 0; i < count; ++i)
-    if (st[i] != VT_OK) {
-      first_bad = i;
-      break;
-    }
+  auto refused = [](int s) { return s != VT_OK; };
+  const size_t first_bad = std::find_if(st.begin(), st.end(), refused) - st.begin();
   // without a place for statuses only the sets before the first refused one can change the answer (an earlier
   // "encoding overflow" comes first)
   const size_t todo = report_first ? first_bad : count;
-  size_t valid = 0;
-  for (size_t i = 0; i < todo; ++i) valid += st[i] == VT_OK;
+  const size_t valid = std::count(st.begin(), st.begin() + todo, VT_OK);
 
   if (valid > 0) {
     if (m.d > vt::kMuveraMaxDim) return fail(VT_ERR_UNSUPPORTED, "vector dimension exceeds what the MUVERA kernel stages in LDS");
@@ -139,17 +108,12 @@ int muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off,
     const size_t C = m.k + (identity ? 0 : m.pd);
     const size_t table_floats = m.R * m.d * C;
     if (table_floats > kMuveraMaxTable) return fail(VT_ERR_UNSUPPORTED, "MUVERA weight table exceeds 1 GiB");
-    Ctx *cp = nullptr;
-    VT_TRY(stateless_ctx(device, &cp));
-    Ctx &c = *cp;
-    std::lock_guard<std::mutex> g(g_ctx_mu);
-    auto it = g_muvera.find(device);
-    if (it == g_muvera.end()) {
-      auto p = std::make_unique<MuveraPipe>();
-      VT_TRY(p->init());
-      it = g_muvera.emplace(device, std::move(p)).first;
-    }
-    MuveraPipe &P = *it->second;
+    StatelessLease lease;
+    VT_TRY(stateless_lease(device, &lease));
+    Ctx &c = lease.s->ctx;
+    UploadRing &ring = lease.s->ring;
+    MuveraState &P = lease.s->muvera;
+    VT_TRY(ring.open());
 
     vt::MuveraArgs a = muvera_args(m.d, m.R, m.k, m.pd, mode, out_size);
     const bool global_counts = mode == 1 && ((size_t)1 << m.k) > vt::kMuveraLdsPartitions;
@@ -196,25 +160,19 @@ int muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off,
       for (size_t i = i0; i < i1; ++i)
         if (st[i] == VT_OK) rows += set_vec_off[i + 1] - set_vec_off[i];
       if (rows > 0xFFFFFFF0ull) return fail(VT_ERR_UNSUPPORTED, "more than 2^32-16 vectors in one chunk of sets");
-      VT_TRY(P.hX[b].ensure(std::max<size_t>(rows * m.d, 1)));
-      VT_TRY(P.hOff[b].ensure(i1 - i0 + 1));
-      VT_TRY(P.dX[b].ensure(std::max<size_t>(rows * m.d, 1)));
-      VT_TRY(P.dOff[b].ensure(i1 - i0 + 1));
+      VT_TRY(ring.reserve(b, rows * m.d, i1 - i0 + 1));
       size_t at = 0;
       for (size_t i = i0; i < i1; ++i) {
-        P.hOff[b].p[i - i0] = (uint32_t)at;
+        ring.hOff[b].p[i - i0] = (uint32_t)at;
         if (st[i] != VT_OK) continue;
         const size_t n = set_vec_off[i + 1] - set_vec_off[i];
         const float *src = values + value_off[set_vec_off[i]];
-        float *dst = P.hX[b].p + at * m.d;
+        float *dst = ring.hX[b].p + at * m.d;
         parallel_for(n * m.d, (size_t)1 << 20, [&](size_t lo, size_t hi) { std::memcpy(dst + lo, src + lo, (hi - lo) * sizeof(float)); });
         at += n;
       }
-      P.hOff[b].p[i1 - i0] = (uint32_t)at;
-      VT_HIP(hipMemcpyAsync(P.dX[b].p, P.hX[b].p, rows * m.d * sizeof(float), hipMemcpyHostToDevice, P.copy));
-      VT_HIP(hipMemcpyAsync(P.dOff[b].p, P.hOff[b].p, (i1 - i0 + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, P.copy));
-      VT_HIP(hipEventRecord(P.copied[b], P.copy));
-      return VT_OK;
+      ring.hOff[b].p[i1 - i0] = (uint32_t)at;
+      return ring.send(b, rows * m.d, i1 - i0 + 1);
     };
 
     VT_TRY(stage(0));
@@ -224,7 +182,7 @@ int muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off,
       VT_TRY(P.dFull.ensure(nsets * out_size));
       VT_TRY(P.dStatus.ensure(nsets));
       VT_TRY(P.hStatus.ensure(nsets));
-      VT_HIP(hipStreamWaitEvent(c.stream, P.copied[b], 0));
+      VT_TRY(ring.wait_ready(b, c.stream));
       VT_HIP(hipMemsetAsync(P.dFull.p, 0, nsets * out_size * sizeof(float), c.stream));
       VT_HIP(hipMemsetAsync(P.dStatus.p, 0, nsets * sizeof(int), c.stream));
       a.counts = nullptr;
@@ -234,8 +192,8 @@ int muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off,
         VT_HIP(hipMemsetAsync(P.dCounts.p, 0, words * sizeof(uint32_t), c.stream));
         a.counts = P.dCounts.p;
       }
-      a.X = P.dX[b].p;
-      a.set_off = P.dOff[b].p;
+      a.X = ring.dX[b].p;
+      a.set_off = ring.dOff[b].p;
       a.nsets = (uint32_t)nsets;
       a.full = P.dFull.p;
       a.status = P.dStatus.p;
@@ -248,24 +206,22 @@ int muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off,
                                         P.dStatus.p, c.stream));
         rows = P.dFinal.p;
       }
-      if (k + 1 < nchunks) VT_TRY(stage(k + 1));  // (the other staging block and device buffer: chunk k - 1 is done)
+      VT_TRY(ring.mark_consumed(b, c.stream));    // (the last kernel that reads slot b is behind this)
+      if (k + 1 < nchunks) VT_TRY(stage(k + 1));  // (the other slot, while this chunk is encoded)
       VT_HIP(hipMemcpyAsync(out + i0 * fde, rows, nsets * fde * sizeof(float), hipMemcpyDeviceToHost, c.stream));
       VT_HIP(hipMemcpyAsync(P.hStatus.p, P.dStatus.p, nsets * sizeof(int), hipMemcpyDeviceToHost, c.stream));
-      VT_HIP(hipStreamSynchronize(c.stream));
+      VT_HIP(hipStreamSynchronize(c.stream));  // (for the host's read of the rows and the statuses, not for the ring)
       for (size_t i = 0; i < nsets; ++i)
         if (st[i0 + i] == VT_OK && P.hStatus.p[i] != 0) st[i0 + i] = P.hStatus.p[i];
     }
-    VT_HIP(hipStreamSynchronize(P.copy));
   }
   // a set that failed, on the host or on the device, and every set that was not reached: a zero row
   for (size_t i = 0; i < count; ++i)
     if (i >= todo || st[i] != VT_OK) std::memset(out + i * fde, 0, fde * sizeof(float));
 
   if (set_status) std::memcpy(set_status, st.data(), count * sizeof(int));
-  if (report_first)
-    for (size_t i = 0; i < count; ++i)
-      if (st[i] != VT_OK) return st[i];
-  return VT_OK;
+  const auto bad = std::find_if(st.begin(), st.end(), refused);  // (after the device's statuses: maybe an earlier set)
+  return report_first && bad != st.end() ? *bad : VT_OK;
 }
 
 }  // namespace

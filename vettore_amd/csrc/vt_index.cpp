@@ -44,6 +44,7 @@
 #include "host/vt_quantized.h"
 #include "host/vt_funnel.h"
 #include "host/vt_hybrid.h"
+#include "host/vt_stateless.h"
 #include "host/vt_maxsim.h"
 #include "host/vt_muvera.h"
 #include "host/vt_multi.h"
@@ -770,67 +771,7 @@ int vt_vector_top_k(int device, size_t count, const char *ids, const size_t *id_
   return guarded([&]() -> int {
   if (!out || (count && (!id_off || !value_off))) return VT_ERR_ARGUMENT;
   *out = nullptr;
-  // nifs.rs:158-161: metric decode first, then search.rs:38-73
-  if (metric_code < VT_L2 || metric_code > VT_JACCARD) return VT_ERR_UNKNOWN_METRIC;
-  if (dimensions == 0 || dimensions > nq) return VT_ERR_PREFIX;
-  VT_TRY(validate_finite(query, dimensions));
-  // the reference walks the batch in order and stops at the first error;
-  // rows before the first invalid one may still overflow and win the race
-  size_t good = count;
-  int first_error = VT_OK;
-  for (size_t i = 0; i < count; ++i) {
-    const size_t len = value_off[i + 1] - value_off[i];
-    int e = VT_OK;
-    if (dimensions > len) e = VT_ERR_DIMENSION;
-    else e = validate_finite(values + value_off[i], dimensions);
-    if (e != VT_OK) {
-      good = i;
-      first_error = e;
-      break;
-    }
-  }
-  if (dimensions > 0x7fffffffu || vt::scan_lds_bytes((uint32_t)dimensions, 1) == 0)
-    return fail(VT_ERR_UNSUPPORTED, "prefix dimension exceeds what the scan kernel stages in LDS");
-  if (count > 0xFFFFFFF0ull) return fail(VT_ERR_UNSUPPORTED, "more than 2^32-16 rows");
-  Ctx *cp = nullptr;
-  VT_TRY(stateless_ctx(device, &cp));
-  Ctx &c = *cp;
-  std::lock_guard<std::mutex> g(g_ctx_mu);
-  std::vector<vt::Entry> entries;
-  if (good > 0) {
-    const uint32_t d = (uint32_t)dimensions, ld = vt::padded_dim(d);
-    const uint32_t n = (uint32_t)good;
-    const uint32_t cap = round_up_u32(n, vt::kTileRows);
-    std::vector<float> packed((size_t)cap * ld, 0.0f);
-    for (size_t i = 0; i < good; ++i) std::memcpy(&packed[i * ld], values + value_off[i], (size_t)d * sizeof(float));
-    std::vector<uint32_t> rank;
-    ranks_for_ids(ids, id_off, good, rank);
-    DevBuf<float> dX;
-    DevBuf<uint32_t> dRank;
-    VT_TRY(dX.ensure(packed.size()));
-    VT_TRY(dRank.ensure(n));
-    VT_HIP(hipMemcpyAsync(dX.p, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice, c.stream));
-    VT_HIP(hipMemcpyAsync(dRank.p, rank.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
-    uint32_t qnz = 0;
-    VT_TRY(upload_query(c, query, dimensions, &qnz));
-    const size_t want = first_error == VT_OK ? limit : (size_t)1;  // only the overflow flag matters then
-    const RowSet rows{dX.p, ld, dRank.p, n, metric_code, default_order()};
-    if (metric_code == VT_COSINE) {
-      VT_TRY(c.ensure_cand_lists(n));
-      VT_HIP(vt::launch_cosine_rerank(cosine_rerank_args(rows, c, d), c.stream));
-      // limit == 0 still has to surface "metric overflow": select one
-      VT_TRY(collect_from_keys(c, c.dCandKeys.p, c.dCandPay.p, n, std::max<size_t>(want, 1), entries));
-      if (limit == 0) entries.clear();
-    } else {
-      vt::ScanArgs j = scan_args(rows, c, d);
-      j.q_nonzero = qnz;
-      // limit == 0 still has to surface "metric overflow": scan for one hit
-      VT_TRY(run_scan(c, j, std::max<size_t>(want, 1), entries, false));
-      if (limit == 0) entries.clear();
-    }
-  }
-  if (first_error != VT_OK) return first_error;
-  return hits_from_batch(ids, id_off, entries, out);
+  return vector_top_k(device, count, ids, id_off, values, value_off, query, nq, metric_code, dimensions, limit, out);
   });
 }
 
@@ -890,83 +831,21 @@ int vt_binary_top_k(int device, size_t count, const char *ids, const size_t *id_
   return guarded([&]() -> int {
   if (!out || (count && (!id_off || !word_off))) return VT_ERR_ARGUMENT;
   *out = nullptr;
-  // search.rs:82-84: the query is validated against itself first
-  const size_t W = (dimensions + 63) / 64;
-  if (dimensions == 0) return VT_ERR_DIMS_POSITIVE;
-  if (nq != W) return VT_ERR_DIMENSION;
-  for (size_t i = 0; i < count; ++i)
-    if (word_off[i + 1] - word_off[i] != W) return VT_ERR_DIMENSION;
-  if (count == 0 || limit == 0) return empty_hits(out);
-  if (count > 0xFFFFFFF0ull || dimensions > 0x7fffffffu) return fail(VT_ERR_UNSUPPORTED, "batch too large");
-  Ctx *cp = nullptr;
-  VT_TRY(stateless_ctx(device, &cp));
-  Ctx &c = *cp;
-  std::lock_guard<std::mutex> g(g_ctx_mu);
-  const uint32_t n = (uint32_t)count;
-  // K4 reads the tiled layout: [tile of 64 rows][word pair][row][2]
-  const uint32_t pairs = (uint32_t)((W + 1) / 2);
-  std::vector<uint64_t> packed(vt::hamming_matrix_words(n, (uint32_t)W), 0);
-  for (size_t i = 0; i < count; ++i)
-    for (size_t w = 0; w < W; ++w) packed[vt::hamming_word_index((uint32_t)i, (uint32_t)w, pairs)] = words[word_off[i] + w];
-  std::vector<uint32_t> rank;
-  ranks_for_ids(ids, id_off, count, rank);
-  DevBuf<uint64_t> dBits, dQ;
-  DevBuf<uint32_t> dRank;
-  VT_TRY(dBits.ensure(packed.size()));
-  std::vector<uint64_t> qwords(2 * (size_t)pairs, 0);  // (K4 reads whole word pairs: an odd count is padded with a zero word)
-  std::copy(query, query + W, qwords.begin());
-  VT_TRY(dQ.ensure(qwords.size()));
-  VT_TRY(dRank.ensure(n));
-  VT_HIP(hipMemcpyAsync(dBits.p, packed.data(), packed.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-  VT_HIP(hipMemcpyAsync(dQ.p, qwords.data(), qwords.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-  VT_HIP(hipMemcpyAsync(dRank.p, rank.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
-  std::vector<vt::Entry> entries;
-  VT_TRY(run_hamming(c, dBits.p, dQ.p, dRank.p, n, (uint32_t)dimensions, limit, entries, false));
-  return hits_from_batch(ids, id_off, entries, out);
+  return binary_top_k(device, count, ids, id_off, words, word_off, query, nq, dimensions, limit, out);
   });
 }
 
 int vt_normalize_l2(int device, size_t count, size_t d, const float *in, float *out) {
   return guarded([&]() -> int {
   if ((count && d) && (!in || !out)) return VT_ERR_ARGUMENT;
-  // distances.rs:350-361: finiteness first
-  VT_TRY(validate_finite(in, count * d));
-  if (count == 0 || d == 0) return VT_OK;
-  if (count > 0xFFFFFFF0ull || d > 0x7fffffffu) return fail(VT_ERR_UNSUPPORTED, "batch too large");
-  Ctx *cp = nullptr;
-  VT_TRY(stateless_ctx(device, &cp));
-  Ctx &c = *cp;
-  std::lock_guard<std::mutex> g(g_ctx_mu);
-  DevBuf<float> dIn, dOut;
-  VT_TRY(dIn.ensure(count * d));
-  VT_TRY(dOut.ensure(count * d));
-  VT_HIP(hipMemcpyAsync(dIn.p, in, count * d * sizeof(float), hipMemcpyHostToDevice, c.stream));
-  VT_HIP(vt::launch_normalize_l2(dIn.p, (uint32_t)count, (uint32_t)d, dOut.p, c.stream));
-  VT_HIP(hipMemcpyAsync(out, dOut.p, count * d * sizeof(float), hipMemcpyDeviceToHost, c.stream));
-  VT_HIP(hipStreamSynchronize(c.stream));
-  return VT_OK;
+  return normalize_l2(device, count, d, in, out);
   });
 }
 
 int vt_compress_sign_bits(int device, size_t count, size_t d, const float *in, uint64_t *out) {
   return guarded([&]() -> int {
   if ((count && d) && (!in || !out)) return VT_ERR_ARGUMENT;
-  if (count == 0 || d == 0) return VT_OK;
-  if (count > 0xFFFFFFF0ull || d > 0x7fffffffu) return fail(VT_ERR_UNSUPPORTED, "batch too large");
-  Ctx *cp = nullptr;
-  VT_TRY(stateless_ctx(device, &cp));
-  Ctx &c = *cp;
-  std::lock_guard<std::mutex> g(g_ctx_mu);
-  const size_t W = (d + 63) / 64;
-  DevBuf<float> dIn;
-  DevBuf<uint64_t> dOut;
-  VT_TRY(dIn.ensure(count * d));
-  VT_TRY(dOut.ensure(count * W));
-  VT_HIP(hipMemcpyAsync(dIn.p, in, count * d * sizeof(float), hipMemcpyHostToDevice, c.stream));
-  VT_HIP(vt::launch_sign_pack(dIn.p, d, (uint32_t)count, (uint32_t)d, dOut.p, 0, c.stream));
-  VT_HIP(hipMemcpyAsync(out, dOut.p, count * W * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
-  VT_HIP(hipStreamSynchronize(c.stream));
-  return VT_OK;
+  return compress_sign_bits(device, count, d, in, out);
   });
 }
 
