@@ -415,6 +415,40 @@ int vt_multi_vector_top_k(int device, size_t count, const char *ids, const size_
                           const float *values, const size_t *value_off, const float *query, const size_t *query_off,
                           size_t nquery, int metric_code, size_t limit, vt_hits **out);
 
+/* ------------------------------------------- resident multi-vector store
+ * The documents of vt_multi_vector_top_k, put once and kept in device memory: a search uploads the query vectors and
+ * nothing else.  After any sequence of puts and deletes, vt_mv_top_k returns exactly what vt_multi_vector_top_k returns
+ * for the live documents handed over in the order of their last put (an upsert moves a document to the end): ids,
+ * order, score bits and status -- when several documents fail on the device, the earliest in that order.
+ * vt_mv_put_many is atomic: every vector is checked before anything changes (a zero-length vector is
+ * VT_ERR_EMPTY_VECTORS, a length other than the store's dimension -- or, while the store has none, than the call's first
+ * vector's -- VT_ERR_DIMENSION, then VT_ERR_NON_FINITE), the last of several equal ids of a call is the one stored, and
+ * a failed allocation (VT_ERR_NOMEM) leaves the store as it was.  A document without vectors is legal and scores 0.0.
+ * A search decodes the metric, validates the query vectors on their own, then compares their length with the store's
+ * dimension (VT_ERR_DIMENSION) and only then goes to the device; without query vectors every document scores 0.0;
+ * limit 0 still scores everything and returns an empty list.  Every call on a handle excludes every other call on it.
+ * No CPU fallback: vt_mv_new without a device returns VT_ERR_DEVICE; a NULL handle is VT_ERR_ARGUMENT. */
+typedef struct vt_mv vt_mv;
+int vt_mv_new(int device, vt_mv **out);
+void vt_mv_free(vt_mv *store);
+/* upsert `count` documents; the layout is vt_multi_vector_top_k's (ids / id_off, doc_vec_off[count + 1], values / value_off) */
+int vt_mv_put_many(vt_mv *store, size_t count, const char *ids, const size_t *id_off, const size_t *doc_vec_off,
+                   const float *values, const size_t *value_off);
+int vt_mv_delete(vt_mv *store, const char *id, size_t id_len); /* an unknown id: nothing happens, VT_OK */
+size_t vt_mv_len(const vt_mv *store);                          /* live documents */
+long vt_mv_dimension(const vt_mv *store);                      /* -1: no live document holds a vector */
+int vt_mv_top_k(vt_mv *store, const float *query, const size_t *query_off, size_t nquery, int metric_code, size_t limit,
+                vt_hits **out);
+/* the same over the listed live documents only (unknown ids are skipped, a duplicate counts once; order and error
+ * priority follow the store's order, not the list's) */
+int vt_mv_top_k_ids(vt_mv *store, size_t count, const char *ids, const size_t *id_off, const float *query,
+                    const size_t *query_off, size_t nquery, int metric_code, size_t limit, vt_hits **out);
+/* vectors: rows of live documents; row_capacity: rows the slab holds; dead_rows: rows of deleted or replaced documents
+ * still in the slab; uploaded_bytes: bytes of document rows sent to the device since vt_mv_new (rows * row stride * 4:
+ * searches add nothing); compactions: puts that closed the slab up first.  Any out pointer may be NULL. */
+int vt_mv_memory(const vt_mv *store, size_t *vectors, size_t *row_capacity, size_t *dead_rows, uint64_t *uploaded_bytes,
+                 uint64_t *compactions);
+
 /* ------------------------------------------- MUVERA (fixed-dimensional encoding)
  * muvera_encode_query/7, muvera_encode_document/7, nifs.rs:430-476 -> muvera.rs:26-74, for `count` sets of
  * vectors at once.  Set i owns vectors [set_vec_off[i], set_vec_off[i + 1]); vector j is

@@ -33,6 +33,8 @@ SYMBOLS = [
     "vt_rank_ids", "vt_flat_set_id_ranks", "vt_flat_stream", "vt_flat_search_begin", "vt_flat_merge_gathered",
     "vt_vector_top_k", "vt_binary_top_k", "vt_normalize_l2", "vt_compress_sign_bits",
     "vt_multi_vector_score", "vt_multi_vector_top_k", "vt_muvera_encode", "vt_muvera_fde_dimension",
+    "vt_mv_new", "vt_mv_free", "vt_mv_put_many", "vt_mv_delete", "vt_mv_len", "vt_mv_dimension", "vt_mv_top_k", "vt_mv_top_k_ids",
+    "vt_mv_memory",
     "vt_flat_set_profiling", "vt_flat_get_profile", "vt_flat_get_profile_sized",
     "vt_flat_set_batch_shadow", "vt_flat_batch_shadow", "vt_flat_set_single_nominate", "vt_flat_single_nominate",
 ]
@@ -161,6 +163,18 @@ def load() -> C.CDLL:
                                         C.c_int, C.c_size_t, C.POINTER(vp)]
     L.vt_muvera_encode.argtypes = [C.c_int, C.c_int, C.c_size_t, szp, f32p, szp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64,
                                    C.c_size_t, C.c_size_t, C.c_int, f32p, C.POINTER(C.c_int)]
+    L.vt_mv_new.argtypes = [C.c_int, C.POINTER(vp)]
+    L.vt_mv_free.restype = None
+    L.vt_mv_free.argtypes = [vp]
+    L.vt_mv_put_many.argtypes = [vp, C.c_size_t, C.c_char_p, szp, szp, f32p, szp]
+    L.vt_mv_delete.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.vt_mv_len.restype = C.c_size_t
+    L.vt_mv_len.argtypes = [vp]
+    L.vt_mv_dimension.restype = C.c_long
+    L.vt_mv_dimension.argtypes = [vp]
+    L.vt_mv_top_k.argtypes = [vp, f32p, szp, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.vt_mv_top_k_ids.argtypes = [vp, C.c_size_t, C.c_char_p, szp, f32p, szp, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.vt_mv_memory.argtypes = [vp, szp, szp, szp, u64p, u64p]
     L.vt_muvera_fde_dimension.restype = C.c_size_t
     L.vt_muvera_fde_dimension.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.vt_flat_set_profiling.argtypes = [vp, C.c_int]

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import nifs
 from .index_flat import FlatGpu, Result, result_values, MAX_NIF_USIZE
+from .mv_store import ResidentMultiVector
 
 F32_MAX = 3.4028234663852886e38  # collection.ex:61
 METRIC_ALIASES = {"euclidean": "l2", "dot": "inner_product", "dot_product": "inner_product"}  # :1300-1304
@@ -75,10 +76,26 @@ class Collection:
         for cb in ("new", "put", "put_many", "delete", "search"):
             if not hasattr(index_mod, cb):
                 return ("error", "invalid_index")
+        # `resident_multi_vector: true` is the collection's own option (not the index module's): every stored
+        # embedding's vectors are mirrored into a device-resident store (mv_store.py) that the multi-vector searches read
+        resident = False
+        if isinstance(index_options, dict) and "resident_multi_vector" in index_options:
+            index_options = dict(index_options)
+            resident = index_options.pop("resident_multi_vector")
+            if not isinstance(resident, bool):
+                return ("error", "invalid_index_options")
         made = index_mod.new(metric, index_options or [])
         if made[0] != "ok":
             return made
+        mv_store = None
+        if resident:
+            device = (index_options or {}).get("device", ((index_options or {}).get("devices") or [nifs.DEVICE])[0])
+            try:
+                mv_store = ResidentMultiVector(device)
+            except RuntimeError as e:
+                return ("error", str(e))
         self = object.__new__(cls)
+        self.mv_store = mv_store
         self.name, self.dimensions, self.metric = name, dimensions, metric
         self.normalize, self.score = normalize, score
         self.index_mod, self.index_state = index_mod, made[1]
@@ -173,6 +190,8 @@ class Collection:
             return ("error", "duplicate_id")
         self.store[e.id] = e
         res = self.index_mod.put(self, e)
+        if res == "ok":
+            res = self._mirror_put([e])
         if res != "ok":
             self._rollback([e])
             return res
@@ -193,6 +212,8 @@ class Collection:
         for e in prepared:
             self.store[e.id] = e
         res = self.index_mod.put_many(self, prepared)
+        if res == "ok":
+            res = self._mirror_put(prepared)
         if res != "ok":
             self._rollback(prepared)
             return res
@@ -201,7 +222,20 @@ class Collection:
     def _rollback(self, embs):
         for e in embs:
             self.index_mod.delete(self, e.id)
+            if self.mv_store is not None:
+                self.mv_store.delete(e.id)
             self.store.pop(e.id, None)
+
+    _MV_ERRORS = {"score overflow": "score_overflow", "dimension mismatch": "dimension_mismatch",
+                  "vector contains a non-finite value": "invalid_multi_vector"}
+
+    def _mirror_put(self, embs):
+        """The resident store follows the index: the embedding's prepared `vectors`, or its one `vector` (what
+        _multi_vector_results hands over per call).  All or nothing, like the index's put_many."""
+        if self.mv_store is None:
+            return "ok"
+        res = self.mv_store.put_many([(e.id, e.vectors if e.vectors else [e.vector]) for e in embs])
+        return res if res == "ok" else ("error", self._MV_ERRORS.get(res[1], res[1]))
 
     def delete(self, id_):
         if not isinstance(id_, (str, bytes)):
@@ -209,6 +243,8 @@ class Collection:
         idb = nifs._bytes(id_)
         res = self.index_mod.delete(self, idb)
         if res == "ok":
+            if self.mv_store is not None:
+                self.mv_store.delete(idb)
             self.store.pop(idb, None)
         return res
 
@@ -267,6 +303,8 @@ class Collection:
         qv = self._prepare_vectors(query_vectors)
         if qv[0] != "ok":
             return qv
+        if self.mv_store is not None:
+            return self._resident_results(qv[1], None, metric, limit)
         return self._multi_vector_results(qv[1], list(self.store.values()), metric, limit)
 
     # -- collection.ex:742-806: the documents, one native call, errors as atoms, Results with score only
@@ -281,11 +319,22 @@ class Collection:
             documents.append((e.id, vectors))
         res = nifs.multi_vector_top_k(documents, query_vectors, nifs.METRIC_CODE[metric], limit)
         if res[0] != "ok":
-            return ("error", {"score overflow": "score_overflow", "dimension mismatch": "dimension_mismatch",
-                              "vector contains a non-finite value": "invalid_multi_vector"}.get(res[1], res[1]))
+            return ("error", self._MV_ERRORS.get(res[1], res[1]))
         by_id = {e.id: e for e in embeddings}
         return ("ok", [Result(id=i, value=by_id[i].value, score=float(score), distance=None, metric=metric,
                               metadata=by_id[i].metadata) for i, score in res[1] if i in by_id])
+
+    def _resident_results(self, query_vectors, ids, metric, limit):
+        """_multi_vector_results from the resident store: over every stored embedding (ids None) or the listed ones."""
+        code = nifs.METRIC_CODE[metric]
+        if ids is None:
+            res = self.mv_store.top_k(query_vectors, code, limit)
+        else:
+            res = self.mv_store.top_k_ids(ids, query_vectors, code, limit)
+        if res[0] != "ok":
+            return ("error", self._MV_ERRORS.get(res[1], res[1]))
+        return ("ok", [Result(id=i, value=self.store[i].value, score=float(score), distance=None, metric=metric,
+                              metadata=self.store[i].metadata) for i, score in res[1] if i in self.store])
 
     # (extensions of the adapter: lists of queries, one call)
     def search_batch(self, queries, opts=None):

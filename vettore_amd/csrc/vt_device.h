@@ -547,6 +547,9 @@ struct MaxSimArgs {
   uint64_t *keys;           // [ndoc]
   Payload *pay;             // [ndoc] {row0 + i, score}
   unsigned long long *first_error;  // (row << 8 | status), ~0 when none
+  // A resident store's slot list (vt_mv, K9r below): document i owns rows [doc_off[i], doc_off[i] + doc_cnt[i]) -- its
+  // documents are not adjacent.  Null (every stateless launch): doc_off[i + 1] - doc_off[i] rows.
+  const uint32_t *doc_cnt;
 };
 // Query vectors per panel for dimension d (0: a single query vector does not fit in LDS) and the LDS bytes of a panel.
 uint32_t maxsim_panel_rows(uint32_t d, uint32_t *q_stride);
@@ -554,6 +557,25 @@ size_t maxsim_lds_bytes(uint32_t panel_qn, uint32_t q_stride);
 hipError_t launch_maxsim(const MaxSimArgs &a, uint32_t blocks, hipStream_t s);
 // norms[i] = sqrt(f64 sum of x[i][j]^2, j in order) for n rows `stride` floats apart (distances.rs:166-167)
 hipError_t launch_maxsim_norms(const float *X, size_t stride, uint32_t n, uint32_t d, double *norms, hipStream_t s);
+
+// K9r (vt_maxsim_resident.hip): K9's arithmetic for the documents of a resident store (host/vt_mvstore.h), which are a
+// slot list over one slab: MaxSimArgs with doc_cnt set, stride = round_up(d, 4), and -- cosine -- tnorm the store's norm
+// column.  A wave stages a document's rows through LDS, `1 << tile_log2` at a time, with coalesced 16-byte loads; a lane is
+// (row of the tile, group of eight query vectors), 64 >> tile_log2 groups side by side.  maxsim_resident_plan chooses the
+// tile by the call's query vectors and says how many of them one panel holds; false: K9r does not serve the call (no
+// query vector, float Hamming / Jaccard, a dimension whose tiles do not fit in LDS) -- launch_maxsim does, over the same slab.
+struct MaxSimResidentPlan {
+  uint32_t tile_log2;  // 6, 5 or 4
+  uint32_t ld;         // floats between the rows of an LDS tile (ld / 4 odd)
+  uint32_t q_stride;   // round_up(d, 8), as K9's
+  uint32_t panel;      // query vectors per launch, a multiple of a pass (8 * (64 >> tile_log2))
+};
+bool maxsim_resident_plan(uint32_t d, uint32_t nq, int metric, MaxSimResidentPlan *out);
+size_t maxsim_resident_lds_bytes(uint32_t panel_qn, uint32_t q_stride, const MaxSimResidentPlan &p);
+hipError_t launch_maxsim_resident(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s);
+// Compaction of a store: row j of outX / out_norms = row src[j] of X / norms (`stride` floats a row, a multiple of 4).
+hipError_t launch_mv_compact(const float *X, const double *norms, const uint32_t *src, uint32_t rows, uint32_t stride,
+                             float *outX, double *out_norms, hipStream_t s);
 
 // K10: MUVERA fixed-dimensional encoding (muvera.rs:26-74) of a chunk of vector sets, for vt_muvera_encode.
 // The chunk's vectors are one row-major matrix X, d floats apart; set i owns rows [set_off[i], set_off[i + 1]) (a set

@@ -33,6 +33,7 @@
 
 // The host side in reading order (one translation unit; see the note at the top of each part):
 #include "host/vt_idtable.h"
+#include "host/vt_mvstore.h"
 #include "host/vt_concurrency.h"
 #include "host/vt_base.h"
 #include "host/vt_types.h"
@@ -47,6 +48,7 @@
 #include "host/vt_stateless.h"
 #include "host/vt_maxsim.h"
 #include "host/vt_muvera.h"
+#include "host/vt_mvsearch.h"
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
 
@@ -802,6 +804,91 @@ int vt_multi_vector_score(int device, const float *query, const size_t *query_of
   *out = entries[0].raw;
   return VT_OK;
   });
+}
+
+int vt_mv_new(int device, vt_mv **out) {
+  return guarded([&]() -> int {
+  if (!out) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  auto s = std::make_unique<vt_mv>();
+  VT_TRY(s->ctx.init(device));
+  *out = s.release();
+  return VT_OK;
+  });
+}
+
+void vt_mv_free(vt_mv *s) {
+  if (!s) return;
+  (void)guarded([&]() -> int {
+    (void)s->ctx.bind();
+    delete s;
+    return VT_OK;
+  });
+}
+
+int vt_mv_put_many(vt_mv *s, size_t count, const char *ids, const size_t *id_off, const size_t *doc_vec_off,
+                   const float *values, const size_t *value_off) {
+  return guarded([&]() -> int {
+  if (!s || (count && (!id_off || !doc_vec_off || !value_off))) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(s->mu);
+  return mv_put_many(s, count, ids, id_off, doc_vec_off, values, value_off);
+  });
+}
+
+int vt_mv_delete(vt_mv *s, const char *id, size_t id_len) {
+  return guarded([&]() -> int {
+  if (!s || (id_len && !id)) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(s->mu);
+  if (s->table.erase(id_len ? id : "", id_len)) {
+    (void)s->ctx.bind();
+    mv_after_mutation(s);
+  }
+  return VT_OK;
+  });
+}
+
+size_t vt_mv_len(const vt_mv *s) {
+  if (!s) return 0;
+  std::lock_guard<std::mutex> g(const_cast<vt_mv *>(s)->mu);
+  return s->table.len();
+}
+
+long vt_mv_dimension(const vt_mv *s) {
+  if (!s) return -1;
+  std::lock_guard<std::mutex> g(const_cast<vt_mv *>(s)->mu);
+  return s->table.dimension();
+}
+
+int vt_mv_top_k(vt_mv *s, const float *query, const size_t *query_off, size_t nquery, int metric_code, size_t limit,
+                vt_hits **out) {
+  return guarded([&]() -> int {
+  if (!s || !out || (nquery && !query_off)) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(s->mu);
+  return mv_search(s, false, 0, nullptr, nullptr, query, query_off, nquery, metric_code, limit, out);
+  });
+}
+
+int vt_mv_top_k_ids(vt_mv *s, size_t count, const char *ids, const size_t *id_off, const float *query,
+                    const size_t *query_off, size_t nquery, int metric_code, size_t limit, vt_hits **out) {
+  return guarded([&]() -> int {
+  if (!s || !out || (count && !id_off) || (nquery && !query_off)) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(s->mu);
+  return mv_search(s, true, count, ids, id_off, query, query_off, nquery, metric_code, limit, out);
+  });
+}
+
+int vt_mv_memory(const vt_mv *s, size_t *vectors, size_t *row_capacity, size_t *dead_rows, uint64_t *uploaded_bytes,
+                 uint64_t *compactions) {
+  if (!s) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(const_cast<vt_mv *>(s)->mu);
+  if (vectors) *vectors = (size_t)s->table.live_rows();
+  if (row_capacity) *row_capacity = (size_t)s->table.capacity();
+  if (dead_rows) *dead_rows = (size_t)s->table.dead_rows();
+  if (uploaded_bytes) *uploaded_bytes = s->uploaded_bytes;
+  if (compactions) *compactions = s->table.compactions();
+  return VT_OK;
 }
 
 int vt_muvera_encode(int device, int mode, size_t count, const size_t *set_vec_off, const float *values, const size_t *value_off,

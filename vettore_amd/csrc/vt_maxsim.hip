@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_kernel(const Max
 
   for (uint32_t i = blockIdx.x * kWavesPerBlock + wib; i < a.ndoc; i += total_waves) {
     const uint32_t t0 = a.nq ? a.doc_off[i] : 0u;
-    const uint32_t T = a.nq ? a.doc_off[i + 1] - t0 : 0u;  // (a document without vectors scores 0.0)
+    const uint32_t T = !a.nq ? 0u : a.doc_cnt ? a.doc_cnt[i] : a.doc_off[i + 1] - t0;  // (a document without vectors scores 0.0)
     float tot = first_panel ? 0.0f : a.total[i];
     int st = first_panel ? 0 : a.status[i];
     for (uint32_t g = 0; g < qn && T && !st; g += kQB) {

@@ -1,0 +1,290 @@
+// vt_maxsim_resident.hip -- K9r: MaxSim over documents that stay in device memory (vt_mv, host/vt_mvstore.h) (gfx950).
+//
+// K9's arithmetic (vt_maxsim.hip: one lane computes one (query vector, document vector) pair from start to finish, so
+// the reference's order needs no cross-lane exchange), fed differently.  K9 lets every lane walk its own document
+// vector out of global memory, `stride * 4` bytes from its neighbour's: one load instruction touches 64 cache lines.
+// Here a wave takes one document of the slot list at a time and brings its token rows into its own LDS tile with
+// coalesced 16-byte loads -- the rows of a document are one contiguous run of the slab --, `tt` rows per tile; a lane
+// then reads ITS row out of LDS.  The tile's rows are `ld` floats apart with ld / 4 odd, so the 64 lanes' 16-byte reads
+// of one column fall into different banks.
+// Lane mapping: lane = (token of the tile, group of eight query vectors).  tt is 64, 32 or 16 (the launcher chooses by
+// the number of query vectors), so 64 / tt query groups run side by side: a document with 16 tokens and 32 query
+// vectors keeps all 64 lanes busy, and its tokens are staged once for all 32.  The maximum over the document's tokens is a
+// reduction over the tt lanes of a group; the sum over query vectors stays one sequential wave-uniform f32 chain in
+// query order (the groups' maxima are broadcast in that order), with the error of the first query vector that has one.
+#include "vt_scan.cuh"
+
+namespace vt {
+namespace dev {
+
+namespace {
+
+constexpr int kQB = 8;                       // query vectors per lane pass (as in K9)
+constexpr size_t kResidentLds = 128 * 1024;  // LDS of a block: the query panel and four tiles
+enum { MS_COS = 6 };                         // beside OP_DOT / OP_L2 / OP_L1 / OP_LINF
+
+// compute() (distances.rs:42-68) after the f32 chain, and similarity_value (distances.rs:122-128): K9's, word for word
+template <int OP>
+__device__ __forceinline__ float finish_raw(int metric, float acc, const float *q, const float *x, uint32_t d) {
+  float raw = acc;
+  if (metric == M_NIP) raw = -acc;
+  else if (metric == M_L2) raw = finite_f32(acc) ? __builtin_sqrtf(acc) : acc;
+  if (!finite_f32(raw)) raw = recover_overflow(metric, q, x, d);
+  return raw;
+}
+__device__ __forceinline__ float similarity(int metric, float raw) {
+  if (metric == M_COS || metric == M_IP) return raw;
+  if (metric == M_NIP) return -raw;
+  return 1.0f / (1.0f + raw);
+}
+
+template <int OP, int ORDER>
+__global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(const MaxSimArgs a, const uint32_t ttl,
+                                                                               const uint32_t ld) {
+  extern __shared__ __align__(16) float lds[];  // [panel_qn][q_stride], then per wave [tt][ld]
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t qn = a.panel_qn, qst = a.q_stride;
+  float *qs = lds;
+  {
+    const f32x4 *src = reinterpret_cast<const f32x4 *>(a.Q + (size_t)a.panel_q0 * qst);
+    const uint32_t n4 = qn * qst / 4;
+    for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) reinterpret_cast<f32x4 *>(qs)[i] = src[i];
+  }
+  __syncthreads();
+  const uint32_t tt = 1u << ttl, groups = (uint32_t)kWave >> ttl;
+  float *tile = lds + (size_t)qn * qst + (size_t)wib * tt * ld;
+  const uint32_t tok = lane & (tt - 1), qg = lane >> ttl;
+  const int metric = a.metric;
+  const uint32_t d = a.d, cfull = d / 8;
+  // the staging walk: 16-byte unit u of a tile is (row u / rs4, column u % rs4); a lane takes units lane, lane + 64, ...
+  const uint32_t rs4 = (uint32_t)a.stride / 4, ld4 = ld / 4;
+  const uint32_t row_first = lane / rs4, col_first = lane % rs4, row_step = kWave / rs4, col_step = kWave % rs4;
+  const bool first_panel = a.panel_q0 == 0, last_panel = a.panel_q0 + qn >= a.nq;
+  const uint32_t total_waves = gridDim.x * kWavesPerBlock;
+
+  for (uint32_t i = blockIdx.x * kWavesPerBlock + wib; i < a.ndoc; i += total_waves) {
+    const uint32_t t0 = a.doc_off[i], T = a.doc_cnt[i];  // (a document without vectors scores 0.0)
+    float tot = first_panel ? 0.0f : a.total[i];
+    int st = first_panel ? 0 : a.status[i];
+    for (uint32_t g = 0; g < qn && T && !st; g += kQB * groups) {
+      const uint32_t gq = g + qg * kQB;  // this lane's first query vector of the pass
+      const float *qk[kQB];
+#pragma unroll
+      for (int k = 0; k < kQB; ++k) qk[k] = qs + (size_t)(gq + k < qn ? gq + k : qn - 1) * qst;
+      float best[kQB];
+      bool bad[kQB];
+#pragma unroll
+      for (int k = 0; k < kQB; ++k) {
+        best[k] = -__builtin_inff();
+        bad[k] = false;
+      }
+      for (uint32_t j0 = 0; j0 < T; j0 += tt) {
+        const uint32_t cnt = T - j0 < tt ? T - j0 : tt;
+        if (g == 0 || T > tt) {  // (a document of one tile stays staged for the later passes)
+          wave_lds_fence();      // the readers of the tile's previous rows are done
+          const f32x4 *src = reinterpret_cast<const f32x4 *>(a.X + (size_t)(t0 + j0) * a.stride);
+          const uint32_t units = cnt * rs4;
+          uint32_t row = row_first, col = col_first;
+          for (uint32_t u = lane; u < units; u += kWave) {
+            reinterpret_cast<f32x4 *>(tile)[row * ld4 + col] = src[u];
+            row += row_step;
+            col += col_step;
+            if (col >= rs4) {
+              col -= rs4;
+              ++row;
+            }
+          }
+          wave_lds_fence();
+        }
+        const bool live = tok < cnt && gq < qn;   // (the others compute row 0 of the tile and drop it)
+        const float *x = tile + (size_t)(tok < cnt ? tok : 0) * ld;
+        float raw[kQB];
+        if (OP == MS_COS) {
+          // distances.rs:160-185 cosine(): fma(q, t, acc) == acc + q*t (a product of two f32 is exact in f64)
+          double dot[kQB];
+#pragma unroll
+          for (int k = 0; k < kQB; ++k) dot[k] = 0.0;
+          for (uint32_t e = 0; e < d; ++e) {
+            const double xv = (double)x[e];
+#pragma unroll
+            for (int k = 0; k < kQB; ++k) dot[k] = __builtin_fma((double)qk[k][e], xv, dot[k]);
+          }
+          const double rn = a.tnorm[t0 + j0 + (tok < cnt ? tok : 0)];
+#pragma unroll
+          for (int k = 0; k < kQB; ++k) {
+            const double ln = a.qnorm[a.panel_q0 + (gq + k < qn ? gq + k : qn - 1)];
+            raw[k] = 0.0f;
+            if (!(ln == 0.0 || rn == 0.0)) {
+              const double sim = dot[k] / (ln * rn);
+              raw[k] = isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
+            }
+          }
+        } else {
+          float acc[kQB];
+#pragma unroll
+          for (int k = 0; k < kQB; ++k) acc[k] = 0.0f;
+          for (uint32_t c = 0; c < cfull; ++c) {
+            const f32x4 xa = *reinterpret_cast<const f32x4 *>(x + c * 8);
+            const f32x4 xb = *reinterpret_cast<const f32x4 *>(x + c * 8 + 4);
+#pragma unroll
+            for (int k = 0; k < kQB; ++k) {
+              const f32x4 qa = *reinterpret_cast<const f32x4 *>(qk[k] + c * 8);
+              const f32x4 qb = *reinterpret_cast<const f32x4 *>(qk[k] + c * 8 + 4);
+              const float l[8] = {elem<OP>(0, qa.x, xa.x), elem<OP>(0, qa.y, xa.y), elem<OP>(0, qa.z, xa.z),
+                                  elem<OP>(0, qa.w, xa.w), elem<OP>(0, qb.x, xb.x), elem<OP>(0, qb.y, xb.y),
+                                  elem<OP>(0, qb.z, xb.z), elem<OP>(0, qb.w, xb.w)};
+              acc[k] = comb<OP>(0, acc[k], chunk_sum1<OP, ORDER>(l));
+            }
+          }
+          for (uint32_t e = cfull * 8; e < d; ++e) {  // the scalar tail, one element at a time (never the row's pad)
+            const float xe = x[e];
+#pragma unroll
+            for (int k = 0; k < kQB; ++k) acc[k] = comb<OP>(0, acc[k], elem<OP>(0, qk[k][e], xe));
+          }
+#pragma unroll
+          for (int k = 0; k < kQB; ++k) raw[k] = finish_raw<OP>(metric, acc[k], qk[k], x, d);
+        }
+#pragma unroll
+        for (int k = 0; k < kQB; ++k) {
+          if (!live) continue;
+          if (raw[k] != raw[k]) bad[k] = true;
+          else best[k] = fmaxf(best[k], similarity(metric, raw[k]));
+        }
+      }
+      // The maximum over the document's vectors as a tree over the tt lanes of a query group (K9 says why a tree may
+      // stand for the reference's fold in vector order), a failed pair anywhere in the group as a flag.
+#pragma unroll
+      for (int k = 0; k < kQB; ++k) {
+        float b = best[k];
+        int f = bad[k] ? 1 : 0;
+        for (uint32_t o = tt >> 1; o > 0; o >>= 1) {
+          b = fmaxf(b, __shfl_xor(b, (int)o, kWave));
+          f |= __shfl_xor(f, (int)o, kWave);
+        }
+        best[k] = b;
+        bad[k] = f != 0;
+      }
+      // the sum over query vectors: sequential, in query order -- group after group, each group's eight from its first
+      // lane -- and the reference's error at the first query vector that has one (wave-uniform)
+      for (uint32_t h = 0; h < groups; ++h) {
+#pragma unroll
+        for (int k = 0; k < kQB; ++k) {
+          const float b = __shfl(best[k], (int)(h << ttl), kWave);
+          const int f = __shfl(bad[k] ? 1 : 0, (int)(h << ttl), kWave);
+          if (st || g + h * kQB + k >= qn) continue;
+          if (f) {
+            st = kErrOverflow;
+            continue;
+          }
+          tot += b;
+          if (!finite_f32(tot)) st = kErrScoreOverflow;
+        }
+      }
+    }
+    if (lane != 0) continue;
+    if (!last_panel) {
+      a.total[i] = tot;
+      a.status[i] = st;
+      continue;
+    }
+    if (st) {
+      a.keys[i] = kEmptyKey;
+      atomicMin(a.first_error, ((unsigned long long)(a.row0 + i) << 8) | (unsigned)st);
+    } else {
+      a.keys[i] = ((uint64_t)~orderable(tot) << 32) | a.id_rank[i];  // descending score, then id
+      Payload p;
+      p.row = a.row0 + i;
+      p.raw = tot;
+      a.pay[i] = p;
+    }
+  }
+}
+
+// Compaction of a store's slab (host/vt_mvstore.h): row j of the new slab and of the new norm column is row src[j] of
+// the old ones -- order kept, 16 bytes per thread.
+__global__ void mv_compact_kernel(const float *X, const double *norms, const uint32_t *src, uint32_t rows, uint32_t rs4,
+                                  float *outX, double *out_norms) {
+  const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= (size_t)rows * rs4) return;
+  const uint32_t j = (uint32_t)(u / rs4), c = (uint32_t)(u % rs4);
+  const uint32_t s = src[j];
+  reinterpret_cast<f32x4 *>(outX)[u] = reinterpret_cast<const f32x4 *>(X)[(size_t)s * rs4 + c];
+  if (c == 0) out_norms[j] = norms[s];
+}
+
+template <int OP, int ORDER>
+hipError_t launch_t(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s) {
+  auto kern = maxsim_resident_kernel<OP, ORDER>;
+  const size_t lds = maxsim_resident_lds_bytes(a.panel_qn, a.q_stride, p);
+  hipError_t e = allow_lds(kern, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a, p.tile_log2, p.ld);
+  return hipGetLastError();
+}
+
+template <int OP>
+hipError_t launch_ordered(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s) {
+  switch (a.order) {
+    case 0: return launch_t<OP, 0>(a, p, blocks, s);
+    case 1: return launch_t<OP, 1>(a, p, blocks, s);
+    case 2: return launch_t<OP, 2>(a, p, blocks, s);
+    default: return launch_t<OP, 3>(a, p, blocks, s);
+  }
+}
+
+}  // namespace
+
+}  // namespace dev
+
+bool maxsim_resident_plan(uint32_t d, uint32_t nq, int metric, MaxSimResidentPlan *out) {
+  if (nq == 0 || metric == dev::M_HAM || metric == dev::M_JAC) return false;
+  MaxSimResidentPlan p{};
+  const uint32_t rs = dev::round_up(d, 4);
+  p.ld = (rs / 4) % 2 ? rs : rs + 4;  // ld / 4 odd: one column of 64 rows is 64 different 16-byte banks
+  p.q_stride = dev::round_up(d, 8);
+  // as many query groups side by side as the call has use for, fewer rows per tile when the tiles would not fit
+  p.tile_log2 = nq <= 8 ? 6 : nq <= 16 ? 5 : 4;
+  const size_t qrow = (size_t)p.q_stride * sizeof(float);
+  for (;; --p.tile_log2) {
+    const size_t tiles = (size_t)kWavesPerBlock * ((size_t)1 << p.tile_log2) * p.ld * sizeof(float);
+    const uint32_t pass = 8u * (64u >> p.tile_log2);  // query vectors of one pass: a panel holds whole passes
+    if (tiles + (size_t)pass * qrow <= dev::kResidentLds) {
+      const size_t fit = (dev::kResidentLds - tiles) / qrow / pass * pass;
+      p.panel = (uint32_t)std::min<size_t>(fit, dev::round_up(nq, pass));
+      break;
+    }
+    if (p.tile_log2 == 4) return false;  // (K9 serves such a dimension)
+  }
+  *out = p;
+  return true;
+}
+
+size_t maxsim_resident_lds_bytes(uint32_t panel_qn, uint32_t q_stride, const MaxSimResidentPlan &p) {
+  return ((size_t)panel_qn * q_stride + (size_t)kWavesPerBlock * ((size_t)1 << p.tile_log2) * p.ld) * sizeof(float);
+}
+
+hipError_t launch_maxsim_resident(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s) {
+  using namespace dev;
+  switch (a.metric) {
+    case M_COS: return launch_t<MS_COS, 0>(a, p, blocks, s);
+    case M_IP:
+    case M_NIP: return launch_ordered<OP_DOT>(a, p, blocks, s);
+    case M_L2:
+    case M_L2SQ: return launch_ordered<OP_L2>(a, p, blocks, s);
+    case M_L1: return launch_ordered<OP_L1>(a, p, blocks, s);
+    case M_LINF: return launch_ordered<OP_LINF>(a, p, blocks, s);
+    default: return hipErrorInvalidValue;  // (float Hamming / Jaccard: K9 over the slab)
+  }
+}
+
+hipError_t launch_mv_compact(const float *X, const double *norms, const uint32_t *src, uint32_t rows, uint32_t stride,
+                             float *outX, double *out_norms, hipStream_t s) {
+  if (rows == 0) return hipSuccess;
+  const size_t units = (size_t)rows * (stride / 4);
+  hipLaunchKernelGGL(dev::mv_compact_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, X, norms, src, rows,
+                     stride / 4, outX, out_norms);
+  return hipGetLastError();
+}
+
+}  // namespace vt

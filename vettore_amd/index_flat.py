@@ -313,6 +313,8 @@ class FlatGpu:
                 if id_ not in seen and got[0] == "ok":
                     seen.add(id_)
                     candidates.append(got[1])
+        if getattr(collection, "mv_store", None) is not None:   # the candidates' vectors are already on the device
+            return collection._resident_results(qv[1], [e.id for e in candidates], metric, limit)
         return collection._multi_vector_results(qv[1], candidates, metric, limit)
 
 

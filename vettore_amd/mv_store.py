@@ -1,0 +1,36 @@
+"""A resident multi-vector store: documents -- lists of vectors -- put once and kept in device memory, searched by
+MaxSim (K9r) without another upload.  A thin object over the vt_mv_* entry points (include/vettore_flat.h): a search
+returns what `nifs.multi_vector_top_k` returns for the live documents in the order of their last put, bit for bit."""
+from __future__ import annotations
+
+from . import nifs
+
+
+class ResidentMultiVector:
+    def __init__(self, device=None):
+        self.ref = nifs.mv_new(device)
+
+    def put_many(self, documents):
+        """Upsert [(id, [[float]])]; all or nothing: "ok" or ("error", reason)."""
+        return nifs.mv_put_many(self.ref, documents)
+
+    def delete(self, id_):
+        """An unknown id is "ok" as well."""
+        return nifs.mv_delete(self.ref, id_)
+
+    def top_k(self, query_vectors, metric_code, limit):
+        return nifs.mv_top_k(self.ref, query_vectors, metric_code, limit)
+
+    def top_k_ids(self, ids, query_vectors, metric_code, limit):
+        """Over the listed live documents only: unknown ids are skipped, a duplicate counts once."""
+        return nifs.mv_top_k_ids(self.ref, ids, query_vectors, metric_code, limit)
+
+    def memory(self):
+        return nifs.mv_memory(self.ref)
+
+    def __len__(self):
+        return nifs.mv_len(self.ref)
+
+    @property
+    def dimension(self):
+        return nifs.mv_dimension(self.ref)

@@ -15,7 +15,7 @@ typed arguments raise (the NIF's ArgumentError / badarg).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Iterable, List, Sequence, Tuple
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -420,6 +420,99 @@ def multi_vector_top_k(documents, query_vectors, metric_code: int, limit: int):
                                            _szp(voff), _fp(qv), _szp(qoff), qoff.size - 1, metric_code, limit,
                                            C.byref(h))
     return ("ok", _take_hits(h)) if st == 0 else _err(st)
+
+
+# ---------------------------------------------- resident multi-vector store (vt_mv_*; no NIF of the reference's)
+class MvRef:
+    """A vt_mv handle, freed with the object."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _lib.load().vt_mv_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def mv_new(device: Optional[int] = None) -> MvRef:
+    h = C.c_void_p()
+    st = _lib.load().vt_mv_new(DEVICE if device is None else device, C.byref(h))
+    if st != 0:
+        raise RuntimeError("mv_new: " + _lib.error_text(st))
+    return MvRef(h)
+
+
+def _pack_documents(documents):
+    ids, ioff = _pack_ids(i for i, _ in documents)
+    per_doc = [[_f32_list(v) for v in vecs] for _, vecs in documents]
+    doc_vec_off = np.zeros(len(per_doc) + 1, dtype=np.uintp)
+    if per_doc:
+        doc_vec_off[1:] = np.cumsum([len(v) for v in per_doc])
+    vals, voff = _pack_ragged([v for vecs in per_doc for v in vecs], np.float32)
+    return ids, ioff, doc_vec_off, vals, voff
+
+
+def mv_put_many(store: MvRef, documents):
+    """Upsert [(id, [[float]])]: "ok" or ("error", reason); nothing changes on an error."""
+    ids, ioff, doc_vec_off, vals, voff = _pack_documents(documents)
+    st = _lib.load().vt_mv_put_many(store.handle, len(documents), ids, _szp(ioff), _szp(doc_vec_off), _fp(vals), _szp(voff))
+    return "ok" if st == 0 else _err(st)
+
+
+def mv_delete(store: MvRef, id_):
+    b = _bytes(id_)
+    st = _lib.load().vt_mv_delete(store.handle, b, len(b))
+    return "ok" if st == 0 else _err(st)
+
+
+def mv_len(store: MvRef) -> int:
+    return _lib.load().vt_mv_len(store.handle)
+
+
+def mv_dimension(store: MvRef):
+    d = _lib.load().vt_mv_dimension(store.handle)
+    return None if d < 0 else d
+
+
+def _mv_search_args(metric_code, limit):
+    if not isinstance(metric_code, int) or not 0 <= metric_code <= 255:
+        raise TypeError("badarg: metric_code is a u8")
+    if not isinstance(limit, int) or not 0 <= limit <= USIZE_MAX:
+        raise TypeError("badarg: limit is a usize")
+
+
+def mv_top_k(store: MvRef, query_vectors, metric_code: int, limit: int):
+    """multi_vector_top_k over the store's live documents in the order of their last put."""
+    _mv_search_args(metric_code, limit)
+    qv, qoff = _vector_list(query_vectors)
+    h = C.c_void_p()
+    st = _lib.load().vt_mv_top_k(store.handle, _fp(qv), _szp(qoff), qoff.size - 1, metric_code, limit, C.byref(h))
+    return ("ok", _take_hits(h)) if st == 0 else _err(st)
+
+
+def mv_top_k_ids(store: MvRef, ids, query_vectors, metric_code: int, limit: int):
+    """The same over the listed live documents only."""
+    _mv_search_args(metric_code, limit)
+    idb, ioff = _pack_ids(ids)
+    qv, qoff = _vector_list(query_vectors)
+    h = C.c_void_p()
+    st = _lib.load().vt_mv_top_k_ids(store.handle, ioff.size - 1, idb, _szp(ioff), _fp(qv), _szp(qoff), qoff.size - 1,
+                                     metric_code, limit, C.byref(h))
+    return ("ok", _take_hits(h)) if st == 0 else _err(st)
+
+
+def mv_memory(store: MvRef) -> dict:
+    vectors, cap, dead = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    up, comp = C.c_uint64(), C.c_uint64()
+    st = _lib.load().vt_mv_memory(store.handle, C.byref(vectors), C.byref(cap), C.byref(dead), C.byref(up), C.byref(comp))
+    if st != 0:
+        raise RuntimeError("mv_memory: " + _lib.error_text(st))
+    return {"vectors": vectors.value, "row_capacity": cap.value, "dead_rows": dead.value, "uploaded_bytes": up.value,
+            "compactions": comp.value}
 
 
 # ------------------------------------------------------------------ MUVERA
