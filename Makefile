@@ -24,7 +24,7 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_muvera vt_sketch
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -47,6 +47,8 @@ EXTRA_vt_prefix_multi     := -fno-slp-vectorize
 NOSCRATCH_vt_maxsim       := maxsim_kernel
 # K9r (MaxSim over a resident store): K9's arithmetic and its recovery by value -- no scratch segment either
 NOSCRATCH_vt_maxsim_resident := maxsim_resident_kernel
+# K9rb (K9r over many query sets): the same pass (vt_maxsim_pair.cuh), the sets' totals in registers -- no scratch segment
+NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 # K10 (MUVERA): one lane's f64 chain per dot product, nothing indexed dynamically in registers
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
 # K1q (the int8 sketch pass): its register ring must stay in registers; its tail (one block behind every pass) likewise
@@ -61,6 +63,9 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/$*.resources || { grep -v 'remark:' $(LIBDIR)/$*.resources >&2; exit 1; }
 	$(if $(NOSCRATCH_$*),$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/$*.resources $(NOSCRATCH_$*))
 	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
+
+# (the pass K9r and K9rb share)
+$(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o: $(CSRC)/vt_maxsim_pair.cuh
 
 HOSTHDR := $(wildcard $(CSRC)/host/*.h)
 $(LIBDIR)/vt_index.o: $(CSRC)/vt_index.cpp $(HOSTHDR) $(CSRC)/vt_device.h $(CSRC)/vt_env.h include/vettore_flat.h

@@ -443,6 +443,28 @@ int vt_mv_top_k(vt_mv *store, const float *query, const size_t *query_off, size_
  * priority follow the store's order, not the list's) */
 int vt_mv_top_k_ids(vt_mv *store, size_t count, const char *ids, const size_t *id_off, const float *query,
                     const size_t *query_off, size_t nquery, int metric_code, size_t limit, vt_hits **out);
+/* Many query sets in one call.  Set b owns query vectors [set_vec_off[b], set_vec_off[b + 1]) of query / query_off, and,
+ * for vt_mv_top_k_ids_batch, the candidate ids [set_id_off[b], set_id_off[b + 1]) of ids / id_off.  out[b] and
+ * set_status[b] are exactly what vt_mv_top_k / vt_mv_top_k_ids return for set b called alone on the same store state:
+ * ids, order, score bits, rank keys and status, the earliest failing document in store order deciding a set's status.
+ * The whole call holds the handle's mutex once, so every set sees the same store.
+ * The call's own failures return their status and leave every out[b] NULL: a NULL store, `out` or offset array is
+ * VT_ERR_ARGUMENT, then an unknown metric VT_ERR_UNKNOWN_METRIC (decoded before any set is looked at).  A set's own
+ * error -- an empty vector, ragged lengths, a non-finite value, a length other than the store's dimension, "metric
+ * overflow" or "score overflow" on the device -- goes to set_status[b] with out[b] NULL while the call returns VT_OK
+ * and the other sets are answered.  Without set_status (NULL) the first failing set in batch order gives the returned
+ * status and every out[b] is NULL (vt_muvera_encode's convention).  nsets == 0 is VT_OK; limit 0 still scores, so
+ * errors surface, and returns empty lists; a set without query vectors scores every document 0.0. */
+int vt_mv_top_k_batch(vt_mv *store, size_t nsets, const size_t *set_vec_off /* nsets + 1 */, const float *query,
+                      const size_t *query_off /* vectors + 1 */, int metric_code, size_t limit, vt_hits **out /* nsets */,
+                      int *set_status /* nsets, may be NULL */);
+int vt_mv_top_k_ids_batch(vt_mv *store, size_t nsets, const size_t *set_id_off /* nsets + 1 */, const char *ids,
+                          const size_t *id_off, const size_t *set_vec_off, const float *query, const size_t *query_off,
+                          int metric_code, size_t limit, vt_hits **out, int *set_status);
+/* Totals since vt_mv_new -- scoring_launches: launches of a MaxSim scoring kernel by this handle's searches, single or
+ * batched; batched_sets: query sets scored by the batched kernel (the others of a batch went through the single-set
+ * path inside the same call).  Any out pointer may be NULL. */
+int vt_mv_counters(const vt_mv *store, uint64_t *scoring_launches, uint64_t *batched_sets);
 /* vectors: rows of live documents; row_capacity: rows the slab holds; dead_rows: rows of deleted or replaced documents
  * still in the slab; uploaded_bytes: bytes of document rows sent to the device since vt_mv_new (rows * row stride * 4:
  * searches add nothing); compactions: puts that closed the slab up first.  Any out pointer may be NULL. */

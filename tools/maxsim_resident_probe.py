@@ -17,6 +17,14 @@ could not be told from the forced ones):
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o probe -- \\
         python3 tools/maxsim_resident_probe.py --skip-stateless --out Y.json
     python3 tools/maxsim_resident_probe.py --out X.json --stats DIR/.../probe_kernel_stats.csv    (no GPU needed)
+
+--batch: the batched calls (vt_mv_top_k_ids_batch / vt_mv_top_k_batch, K9rb) on the same store against a loop of single
+calls -- the loop is the parent commit's path, unchanged --, inner product, limit 10: B in {1, 8, 64} query sets of 32
+vectors with their own 100 and 1 000 random candidate ids each, and B in {1, 8} sets over the whole store.  Batch call and
+loop alternate in one process, REPS times after a warm-up round; per shape both legs' best / median / worst, the ratio of
+the medians, and the launches and batched sets the handle counted for one batch call:
+
+    python3 tools/maxsim_resident_probe.py --batch --out profiles/maxsim_resident_batch.json
 """
 import argparse
 import csv
@@ -58,11 +66,82 @@ def summary(times):
             "spread": (worst - best) / best}
 
 
+BATCH_LIMIT, BATCH_CODE = 10, 3
+
+
+def batch_probe(L, _lib, nifs, store, rng, nvec, put_s):
+    """--batch: see the module's docstring."""
+    def counters():
+        a, b = C.c_uint64(), C.c_uint64()
+        assert L.vt_mv_counters(store, C.byref(a), C.byref(b)) == 0
+        return a.value, b.value
+
+    shapes = [("ids", B, cands) for cands in (100, 1000) for B in (1, 8, 64)] + [("whole", B, None) for B in (1, 8)]
+    res = {"shape": {"documents": N, "d": D, "query_vectors": NQ, "vectors": nvec, "limit": BATCH_LIMIT, "metric": "inner_product"},
+           "put_s": put_s, "reps": REPS, "shapes": []}
+    for mode, B, cands in shapes:
+        query = rng.standard_normal(size=(B * NQ, D), dtype=np.float32).reshape(-1)
+        qoff = (np.arange(B * NQ + 1, dtype=np.uintp) * D).astype(np.uintp)
+        set_off = (np.arange(B + 1, dtype=np.uintp) * NQ).astype(np.uintp)
+        lists = [["doc%06d" % i for i in rng.choice(N, size=cands, replace=False)] for _ in range(B)] if cands else []
+        packed = [nifs._pack_ids(ids) for ids in lists]
+        idb, ioff = nifs._pack_ids(i for ids in lists for i in ids)
+        set_id_off = (np.arange(B + 1, dtype=np.uintp) * (cands or 0)).astype(np.uintp)
+
+        def batch():
+            outs, status = (C.c_void_p * B)(), (C.c_int * B)()
+            if cands:
+                st = L.vt_mv_top_k_ids_batch(store, B, nifs._szp(set_id_off), idb, nifs._szp(ioff), nifs._szp(set_off),
+                                             nifs._fp(query), nifs._szp(qoff), BATCH_CODE, BATCH_LIMIT, outs, status)
+            else:
+                st = L.vt_mv_top_k_batch(store, B, nifs._szp(set_off), nifs._fp(query), nifs._szp(qoff), BATCH_CODE, BATCH_LIMIT,
+                                         outs, status)
+            assert st == 0 and not any(status), _lib.error_text(st)
+            return outs
+
+        def loop():
+            outs = (C.c_void_p * B)()
+            for b in range(B):
+                h = C.c_void_p()
+                qb, ob = query[b * NQ * D:], qoff[:NQ + 1]
+                if cands:
+                    st = L.vt_mv_top_k_ids(store, cands, packed[b][0], nifs._szp(packed[b][1]), nifs._fp(qb), nifs._szp(ob), NQ,
+                                           BATCH_CODE, BATCH_LIMIT, C.byref(h))
+                else:
+                    st = L.vt_mv_top_k(store, nifs._fp(qb), nifs._szp(ob), NQ, BATCH_CODE, BATCH_LIMIT, C.byref(h))
+                assert st == 0, _lib.error_text(st)
+                outs[b] = h.value
+            return outs
+
+        times = {"batch": [], "loop": []}
+        counted = None
+        for r in range(REPS + 1):  # round 0 warms up (allocations, code objects)
+            hits = {}
+            for leg, fn in (("batch", batch), ("loop", loop)):
+                c0 = counters()
+                t0 = time.perf_counter()
+                outs = fn()
+                dt = time.perf_counter() - t0
+                c1 = counters()
+                if r:
+                    times[leg].append(dt)
+                if leg == "batch":
+                    counted = {"scoring_launches": c1[0] - c0[0], "batched_sets": c1[1] - c0[1]}
+                hits[leg] = [nifs._take_hits(C.c_void_p(outs[b])) for b in range(B)]   # (outside the timed part, for both legs)
+            assert hits["batch"] == hits["loop"], "the batch call and the loop disagree"   # ids, order and score bits
+        m = {"mode": mode, "sets": B, "candidates": cands, "batch": summary(times["batch"]), "loop": summary(times["loop"]),
+             "one_batch_call": counted}
+        m["batch_over_loop_median"] = m["batch"]["median_ms"] / m["loop"]["median_ms"]
+        res["shapes"].append(m)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
     ap.add_argument("--stats")
     ap.add_argument("--skip-stateless", action="store_true")
+    ap.add_argument("--batch", action="store_true")
     args = ap.parse_args()
     if args.stats:  # merge the profiler's kernel statistics into an earlier run's JSON
         res = json.load(open(args.out))
@@ -93,6 +172,13 @@ def main():
                               nifs._fp(values), nifs._szp(voff))
         assert st == 0, _lib.error_text(st)
     put_s = time.perf_counter() - t0
+    if args.batch:
+        res = batch_probe(L, _lib, nifs, store, rng, nvec, put_s)
+        L.vt_mv_free(store)
+        if args.out:
+            json.dump(res, open(args.out, "w"), indent=1)
+        print(json.dumps(res))
+        return
     try:
         nifs.debug_get("test_mv_k9")
         have_hook = True

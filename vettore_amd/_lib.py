@@ -34,7 +34,7 @@ SYMBOLS = [
     "vt_vector_top_k", "vt_binary_top_k", "vt_normalize_l2", "vt_compress_sign_bits",
     "vt_multi_vector_score", "vt_multi_vector_top_k", "vt_muvera_encode", "vt_muvera_fde_dimension",
     "vt_mv_new", "vt_mv_free", "vt_mv_put_many", "vt_mv_delete", "vt_mv_len", "vt_mv_dimension", "vt_mv_top_k", "vt_mv_top_k_ids",
-    "vt_mv_memory",
+    "vt_mv_memory", "vt_mv_top_k_batch", "vt_mv_top_k_ids_batch", "vt_mv_counters",
     "vt_flat_set_profiling", "vt_flat_get_profile", "vt_flat_get_profile_sized",
     "vt_flat_set_batch_shadow", "vt_flat_batch_shadow", "vt_flat_set_single_nominate", "vt_flat_single_nominate",
 ]
@@ -175,6 +175,10 @@ def load() -> C.CDLL:
     L.vt_mv_top_k.argtypes = [vp, f32p, szp, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(vp)]
     L.vt_mv_top_k_ids.argtypes = [vp, C.c_size_t, C.c_char_p, szp, f32p, szp, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(vp)]
     L.vt_mv_memory.argtypes = [vp, szp, szp, szp, u64p, u64p]
+    L.vt_mv_top_k_batch.argtypes = [vp, C.c_size_t, szp, f32p, szp, C.c_int, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.vt_mv_top_k_ids_batch.argtypes = [vp, C.c_size_t, szp, C.c_char_p, szp, szp, f32p, szp, C.c_int, C.c_size_t,
+                                        C.POINTER(vp), C.POINTER(C.c_int)]
+    L.vt_mv_counters.argtypes = [vp, u64p, u64p]
     L.vt_muvera_fde_dimension.restype = C.c_size_t
     L.vt_muvera_fde_dimension.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.vt_flat_set_profiling.argtypes = [vp, C.c_int]

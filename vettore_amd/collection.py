@@ -288,6 +288,19 @@ class Collection:
     # -- collection.ex:298-323 ------------------------------------------------
     def multi_vector_search(self, query_vectors, opts=None):
         """MaxSim over every stored embedding (its `vectors`, or its one `vector`): Results carry the score."""
+        parsed = self._multi_vector_options(opts)
+        if parsed[0] != "ok":
+            return parsed
+        _, metric, limit = parsed
+        qv = self._prepare_vectors(query_vectors)
+        if qv[0] != "ok":
+            return qv
+        if self.mv_store is not None:
+            return self._resident_results(qv[1], None, metric, limit)
+        return self._multi_vector_results(qv[1], list(self.store.values()), metric, limit)
+
+    def _multi_vector_options(self, opts):
+        """("ok", metric, limit) of multi_vector_search's options, or the error every search with them returns."""
         opts = {} if opts is None else opts
         if not isinstance(opts, dict):
             return ("error", "invalid_options")
@@ -300,12 +313,26 @@ class Collection:
         metric = METRIC_ALIASES.get(opts.get("metric", self.metric), opts.get("metric", self.metric))
         if metric not in METRICS:
             return ("error", "invalid_metric")
-        qv = self._prepare_vectors(query_vectors)
-        if qv[0] != "ok":
-            return qv
-        if self.mv_store is not None:
-            return self._resident_results(qv[1], None, metric, limit)
-        return self._multi_vector_results(qv[1], list(self.store.values()), metric, limit)
+        return ("ok", metric, limit)
+
+    def multi_vector_search_batch(self, query_vector_lists, opts=None):
+        """multi_vector_search for every entry of a list of query-vector lists (an extension of the adapter): a list,
+        element-wise equal to calling multi_vector_search per entry.  With a resident store the valid entries are one
+        batched call on it; without one, a loop."""
+        if not isinstance(query_vector_lists, (list, tuple)):
+            return ("error", "invalid_multi_vector")
+        parsed = self._multi_vector_options(opts)
+        if self.mv_store is None or parsed[0] != "ok":
+            return [self.multi_vector_search(q, opts) for q in query_vector_lists]
+        _, metric, limit = parsed
+        out = [self._prepare_vectors(q) for q in query_vector_lists]
+        valid = [i for i, qv in enumerate(out) if qv[0] == "ok"]
+        res = self.mv_store.top_k_batch([out[i][1] for i in valid], nifs.METRIC_CODE[metric], limit)
+        if not isinstance(res, list):   # the call itself failed: every entry's answer
+            res = [res] * len(valid)
+        for i, r in zip(valid, res):
+            out[i] = self._resident_answer(r, metric)
+        return out
 
     # -- collection.ex:742-806: the documents, one native call, errors as atoms, Results with score only
     def _multi_vector_results(self, query_vectors, embeddings, metric, limit):
@@ -331,6 +358,9 @@ class Collection:
             res = self.mv_store.top_k(query_vectors, code, limit)
         else:
             res = self.mv_store.top_k_ids(ids, query_vectors, code, limit)
+        return self._resident_answer(res, metric)
+
+    def _resident_answer(self, res, metric):
         if res[0] != "ok":
             return ("error", self._MV_ERRORS.get(res[1], res[1]))
         return ("ok", [Result(id=i, value=self.store[i].value, score=float(score), distance=None, metric=metric,

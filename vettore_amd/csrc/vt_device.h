@@ -573,6 +573,40 @@ struct MaxSimResidentPlan {
 bool maxsim_resident_plan(uint32_t d, uint32_t nq, int metric, MaxSimResidentPlan *out);
 size_t maxsim_resident_lds_bytes(uint32_t panel_qn, uint32_t q_stride, const MaxSimResidentPlan &p);
 hipError_t launch_maxsim_resident(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s);
+// K9rb (vt_maxsim_batch.hip): K9r over many query sets in one launch.  The sets' query vectors are one matrix of slots,
+// each set padded with zero rows to whole groups of eight; desc[g] describes group g (slots [8 g, 8 g + 8)): the set it
+// belongs to and, in `info`, its real slots (1..8), kMaxSimBatchFirst / kMaxSimBatchLast at the set's first / last group.
+// blockIdx.y picks groups[y]: a panel -- descriptors [desc0, desc0 + ndesc), whole sets, staged in LDS -- and the
+// document list it is scored against, entries [list0, list0 + ndoc) of doc_first / doc_cnt / doc_rank.  Document i of
+// the list leaves set s's key and payload {i, score} at keys / pay[s * key_stride + i], or kEmptyKey there and
+// (i << 8 | status) in first_error[s] (atomicMin).  host/vt_mvbatch.h packs sets into panels; the tile and the slots a
+// panel may hold are maxsim_resident_plan's, asked for the slots of the largest panel wanted.
+constexpr uint32_t kMaxSimBatchFirst = 1u << 8, kMaxSimBatchLast = 1u << 9;
+struct MaxSimBatchDesc {
+  uint32_t set, info;
+};
+struct MaxSimBatchGroup {
+  uint32_t desc0, ndesc, list0, ndoc;
+};
+struct MaxSimBatchArgs {
+  const float *X;                  // the store's slab
+  size_t stride;                   // round_up(d, 4)
+  const float *Q;                  // [slots][q_stride], zero-padded rows and zero pad slots
+  uint32_t q_stride, d;
+  int metric, order;
+  const double *qnorm;             // cosine: [slots]
+  const double *tnorm;             // cosine: per row of X
+  const MaxSimBatchGroup *groups;  // [ngroups]
+  const MaxSimBatchDesc *desc;
+  const uint32_t *doc_first, *doc_cnt, *doc_rank;
+  uint32_t ngroups;                // gridDim.y (<= 65535)
+  uint32_t max_ndesc;              // the longest panel of the launch: sizes the LDS request
+  uint32_t key_stride;             // >= every list's ndoc
+  uint64_t *keys;
+  Payload *pay;
+  unsigned long long *first_error;  // [sets], ~0 when none
+};
+hipError_t launch_maxsim_batch(const MaxSimBatchArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s);
 // Compaction of a store: row j of outX / out_norms = row src[j] of X / norms (`stride` floats a row, a multiple of 4).
 hipError_t launch_mv_compact(const float *X, const double *norms, const uint32_t *src, uint32_t rows, uint32_t stride,
                              float *outX, double *out_norms, hipStream_t s);

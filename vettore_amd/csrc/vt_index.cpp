@@ -34,6 +34,7 @@
 // The host side in reading order (one translation unit; see the note at the top of each part):
 #include "host/vt_idtable.h"
 #include "host/vt_mvstore.h"
+#include "host/vt_mvbatch.h"
 #include "host/vt_concurrency.h"
 #include "host/vt_base.h"
 #include "host/vt_types.h"
@@ -877,6 +878,77 @@ int vt_mv_top_k_ids(vt_mv *s, size_t count, const char *ids, const size_t *id_of
   std::lock_guard<std::mutex> g(s->mu);
   return mv_search(s, true, count, ids, id_off, query, query_off, nquery, metric_code, limit, out);
   });
+}
+
+namespace {
+
+// vt_mv_top_k_batch / vt_mv_top_k_ids_batch behind their argument checks
+int mv_batch_call(vt_mv *s, bool subset, size_t nsets, const size_t *set_id_off, const char *ids, const size_t *id_off,
+                  const size_t *set_vec_off, const float *query, const size_t *query_off, int metric_code, size_t limit,
+                  vt_hits **out, int *set_status) {
+  for (size_t b = 0; b < nsets; ++b) out[b] = nullptr;
+  if (metric_code < VT_L2 || metric_code > VT_JACCARD) return VT_ERR_UNKNOWN_METRIC;  // (decoded first, as in the single call)
+  if (nsets == 0) return VT_OK;
+  std::vector<int> status(nsets, VT_OK);
+  auto drop = [&]() {  // a call that fails leaves every out[b] NULL
+    for (size_t b = 0; b < nsets; ++b) {
+      delete out[b];
+      out[b] = nullptr;
+    }
+  };
+  int rc;
+  try {
+    std::lock_guard<std::mutex> g(s->mu);
+    rc = mv_search_batch(s, subset, nsets, set_id_off, ids, id_off, set_vec_off, query, query_off, metric_code, limit, out,
+                         status.data());
+  } catch (...) {  // (bad_alloc under a later set: the lists of the earlier ones go before `guarded` turns it into a status)
+    drop();
+    throw;
+  }
+  // without set_status the first failing set, in batch order, fails the call (vt_muvera_encode's convention)
+  for (size_t b = 0; b < nsets && rc == VT_OK && !set_status; ++b) rc = status[b];
+  if (rc != VT_OK) {
+    drop();
+    return rc;
+  }
+  for (size_t b = 0; b < nsets && set_status; ++b) {
+    set_status[b] = status[b];
+    if (status[b] != VT_OK && out[b]) {
+      delete out[b];
+      out[b] = nullptr;
+    }
+  }
+  return VT_OK;
+}
+
+}  // namespace
+
+int vt_mv_top_k_batch(vt_mv *s, size_t nsets, const size_t *set_vec_off, const float *query, const size_t *query_off,
+                      int metric_code, size_t limit, vt_hits **out, int *set_status) {
+  return guarded([&]() -> int {
+  if (!s || !out || !set_vec_off || (set_vec_off[nsets] && !query_off)) return VT_ERR_ARGUMENT;
+  return mv_batch_call(s, false, nsets, nullptr, nullptr, nullptr, set_vec_off, query, query_off, metric_code, limit, out,
+                       set_status);
+  });
+}
+
+int vt_mv_top_k_ids_batch(vt_mv *s, size_t nsets, const size_t *set_id_off, const char *ids, const size_t *id_off,
+                          const size_t *set_vec_off, const float *query, const size_t *query_off, int metric_code,
+                          size_t limit, vt_hits **out, int *set_status) {
+  return guarded([&]() -> int {
+  if (!s || !out || !set_vec_off || !set_id_off || (set_vec_off[nsets] && !query_off) || (set_id_off[nsets] && !id_off))
+    return VT_ERR_ARGUMENT;
+  return mv_batch_call(s, true, nsets, set_id_off, ids, id_off, set_vec_off, query, query_off, metric_code, limit, out,
+                       set_status);
+  });
+}
+
+int vt_mv_counters(const vt_mv *s, uint64_t *scoring_launches, uint64_t *batched_sets) {
+  if (!s) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(const_cast<vt_mv *>(s)->mu);
+  if (scoring_launches) *scoring_launches = s->scoring_launches;
+  if (batched_sets) *batched_sets = s->batched_sets;
+  return VT_OK;
 }
 
 int vt_mv_memory(const vt_mv *s, size_t *vectors, size_t *row_capacity, size_t *dead_rows, uint64_t *uploaded_bytes,

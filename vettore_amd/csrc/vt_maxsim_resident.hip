@@ -12,31 +12,12 @@
 // vectors keeps all 64 lanes busy, and its tokens are staged once for all 32.  The maximum over the document's tokens is a
 // reduction over the tt lanes of a group; the sum over query vectors stays one sequential wave-uniform f32 chain in
 // query order (the groups' maxima are broadcast in that order), with the error of the first query vector that has one.
-#include "vt_scan.cuh"
+#include "vt_maxsim_pair.cuh"  // the pass over one document, shared with K9rb (vt_maxsim_batch.hip)
 
 namespace vt {
 namespace dev {
 
 namespace {
-
-constexpr int kQB = 8;                       // query vectors per lane pass (as in K9)
-constexpr size_t kResidentLds = 128 * 1024;  // LDS of a block: the query panel and four tiles
-enum { MS_COS = 6 };                         // beside OP_DOT / OP_L2 / OP_L1 / OP_LINF
-
-// compute() (distances.rs:42-68) after the f32 chain, and similarity_value (distances.rs:122-128): K9's, word for word
-template <int OP>
-__device__ __forceinline__ float finish_raw(int metric, float acc, const float *q, const float *x, uint32_t d) {
-  float raw = acc;
-  if (metric == M_NIP) raw = -acc;
-  else if (metric == M_L2) raw = finite_f32(acc) ? __builtin_sqrtf(acc) : acc;
-  if (!finite_f32(raw)) raw = recover_overflow(metric, q, x, d);
-  return raw;
-}
-__device__ __forceinline__ float similarity(int metric, float raw) {
-  if (metric == M_COS || metric == M_IP) return raw;
-  if (metric == M_NIP) return -raw;
-  return 1.0f / (1.0f + raw);
-}
 
 template <int OP, int ORDER>
 __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(const MaxSimArgs a, const uint32_t ttl,
@@ -53,13 +34,17 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(
   }
   __syncthreads();
   const uint32_t tt = 1u << ttl, groups = (uint32_t)kWave >> ttl;
-  float *tile = lds + (size_t)qn * qst + (size_t)wib * tt * ld;
-  const uint32_t tok = lane & (tt - 1), qg = lane >> ttl;
-  const int metric = a.metric;
-  const uint32_t d = a.d, cfull = d / 8;
-  // the staging walk: 16-byte unit u of a tile is (row u / rs4, column u % rs4); a lane takes units lane, lane + 64, ...
-  const uint32_t rs4 = (uint32_t)a.stride / 4, ld4 = ld / 4;
-  const uint32_t row_first = lane / rs4, col_first = lane % rs4, row_step = kWave / rs4, col_step = kWave % rs4;
+  const uint32_t qg = lane >> ttl;
+  MaxSimTileWalk w;
+  w.X = a.X;
+  w.stride = a.stride;
+  w.tnorm = a.tnorm;
+  w.tile = lds + (size_t)qn * qst + (size_t)wib * tt * ld;
+  w.d = a.d;
+  w.ttl = ttl;
+  w.ld = ld;
+  w.metric = a.metric;
+  w.lane = lane;
   const bool first_panel = a.panel_q0 == 0, last_panel = a.panel_q0 + qn >= a.nq;
   const uint32_t total_waves = gridDim.x * kWavesPerBlock;
 
@@ -70,101 +55,15 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(
     for (uint32_t g = 0; g < qn && T && !st; g += kQB * groups) {
       const uint32_t gq = g + qg * kQB;  // this lane's first query vector of the pass
       const float *qk[kQB];
+      uint32_t qi[kQB];
 #pragma unroll
-      for (int k = 0; k < kQB; ++k) qk[k] = qs + (size_t)(gq + k < qn ? gq + k : qn - 1) * qst;
+      for (int k = 0; k < kQB; ++k) {
+        qi[k] = gq + k < qn ? gq + k : qn - 1;
+        qk[k] = qs + (size_t)qi[k] * qst;
+      }
       float best[kQB];
       bool bad[kQB];
-#pragma unroll
-      for (int k = 0; k < kQB; ++k) {
-        best[k] = -__builtin_inff();
-        bad[k] = false;
-      }
-      for (uint32_t j0 = 0; j0 < T; j0 += tt) {
-        const uint32_t cnt = T - j0 < tt ? T - j0 : tt;
-        if (g == 0 || T > tt) {  // (a document of one tile stays staged for the later passes)
-          wave_lds_fence();      // the readers of the tile's previous rows are done
-          const f32x4 *src = reinterpret_cast<const f32x4 *>(a.X + (size_t)(t0 + j0) * a.stride);
-          const uint32_t units = cnt * rs4;
-          uint32_t row = row_first, col = col_first;
-          for (uint32_t u = lane; u < units; u += kWave) {
-            reinterpret_cast<f32x4 *>(tile)[row * ld4 + col] = src[u];
-            row += row_step;
-            col += col_step;
-            if (col >= rs4) {
-              col -= rs4;
-              ++row;
-            }
-          }
-          wave_lds_fence();
-        }
-        const bool live = tok < cnt && gq < qn;   // (the others compute row 0 of the tile and drop it)
-        const float *x = tile + (size_t)(tok < cnt ? tok : 0) * ld;
-        float raw[kQB];
-        if (OP == MS_COS) {
-          // distances.rs:160-185 cosine(): fma(q, t, acc) == acc + q*t (a product of two f32 is exact in f64)
-          double dot[kQB];
-#pragma unroll
-          for (int k = 0; k < kQB; ++k) dot[k] = 0.0;
-          for (uint32_t e = 0; e < d; ++e) {
-            const double xv = (double)x[e];
-#pragma unroll
-            for (int k = 0; k < kQB; ++k) dot[k] = __builtin_fma((double)qk[k][e], xv, dot[k]);
-          }
-          const double rn = a.tnorm[t0 + j0 + (tok < cnt ? tok : 0)];
-#pragma unroll
-          for (int k = 0; k < kQB; ++k) {
-            const double ln = a.qnorm[a.panel_q0 + (gq + k < qn ? gq + k : qn - 1)];
-            raw[k] = 0.0f;
-            if (!(ln == 0.0 || rn == 0.0)) {
-              const double sim = dot[k] / (ln * rn);
-              raw[k] = isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
-            }
-          }
-        } else {
-          float acc[kQB];
-#pragma unroll
-          for (int k = 0; k < kQB; ++k) acc[k] = 0.0f;
-          for (uint32_t c = 0; c < cfull; ++c) {
-            const f32x4 xa = *reinterpret_cast<const f32x4 *>(x + c * 8);
-            const f32x4 xb = *reinterpret_cast<const f32x4 *>(x + c * 8 + 4);
-#pragma unroll
-            for (int k = 0; k < kQB; ++k) {
-              const f32x4 qa = *reinterpret_cast<const f32x4 *>(qk[k] + c * 8);
-              const f32x4 qb = *reinterpret_cast<const f32x4 *>(qk[k] + c * 8 + 4);
-              const float l[8] = {elem<OP>(0, qa.x, xa.x), elem<OP>(0, qa.y, xa.y), elem<OP>(0, qa.z, xa.z),
-                                  elem<OP>(0, qa.w, xa.w), elem<OP>(0, qb.x, xb.x), elem<OP>(0, qb.y, xb.y),
-                                  elem<OP>(0, qb.z, xb.z), elem<OP>(0, qb.w, xb.w)};
-              acc[k] = comb<OP>(0, acc[k], chunk_sum1<OP, ORDER>(l));
-            }
-          }
-          for (uint32_t e = cfull * 8; e < d; ++e) {  // the scalar tail, one element at a time (never the row's pad)
-            const float xe = x[e];
-#pragma unroll
-            for (int k = 0; k < kQB; ++k) acc[k] = comb<OP>(0, acc[k], elem<OP>(0, qk[k][e], xe));
-          }
-#pragma unroll
-          for (int k = 0; k < kQB; ++k) raw[k] = finish_raw<OP>(metric, acc[k], qk[k], x, d);
-        }
-#pragma unroll
-        for (int k = 0; k < kQB; ++k) {
-          if (!live) continue;
-          if (raw[k] != raw[k]) bad[k] = true;
-          else best[k] = fmaxf(best[k], similarity(metric, raw[k]));
-        }
-      }
-      // The maximum over the document's vectors as a tree over the tt lanes of a query group (K9 says why a tree may
-      // stand for the reference's fold in vector order), a failed pair anywhere in the group as a flag.
-#pragma unroll
-      for (int k = 0; k < kQB; ++k) {
-        float b = best[k];
-        int f = bad[k] ? 1 : 0;
-        for (uint32_t o = tt >> 1; o > 0; o >>= 1) {
-          b = fmaxf(b, __shfl_xor(b, (int)o, kWave));
-          f |= __shfl_xor(f, (int)o, kWave);
-        }
-        best[k] = b;
-        bad[k] = f != 0;
-      }
+      maxsim_pass<OP, ORDER>(w, t0, T, g == 0, gq < qn, qk, a.qnorm + a.panel_q0, qi, best, bad);
       // the sum over query vectors: sequential, in query order -- group after group, each group's eight from its first
       // lane -- and the reference's error at the first query vector that has one (wave-uniform)
       for (uint32_t h = 0; h < groups; ++h) {

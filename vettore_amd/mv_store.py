@@ -1,5 +1,5 @@
 """A resident multi-vector store: documents -- lists of vectors -- put once and kept in device memory, searched by
-MaxSim (K9r) without another upload.  A thin object over the vt_mv_* entry points (include/vettore_flat.h): a search
+MaxSim (K9r; K9rb for many query sets in one call) without another upload.  A thin object over the vt_mv_* entry points (include/vettore_flat.h): a search
 returns what `nifs.multi_vector_top_k` returns for the live documents in the order of their last put, bit for bit."""
 from __future__ import annotations
 
@@ -24,6 +24,19 @@ class ResidentMultiVector:
     def top_k_ids(self, ids, query_vectors, metric_code, limit):
         """Over the listed live documents only: unknown ids are skipped, a duplicate counts once."""
         return nifs.mv_top_k_ids(self.ref, ids, query_vectors, metric_code, limit)
+
+    def top_k_batch(self, query_sets, metric_code, limit):
+        """top_k for every query set in one call: [("ok", hits) | ("error", reason)], each what top_k returns for that
+        set alone on the same store state; ("error", reason) when the call itself fails."""
+        return nifs.mv_top_k_batch(self.ref, query_sets, metric_code, limit)
+
+    def top_k_ids_batch(self, id_lists, query_sets, metric_code, limit):
+        """top_k_ids for every (id list, query set) pair in one call."""
+        return nifs.mv_top_k_ids_batch(self.ref, id_lists, query_sets, metric_code, limit)
+
+    def counters(self):
+        """{"scoring_launches", "batched_sets"}: MaxSim kernel launches and query sets scored by K9rb since the store was made."""
+        return nifs.mv_counters(self.ref)
 
     def memory(self):
         return nifs.mv_memory(self.ref)

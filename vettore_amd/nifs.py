@@ -485,16 +485,17 @@ def _mv_search_args(metric_code, limit):
         raise TypeError("badarg: limit is a usize")
 
 
-def mv_top_k(store: MvRef, query_vectors, metric_code: int, limit: int):
-    """multi_vector_top_k over the store's live documents in the order of their last put."""
+def mv_top_k(store: MvRef, query_vectors, metric_code: int, limit: int, with_keys: bool = False):
+    """multi_vector_top_k over the store's live documents in the order of their last put (`with_keys`: each hit's rank
+    sort key as well)."""
     _mv_search_args(metric_code, limit)
     qv, qoff = _vector_list(query_vectors)
     h = C.c_void_p()
     st = _lib.load().vt_mv_top_k(store.handle, _fp(qv), _szp(qoff), qoff.size - 1, metric_code, limit, C.byref(h))
-    return ("ok", _take_hits(h)) if st == 0 else _err(st)
+    return ("ok", _export_hits(h, with_keys)) if st == 0 else _err(st)
 
 
-def mv_top_k_ids(store: MvRef, ids, query_vectors, metric_code: int, limit: int):
+def mv_top_k_ids(store: MvRef, ids, query_vectors, metric_code: int, limit: int, with_keys: bool = False):
     """The same over the listed live documents only."""
     _mv_search_args(metric_code, limit)
     idb, ioff = _pack_ids(ids)
@@ -502,7 +503,63 @@ def mv_top_k_ids(store: MvRef, ids, query_vectors, metric_code: int, limit: int)
     h = C.c_void_p()
     st = _lib.load().vt_mv_top_k_ids(store.handle, ioff.size - 1, idb, _szp(ioff), _fp(qv), _szp(qoff), qoff.size - 1,
                                      metric_code, limit, C.byref(h))
-    return ("ok", _take_hits(h)) if st == 0 else _err(st)
+    return ("ok", _export_hits(h, with_keys)) if st == 0 else _err(st)
+
+
+def _pack_sets(sets):
+    """[[vector]] per set -> (values, vector offsets, per-set vector offsets)."""
+    per_set = [[_f32_list(v) for v in vecs] for vecs in sets]
+    set_off = np.zeros(len(per_set) + 1, dtype=np.uintp)
+    if per_set:
+        set_off[1:] = np.cumsum([len(v) for v in per_set])
+    vals, voff = _pack_ragged([v for vecs in per_set for v in vecs], np.float32)
+    return vals, voff, set_off
+
+
+def _mv_batch_results(st, outs, status, nsets, with_keys):
+    """Takes (and frees) every hit list a batch call left; one ("ok", hits) | ("error", reason) per set."""
+    take = _take_hits_with_keys if with_keys else _take_hits
+    lists = [take(C.c_void_p(outs[b])) if outs[b] else None for b in range(nsets)]
+    if st != 0:
+        return _err(st)
+    return [("ok", lists[b]) if status[b] == 0 else _err(status[b]) for b in range(nsets)]
+
+
+def mv_top_k_batch(store: MvRef, sets, metric_code: int, limit: int, with_keys: bool = False):
+    """mv_top_k for every query set of `sets` in one call: [("ok", hits) | ("error", reason)] per set, each exactly what
+    mv_top_k returns for that set alone; ("error", reason) when the call itself fails (an unknown metric)."""
+    _mv_search_args(metric_code, limit)
+    qv, qoff, set_off = _pack_sets(sets)
+    n = len(set_off) - 1
+    outs, status = (C.c_void_p * max(n, 1))(), (C.c_int * max(n, 1))()
+    st = _lib.load().vt_mv_top_k_batch(store.handle, n, _szp(set_off), _fp(qv), _szp(qoff), metric_code, limit, outs, status)
+    return _mv_batch_results(st, outs, status, n, with_keys)
+
+
+def mv_top_k_ids_batch(store: MvRef, id_lists, sets, metric_code: int, limit: int, with_keys: bool = False):
+    """mv_top_k_ids for every (id list, query set) pair in one call."""
+    _mv_search_args(metric_code, limit)
+    if len(id_lists) != len(sets):
+        raise ValueError("badarg: one id list per query set")
+    id_lists = [list(ids) for ids in id_lists]
+    idb, ioff = _pack_ids(i for ids in id_lists for i in ids)
+    set_id_off = np.zeros(len(id_lists) + 1, dtype=np.uintp)
+    if id_lists:
+        set_id_off[1:] = np.cumsum([len(ids) for ids in id_lists])
+    qv, qoff, set_off = _pack_sets(sets)
+    n = len(set_off) - 1
+    outs, status = (C.c_void_p * max(n, 1))(), (C.c_int * max(n, 1))()
+    st = _lib.load().vt_mv_top_k_ids_batch(store.handle, n, _szp(set_id_off), idb, _szp(ioff), _szp(set_off), _fp(qv),
+                                           _szp(qoff), metric_code, limit, outs, status)
+    return _mv_batch_results(st, outs, status, n, with_keys)
+
+
+def mv_counters(store: MvRef) -> dict:
+    launches, sets = C.c_uint64(), C.c_uint64()
+    st = _lib.load().vt_mv_counters(store.handle, C.byref(launches), C.byref(sets))
+    if st != 0:
+        raise RuntimeError("mv_counters: " + _lib.error_text(st))
+    return {"scoring_launches": launches.value, "batched_sets": sets.value}
 
 
 def mv_memory(store: MvRef) -> dict:
