@@ -51,9 +51,9 @@ NOSCRATCH_vt_maxsim_resident := maxsim_resident_kernel
 NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 # K10 (MUVERA): one lane's f64 chain per dot product, nothing indexed dynamically in registers
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
-# K1q (the int8 sketch pass): its register ring must stay in registers; its tail (one block behind every pass) likewise
+# K1q and K1s (the int8 and 6-bit sketch passes): the register ring must stay in registers; its tail (one block behind every pass) likewise
 # carries no scratch segment
-NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel
+NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch6_scan_kernel
 NOSPILL_vt_batch_bf16     := bf16_scores_kernel
 NOSPILL_vt_batch_shadow   := shadow_scores_kernel
 

@@ -61,6 +61,9 @@ class Profile(C.Structure):
         ("sketch_candidates", C.c_uint64), ("sketch_fallbacks", C.c_uint64), ("sketch_builds", C.c_uint64),
         ("sketch_patched_rows", C.c_uint64),
         ("sketch_tail_rescored", C.c_uint64),
+        ("sketch6_launches", C.c_uint64), ("sketch6_ms", C.c_double), ("sketch6_bytes", C.c_uint64),
+        ("sketch6_candidates", C.c_uint64), ("sketch6_fallbacks", C.c_uint64), ("sketch6_builds", C.c_uint64),
+        ("sketch6_patched_rows", C.c_uint64),
     ]
 
 

@@ -66,14 +66,38 @@ bool sketch_wanted(const Shard *ix, size_t limit) {
   if (!ix->ranks_clean || ix->n == 0 || ix->dim <= 0 || (uint32_t)ix->dim > vt::kSketchMaxDim) return false;
   if (limit == 0 || sketch_list_k(limit) > (size_t)vt::kMaxFusedK || vt::sketch_scan_lds_bytes((uint32_t)ix->dim, sketch_list_k(limit)) == 0)
     return false;
-  return vt::env::on(vt::env::FORCE_SKETCH) || (double)ix->n * ix->ld * 4.0 >= kSketchMinBytes;
+  // (force_sketch6 brings the int8 sketch with it: it is the 6-bit pass's fallback, and serves the limits that pass declines)
+  return vt::env::on(vt::env::FORCE_SKETCH) || vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= kSketchMinBytes;
 }
 size_t sketch_elems(const Shard *ix) { return vt::sketch_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
+
+// K1s (vt_sketch.hip): where K1q applies, limits up to kSketch6MaxLimit over f32 rows of at least
+// kSketch6MinBytes read the 6-bit sketch instead -- 0.755 of the int8 sketch's bytes -- with block lists of kSketch6ListK
+// entries; its wider intervals leave hundreds of candidates, which always go through the gathered K1.  The int8 pass is
+// its fallback: a pass that does not certify is followed by K1q, and after kSketch6MissLimit such passes in a row the
+// shard stops taking K1s until the column is built anew (spiky rows never certify: DESIGN 4.10).  force_sketch alone
+// never selects it.
+// kSketch6MinBytes: the longer chain behind the pass (certify-only tail 57 us, gathered K1 16.5, select 8.8 against K1q's
+// tail of 26: +56 us in the headline's trace) is paid back at 22.5 ps per row (592 B at 6.37 TB/s against 784 B at
+// 6.79 TB/s), i.e. near 2.5 M rows of d = 768 = 7.6 GB of f32 rows; the cut sits at twice that, where the path has been
+// measured to win.  Rows below it are served exactly as before.
+constexpr double kSketch6MinBytes = 16.0 * 1024 * (1 << 20);
+constexpr size_t kSketch6MaxLimit = 32;
+constexpr uint32_t kSketch6ListK = 64;
+constexpr uint32_t kSketch6CandCap = 32768;       // ~100 MB of f32 rows at d = 768
+constexpr uint32_t kSketch6RescoreBlocks = 256;
+constexpr uint32_t kSketch6MissLimit = 4;
+bool sketch6_wanted(const Shard *ix, size_t limit) {
+  if (!sketch_wanted(ix, limit) || limit > kSketch6MaxLimit || !vt::env::on(vt::env::SKETCH6) || ix->sketch6.refused) return false;
+  if (vt::sketch6_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
+  return vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= kSketch6MinBytes;
+}
+size_t sketch6_elems(const Shard *ix) { return vt::sketch6_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
 // The derived columns a reader with `need` / `limit` wants current, as the elements each must hold (0: not wanted).
 // shard_stale and shard_prepare both go by this one answer.  (A shard with rows.)
 struct ColumnsWanted {
-  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0;
+  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0, sketch6 = 0;
 };
 ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   ColumnsWanted w;
@@ -84,6 +108,7 @@ ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   if (need & NEED_NORMS) w.norms = rows;
   if ((need & NEED_NORMS) && shadow_wanted(ix)) w.shadow = shadow_elems(ix);
   if ((need & NEED_SKETCH) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
+  if ((need & NEED_SKETCH) && sketch6_wanted(ix, limit)) w.sketch6 = sketch6_elems(ix);
   return w;
 }
 
@@ -97,13 +122,13 @@ bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
   const ColumnsWanted w = columns_wanted(ix, need, limit);
   return (w.bits && !ix->bits.current(w.bits)) || (w.nz_bits && !ix->nz_bits.current(w.nz_bits)) ||
          (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow)) ||
-         (w.sketch && !ix->sketch.current(w.sketch));
+         (w.sketch && !ix->sketch.current(w.sketch)) || (w.sketch6 && !ix->sketch6.current(w.sketch6));
 }
 
 int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords);
 int index_ensure_norms(Shard *ix, size_t rows);
 int index_ensure_shadow(Shard *ix, size_t elems);
-int index_ensure_sketch(Shard *ix, size_t bytes);
+int index_ensure_sketch(Shard *ix, size_t bytes, bool six = false);
 
 // Brings the derived columns a reader needs up to date (exclusive access; primary context).
 int shard_prepare(Shard *ix, unsigned need, size_t limit) {
@@ -118,6 +143,7 @@ int shard_prepare(Shard *ix, unsigned need, size_t limit) {
   if (w.norms) VT_TRY(index_ensure_norms(ix, w.norms));
   if (w.shadow) VT_TRY(index_ensure_shadow(ix, w.shadow));
   if (w.sketch) VT_TRY(index_ensure_sketch(ix, w.sketch));
+  if (w.sketch6) VT_TRY(index_ensure_sketch(ix, w.sketch6, true));
   return VT_OK;
 }
 
@@ -286,6 +312,115 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   return VT_OK;
 }
 
+// K1s, one host wait: blit, the 6-bit pass, the tail in its certify-only mode, the gathered K1 over the candidate rows it
+// left (the count read on the device: none when the pass did not certify) and K1's select, all queued before the wait.
+// *done as sketch_search has it; a pass that does not certify counts towards the shard's miss limit.
+int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
+  *done = false;
+  const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d);
+  double qq = 0.0;
+  for (uint32_t i = 0; i < d; ++i) qq += (double)query[i] * (double)query[i];
+  const double up = 1.0 + 0x1p-30;
+  const double qn = std::sqrt(qq) * up;
+  if (!(qn * ix->sketch6_max_norm * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
+  const uint32_t lw = vt_host::sketch6_level_words(d);
+  const size_t total = (size_t)ld + (size_t)vt::kSketch6Levels * lw;
+  VT_TRY(c.dQ.ensure(total));
+  VT_TRY(c.hQ.ensure(total));
+  if (c.hSkResid.size() < d) c.hSkResid.resize(d);
+  float *hq = c.hQ.p;
+  std::memcpy(hq, query, (size_t)d * sizeof(float));
+  for (uint32_t i = d; i < ld; ++i) hq[i] = 0.0f;
+  float t[vt::kSketch6Levels];
+  double ee = 0.0;
+  static_assert(vt::kSketch6Levels == vt_host::kSketch6Levels, "one number of query levels on both sides");
+  vt_host::sketch6_query_levels(query, d, reinterpret_cast<uint32_t *>(hq + ld), c.hSkResid.data(), t, &ee);
+  c.qbits_kind = 0;
+  c.qsrc = c.dQ.p;
+  VT_HIP(hipMemcpyAsync(c.dQ.p, c.hQ.p, total * sizeof(float), hipMemcpyHostToDevice, c.stream));
+
+  const uint32_t kp = kSketch6ListK, k = (uint32_t)limit;
+  const uint32_t blocks = (uint32_t)c.num_cus * 4u;
+  VT_TRY(c.dSkKeys.ensure((size_t)blocks * kp));
+  VT_TRY(c.dSkPay.ensure((size_t)blocks * kp));
+  VT_TRY(c.dSk6Rows.ensure(kSketch6CandCap));
+  VT_TRY(c.dSkCount.ensure(1));
+  VT_TRY(c.hSkInfo.ensure(4));
+  VT_TRY(c.ensure_part_lists((size_t)kSketch6RescoreBlocks * k));
+  uint32_t *info = c.hSkInfo.mapped();
+  if (!info) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch status)");
+  vt::Sketch6ScanArgs a{};
+  a.img = ix->sketch6.buf.p;
+  a.id_rank = ix->dRank.p;
+  a.qimg = reinterpret_cast<const uint32_t *>(c.dQ.p + ld);
+  a.n = ix->n;
+  a.d = d;
+  a.ld8 = ld8;
+  a.metric = ix->metric;
+  for (int j = 0; j < vt::kSketch6Levels; ++j) a.t[j] = t[j];
+  a.qn = qn;
+  a.eta = std::sqrt(ee) * up;
+  a.kerr = 8.0 * d * 0x1p-24;  // K1's summation error per unit of ||q|| ||x_r|| (DESIGN_APPENDIX A.5)
+  a.k = kp;
+  a.part_keys = c.dSkKeys.p;
+  a.part_pay = c.dSkPay.p;
+  VT_TRY(c.mark_begin());
+  VT_HIP(vt::launch_sketch6_scan(a, blocks, c.stream));
+  VT_TRY(c.mark_end());
+  vt::SketchTailArgs ta{};
+  ta.keys = c.dSkKeys.p;
+  ta.pay = c.dSkPay.p;
+  ta.lists = blocks;
+  ta.kp = kp;
+  ta.k = k;
+  ta.cap = kSketch6CandCap;
+  ta.rows = c.dSk6Rows.p;
+  ta.count = c.dSkCount.p;
+  ta.info = info;
+  ta.X = ix->dX;
+  ta.stride = ld;
+  ta.q = c.qsrc;
+  ta.id_rank = ix->dRank.p;
+  ta.d = d;
+  ta.metric = ix->metric;
+  ta.order = ix->order;
+  ta.status = c.dStatus.p;
+  ta.out = c.dResMapped;
+  ta.certify_only = 1;
+  VT_HIP(vt::launch_sketch_tail(ta, c.stream));
+  vt::ScanArgs sa = scan_args(ix, c, d);
+  set_gather(sa, gather_of(c.dSk6Rows.p), kSketch6CandCap);  // (the list's room: the count is batch_counts[0])
+  sa.k = k;
+  use_part_lists(sa, c);
+  sa.batch_counts = c.dSkCount.p;
+  sa.batch_cap = kSketch6CandCap;
+  VT_HIP(vt::launch_scan_batch(sa, kSketch6RescoreBlocks, 1, c.stream));
+  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, kSketch6RescoreBlocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
+                           c.dSelKeys.p, c.dSelPay.p, c.stream));
+  VT_HIP(hipStreamSynchronize(c.stream));
+  const bool certified = c.hSkInfo.p[0] == 2u && c.hRes.p->status == 0;
+  if (c.profiling) {
+    float ms = 0.f;
+    VT_TRY(c.span_ms(&ms));
+    const uint64_t bytes = (uint64_t)vt::sketch6_bytes(ix->n, d);
+    c.prof.sketch6_launches += 1;
+    c.prof.sketch6_ms += ms;
+    c.prof.sketch6_bytes += bytes;
+    c.prof.sketch6_candidates += c.hSkInfo.p[1];
+    VT_TRY(c.book_scan(1, ix->n, bytes));
+  }
+  if (!certified) {
+    c.prof.sketch6_fallbacks += 1;
+    ix->sketch6_misses.fetch_add(1, std::memory_order_relaxed);
+    return VT_OK;
+  }
+  ix->sketch6_misses.store(0, std::memory_order_relaxed);
+  std::vector<vt::Entry> entries(c.hRes.p->e, c.hRes.p->e + c.hRes.p->count);
+  VT_TRY(make_hits(ix, entries, out));
+  *done = true;
+  return VT_OK;
+}
+
 // flat.rs:96-124 on a shard whose rank column shard_prepare has brought up to date --
 // strictly (ranks_clean) or lazily (newcomers share kUnranked).  Read-only on the shard.
 // `lone`: a search on its own (flat_search), which takes K1q when the sketch is current; the single searches a batch
@@ -294,6 +429,12 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
   if (limit == 0) return empty_hits(out);
   VT_TRY(validate_vector(query, n, ix->dim));
   if (ix->n == 0) return empty_hits(out);
+  if (lone && sketch6_wanted(ix, limit) && ix->sketch6.current(sketch6_elems(ix)) &&
+      ix->sketch6_misses.load(std::memory_order_relaxed) < kSketch6MissLimit) {
+    bool done = false;
+    VT_TRY(sketch6_search(ix, c, query, limit, &done, out));
+    if (done) return VT_OK;
+  }
   if (lone && sketch_wanted(ix, limit) && ix->sketch.current(sketch_elems(ix))) {
     bool done = false;
     VT_TRY(sketch_search(ix, c, query, limit, &done, out));
@@ -647,22 +788,25 @@ int index_ensure_shadow(Shard *ix, size_t elems) {
 // its last use are re-quantised in place; a first use, a slab that outgrew it or more than kMaxDerivedDirty mutations
 // rebuild it (one pass over the rows); without room for it -- a quarter of the card must stay free -- it is refused and
 // lone searches keep scanning the f32 rows.  The bound on every row's norm comes back with it (the overflow guard).
-int index_ensure_sketch(Shard *ix, size_t bytes) {
+// `six`: the 6-bit sketch on the same terms (its own bound, its own counters); a whole build starts its misses over.
+int index_ensure_sketch(Shard *ix, size_t bytes, bool six) {
   Ctx &c = ix->ctx;
-  DerivedColumn<unsigned char> &col = ix->sketch;
+  DerivedColumn<unsigned char> &col = six ? ix->sketch6 : ix->sketch;
+  double &max_norm = six ? ix->sketch6_max_norm : ix->sketch_max_norm;
   if (col.current(bytes)) return VT_OK;
   const uint32_t d = (uint32_t)ix->dim;
-  const size_t tile_bytes = vt::sketch_bytes(vt::kSketchTileRows, d);
+  const size_t tile_bytes = six ? vt::sketch6_bytes(vt::kSketchTileRows, d) : vt::sketch_bytes(vt::kSketchTileRows, d);
   VT_TRY(c.dBNorm.ensure(1));
   unsigned long long bits = 0;
   if (col.patchable(bytes)) {
     uint32_t count = 0;
     VT_TRY(upload_row_list(ix, col.dirty, &count));
-    std::memcpy(&bits, &ix->sketch_max_norm, sizeof(double));
+    std::memcpy(&bits, &max_norm, sizeof(double));
     VT_HIP(hipMemcpyAsync(c.dBNorm.p, &bits, sizeof(bits), hipMemcpyHostToDevice, c.stream));
     const uint32_t rows_img = (uint32_t)(col.buf.count / tile_bytes * vt::kSketchTileRows);
-    VT_HIP(vt::launch_sketch_rows(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
-    c.prof.sketch_patched_rows += count;
+    VT_HIP((six ? vt::launch_sketch6_rows : vt::launch_sketch_rows)(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p,
+                                                                    c.dBNorm.p, c.stream));
+    (six ? c.prof.sketch6_patched_rows : c.prof.sketch_patched_rows) += count;
   } else {
     col.forget();
     if (col.buf.count < bytes) {
@@ -679,7 +823,7 @@ int index_ensure_sketch(Shard *ix, size_t bytes) {
       }
 #ifdef VT_TEST_HOOKS
       // (libvettore_hip_hooks.so only: the allocation "fails", tests/test_gpu_sketch.py checks what follows)
-      refused = refused || vt::env::on(vt::env::TEST_REFUSE_SKETCH);
+      refused = refused || vt::env::on(six ? vt::env::TEST_REFUSE_SKETCH6 : vt::env::TEST_REFUSE_SKETCH);
 #endif
       if (refused) {
         col.refuse();
@@ -688,13 +832,15 @@ int index_ensure_sketch(Shard *ix, size_t bytes) {
     }
     const uint32_t rows_img = (uint32_t)(bytes / tile_bytes * vt::kSketchTileRows);
     VT_HIP(hipMemsetAsync(c.dBNorm.p, 0, sizeof(unsigned long long), c.stream));
-    VT_HIP(vt::launch_sketch_build(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
-    c.prof.sketch_builds += 1;
+    VT_HIP((six ? vt::launch_sketch6_build : vt::launch_sketch_build)(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p,
+                                                                      c.stream));
+    (six ? c.prof.sketch6_builds : c.prof.sketch_builds) += 1;
+    if (six) ix->sketch6_misses.store(0, std::memory_order_relaxed);
   }
   VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
   // current from here on, for readers on other streams too: the build has finished before the exclusive lock can drop
   VT_HIP(hipStreamSynchronize(c.stream));
-  std::memcpy(&ix->sketch_max_norm, &bits, sizeof(double));
+  std::memcpy(&max_norm, &bits, sizeof(double));
   col.mark_current();
   return VT_OK;
 }

@@ -55,6 +55,7 @@ struct Ctx {
   DevBuf<uint32_t> dSkRows, dSkCount;
   PinnedBuf<uint32_t> hSkInfo;
   std::vector<double> hSkResid;
+  DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
   // grouped quantized searches: one stage-1 block per query
   DevBuf<ResultBlock> dStageB;
   PinnedBuf<float> hBQ, hBTau;
@@ -198,7 +199,7 @@ struct Ctx {
 constexpr size_t kMaxDerivedDirty = 65536;  // more mutated rows than this: rebuild instead of patching
 
 // A per-row column computed from a shard's rows and kept across searches (Shard: sign bits, non-zero bits, squared
-// norms, bf16 shadow, int8 sketch), so that a search after a mutation need not pass over all the rows again.  One policy for all:
+// norms, bf16 shadow, int8 and 6-bit sketch), so that a search after a mutation need not pass over all the rows again.  One policy for all:
 //  - a mutated row joins `dirty` while the column is valid; past kMaxDerivedDirty of them the column is forgotten, and
 //    the next reader rebuilds it from scratch instead of patching row by row;
 //  - a reader that wants `elems` elements may use it under the shared lock only while it is current(elems); otherwise
@@ -324,6 +325,14 @@ struct Shard {
   // sketch_max_norm: an upper bound of every row's norm (a value only while the column is valid; patches only raise it).
   DerivedColumn<unsigned char> sketch;
   double sketch_max_norm = 0.0;
+  // K1s: the rows in six bits, two planes (vt_device.h, Sketch6ScanArgs) -- 0.755 of the int8 sketch's bytes, read by the
+  // largest lone searches (vt_search.h, sketch6_search) with the int8 sketch as its fallback.  Kept on the int8 sketch's
+  // terms; the first column to go when the slab needs room.  sketch6_misses: consecutive passes the bound could not
+  // certify (readers under the shared lock count; a rebuild of the column starts over) -- at kSketch6MissLimit the shard
+  // stops taking the path.
+  DerivedColumn<unsigned char> sketch6;
+  double sketch6_max_norm = 0.0;
+  std::atomic<uint32_t> sketch6_misses{0};
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
   // ids
@@ -385,6 +394,7 @@ struct Shard {
       norms.touch(rows[i]);
       shadow.touch(rows[i]);
       sketch.touch(rows[i]);
+      sketch6.touch(rows[i]);
     }
   }
   void forget_derived() {
@@ -393,6 +403,7 @@ struct Shard {
     norms.forget();
     shadow.forget();
     sketch.forget();
+    sketch6.forget();
   }
   // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
   // shadow gives its room back.
@@ -404,6 +415,8 @@ struct Shard {
     shadow.buf.release();
     sketch.reset();
     sketch.buf.release();
+    sketch6.reset();
+    sketch6.buf.release();
   }
 };
 

@@ -713,7 +713,48 @@ struct SketchTailArgs {
   int *status;
   ResultBlock *out;
   uint32_t ld, ss, lds_words;  // set by the launcher
+  // certify only: Kt, the candidate rows, their count and the full-list check as ever, but the block never rescores
+  // (outcome 2 or 0): the caller has queued the gathered K1 and its select behind this kernel already (K1s)
+  uint32_t certify_only;
 };
 hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s);
+
+// ---- K1s (vt_sketch.hip): the same search over a 6-bit sketch in two planes -- 0.755 of K1q's bytes ------------------
+// Row r is kept as X_r = round(x_r / s_r) in [-31, 31] with s_r = max_i |x_ri| / 31, split as X = 4 H + L: H = X >> 2
+// (arithmetic, [-8, 7]) a signed nibble, L = X & 3 two bits; rho_r and nu_r as K1q has them.  Layout, per tile of 64 rows,
+// in 1-KiB runs of 16 bytes per row (lane l: row 64 t + l): ld8 / 32 runs of H -- run c holds elements [32 c, 32 c + 32),
+// nibble i of dword j is element 32 c + 8 j + i --, then ld8 / 64 runs of L -- in dword j of run c', bits [4 i, 4 i + 2)
+// are element 64 c' + 8 j + i and bits [4 i + 2, 4 i + 4) element 64 c' + 32 + 8 j + i, so that w & 0x33333333 and
+// (w >> 2) & 0x33333333 are nibble vectors aligned with the H-runs 2 c' and 2 c' + 1 --, then one run of {s, rho, nu, 0}.
+constexpr int kSketch6Levels = 3;  // the query's signed-nibble levels (host/vt_sketch6.h writes them)
+__host__ __device__ inline uint32_t sketch6_runs(uint32_t d) { return 3 * (sketch_ld8(d) / 64) + 1; }  // per tile
+__host__ __device__ inline size_t sketch6_offset(uint32_t row, uint32_t run, uint32_t runs) {
+  return ((size_t)(row / kSketchTileRows) * runs + run) * 1024 + (size_t)(row % kSketchTileRows) * 16;
+}
+inline size_t sketch6_bytes(uint32_t rows, uint32_t d) {
+  const size_t tiles = ((size_t)rows + kSketchTileRows - 1) / kSketchTileRows;
+  return tiles * sketch6_runs(d) * 1024;
+}
+// (as launch_sketch_build / launch_sketch_rows)
+hipError_t launch_sketch6_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                                unsigned long long *max_norm, hipStream_t s);
+hipError_t launch_sketch6_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                               void *img, unsigned long long *max_norm, hipStream_t s);
+
+struct Sketch6ScanArgs {
+  const void *img;
+  const uint32_t *id_rank;
+  const uint32_t *qimg;     // [kSketch6Levels][ld8 / 8]: the query's signed-nibble levels, q ~ sum_j t_j Q_j
+  uint32_t n, d, ld8;
+  int metric;
+  float t[kSketch6Levels];
+  double qn, eta, kerr;     // as SketchScanArgs
+  uint32_t k;               // entries per block list
+  uint64_t *part_keys;      // [blocks][k], as launch_sketch_scan writes them: launch_sketch_tail reads either
+  Payload *part_pay;
+};
+// k <= kSmallK and ld8 >= 256 (a tile of ld8 = 128 is shorter than the load ring: K1q serves those); 0: not supported
+size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k);
+hipError_t launch_sketch6_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
 
 }  // namespace vt

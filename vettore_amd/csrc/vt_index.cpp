@@ -33,6 +33,7 @@
 
 // The host side in reading order (one translation unit; see the note at the top of each part):
 #include "host/vt_idtable.h"
+#include "host/vt_sketch6.h"
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_concurrency.h"
@@ -1066,6 +1067,13 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch_builds += p.sketch_builds;
       t.sketch_patched_rows += p.sketch_patched_rows;
       t.sketch_tail_rescored += p.sketch_tail_rescored;
+      t.sketch6_launches += p.sketch6_launches;
+      t.sketch6_ms += p.sketch6_ms;
+      t.sketch6_bytes += p.sketch6_bytes;
+      t.sketch6_candidates += p.sketch6_candidates;
+      t.sketch6_fallbacks += p.sketch6_fallbacks;
+      t.sketch6_builds += p.sketch6_builds;
+      t.sketch6_patched_rows += p.sketch6_patched_rows;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

@@ -1,4 +1,5 @@
-// vt_sketch.hip -- K1q: a lone cosine / dot search nominated from an int8 sketch of the rows (gfx950).
+// vt_sketch.hip -- K1q: a lone cosine / dot search nominated from an int8 sketch of the rows (gfx950); K1s, the same
+// search over a 6-bit sketch in two planes, follows it below.
 //
 // The sketch (layout and bounds: vt_device.h, SketchScanArgs) holds a quarter of the f32 rows' bytes.  K1q streams it
 // once and gives every row an interval [lo_r, hi_r] that provably holds what K1 would compute for it:
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   __syncthreads();
   const uint32_t cnt = s_count;
   const bool ok = !s_fail && cnt <= a.cap;
-  const bool fused = ok && cnt <= kTailFuseMax && lists4 + cnt * a.ss <= a.lds_words;
+  const bool fused = ok && !a.certify_only && cnt <= kTailFuseMax && lists4 + cnt * a.ss <= a.lds_words;
   if (!fused) {
     if (tid == 0) {
       *a.count = ok ? cnt : 0u;
@@ -536,6 +537,213 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   }
 }
 
+// ---- K1s: the 6-bit sketch in two planes (layout: vt_device.h, Sketch6ScanArgs) ---------------------------------------
+// One wave per row, a lane per 64 elements: quantise to [-31, 31], write the two H-runs and the L-run of those elements.
+__device__ __forceinline__ void sketch6_row(const float *__restrict__ X, size_t stride, uint32_t row, bool have_row, uint32_t d,
+                                            uint32_t ld8, unsigned char *__restrict__ img, unsigned long long *max_norm, int lane) {
+  const float *src = X + (size_t)row * stride;
+  float m = 0.0f;
+  if (have_row)
+    for (uint32_t i = lane; i < d; i += kWave) m = fmaxf(m, fabsf(src[i]));
+  m = wave_max_f(m);
+  float s = m / 31.0f;
+  float inv = 31.0f / m;
+  const bool quantise = have_row && m > 0.0f && finite_f32(inv) && s > 0.0f;
+  if (!quantise) s = 0.0f;
+  const uint32_t nh = ld8 / 32, nl = ld8 / 64, runs = nh + nl + 1;
+  double res = 0.0;   // sum of (x - s X)^2, f64
+  uint32_t xx = 0;    // sum of X^2, exact
+  for (uint32_t c = lane; c < nl; c += kWave) {
+    uint32_t lw[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      uint32_t hw[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+          const uint32_t i = c * 64 + h * 32 + j * 8 + b;
+          const float x = have_row && i < d ? src[i] : 0.0f;
+          int q = 0;
+          if (quantise) {
+            q = (int)rintf(x * inv);
+            q = q > 31 ? 31 : (q < -31 ? -31 : q);
+          }
+          const double r = (double)x - (double)s * (double)q;  // (exact: s q has at most 29 significant bits)
+          res += r * r;
+          xx += (uint32_t)(q * q);
+          word |= ((uint32_t)(q >> 2) & 0xfu) << (4 * b);
+          lw[j] |= ((uint32_t)q & 3u) << (4 * b + 2 * h);
+        }
+        hw[j] = word;
+      }
+      *reinterpret_cast<u32x4 *>(img + sketch6_offset(row, 2 * c + h, runs)) = u32x4{hw[0], hw[1], hw[2], hw[3]};
+    }
+    *reinterpret_cast<u32x4 *>(img + sketch6_offset(row, nh + c, runs)) = u32x4{lw[0], lw[1], lw[2], lw[3]};
+  }
+  res = wave_sum_d(res);
+  xx = wave_sum_u(xx);
+  if (lane == 0) {
+    const double rho = sqrt(res) * (1.0 + 0x1p-30);
+    const double nu = (double)s * sqrt((double)xx) * (1.0 + 0x1p-30);
+    const float rho_f = f32_up(rho), nu_f = f32_up(nu);
+    *reinterpret_cast<u32x4 *>(img + sketch6_offset(row, nh + nl, runs)) =
+        u32x4{__float_as_uint(s), __float_as_uint(rho_f), __float_as_uint(nu_f), 0u};
+    const double bound = ((double)rho_f + (double)nu_f) * kSlack;
+    atomicMax(max_norm, (unsigned long long)__double_as_longlong(bound));
+  }
+}
+
+__global__ __launch_bounds__(256) void sketch6_build_kernel(const float *__restrict__ X, size_t stride, uint32_t n_src,
+                                                            uint32_t rows_img, uint32_t d, uint32_t ld8, unsigned char *img,
+                                                            unsigned long long *max_norm) {
+  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (w >= rows_img) return;
+  sketch6_row(X, stride, w, w < n_src, d, ld8, img, max_norm, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void sketch6_rows_kernel(const float *__restrict__ X, size_t stride, const uint32_t *__restrict__ list,
+                                                           uint32_t count, uint32_t rows_img, uint32_t d, uint32_t ld8,
+                                                           unsigned char *img, unsigned long long *max_norm) {
+  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (w >= count) return;
+  const uint32_t row = list[w];
+  if (row >= rows_img) return;
+  sketch6_row(X, stride, row, true, d, ld8, img, max_norm, threadIdx.x & 63);
+}
+
+// The pass: K1q's skeleton (a wave owns tiles wave, wave + waves, ...; a ring of kU one-KiB non-temporal loads that runs on
+// across tiles; the metadata as the tile's last load; WaveTopK lists of (key(hi), id rank) with key(lo) beside them).
+// The query's kSketch6Levels nibble levels sit in LDS.  An H-run costs one broadcast ds_read_b128 and four v_dot8_i32_i4
+// per level; an L-run two reads and, after four masks and four shifts, eight dots per level.  Per level the H and L sums
+// stay apart (exact: 8 * 7 * 32768 < 2^23) and meet in f64: a_r = s_r sum_j t_j (4 accH_j + accL_j).
+__global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch6_scan_kernel(const Sketch6ScanArgs a) {
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  constexpr int J = kSketch6Levels;
+  const uint32_t nh = a.ld8 / 32, nl = a.ld8 / 64;  // (nh: also the u32x4 words of one level of the query)
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const u32x4 *qlds = reinterpret_cast<const u32x4 *>(lds_raw);  // [J][nh]
+  unsigned char *tkbuf = lds_raw + (size_t)J * nh * 16 + wib * WaveTopK<kCapSmall>::lds_bytes();
+  for (uint32_t i = threadIdx.x; i < J * nh; i += blockDim.x)
+    reinterpret_cast<u32x4 *>(lds_raw)[i] = reinterpret_cast<const u32x4 *>(a.qimg)[i];
+  __syncthreads();
+
+  WaveTopK<kCapSmall> tk;
+  tk.init(tkbuf, a.k);
+  const uint32_t ntiles = (a.n + kSketchTileRows - 1) / kSketchTileRows;
+  const uint32_t waves = gridDim.x * kWavesPerBlock;
+  const uint32_t wave = blockIdx.x * kWavesPerBlock + wib;
+  const unsigned char *img = static_cast<const unsigned char *>(a.img);
+  const uint32_t seg = nh + nl + 1;  // loads per tile (> kU: the launcher refuses ld8 = 128)
+
+  if (wave < ntiles) {
+    const uint32_t last_tile = wave + ((ntiles - 1 - wave) / waves) * waves;
+    uint32_t pt = wave, pc = 0;  // load cursor
+    auto load = [&]() -> u32x4 {
+      const uint32_t t = pt < last_tile ? pt : last_tile;  // (past the end: the last tile again, never used)
+      const u32x4 v = __builtin_nontemporal_load(
+          reinterpret_cast<const u32x4 *>(img + ((size_t)t * seg + pc) * 1024 + (uint32_t)lane * 16));
+      if (++pc == seg) {
+        pc = 0;
+        pt += waves;
+      }
+      return v;
+    };
+    u32x4 buf[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) buf[u] = load();
+
+    const double qn = a.qn, eta = a.eta, kerr = a.kerr;
+    const double tiny = ((double)a.d + 16.0) * 0x1p-125;  // (K1's subnormal products, as in K1q)
+    uint32_t ct = wave, cc = 0;  // compute cursor
+    int aH[J], aL[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) aH[j] = aL[j] = 0;
+    while (ct < ntiles) {
+      bool fin = false;
+      int fH[J], fL[J];
+#pragma unroll
+      for (int j = 0; j < J; ++j) fH[j] = fL[j] = 0;
+      u32x4 meta = u32x4{0u, 0u, 0u, 0u};
+      uint32_t ftile = 0;
+#pragma unroll
+      for (int u = 0; u < kU; ++u) {
+        const u32x4 x = buf[u];
+        buf[u] = load();
+        if (ct < ntiles) {
+          if (cc < nh) {
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+              const u32x4 q = qlds[j * nh + cc];
+              aH[j] = __builtin_amdgcn_sdot8((int)x.x, (int)q.x, aH[j], false);
+              aH[j] = __builtin_amdgcn_sdot8((int)x.y, (int)q.y, aH[j], false);
+              aH[j] = __builtin_amdgcn_sdot8((int)x.z, (int)q.z, aH[j], false);
+              aH[j] = __builtin_amdgcn_sdot8((int)x.w, (int)q.w, aH[j], false);
+            }
+            ++cc;
+          } else if (cc < nh + nl) {
+            const uint32_t c2 = 2 * (cc - nh);
+            const u32x4 lo = x & 0x33333333u, hi = (x >> 2) & 0x33333333u;
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+              const u32x4 qa = qlds[j * nh + c2], qb = qlds[j * nh + c2 + 1];
+              aL[j] = __builtin_amdgcn_sdot8((int)lo.x, (int)qa.x, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)lo.y, (int)qa.y, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)lo.z, (int)qa.z, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)lo.w, (int)qa.w, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)hi.x, (int)qb.x, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)hi.y, (int)qb.y, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)hi.z, (int)qb.z, aL[j], false);
+              aL[j] = __builtin_amdgcn_sdot8((int)hi.w, (int)qb.w, aL[j], false);
+            }
+            ++cc;
+          } else {  // the tile's metadata: the rows are complete (at most one per group: seg > kU)
+            fin = true;
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+              fH[j] = aH[j];
+              fL[j] = aL[j];
+              aH[j] = aL[j] = 0;
+            }
+            meta = x;
+            ftile = ct;
+            cc = 0;
+            ct += waves;
+          }
+        }
+      }
+      if (fin) {
+        const uint32_t row = ftile * kSketchTileRows + (uint32_t)lane;
+        const bool valid = row < a.n;
+        const double s = (double)__uint_as_float(meta.x);
+        const double rho = (double)__uint_as_float(meta.y), nu = (double)__uint_as_float(meta.z);
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; ++j) sum += (double)a.t[j] * (double)(4 * fH[j] + fL[j]);  // (each product exact)
+        const double av = s * sum;
+        const double e = (qn * rho + eta * nu + kerr * qn * (nu + rho) + 0x1p-40 * nu * (qn + eta)) * kSlack + tiny;
+        const float hi = f32_up(av + e), lo = f32_down(av - e);
+        float khi_rank, klo_rank;  // key(lo) >= key(hi): the rank functions fall as the dot rises
+        if (a.metric == M_COS) {
+          klo_rank = 1.0f - hi;
+          khi_rank = 1.0f - lo;
+        } else {
+          klo_rank = -hi;
+          khi_rank = -lo;
+        }
+        const uint32_t rank = valid ? (a.id_rank ? a.id_rank[row] : row) : 0u;
+        const uint64_t key = ((uint64_t)orderable(klo_rank) << 32) | rank;
+        tk.offer(valid, key, row, khi_rank, lane);
+      }
+    }
+  }
+  __shared__ uint32_t s_counts[kWavesPerBlock];
+  tk.merge_block(wib, kWavesPerBlock, s_counts, lane);
+  if (wib == 0) tk.store(a.part_keys + (size_t)blockIdx.x * a.k, a.part_pay + (size_t)blockIdx.x * a.k, lane);
+}
+
 }  // namespace
 
 hipError_t launch_sketch_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
@@ -597,6 +805,40 @@ hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s) {
   hipError_t e = allow_lds(sketch_tail_kernel, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sketch_tail_kernel, dim3(1), dim3(kTailThreads), lds, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sketch6_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                                unsigned long long *max_norm, hipStream_t s) {
+  if (d == 0 || d > kSketchMaxDim || rows_img % kSketchTileRows) return hipErrorInvalidValue;
+  if (rows_img == 0) return hipSuccess;
+  hipLaunchKernelGGL(sketch6_build_kernel, dim3((rows_img + 3) / 4), dim3(256), 0, s, X, stride, n_src, rows_img, d,
+                     sketch_ld8(d), static_cast<unsigned char *>(img), max_norm);
+  return hipGetLastError();
+}
+
+hipError_t launch_sketch6_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                               void *img, unsigned long long *max_norm, hipStream_t s) {
+  if (d == 0 || d > kSketchMaxDim) return hipErrorInvalidValue;
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(sketch6_rows_kernel, dim3((count + 3) / 4), dim3(256), 0, s, X, stride, list, count, rows_img, d,
+                     sketch_ld8(d), static_cast<unsigned char *>(img), max_norm);
+  return hipGetLastError();
+}
+
+size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k) {
+  if (d == 0 || d > kSketchMaxDim || k == 0 || k > (uint32_t)kSmallK) return 0;
+  if (sketch6_runs(d) <= (uint32_t)kU) return 0;  // (ld8 = 128: two tiles could end in one group of loads)
+  const size_t bytes = (size_t)kSketch6Levels * sketch_ld8(d) / 2 + kWavesPerBlock * WaveTopK<kCapSmall>::lds_bytes();
+  return bytes <= kMaxLds ? bytes : 0;
+}
+
+hipError_t launch_sketch6_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s) {
+  const size_t lds = sketch6_scan_lds_bytes(a.d, a.k);
+  if (!lds || a.ld8 != sketch_ld8(a.d) || blocks == 0 || !a.part_keys || !a.part_pay) return hipErrorInvalidValue;
+  hipError_t e = allow_lds(sketch6_scan_kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sketch6_scan_kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
   return hipGetLastError();
 }
 
