@@ -24,7 +24,7 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -53,7 +53,17 @@ NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
 # K1q and K1s (the int8 and 6-bit sketch passes): the register ring must stay in registers; its tail (one block behind every pass) likewise
 # carries no scratch segment
-NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch6_scan_kernel
+NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel
+NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
+# K1s's pass branches three ways per run on wave-uniform cursors.  By default the CFG structurizer lays the three arms out in
+# a row behind flags, as it must for divergent branches, and every sum then lives across all arms and is copied in each
+# (about 400 v_mov_b32 per tile at d = 768, profiles/sketch6_loop/isa_counts.txt); told to leave wave-uniform regions as
+# written, the arms hold their dots alone.  For that unit only: no other kernel is built this way.
+# The option is an internal one of LLVM, off by default: the figures (85 VGPRs, 5 waves / SIMD, 648 VALU instructions in a
+# tile's run blocks) are this toolchain's.  A compiler without it fails the build (unknown argument); one that changes what
+# it does still builds a correct kernel (every test holds either way) but may bring the copies back: after a ROCm update
+# count again as profiles/sketch6_loop/isa_counts.txt says, and compare the pass's time.
+EXTRA_vt_sketch6          := -mllvm -structurizecfg-skip-uniform-regions=true
 NOSPILL_vt_batch_bf16     := bf16_scores_kernel
 NOSPILL_vt_batch_shadow   := shadow_scores_kernel
 
@@ -63,6 +73,9 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(LIBDIR)/$*.resources || { grep -v 'remark:' $(LIBDIR)/$*.resources >&2; exit 1; }
 	$(if $(NOSCRATCH_$*),$(CHECK_SCRATCH) --no-scratch $(LIBDIR)/$*.resources $(NOSCRATCH_$*))
 	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
+
+# (what the sketch units share)
+$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o: $(CSRC)/vt_sketch.cuh
 
 # (the pass K9r and K9rb share)
 $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o: $(CSRC)/vt_maxsim_pair.cuh

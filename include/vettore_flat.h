@@ -550,6 +550,7 @@ typedef struct vt_profile {
   uint64_t sketch6_fallbacks;        /* passes the bound could not certify (the int8 sketch or the f32 rows then served) */
   uint64_t sketch6_builds;           /* whole builds of the 6-bit sketch */
   uint64_t sketch6_patched_rows;     /* rows re-quantised in place after mutations */
+  uint64_t sketch6_tail_words;       /* passes whose tail read the pass's word arrays (not the lists themselves) */
 } vt_profile;
 int vt_flat_set_profiling(vt_flat *index, int enabled);
 int vt_flat_get_profile(vt_flat *index, vt_profile *out, int reset);

@@ -63,7 +63,7 @@ class Profile(C.Structure):
         ("sketch_tail_rescored", C.c_uint64),
         ("sketch6_launches", C.c_uint64), ("sketch6_ms", C.c_double), ("sketch6_bytes", C.c_uint64),
         ("sketch6_candidates", C.c_uint64), ("sketch6_fallbacks", C.c_uint64), ("sketch6_builds", C.c_uint64),
-        ("sketch6_patched_rows", C.c_uint64),
+        ("sketch6_patched_rows", C.c_uint64), ("sketch6_tail_words", C.c_uint64),
     ]
 
 

@@ -71,16 +71,17 @@ bool sketch_wanted(const Shard *ix, size_t limit) {
 }
 size_t sketch_elems(const Shard *ix) { return vt::sketch_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
-// K1s (vt_sketch.hip): where K1q applies, limits up to kSketch6MaxLimit over f32 rows of at least
+// K1s (vt_sketch6.hip; its tail and builders: vt_sketch.hip): where K1q applies, limits up to kSketch6MaxLimit over f32 rows of at least
 // kSketch6MinBytes read the 6-bit sketch instead -- 0.755 of the int8 sketch's bytes -- with block lists of kSketch6ListK
 // entries; its wider intervals leave hundreds of candidates, which always go through the gathered K1.  The int8 pass is
 // its fallback: a pass that does not certify is followed by K1q, and after kSketch6MissLimit such passes in a row the
 // shard stops taking K1s until the column is built anew (spiky rows never certify: DESIGN 4.10).  force_sketch alone
 // never selects it.
-// kSketch6MinBytes: the longer chain behind the pass (certify-only tail 57 us, gathered K1 16.5, select 8.8 against K1q's
-// tail of 26: +56 us in the headline's trace) is paid back at 22.5 ps per row (592 B at 6.37 TB/s against 784 B at
-// 6.79 TB/s), i.e. near 2.5 M rows of d = 768 = 7.6 GB of f32 rows; the cut sits at twice that, where the path has been
-// measured to win.  Rows below it are served exactly as before.
+// kSketch6MinBytes: the chain behind the pass (certify-only tail 40 us, gathered K1 16, select 8.5 against K1q's tail of
+// 26: +39 us in the headline's trace) is paid back at 26 ps per row (592 B at 6.63 TB/s against 784 B at 6.79 TB/s), i.e.
+// near 1.5 M rows of d = 768 = 4.6 GB of f32 rows.  That is an estimate from two traces: the sweep over sizes that would
+// place the meeting point has not been run, so the cut stays where the path has been measured to win.  Rows
+// below it are served exactly as before.
 constexpr double kSketch6MinBytes = 16.0 * 1024 * (1 << 20);
 constexpr size_t kSketch6MaxLimit = 32;
 constexpr uint32_t kSketch6ListK = 64;
@@ -343,6 +344,8 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   const uint32_t blocks = (uint32_t)c.num_cus * 4u;
   VT_TRY(c.dSkKeys.ensure((size_t)blocks * kp));
   VT_TRY(c.dSkPay.ensure((size_t)blocks * kp));
+  VT_TRY(c.dSkLoWords.ensure((size_t)blocks * kp));
+  VT_TRY(c.dSkHiWords.ensure((size_t)blocks * kp));
   VT_TRY(c.dSk6Rows.ensure(kSketch6CandCap));
   VT_TRY(c.dSkCount.ensure(1));
   VT_TRY(c.hSkInfo.ensure(4));
@@ -361,9 +364,19 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   a.qn = qn;
   a.eta = std::sqrt(ee) * up;
   a.kerr = 8.0 * d * 0x1p-24;  // K1's summation error per unit of ||q|| ||x_r|| (DESIGN_APPENDIX A.5)
+  {  // the last level stays off the L plane: its share there is c3 -+ w3 per unit of s_r (exact: 25 bits times 19)
+    int64_t pos = 0, neg = 0, l1 = 0;
+    const uint32_t *last = reinterpret_cast<const uint32_t *>(hq + ld) + (size_t)(vt::kSketch6Levels - 1) * lw;
+    vt_host::sketch6_level_sums(last, lw, &pos, &neg, &l1);
+    const double t3 = 1.5 * (double)t[vt::kSketch6Levels - 1];
+    a.c3 = t3 * (double)(pos + neg);
+    a.w3 = t3 * (double)l1;
+  }
   a.k = kp;
   a.part_keys = c.dSkKeys.p;
   a.part_pay = c.dSkPay.p;
+  a.lo_words = c.dSkLoWords.p;
+  a.hi_words = c.dSkHiWords.p;
   VT_TRY(c.mark_begin());
   VT_HIP(vt::launch_sketch6_scan(a, blocks, c.stream));
   VT_TRY(c.mark_end());
@@ -387,6 +400,8 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   ta.status = c.dStatus.p;
   ta.out = c.dResMapped;
   ta.certify_only = 1;
+  ta.lo_words = c.dSkLoWords.p;
+  ta.hi_words = c.dSkHiWords.p;
   VT_HIP(vt::launch_sketch_tail(ta, c.stream));
   vt::ScanArgs sa = scan_args(ix, c, d);
   set_gather(sa, gather_of(c.dSk6Rows.p), kSketch6CandCap);  // (the list's room: the count is batch_counts[0])
@@ -407,6 +422,7 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
     c.prof.sketch6_ms += ms;
     c.prof.sketch6_bytes += bytes;
     c.prof.sketch6_candidates += c.hSkInfo.p[1];
+    c.prof.sketch6_tail_words += c.hSkInfo.p[3] == 1u ? 1 : 0;
     VT_TRY(c.book_scan(1, ix->n, bytes));
   }
   if (!certified) {

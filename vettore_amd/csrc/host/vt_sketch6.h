@@ -1,6 +1,7 @@
-// vt_sketch6.h -- the host side of the 6-bit sketch (K1s, vt_sketch.hip): the query's signed-nibble levels and
-// a restatement of the row quantiser.  Stand-alone on purpose (no HIP, no other header of the library): vt_search.h uses
-// it, and tests/sketch6_query_check.cpp builds it with plain g++ under AddressSanitizer and UBSan.
+// vt_sketch6.h -- the host side of the 6-bit sketch (K1s: vt_sketch6.hip the pass, vt_sketch.hip the builders):
+// the query's signed-nibble levels, the sums that bound the level kept off the L plane, and a restatement of the row
+// quantiser.  Stand-alone on purpose (no HIP, no other header of the library): vt_search.h uses it, and
+// tests/sketch6_query_check.cpp and tests/sketch6_split_check.cpp build it with plain g++ under AddressSanitizer and UBSan.
 #pragma once
 
 #include <algorithm>
@@ -42,6 +43,25 @@ inline void sketch6_query_levels(const float *q, uint32_t d, uint32_t *img, doub
   double s = 0.0;
   for (uint32_t i = 0; i < d; ++i) s += resid[i] * resid[i];
   *ee = s;
+}
+
+// What the pass needs to bound a level it keeps off the L plane (0 <= L_i <= 3): over one level's nibble image
+// (lw dwords, sketch6_query_levels' layout; padding nibbles are 0), *pos = the sum of its positive entries, *neg = the sum
+// of its negative entries (<= 0), *l1 = sum |Q_i| = *pos - *neg.  Q.L then lies in [3 *neg, 3 *pos].
+inline void sketch6_level_sums(const uint32_t *level, uint32_t lw, int64_t *pos, int64_t *neg, int64_t *l1) {
+  int64_t p = 0, n = 0;
+  for (uint32_t g = 0; g < lw; ++g) {
+    const uint32_t w = level[g];
+    for (int i = 0; i < 8; ++i) {
+      const int nib = (int)((w >> (4 * i)) & 0xfu);
+      const int v = nib >= 8 ? nib - 16 : nib;  // (the signed nibble)
+      if (v > 0) p += v;
+      else n += v;
+    }
+  }
+  *pos = p;
+  *neg = n;
+  *l1 = p - n;
 }
 
 // The row quantiser as sketch6_row (vt_sketch.hip) has it: s = max|x| / 31 in f32, X = round(x * (31 / max|x|)) clamped

@@ -56,6 +56,7 @@ struct Ctx {
   PinnedBuf<uint32_t> hSkInfo;
   std::vector<double> hSkResid;
   DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
+  DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
   // grouped quantized searches: one stage-1 block per query
   DevBuf<ResultBlock> dStageB;
   PinnedBuf<float> hBQ, hBTau;

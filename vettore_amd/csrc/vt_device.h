@@ -654,7 +654,7 @@ hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *o
 // rows' 16-byte chunk c is one 1-KiB run ((tile * (nch + 1) + c) * 1024 + (r % 64) * 16), c < nch = ld8 / 16, and the
 // tile ends with one more run of {s, rho, nu, 0} per row -- a wave streams a tile, metadata included, in whole 1-KiB loads.
 constexpr uint32_t kSketchTileRows = 64;
-constexpr uint32_t kSketchMaxDim = 32768;  // (the query image sits in LDS; and d * 127^2 stays far below 2^31)
+constexpr uint32_t kSketchMaxDim = 32768;  // (K1q's query image sits in LDS; and d * 127^2 stays far below 2^31)
 __host__ __device__ inline uint32_t sketch_ld8(uint32_t d) { return (d + 127) / 128 * 128; }
 __host__ __device__ inline size_t sketch_offset(uint32_t row, uint32_t chunk, uint32_t nch) {
   return ((size_t)(row / kSketchTileRows) * (nch + 1) + chunk) * 1024 + (size_t)(row % kSketchTileRows) * 16;
@@ -691,7 +691,7 @@ hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStrea
 
 // One block over the lists of launch_sketch_scan: Kt = the k-th smallest key(lo) retained; every retained row whose
 // key(hi) <= Kt is a candidate; certified iff they number at most `cap` and no list consists of candidates alone (a
-// full list whose largest key(hi) is <= Kt).  info = {outcome, candidates, Kt bits, 0} (host-mapped), outcome
+// full list whose largest key(hi) is <= Kt).  info = {outcome, candidates, Kt bits, 1 if the word arrays were read} (host-mapped), outcome
 //   1: certified, and the block rescored the candidates itself with K1's arithmetic (X, q, order, metric; *status
 //      raised like K1's) and wrote the k best, sorted, with the status word into *out like launch_select -- taken when
 //      they are few enough for its LDS (at most 256);
@@ -716,6 +716,11 @@ struct SketchTailArgs {
   // certify only: Kt, the candidate rows, their count and the full-list check as ever, but the block never rescores
   // (outcome 2 or 0): the caller has queued the gathered K1 and its select behind this kernel already (K1s)
   uint32_t certify_only;
+  // launch_sketch6_scan's word arrays ([lists][kp] each; kp even), or both null: the sweeps then read keys and pay.  With
+  // them the first sweep reads lo_words alone and stages their upper halves in LDS, the filing sweep compares the staged
+  // halves and reads again only the words it files, the collect reads hi_words and a candidate's pay[i].row.  Taken when
+  // the halves fit the block's LDS (info[3] = 1 then); Kt, the candidates and the full-list check are the ones the lists give.
+  const uint32_t *lo_words, *hi_words;
 };
 hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s);
 
@@ -749,9 +754,16 @@ struct Sketch6ScanArgs {
   int metric;
   float t[kSketch6Levels];
   double qn, eta, kerr;     // as SketchScanArgs
+  // The last level never meets the L plane (0 <= L_i <= 3): Q3.L_r lies in [3 N3, 3 P3], P3 / N3 the sums of Q3's positive /
+  // negative entries (host/vt_sketch6.h).  c3 = 1.5 t3 (P3 + N3) is added to the sum s_r multiplies, s_r w3 with
+  // w3 = 1.5 t3 ||Q3||_1 to e_r; both products are exact in f64.
+  double c3, w3;
   uint32_t k;               // entries per block list
   uint64_t *part_keys;      // [blocks][k], as launch_sketch_scan writes them: launch_sketch_tail reads either
   Payload *part_pay;
+  // [blocks][k] each, beside the lists: a slot's orderable key(lo) word and its orderable key(hi) word, 0xffffffff in both
+  // for an empty slot -- what launch_sketch_tail's certify-only sweeps read in place of the lists themselves
+  uint32_t *lo_words, *hi_words;
 };
 // k <= kSmallK and ld8 >= 256 (a tile of ld8 = 128 is shorter than the load ring: K1q serves those); 0: not supported
 size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k);

@@ -1074,6 +1074,7 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch6_fallbacks += p.sketch6_fallbacks;
       t.sketch6_builds += p.sketch6_builds;
       t.sketch6_patched_rows += p.sketch6_patched_rows;
+      t.sketch6_tail_words += p.sketch6_tail_words;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

@@ -1,5 +1,5 @@
-// vt_sketch.hip -- K1q: a lone cosine / dot search nominated from an int8 sketch of the rows (gfx950); K1s, the same
-// search over a 6-bit sketch in two planes, follows it below.
+// vt_sketch.hip -- K1q: a lone cosine / dot search nominated from an int8 sketch of the rows (gfx950), and the tail behind
+// its pass; the builders of K1s's 6-bit sketch in two planes follow below (its pass: vt_sketch6.hip).
 //
 // The sketch (layout and bounds: vt_device.h, SketchScanArgs) holds a quarter of the f32 rows' bytes.  K1q streams it
 // once and gives every row an interval [lo_r, hi_r] that provably holds what K1 would compute for it:
@@ -10,44 +10,13 @@
 //     every block keeps its k' smallest (key(hi_r), id rank) keys (WaveTopK, K1's list layout) with key(lo_r) beside them.
 // sketch_tail_kernel then proves that the retained rows with key(hi) <= Kt hold the exact top k and rescores those few
 // with K1's exact arithmetic itself; a longer candidate list goes through the gathered K1.
-#include "vt_scan.cuh"
+#include "vt_sketch.cuh"
 
 #include <algorithm>
 
 namespace vt {
 
-using namespace dev;
-
 namespace {
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, kWave);
-  return v;
-}
-
-// f64 -> f32 rounded towards +inf / -inf (finite inputs)
-__device__ __forceinline__ float f32_up(double v) {
-  const float f = (float)v;
-  return (double)f < v ? nextafterf(f, INFINITY) : f;
-}
-__device__ __forceinline__ float f32_down(double v) {
-  const float f = (float)v;
-  return (double)f > v ? nextafterf(f, -INFINITY) : f;
-}
-constexpr double kSlack = 1.0 + 0x1p-40;  // covers the f64 rounding of the bound's own arithmetic
 
 // One wave per row: quantise, write the row's chunks and its {s, rho, nu} in the tiled layout.
 __device__ __forceinline__ void sketch_row(const float *__restrict__ X, size_t stride, uint32_t row, bool have_row, uint32_t d,
@@ -237,6 +206,15 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch_scan_kernel(cons
 // Kt is the maximum.  The collect is one more sweep of independent loads over the 64-bit keys; a list is refused when
 // every one of its k' slots is a candidate (it is full and its largest key(hi) is <= Kt: it may have dropped a row that
 // matters).
+// Behind K1s's pass the lists' words arrive a second time as two plain arrays (SketchTailArgs::lo_words / hi_words), and
+// the sweeps read those: the first the key(lo) words alone, staging their upper halves (two a dword: lists * k' / 2
+// dwords of LDS, 128 KB at the headline); U ends in 0xffff, so the filing sweep compares the staged halves and reads
+// again only the words it files; the collect reads the key(hi) words and a candidate's pay[i].row.  Kt, the candidate set,
+// the count and the full-list check are the ones the lists give.  What may differ on heavy ties is the refusal itself: a
+// thread owns the slot pairs (2 i, 2 i + 1) here, not the slots tid + 1024 j, so the 1 024 minima, U and the entries <= U
+// are other ones, and a pass with about a thousand entries tied around the k-th can be refused (info[1], info[2] then
+// differ too) where the list path files them, or the other way round; either way the search is served by the fallback.
+// info[3] says which path ran (1: the word arrays).
 // Up to kTailFuseMax candidates whose chunk sums fit the same LDS are then rescored here with K1's arithmetic: a wave
 // per row, a lane pair per 8-float chunk (elem4 / chunk_sum of vt_scan.cuh in the index's reduce order), the sums to an
 // LDS row, and one thread per candidate walks its row's sums in order -- the reference's sequential chain -- then the
@@ -287,8 +265,32 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   }
   __syncthreads();
   constexpr uint32_t kUnroll = 8;
+  // the scan's word arrays in place of its lists (SketchTailArgs): dyn holds the key(lo) words' upper halves, two a dword
+  const bool words = a.lo_words && a.hi_words && !(m & 1u) && m / 2 <= a.lds_words;
+  const uint32_t m2 = m / 2;
   uint32_t mine = 0xffffffffu;  // the smallest key(lo) word among this thread's entries
-  {
+  if (words) {
+    uint32_t live = 0;
+    const uint2 *lo2 = reinterpret_cast<const uint2 *>(a.lo_words);
+    for (uint32_t b = tid; b < m2; b += kUnroll * kTailThreads) {
+      uint2 v[kUnroll];
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+        v[u] = i < m2 ? lo2[i] : make_uint2(0xffffffffu, 0xffffffffu);
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+        live += (v[u].x != 0xffffffffu ? 1u : 0u) + (v[u].y != 0xffffffffu ? 1u : 0u);
+        const uint32_t lo = v[u].x < v[u].y ? v[u].x : v[u].y;
+        mine = lo < mine ? lo : mine;
+        if (i < m2) dyn[i] = (v[u].x >> 16) | (v[u].y & 0xffff0000u);
+      }
+    }
+    live = wave_sum_u(live);
+    if (lane == 0 && live) atomicAdd(&s_total, live);
+  } else {
     uint32_t live = 0;
     for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
       uint64_t key[kUnroll];
@@ -358,7 +360,29 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   uint32_t kt = 0xffffffffu;  // (k or fewer entries in all: every one is a candidate)
   if (s_total > a.k) {
     const uint32_t ub = s_prefix | 0xffffu;
-    for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
+    // (ub ends in 0xffff: a word's upper half decides; only the words filed are read again)
+    for (uint32_t b = tid; words && b < m2; b += kUnroll * kTailThreads) {
+      uint32_t h[kUnroll];
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+        h[u] = i < m2 ? dyn[i] : 0xffffffffu;
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < kUnroll; ++u) {
+        const uint32_t i = b + u * kTailThreads;
+#pragma unroll
+        for (uint32_t e = 0; e < 2; ++e) {
+          const uint32_t half = e ? h[u] >> 16 : h[u] & 0xffffu;
+          if (i < m2 && half <= (ub >> 16)) {
+            const uint32_t v = a.lo_words[2 * i + e];
+            const uint32_t pos = atomicAdd(&s_nsv, 1u);
+            if (pos < kTailSurvivors) sv[pos] = v;
+          }
+        }
+      }
+    }
+    for (uint32_t b = tid; !words && b < m; b += kUnroll * kTailThreads) {
       uint32_t v[kUnroll];
 #pragma unroll
       for (uint32_t u = 0; u < kUnroll; ++u) {
@@ -382,7 +406,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
         a.info[0] = 0u;
         a.info[1] = nsv;
         a.info[2] = ub;
-        a.info[3] = 0u;
+        a.info[3] = words ? 1u : 0u;
       }
       return;
     }
@@ -404,7 +428,26 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   const uint32_t lists4 = (a.lists + 3u) & ~3u;
   for (uint32_t l = tid; l < a.lists; l += kTailThreads) dyn[l] = 0;
   __syncthreads();
-  for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
+  for (uint32_t b = tid; words && b < m; b += kUnroll * kTailThreads) {
+    uint32_t h[kUnroll];
+#pragma unroll
+    for (uint32_t u = 0; u < kUnroll; ++u) {
+      const uint32_t i = b + u * kTailThreads;
+      h[u] = i < m ? a.hi_words[i] : 0xffffffffu;
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kUnroll; ++u) {
+      const uint32_t i = b + u * kTailThreads;
+      if (h[u] != 0xffffffffu && h[u] <= kt) {
+        const uint32_t row = a.pay[i].row;
+        const uint32_t pos = atomicAdd(&s_count, 1u);
+        if (pos < a.cap) a.rows[pos] = row;
+        if (pos < kTailFuseMax) c_row[pos] = row;
+        atomicAdd(&dyn[i / a.kp], 1u);
+      }
+    }
+  }
+  for (uint32_t b = tid; !words && b < m; b += kUnroll * kTailThreads) {
     uint64_t key[kUnroll];
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
@@ -436,7 +479,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
       a.info[0] = ok ? 2u : 0u;
       a.info[1] = cnt;
       a.info[2] = kt;
-      a.info[3] = 0u;
+      a.info[3] = words ? 1u : 0u;
     }
     return;
   }
@@ -533,7 +576,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
     a.info[0] = 1u;
     a.info[1] = cnt;
     a.info[2] = kt;
-    a.info[3] = 0u;
+    a.info[3] = words ? 1u : 0u;
   }
 }
 
@@ -611,137 +654,6 @@ __global__ __launch_bounds__(256) void sketch6_rows_kernel(const float *__restri
   const uint32_t row = list[w];
   if (row >= rows_img) return;
   sketch6_row(X, stride, row, true, d, ld8, img, max_norm, threadIdx.x & 63);
-}
-
-// The pass: K1q's skeleton (a wave owns tiles wave, wave + waves, ...; a ring of kU one-KiB non-temporal loads that runs on
-// across tiles; the metadata as the tile's last load; WaveTopK lists of (key(hi), id rank) with key(lo) beside them).
-// The query's kSketch6Levels nibble levels sit in LDS.  An H-run costs one broadcast ds_read_b128 and four v_dot8_i32_i4
-// per level; an L-run two reads and, after four masks and four shifts, eight dots per level.  Per level the H and L sums
-// stay apart (exact: 8 * 7 * 32768 < 2^23) and meet in f64: a_r = s_r sum_j t_j (4 accH_j + accL_j).
-__global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch6_scan_kernel(const Sketch6ScanArgs a) {
-  extern __shared__ __align__(16) unsigned char lds_raw[];
-  constexpr int J = kSketch6Levels;
-  const uint32_t nh = a.ld8 / 32, nl = a.ld8 / 64;  // (nh: also the u32x4 words of one level of the query)
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const u32x4 *qlds = reinterpret_cast<const u32x4 *>(lds_raw);  // [J][nh]
-  unsigned char *tkbuf = lds_raw + (size_t)J * nh * 16 + wib * WaveTopK<kCapSmall>::lds_bytes();
-  for (uint32_t i = threadIdx.x; i < J * nh; i += blockDim.x)
-    reinterpret_cast<u32x4 *>(lds_raw)[i] = reinterpret_cast<const u32x4 *>(a.qimg)[i];
-  __syncthreads();
-
-  WaveTopK<kCapSmall> tk;
-  tk.init(tkbuf, a.k);
-  const uint32_t ntiles = (a.n + kSketchTileRows - 1) / kSketchTileRows;
-  const uint32_t waves = gridDim.x * kWavesPerBlock;
-  const uint32_t wave = blockIdx.x * kWavesPerBlock + wib;
-  const unsigned char *img = static_cast<const unsigned char *>(a.img);
-  const uint32_t seg = nh + nl + 1;  // loads per tile (> kU: the launcher refuses ld8 = 128)
-
-  if (wave < ntiles) {
-    const uint32_t last_tile = wave + ((ntiles - 1 - wave) / waves) * waves;
-    uint32_t pt = wave, pc = 0;  // load cursor
-    auto load = [&]() -> u32x4 {
-      const uint32_t t = pt < last_tile ? pt : last_tile;  // (past the end: the last tile again, never used)
-      const u32x4 v = __builtin_nontemporal_load(
-          reinterpret_cast<const u32x4 *>(img + ((size_t)t * seg + pc) * 1024 + (uint32_t)lane * 16));
-      if (++pc == seg) {
-        pc = 0;
-        pt += waves;
-      }
-      return v;
-    };
-    u32x4 buf[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) buf[u] = load();
-
-    const double qn = a.qn, eta = a.eta, kerr = a.kerr;
-    const double tiny = ((double)a.d + 16.0) * 0x1p-125;  // (K1's subnormal products, as in K1q)
-    uint32_t ct = wave, cc = 0;  // compute cursor
-    int aH[J], aL[J];
-#pragma unroll
-    for (int j = 0; j < J; ++j) aH[j] = aL[j] = 0;
-    while (ct < ntiles) {
-      bool fin = false;
-      int fH[J], fL[J];
-#pragma unroll
-      for (int j = 0; j < J; ++j) fH[j] = fL[j] = 0;
-      u32x4 meta = u32x4{0u, 0u, 0u, 0u};
-      uint32_t ftile = 0;
-#pragma unroll
-      for (int u = 0; u < kU; ++u) {
-        const u32x4 x = buf[u];
-        buf[u] = load();
-        if (ct < ntiles) {
-          if (cc < nh) {
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-              const u32x4 q = qlds[j * nh + cc];
-              aH[j] = __builtin_amdgcn_sdot8((int)x.x, (int)q.x, aH[j], false);
-              aH[j] = __builtin_amdgcn_sdot8((int)x.y, (int)q.y, aH[j], false);
-              aH[j] = __builtin_amdgcn_sdot8((int)x.z, (int)q.z, aH[j], false);
-              aH[j] = __builtin_amdgcn_sdot8((int)x.w, (int)q.w, aH[j], false);
-            }
-            ++cc;
-          } else if (cc < nh + nl) {
-            const uint32_t c2 = 2 * (cc - nh);
-            const u32x4 lo = x & 0x33333333u, hi = (x >> 2) & 0x33333333u;
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-              const u32x4 qa = qlds[j * nh + c2], qb = qlds[j * nh + c2 + 1];
-              aL[j] = __builtin_amdgcn_sdot8((int)lo.x, (int)qa.x, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)lo.y, (int)qa.y, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)lo.z, (int)qa.z, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)lo.w, (int)qa.w, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)hi.x, (int)qb.x, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)hi.y, (int)qb.y, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)hi.z, (int)qb.z, aL[j], false);
-              aL[j] = __builtin_amdgcn_sdot8((int)hi.w, (int)qb.w, aL[j], false);
-            }
-            ++cc;
-          } else {  // the tile's metadata: the rows are complete (at most one per group: seg > kU)
-            fin = true;
-#pragma unroll
-            for (int j = 0; j < J; ++j) {
-              fH[j] = aH[j];
-              fL[j] = aL[j];
-              aH[j] = aL[j] = 0;
-            }
-            meta = x;
-            ftile = ct;
-            cc = 0;
-            ct += waves;
-          }
-        }
-      }
-      if (fin) {
-        const uint32_t row = ftile * kSketchTileRows + (uint32_t)lane;
-        const bool valid = row < a.n;
-        const double s = (double)__uint_as_float(meta.x);
-        const double rho = (double)__uint_as_float(meta.y), nu = (double)__uint_as_float(meta.z);
-        double sum = 0.0;
-#pragma unroll
-        for (int j = 0; j < J; ++j) sum += (double)a.t[j] * (double)(4 * fH[j] + fL[j]);  // (each product exact)
-        const double av = s * sum;
-        const double e = (qn * rho + eta * nu + kerr * qn * (nu + rho) + 0x1p-40 * nu * (qn + eta)) * kSlack + tiny;
-        const float hi = f32_up(av + e), lo = f32_down(av - e);
-        float khi_rank, klo_rank;  // key(lo) >= key(hi): the rank functions fall as the dot rises
-        if (a.metric == M_COS) {
-          klo_rank = 1.0f - hi;
-          khi_rank = 1.0f - lo;
-        } else {
-          klo_rank = -hi;
-          khi_rank = -lo;
-        }
-        const uint32_t rank = valid ? (a.id_rank ? a.id_rank[row] : row) : 0u;
-        const uint64_t key = ((uint64_t)orderable(klo_rank) << 32) | rank;
-        tk.offer(valid, key, row, khi_rank, lane);
-      }
-    }
-  }
-  __shared__ uint32_t s_counts[kWavesPerBlock];
-  tk.merge_block(wib, kWavesPerBlock, s_counts, lane);
-  if (wib == 0) tk.store(a.part_keys + (size_t)blockIdx.x * a.k, a.part_pay + (size_t)blockIdx.x * a.k, lane);
 }
 
 }  // namespace
@@ -823,22 +735,6 @@ hipError_t launch_sketch6_rows(const float *X, size_t stride, const uint32_t *li
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(sketch6_rows_kernel, dim3((count + 3) / 4), dim3(256), 0, s, X, stride, list, count, rows_img, d,
                      sketch_ld8(d), static_cast<unsigned char *>(img), max_norm);
-  return hipGetLastError();
-}
-
-size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k) {
-  if (d == 0 || d > kSketchMaxDim || k == 0 || k > (uint32_t)kSmallK) return 0;
-  if (sketch6_runs(d) <= (uint32_t)kU) return 0;  // (ld8 = 128: two tiles could end in one group of loads)
-  const size_t bytes = (size_t)kSketch6Levels * sketch_ld8(d) / 2 + kWavesPerBlock * WaveTopK<kCapSmall>::lds_bytes();
-  return bytes <= kMaxLds ? bytes : 0;
-}
-
-hipError_t launch_sketch6_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s) {
-  const size_t lds = sketch6_scan_lds_bytes(a.d, a.k);
-  if (!lds || a.ld8 != sketch_ld8(a.d) || blocks == 0 || !a.part_keys || !a.part_pay) return hipErrorInvalidValue;
-  hipError_t e = allow_lds(sketch6_scan_kernel, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sketch6_scan_kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
   return hipGetLastError();
 }
 
