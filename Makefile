@@ -24,7 +24,7 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -51,10 +51,11 @@ NOSCRATCH_vt_maxsim_resident := maxsim_resident_kernel
 NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 # K10 (MUVERA): one lane's f64 chain per dot product, nothing indexed dynamically in registers
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
-# K1q and K1s (the int8 and 6-bit sketch passes): the register ring must stay in registers; its tail (one block behind every pass) likewise
+# K1q, K1s and K1f (the int8, 6-bit and 5-bit sketch passes): the register ring must stay in registers; its tail (one block behind every pass) likewise
 # carries no scratch segment
 NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel
 NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
+NOSCRATCH_vt_sketch5      := sketch5_scan_kernel
 # K1s's pass branches three ways per run on wave-uniform cursors.  By default the CFG structurizer lays the three arms out in
 # a row behind flags, as it must for divergent branches, and every sum then lives across all arms and is copied in each
 # (about 400 v_mov_b32 per tile at d = 768, profiles/sketch6_loop/isa_counts.txt); told to leave wave-uniform regions as
@@ -64,6 +65,8 @@ NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
 # it does still builds a correct kernel (every test holds either way) but may bring the copies back: after a ROCm update
 # count again as profiles/sketch6_loop/isa_counts.txt says, and compare the pass's time.
 EXTRA_vt_sketch6          := -mllvm -structurizecfg-skip-uniform-regions=true
+# (K1f's pass, the 5-bit sketch: the same loop with another L plane)
+EXTRA_vt_sketch5          := $(EXTRA_vt_sketch6)
 NOSPILL_vt_batch_bf16     := bf16_scores_kernel
 NOSPILL_vt_batch_shadow   := shadow_scores_kernel
 
@@ -75,7 +78,7 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
 
 # (what the sketch units share)
-$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o: $(CSRC)/vt_sketch.cuh
+$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o: $(CSRC)/vt_sketch.cuh
 
 # (the pass K9r and K9rb share)
 $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o: $(CSRC)/vt_maxsim_pair.cuh

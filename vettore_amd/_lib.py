@@ -64,6 +64,9 @@ class Profile(C.Structure):
         ("sketch6_launches", C.c_uint64), ("sketch6_ms", C.c_double), ("sketch6_bytes", C.c_uint64),
         ("sketch6_candidates", C.c_uint64), ("sketch6_fallbacks", C.c_uint64), ("sketch6_builds", C.c_uint64),
         ("sketch6_patched_rows", C.c_uint64), ("sketch6_tail_words", C.c_uint64),
+        ("sketch5_launches", C.c_uint64), ("sketch5_ms", C.c_double), ("sketch5_bytes", C.c_uint64),
+        ("sketch5_candidates", C.c_uint64), ("sketch5_fallbacks", C.c_uint64), ("sketch5_builds", C.c_uint64),
+        ("sketch5_patched_rows", C.c_uint64),
     ]
 
 

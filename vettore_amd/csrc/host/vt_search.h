@@ -95,10 +95,35 @@ bool sketch6_wanted(const Shard *ix, size_t limit) {
 }
 size_t sketch6_elems(const Shard *ix) { return vt::sketch6_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
+// K1f (vt_sketch5.hip; its tail: vt_sketch.hip): where K1s applies, limits up to kSketch5MaxLimit over f32 rows
+// of at least kSketch5MinBytes read the 5-bit sketch first -- 0.838 of the 6-bit sketch's bytes.  Its intervals are twice as
+// wide and leave thousands of candidates (about 19 000 of 10 M uniform unit rows at d = 768), so its candidate list has a
+// row for every retained slot of the block lists and the gathered K1 behind it runs on kSketch5RescoreBlocks blocks (8-row
+// tiles, a wave each: 2 048 waves keep 16 MB in flight over a list of some 58 MB).  K1s is its fallback, on K1s's own terms;
+// after kSketch5MissLimit passes in a row that did not certify the shard stops taking K1f until the column is built anew.
+// The settings are K1s's, one value further (the product's list of settings stays as long as it was): VT_SKETCH6=2 keeps
+// K1s and switches K1f off (0: both); force_sketch6 = 1 never selects K1f, force_sketch6 = 2 forces both.
+// kSketch5MaxLimit: on the headline corpus 300 queries at limit 10 left 12 147 ... 38 087 candidates (mean 22 758) and none
+// missed; at limit 16 (mean 30 267, up to 40 685: the lists saturate) 7 missed, over the 1 % a miss's extra pass may cost
+// (profiles/sketch5/candidates.json).
+// kSketch5MinBytes: the sweep over sizes has not been run; the cut stays at the one size the path has been measured at
+// (DESIGN 5), which is K1s's.
+constexpr double kSketch5MinBytes = 16.0 * 1024 * (1 << 20);
+constexpr size_t kSketch5MaxLimit = 10;
+constexpr uint32_t kSketch5CandCap = 65536;       // every retained slot: 1 024 lists of 64
+constexpr uint32_t kSketch5RescoreBlocks = 512;
+constexpr uint32_t kSketch5MissLimit = 4;
+bool sketch5_wanted(const Shard *ix, size_t limit) {
+  if (!sketch6_wanted(ix, limit) || limit > kSketch5MaxLimit || vt::env::get(vt::env::SKETCH6) != 1 || ix->sketch5.refused) return false;
+  if (vt::sketch5_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
+  return vt::env::get(vt::env::FORCE_SKETCH6) >= 2 || (double)ix->n * ix->ld * 4.0 >= kSketch5MinBytes;
+}
+size_t sketch5_elems(const Shard *ix) { return vt::sketch5_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
+
 // The derived columns a reader with `need` / `limit` wants current, as the elements each must hold (0: not wanted).
 // shard_stale and shard_prepare both go by this one answer.  (A shard with rows.)
 struct ColumnsWanted {
-  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0, sketch6 = 0;
+  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0, sketch6 = 0, sketch5 = 0;
 };
 ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   ColumnsWanted w;
@@ -110,6 +135,7 @@ ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   if ((need & NEED_NORMS) && shadow_wanted(ix)) w.shadow = shadow_elems(ix);
   if ((need & NEED_SKETCH) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
   if ((need & NEED_SKETCH) && sketch6_wanted(ix, limit)) w.sketch6 = sketch6_elems(ix);
+  if ((need & NEED_SKETCH) && sketch5_wanted(ix, limit)) w.sketch5 = sketch5_elems(ix);
   return w;
 }
 
@@ -123,13 +149,14 @@ bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
   const ColumnsWanted w = columns_wanted(ix, need, limit);
   return (w.bits && !ix->bits.current(w.bits)) || (w.nz_bits && !ix->nz_bits.current(w.nz_bits)) ||
          (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow)) ||
-         (w.sketch && !ix->sketch.current(w.sketch)) || (w.sketch6 && !ix->sketch6.current(w.sketch6));
+         (w.sketch && !ix->sketch.current(w.sketch)) || (w.sketch6 && !ix->sketch6.current(w.sketch6)) ||
+         (w.sketch5 && !ix->sketch5.current(w.sketch5));
 }
 
 int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords);
 int index_ensure_norms(Shard *ix, size_t rows);
 int index_ensure_shadow(Shard *ix, size_t elems);
-int index_ensure_sketch(Shard *ix, size_t bytes, bool six = false);
+int index_ensure_sketch(Shard *ix, size_t bytes, int bits = 8);
 
 // Brings the derived columns a reader needs up to date (exclusive access; primary context).
 int shard_prepare(Shard *ix, unsigned need, size_t limit) {
@@ -144,7 +171,8 @@ int shard_prepare(Shard *ix, unsigned need, size_t limit) {
   if (w.norms) VT_TRY(index_ensure_norms(ix, w.norms));
   if (w.shadow) VT_TRY(index_ensure_shadow(ix, w.shadow));
   if (w.sketch) VT_TRY(index_ensure_sketch(ix, w.sketch));
-  if (w.sketch6) VT_TRY(index_ensure_sketch(ix, w.sketch6, true));
+  if (w.sketch6) VT_TRY(index_ensure_sketch(ix, w.sketch6, 6));
+  if (w.sketch5) VT_TRY(index_ensure_sketch(ix, w.sketch5, 5));
   return VT_OK;
 }
 
@@ -316,14 +344,16 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
 // K1s, one host wait: blit, the 6-bit pass, the tail in its certify-only mode, the gathered K1 over the candidate rows it
 // left (the count read on the device: none when the pass did not certify) and K1's select, all queued before the wait.
 // *done as sketch_search has it; a pass that does not certify counts towards the shard's miss limit.
-int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
+// `five`: K1f, the same chain over the 5-bit sketch (its pass, its bound of the level kept off the L plane, its longer
+// candidate list, more blocks for the gathered K1, its own counters and misses).
+int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, bool five = false) {
   *done = false;
   const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d);
   double qq = 0.0;
   for (uint32_t i = 0; i < d; ++i) qq += (double)query[i] * (double)query[i];
   const double up = 1.0 + 0x1p-30;
   const double qn = std::sqrt(qq) * up;
-  if (!(qn * ix->sketch6_max_norm * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
+  if (!(qn * (five ? ix->sketch5_max_norm : ix->sketch6_max_norm) * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
   const uint32_t lw = vt_host::sketch6_level_words(d);
   const size_t total = (size_t)ld + (size_t)vt::kSketch6Levels * lw;
   VT_TRY(c.dQ.ensure(total));
@@ -346,14 +376,17 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   VT_TRY(c.dSkPay.ensure((size_t)blocks * kp));
   VT_TRY(c.dSkLoWords.ensure((size_t)blocks * kp));
   VT_TRY(c.dSkHiWords.ensure((size_t)blocks * kp));
-  VT_TRY(c.dSk6Rows.ensure(kSketch6CandCap));
+  const uint32_t cand_cap = five ? kSketch5CandCap : kSketch6CandCap;
+  const uint32_t rescore_blocks = five ? kSketch5RescoreBlocks : kSketch6RescoreBlocks;
+  DevBuf<uint32_t> &cand_rows = five ? c.dSk5Rows : c.dSk6Rows;
+  VT_TRY(cand_rows.ensure(cand_cap));
   VT_TRY(c.dSkCount.ensure(1));
   VT_TRY(c.hSkInfo.ensure(4));
-  VT_TRY(c.ensure_part_lists((size_t)kSketch6RescoreBlocks * k));
+  VT_TRY(c.ensure_part_lists((size_t)rescore_blocks * k));
   uint32_t *info = c.hSkInfo.mapped();
   if (!info) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch status)");
   vt::Sketch6ScanArgs a{};
-  a.img = ix->sketch6.buf.p;
+  a.img = five ? ix->sketch5.buf.p : ix->sketch6.buf.p;
   a.id_rank = ix->dRank.p;
   a.qimg = reinterpret_cast<const uint32_t *>(c.dQ.p + ld);
   a.n = ix->n;
@@ -367,10 +400,14 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   {  // the last level stays off the L plane: its share there is c3 -+ w3 per unit of s_r (exact: 25 bits times 19)
     int64_t pos = 0, neg = 0, l1 = 0;
     const uint32_t *last = reinterpret_cast<const uint32_t *>(hq + ld) + (size_t)(vt::kSketch6Levels - 1) * lw;
-    vt_host::sketch6_level_sums(last, lw, &pos, &neg, &l1);
-    const double t3 = 1.5 * (double)t[vt::kSketch6Levels - 1];
-    a.c3 = t3 * (double)(pos + neg);
-    a.w3 = t3 * (double)l1;
+    if (five) {  // (0 <= L <= 1: half of t3 where the 6-bit plane has 1.5)
+      vt_host::sketch5_level_bound(last, lw, t[vt::kSketch6Levels - 1], &a.c3, &a.w3);
+    } else {
+      vt_host::sketch6_level_sums(last, lw, &pos, &neg, &l1);
+      const double t3 = 1.5 * (double)t[vt::kSketch6Levels - 1];
+      a.c3 = t3 * (double)(pos + neg);
+      a.w3 = t3 * (double)l1;
+    }
   }
   a.k = kp;
   a.part_keys = c.dSkKeys.p;
@@ -378,7 +415,7 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   a.lo_words = c.dSkLoWords.p;
   a.hi_words = c.dSkHiWords.p;
   VT_TRY(c.mark_begin());
-  VT_HIP(vt::launch_sketch6_scan(a, blocks, c.stream));
+  VT_HIP((five ? vt::launch_sketch5_scan : vt::launch_sketch6_scan)(a, blocks, c.stream));
   VT_TRY(c.mark_end());
   vt::SketchTailArgs ta{};
   ta.keys = c.dSkKeys.p;
@@ -386,8 +423,8 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   ta.lists = blocks;
   ta.kp = kp;
   ta.k = k;
-  ta.cap = kSketch6CandCap;
-  ta.rows = c.dSk6Rows.p;
+  ta.cap = cand_cap;
+  ta.rows = cand_rows.p;
   ta.count = c.dSkCount.p;
   ta.info = info;
   ta.X = ix->dX;
@@ -404,37 +441,50 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   ta.hi_words = c.dSkHiWords.p;
   VT_HIP(vt::launch_sketch_tail(ta, c.stream));
   vt::ScanArgs sa = scan_args(ix, c, d);
-  set_gather(sa, gather_of(c.dSk6Rows.p), kSketch6CandCap);  // (the list's room: the count is batch_counts[0])
+  set_gather(sa, gather_of(cand_rows.p), cand_cap);  // (the list's room: the count is batch_counts[0])
   sa.k = k;
   use_part_lists(sa, c);
   sa.batch_counts = c.dSkCount.p;
-  sa.batch_cap = kSketch6CandCap;
-  VT_HIP(vt::launch_scan_batch(sa, kSketch6RescoreBlocks, 1, c.stream));
-  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, kSketch6RescoreBlocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
+  sa.batch_cap = cand_cap;
+  VT_HIP(vt::launch_scan_batch(sa, rescore_blocks, 1, c.stream));
+  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, rescore_blocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
                            c.dSelKeys.p, c.dSelPay.p, c.stream));
   VT_HIP(hipStreamSynchronize(c.stream));
   const bool certified = c.hSkInfo.p[0] == 2u && c.hRes.p->status == 0;
   if (c.profiling) {
     float ms = 0.f;
     VT_TRY(c.span_ms(&ms));
-    const uint64_t bytes = (uint64_t)vt::sketch6_bytes(ix->n, d);
-    c.prof.sketch6_launches += 1;
-    c.prof.sketch6_ms += ms;
-    c.prof.sketch6_bytes += bytes;
-    c.prof.sketch6_candidates += c.hSkInfo.p[1];
-    c.prof.sketch6_tail_words += c.hSkInfo.p[3] == 1u ? 1 : 0;
+    const uint64_t bytes = (uint64_t)(five ? vt::sketch5_bytes(ix->n, d) : vt::sketch6_bytes(ix->n, d));
+    if (five) {
+      c.prof.sketch5_launches += 1;
+      c.prof.sketch5_ms += ms;
+      c.prof.sketch5_bytes += bytes;
+      c.prof.sketch5_candidates += c.hSkInfo.p[1];
+    } else {
+      c.prof.sketch6_launches += 1;
+      c.prof.sketch6_ms += ms;
+      c.prof.sketch6_bytes += bytes;
+      c.prof.sketch6_candidates += c.hSkInfo.p[1];
+      c.prof.sketch6_tail_words += c.hSkInfo.p[3] == 1u ? 1 : 0;
+    }
     VT_TRY(c.book_scan(1, ix->n, bytes));
   }
+  std::atomic<uint32_t> &misses = five ? ix->sketch5_misses : ix->sketch6_misses;
   if (!certified) {
-    c.prof.sketch6_fallbacks += 1;
-    ix->sketch6_misses.fetch_add(1, std::memory_order_relaxed);
+    (five ? c.prof.sketch5_fallbacks : c.prof.sketch6_fallbacks) += 1;
+    misses.fetch_add(1, std::memory_order_relaxed);
     return VT_OK;
   }
-  ix->sketch6_misses.store(0, std::memory_order_relaxed);
+  misses.store(0, std::memory_order_relaxed);
   std::vector<vt::Entry> entries(c.hRes.p->e, c.hRes.p->e + c.hRes.p->count);
   VT_TRY(make_hits(ix, entries, out));
   *done = true;
   return VT_OK;
+}
+
+// K1f: blit, the 5-bit pass, the certify-only tail, the gathered K1 and its select behind one host wait.
+int sketch5_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
+  return sketch6_search(ix, c, query, limit, done, out, true);
 }
 
 // flat.rs:96-124 on a shard whose rank column shard_prepare has brought up to date --
@@ -445,6 +495,12 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
   if (limit == 0) return empty_hits(out);
   VT_TRY(validate_vector(query, n, ix->dim));
   if (ix->n == 0) return empty_hits(out);
+  if (lone && sketch5_wanted(ix, limit) && ix->sketch5.current(sketch5_elems(ix)) &&
+      ix->sketch5_misses.load(std::memory_order_relaxed) < kSketch5MissLimit) {
+    bool done = false;
+    VT_TRY(sketch5_search(ix, c, query, limit, &done, out));
+    if (done) return VT_OK;
+  }
   if (lone && sketch6_wanted(ix, limit) && ix->sketch6.current(sketch6_elems(ix)) &&
       ix->sketch6_misses.load(std::memory_order_relaxed) < kSketch6MissLimit) {
     bool done = false;
@@ -804,14 +860,18 @@ int index_ensure_shadow(Shard *ix, size_t elems) {
 // its last use are re-quantised in place; a first use, a slab that outgrew it or more than kMaxDerivedDirty mutations
 // rebuild it (one pass over the rows); without room for it -- a quarter of the card must stay free -- it is refused and
 // lone searches keep scanning the f32 rows.  The bound on every row's norm comes back with it (the overflow guard).
-// `six`: the 6-bit sketch on the same terms (its own bound, its own counters); a whole build starts its misses over.
-int index_ensure_sketch(Shard *ix, size_t bytes, bool six) {
+// `bits` 6 / 5: the 6-bit / 5-bit sketch on the same terms (its own bound, its own counters); a whole build starts its
+// misses over.
+int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
   Ctx &c = ix->ctx;
-  DerivedColumn<unsigned char> &col = six ? ix->sketch6 : ix->sketch;
-  double &max_norm = six ? ix->sketch6_max_norm : ix->sketch_max_norm;
+  const bool six = bits_per == 6, five = bits_per == 5;
+  DerivedColumn<unsigned char> &col = five ? ix->sketch5 : six ? ix->sketch6 : ix->sketch;
+  double &max_norm = five ? ix->sketch5_max_norm : six ? ix->sketch6_max_norm : ix->sketch_max_norm;
   if (col.current(bytes)) return VT_OK;
   const uint32_t d = (uint32_t)ix->dim;
-  const size_t tile_bytes = six ? vt::sketch6_bytes(vt::kSketchTileRows, d) : vt::sketch_bytes(vt::kSketchTileRows, d);
+  const size_t tile_bytes = five  ? vt::sketch5_bytes(vt::kSketchTileRows, d)
+                            : six ? vt::sketch6_bytes(vt::kSketchTileRows, d)
+                                  : vt::sketch_bytes(vt::kSketchTileRows, d);
   VT_TRY(c.dBNorm.ensure(1));
   unsigned long long bits = 0;
   if (col.patchable(bytes)) {
@@ -820,9 +880,9 @@ int index_ensure_sketch(Shard *ix, size_t bytes, bool six) {
     std::memcpy(&bits, &max_norm, sizeof(double));
     VT_HIP(hipMemcpyAsync(c.dBNorm.p, &bits, sizeof(bits), hipMemcpyHostToDevice, c.stream));
     const uint32_t rows_img = (uint32_t)(col.buf.count / tile_bytes * vt::kSketchTileRows);
-    VT_HIP((six ? vt::launch_sketch6_rows : vt::launch_sketch_rows)(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p,
-                                                                    c.dBNorm.p, c.stream));
-    (six ? c.prof.sketch6_patched_rows : c.prof.sketch_patched_rows) += count;
+    VT_HIP((five ? vt::launch_sketch5_rows : six ? vt::launch_sketch6_rows : vt::launch_sketch_rows)(
+        ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    (five ? c.prof.sketch5_patched_rows : six ? c.prof.sketch6_patched_rows : c.prof.sketch_patched_rows) += count;
   } else {
     col.forget();
     if (col.buf.count < bytes) {
@@ -839,7 +899,7 @@ int index_ensure_sketch(Shard *ix, size_t bytes, bool six) {
       }
 #ifdef VT_TEST_HOOKS
       // (libvettore_hip_hooks.so only: the allocation "fails", tests/test_gpu_sketch.py checks what follows)
-      refused = refused || vt::env::on(six ? vt::env::TEST_REFUSE_SKETCH6 : vt::env::TEST_REFUSE_SKETCH);
+      refused = refused || vt::env::on(five ? vt::env::TEST_REFUSE_SKETCH5 : six ? vt::env::TEST_REFUSE_SKETCH6 : vt::env::TEST_REFUSE_SKETCH);
 #endif
       if (refused) {
         col.refuse();
@@ -848,10 +908,11 @@ int index_ensure_sketch(Shard *ix, size_t bytes, bool six) {
     }
     const uint32_t rows_img = (uint32_t)(bytes / tile_bytes * vt::kSketchTileRows);
     VT_HIP(hipMemsetAsync(c.dBNorm.p, 0, sizeof(unsigned long long), c.stream));
-    VT_HIP((six ? vt::launch_sketch6_build : vt::launch_sketch_build)(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p,
-                                                                      c.stream));
-    (six ? c.prof.sketch6_builds : c.prof.sketch_builds) += 1;
+    VT_HIP((five ? vt::launch_sketch5_build : six ? vt::launch_sketch6_build : vt::launch_sketch_build)(
+        ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    (five ? c.prof.sketch5_builds : six ? c.prof.sketch6_builds : c.prof.sketch_builds) += 1;
     if (six) ix->sketch6_misses.store(0, std::memory_order_relaxed);
+    if (five) ix->sketch5_misses.store(0, std::memory_order_relaxed);
   }
   VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
   // current from here on, for readers on other streams too: the build has finished before the exclusive lock can drop

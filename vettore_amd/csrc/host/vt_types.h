@@ -57,6 +57,7 @@ struct Ctx {
   std::vector<double> hSkResid;
   DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
   DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
+  DevBuf<uint32_t> dSk5Rows;  // K1f (sketch5_search): its candidate list, a row for every retained slot
   // grouped quantized searches: one stage-1 block per query
   DevBuf<ResultBlock> dStageB;
   PinnedBuf<float> hBQ, hBTau;
@@ -334,6 +335,12 @@ struct Shard {
   DerivedColumn<unsigned char> sketch6;
   double sketch6_max_norm = 0.0;
   std::atomic<uint32_t> sketch6_misses{0};
+  // K1f: the rows in five bits, two planes (vt_device.h, above launch_sketch5_scan) -- 0.838 of the 6-bit sketch's bytes,
+  // read first by the largest lone searches (vt_search.h, sketch5_search) with the 6-bit and int8 sketches behind it.  Kept
+  // on the 6-bit sketch's terms, misses included (kSketch5MissLimit); the first column to go when the slab needs room.
+  DerivedColumn<unsigned char> sketch5;
+  double sketch5_max_norm = 0.0;
+  std::atomic<uint32_t> sketch5_misses{0};
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
   // ids
@@ -396,6 +403,7 @@ struct Shard {
       shadow.touch(rows[i]);
       sketch.touch(rows[i]);
       sketch6.touch(rows[i]);
+      sketch5.touch(rows[i]);
     }
   }
   void forget_derived() {
@@ -405,6 +413,7 @@ struct Shard {
     shadow.forget();
     sketch.forget();
     sketch6.forget();
+    sketch5.forget();
   }
   // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
   // shadow gives its room back.
@@ -418,6 +427,8 @@ struct Shard {
     sketch.buf.release();
     sketch6.reset();
     sketch6.buf.release();
+    sketch5.reset();
+    sketch5.buf.release();
   }
 };
 

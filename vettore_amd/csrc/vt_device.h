@@ -769,4 +769,26 @@ struct Sketch6ScanArgs {
 size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_sketch6_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
 
+// ---- K1f (vt_sketch5.hip): the same search over a 5-bit sketch in two planes -- 0.838 of K1s's bytes -----------------
+// Row r is kept as X_r = round(x_r / s_r) in [-15, 15] with s_r = max_i |x_ri| / 15, split as X = 2 H + L: H = X >> 1
+// (arithmetic, [-8, 7]) a signed nibble, L = X & 1 one bit; rho_r and nu_r as K1q has them.  Layout, per tile of 64 rows,
+// in 1-KiB runs of 16 bytes per row: ld8 / 32 runs of H in K1s's H layout, then ld8 / 128 runs of L -- in dword j of run
+// c', bit 4 i + b is element 128 c' + 32 b + 8 j + i, so that (w >> b) & 0x11111111 is a nibble vector aligned with dword
+// j of the H-run 4 c' + b --, then one run of {s, rho, nu, 0}: 5 ld8 / 128 + 1 KiB per tile.
+__host__ __device__ inline uint32_t sketch5_runs(uint32_t d) { return 5 * (sketch_ld8(d) / 128) + 1; }  // per tile
+inline size_t sketch5_bytes(uint32_t rows, uint32_t d) {
+  const size_t tiles = ((size_t)rows + kSketchTileRows - 1) / kSketchTileRows;
+  return tiles * sketch5_runs(d) * 1024;
+}
+// (as launch_sketch_build / launch_sketch_rows; a run's place in the image: sketch6_offset with sketch5_runs)
+hipError_t launch_sketch5_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                                unsigned long long *max_norm, hipStream_t s);
+hipError_t launch_sketch5_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                               void *img, unsigned long long *max_norm, hipStream_t s);
+// The pass takes Sketch6ScanArgs as K1s's does (img: the 5-bit column).  Here 0 <= L_i <= 1, so Q3.L_r lies in [N3, P3]:
+// c3 = 0.5 t3 (P3 + N3) and w3 = 0.5 t3 ||Q3||_1 (host/vt_sketch5.h), and a_r = s_r (sum_{j <= 2} t_j (2 accH_j + accL_j)
+// + 2 t3 accH_3 + c3).  k <= kSmallK and ld8 >= 256; 0: not supported
+size_t sketch5_scan_lds_bytes(uint32_t d, uint32_t k);
+hipError_t launch_sketch5_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
+
 }  // namespace vt

@@ -34,6 +34,7 @@
 // The host side in reading order (one translation unit; see the note at the top of each part):
 #include "host/vt_idtable.h"
 #include "host/vt_sketch6.h"
+#include "host/vt_sketch5.h"
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_concurrency.h"
@@ -1075,6 +1076,13 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch6_builds += p.sketch6_builds;
       t.sketch6_patched_rows += p.sketch6_patched_rows;
       t.sketch6_tail_words += p.sketch6_tail_words;
+      t.sketch5_launches += p.sketch5_launches;
+      t.sketch5_ms += p.sketch5_ms;
+      t.sketch5_bytes += p.sketch5_bytes;
+      t.sketch5_candidates += p.sketch5_candidates;
+      t.sketch5_fallbacks += p.sketch5_fallbacks;
+      t.sketch5_builds += p.sketch5_builds;
+      t.sketch5_patched_rows += p.sketch5_patched_rows;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

@@ -1,5 +1,6 @@
 // vt_sketch.hip -- K1q: a lone cosine / dot search nominated from an int8 sketch of the rows (gfx950), and the tail behind
-// its pass; the builders of K1s's 6-bit sketch in two planes follow below (its pass: vt_sketch6.hip).
+// its pass -- which K1s and K1f share --; the builders of K1s's 6-bit sketch in two planes follow below (its pass:
+// vt_sketch6.hip; K1f, the 5-bit sketch: vt_sketch5.hip).
 //
 // The sketch (layout and bounds: vt_device.h, SketchScanArgs) holds a quarter of the f32 rows' bytes.  K1q streams it
 // once and gives every row an interval [lo_r, hi_r] that provably holds what K1 would compute for it:
@@ -201,19 +202,19 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch_scan_kernel(cons
 // loads stages the key(lo) words in LDS when lists * k' of them fit (104 KB at the headline; otherwise later sweeps read
 // global memory again) and leaves every thread the smallest of its own; an empty slot counts as 0xffffffff.  The k-th
 // smallest of those 1 024 minima is located to its top 16 bits by two 8-bit radix passes over one word per thread; U is
-// that bin's upper end.  k distinct entries are <= U, so the entries <= U hold the k smallest of all: they are filed (at
-// most 1 024, else the pass is not certified) and Kt is their k-th smallest by counting.  With k or fewer live entries
-// Kt is the maximum.  The collect is one more sweep of independent loads over the 64-bit keys; a list is refused when
+// that bin's upper end.  k distinct entries are <= U, so the entries <= U hold the k smallest of all: they are filed and
+// Kt is their k-th smallest by counting (at most 1 024; when more tie around the k-th, Kt is found by four radix passes
+// over every word instead).  With k or fewer live entries
+// Kt is the maximum.  The collect is one more sweep of independent loads over the 64-bit keys, its counters (all the
+// candidates; each list's own, exact) raised once per wave, not once per candidate; a list is refused when
 // every one of its k' slots is a candidate (it is full and its largest key(hi) is <= Kt: it may have dropped a row that
 // matters).
 // Behind K1s's pass the lists' words arrive a second time as two plain arrays (SketchTailArgs::lo_words / hi_words), and
 // the sweeps read those: the first the key(lo) words alone, staging their upper halves (two a dword: lists * k' / 2
 // dwords of LDS, 128 KB at the headline); U ends in 0xffff, so the filing sweep compares the staged halves and reads
 // again only the words it files; the collect reads the key(hi) words and a candidate's pay[i].row.  Kt, the candidate set,
-// the count and the full-list check are the ones the lists give.  What may differ on heavy ties is the refusal itself: a
-// thread owns the slot pairs (2 i, 2 i + 1) here, not the slots tid + 1024 j, so the 1 024 minima, U and the entries <= U
-// are other ones, and a pass with about a thousand entries tied around the k-th can be refused (info[1], info[2] then
-// differ too) where the list path files them, or the other way round; either way the search is served by the fallback.
+// the count and the full-list check are the ones the lists give.  (A thread owns the slot pairs
+// (2 i, 2 i + 1) here, not the slots tid + 1024 j, so the 1 024 minima, U and the entries <= U are other ones; Kt is not.)
 // info[3] says which path ran (1: the word arrays).
 // Up to kTailFuseMax candidates whose chunk sums fit the same LDS are then rescored here with K1's arithmetic: a wave
 // per row, a lane pair per 8-float chunk (elem4 / chunk_sum of vt_scan.cuh in the index's reduce order), the sums to an
@@ -240,6 +241,19 @@ __device__ __forceinline__ void hist_add(uint32_t *hist, bool on, uint32_t bin, 
     on = on && bin != lb;
   }
   if (on) atomicAdd(&hist[bin], 1u);
+}
+
+// A place in a list that *counter counts, for each lane with `on`: the wave's lanes are counted by ballot and the counter
+// takes one atomic per wave, not one per lane (thousands of candidates behind the 5-bit pass would queue on it).  Called
+// by the lanes of a wave that are in the loop together; a lane without `on` gets nothing it may use.
+__device__ __forceinline__ uint32_t wave_claim(uint32_t *counter, bool on, int lane) {
+  const uint64_t act = __ballot(on);
+  if (!act) return 0u;
+  const int leader = __ffsll((long long)act) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(act));
+  base = (uint32_t)__shfl((int)base, leader, kWave);
+  return base + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
 }
 
 __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchTailArgs a) {
@@ -316,15 +330,10 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   // U = the upper end of the 16-bit bin that holds the k-th smallest of the 1 024 threads' minima (k <= 256): k distinct
   // entries are <= U, so Kt <= U, and the entries <= U -- a few more than k unless hundreds tie -- hold the k smallest
   // of all.  Two radix passes over one word per thread, in place of four over all lists * k' words.
-  uint32_t mask = 0;
-  for (int pass = 0; pass < 2; ++pass) {
-    const int shift = 24 - 8 * pass;
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    const uint32_t prefix = s_prefix;
-    hist_add(hist, (mine & mask) == prefix, (mine >> shift) & 255u, lane);
-    __syncthreads();
-    if (w == 0) {  // the bin that holds the s_remaining-th smallest of this digit: four bins per lane, one wave scan
+  // wave 0, after a digit's histogram: the bin that holds the s_remaining-th smallest of this digit joins s_prefix (four
+  // bins per lane, one wave scan)
+  auto pick_bin = [&](uint32_t prefix, int shift) {
+    {  // (wave 0)
       const uint32_t krem = s_remaining;
       const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
       const uint32_t sum = h0 + h1 + h2 + h3;
@@ -353,6 +362,16 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
         s_prefix = prefix | ((4u * (uint32_t)lane + b) << shift);
       }
     }
+  };
+  uint32_t mask = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    const uint32_t prefix = s_prefix;
+    hist_add(hist, (mine & mask) == prefix, (mine >> shift) & 255u, lane);
+    __syncthreads();
+    if (w == 0) pick_bin(prefix, shift);
     mask |= 255u << shift;
     __syncthreads();
   }
@@ -400,17 +419,32 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
     }
     __syncthreads();
     const uint32_t nsv = s_nsv;
-    if (nsv > kTailSurvivors) {  // (a thousand entries tie around the k-th: nothing the candidate cap would take)
+    if (nsv > kTailSurvivors) {
+      // Over a thousand entries <= U: they tie around the k-th (thousands of copies of one row behind the 5-bit pass, whose
+      // candidate list has room for them).  Kt is then the k-th smallest word itself, by four radix passes over every word.
       if (tid == 0) {
-        *a.count = 0u;
-        a.info[0] = 0u;
-        a.info[1] = nsv;
-        a.info[2] = ub;
-        a.info[3] = words ? 1u : 0u;
+        s_prefix = 0;
+        s_remaining = a.k;
       }
-      return;
-    }
-    if (tid < nsv) {
+      uint32_t rmask = 0;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const uint32_t prefix = s_prefix;
+        for (uint32_t i = tid; i < m; i += kTailThreads) {
+          uint32_t v;
+          if (words) v = a.lo_words[i];
+          else v = in_lds ? dyn[i] : (a.keys[i] == kEmptyKey ? 0xffffffffu : orderable(a.pay[i].raw));
+          hist_add(hist, (v & rmask) == prefix, (v >> shift) & 255u, lane);
+        }
+        __syncthreads();
+        if (w == 0) pick_bin(prefix, shift);
+        rmask |= 255u << shift;
+        __syncthreads();
+      }
+      if (tid == 0) s_kt = s_prefix;
+    } else if (tid < nsv) {
       const uint32_t v = sv[tid];
       uint32_t lt = 0, le = 0;
       for (uint32_t x = 0; x < nsv; ++x) {
@@ -438,13 +472,14 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
       const uint32_t i = b + u * kTailThreads;
-      if (h[u] != 0xffffffffu && h[u] <= kt) {
+      const bool cand = h[u] != 0xffffffffu && h[u] <= kt;
+      const uint32_t pos = wave_claim(&s_count, cand, lane);
+      if (cand) {
         const uint32_t row = a.pay[i].row;
-        const uint32_t pos = atomicAdd(&s_count, 1u);
         if (pos < a.cap) a.rows[pos] = row;
         if (pos < kTailFuseMax) c_row[pos] = row;
-        atomicAdd(&dyn[i / a.kp], 1u);
       }
+      hist_add(dyn, cand, i / a.kp, lane);
     }
   }
   for (uint32_t b = tid; !words && b < m; b += kUnroll * kTailThreads) {
@@ -457,13 +492,14 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
       const uint32_t i = b + u * kTailThreads;
-      if (key[u] != kEmptyKey && (uint32_t)(key[u] >> 32) <= kt) {
+      const bool cand = key[u] != kEmptyKey && (uint32_t)(key[u] >> 32) <= kt;
+      const uint32_t pos = wave_claim(&s_count, cand, lane);
+      if (cand) {
         const uint32_t row = a.pay[i].row;
-        const uint32_t pos = atomicAdd(&s_count, 1u);
         if (pos < a.cap) a.rows[pos] = row;
         if (pos < kTailFuseMax) c_row[pos] = row;
-        atomicAdd(&dyn[i / a.kp], 1u);
       }
+      hist_add(dyn, cand, i / a.kp, lane);
     }
   }
   __syncthreads();
