@@ -84,7 +84,16 @@ enum {
   VT_ERR_MUVERA_FINAL = 25,       /* "final_projection_dimension must be positive" muvera.rs:94 */
   VT_ERR_FDE_OVERFLOW = 26,       /* "fde dimension overflow"                      muvera.rs:34, :38 */
   VT_ERR_FDE_LIMIT = 27,          /* "fde dimension exceeds safety limit"          muvera.rs:41 */
-  VT_ERR_ENCODING_OVERFLOW = 28   /* "encoding overflow"                           muvera.rs:175, :195 */
+  VT_ERR_ENCODING_OVERFLOW = 28,  /* "encoding overflow"                           muvera.rs:175, :195 */
+  /* HnswParams::validate, hnsw.rs:25-49, and the handle's own poisoning */
+  VT_ERR_HNSW_M = 29,               /* "m must be positive" */
+  VT_ERR_HNSW_M0 = 30,              /* "m0 must be positive" */
+  VT_ERR_HNSW_DEGREE = 31,          /* "invalid hnsw degree" */
+  VT_ERR_HNSW_EF_CONSTRUCTION = 32, /* "ef_construction must be >= m" */
+  VT_ERR_HNSW_EF_LIMIT = 33,        /* "ef_construction exceeds safety limit" */
+  VT_ERR_HNSW_EF_SEARCH = 34,       /* "ef_search must be positive" */
+  VT_ERR_HNSW_MAX_LEVEL = 35,       /* "max_level must be positive" */
+  VT_ERR_HNSW_POISONED = 36         /* "hnsw lock poisoned"                          nifs.rs:376-426 */
 };
 
 /* Lane order of wide::f32x8::reduce_add used for every 8-float chunk
@@ -470,6 +479,56 @@ int vt_mv_counters(const vt_mv *store, uint64_t *scoring_launches, uint64_t *bat
  * searches add nothing); compactions: puts that closed the slab up first.  Any out pointer may be NULL. */
 int vt_mv_memory(const vt_mv *store, size_t *vectors, size_t *row_capacity, size_t *dead_rows, uint64_t *uploaded_bytes,
                  uint64_t *compactions);
+
+/* ------------------------------------------- HNSW index (approximate, graph-identical to the reference)
+ * hnsw_new_*, hnsw_insert, hnsw_insert_many, hnsw_delete, hnsw_search, nifs.rs:311-426 -> hnsw.rs.  The reference's
+ * HNSW is deterministic -- levels from an FNV-1a hash of the external id, neighbour selection a sort by (distance,
+ * internal id), heaps under a total order --, so the contract is the usual one: after any inserts and deletes every
+ * node's level, the entry and every adjacency list are the reference's, and a search returns its ids in its order with
+ * the raw values' bits (vt_hits_raw).  The traversals run on the device, one wave each (csrc/vt_hnsw.hip); the graph's
+ * book-keeping stays on the host (csrc/host/vt_hnswgraph.h).
+ * vt_hnsw_new: a metric other than VT_L2, VT_COSINE (inside the graph the f32 dot with rank 1 - raw, distances.rs:50)
+ * and VT_INNER_PRODUCT is VT_ERR_UNSUPPORTED (vt_last_error says so), then HnswParams::validate in its order
+ * (VT_ERR_HNSW_*), and only then the device: VT_ERR_DEVICE without one, there is no CPU fallback.  The lane order is the
+ * one in force (vt_set_default_reduce_order) when the handle is made.
+ * vt_hnsw_insert: validate_vector against the index's dimension, then an existing node of that id goes, then the insert;
+ * "metric overflow" in its traversal returns VT_ERR_OVERFLOW with the old node gone and the graph otherwise unchanged,
+ * as in the reference.  vt_hnsw_insert_many validates every vector against the dimension -- or the first vector's
+ * length -- before anything changes, then inserts in order: earlier inserts stay when a later one fails.  A device
+ * failure half-way through a mutation poisons the handle (VT_ERR_HNSW_POISONED from then on).
+ * vt_hnsw_search: limit 0 returns an empty list before the query is looked at, then validate_vector, then an empty
+ * index returns an empty list; one traversal launch per call.  vt_hnsw_search_batch answers nq queries of d floats each
+ * with one launch, every answer equal to the lone call's: with query_status a query's own error lands in
+ * query_status[i] with out[i] NULL and the call returns VT_OK; without it the first failing query's status is returned
+ * and every out[i] is NULL (vt_mv_top_k_batch's convention).
+ * One mutex per handle: every call excludes every other.  Rows of deleted nodes stay dead in the slab until the last
+ * node goes (then slab and dimension go, and the next insert may bring another dimension; internal ids keep counting
+ * and are never reused); an internal-id counter at 2^32 returns VT_ERR_NOMEM.  The slab holds at most 2^30 - 64 rows,
+ * dead ones included: a traversal on a larger slab returns VT_ERR_UNSUPPORTED (vt_last_error says so). */
+typedef struct vt_hnsw vt_hnsw;
+int vt_hnsw_new(int metric_code, int device, size_t m, size_t m0, size_t ef_construction, size_t ef_search,
+                size_t max_level, vt_hnsw **out);
+void vt_hnsw_free(vt_hnsw *index);
+int vt_hnsw_insert(vt_hnsw *index, const char *id, size_t id_len, const float *vector, size_t n);
+int vt_hnsw_insert_many(vt_hnsw *index, size_t count, const char *ids, const size_t *id_off /* count + 1 */,
+                        const float *values, const size_t *value_off /* count + 1 */);
+int vt_hnsw_delete(vt_hnsw *index, const char *id, size_t id_len);
+int vt_hnsw_search(vt_hnsw *index, const float *query, size_t n, size_t limit, vt_hits **out);
+int vt_hnsw_search_batch(vt_hnsw *index, const float *queries, size_t nq, size_t d, size_t limit, vt_hits **out /* nq */,
+                         int *query_status /* nq, may be NULL */);
+size_t vt_hnsw_len(const vt_hnsw *index);
+long vt_hnsw_dimension(const vt_hnsw *index); /* -1: empty */
+/* Inspection (tests compare the graph with the reference's): a live id's internal id, level and whether it is the
+ * entry (VT_ERR_ARGUMENT: no such id); the internal ids of a node's list on one layer, in list order -- *count is the
+ * list's length, at most cap of them are written (VT_ERR_ARGUMENT: no such node or layer). */
+int vt_hnsw_node(const vt_hnsw *index, const char *id, size_t id_len, uint64_t *internal_id, uint32_t *level, int *is_entry);
+int vt_hnsw_neighbors(const vt_hnsw *index, uint64_t internal_id, uint32_t layer, uint64_t *out, size_t cap, size_t *count);
+/* Totals since vt_hnsw_new -- traversal_launches: launches of the traversal kernel; traversals: searches and insert
+ * descents asked of it; reruns: traversals that outgrew their scratch and ran again with full-size scratch. */
+int vt_hnsw_counters(const vt_hnsw *index, uint64_t *traversal_launches, uint64_t *traversals, uint64_t *reruns);
+/* rows: slab rows handed out; row_capacity: rows the slab holds; dead_rows: rows of deleted nodes; edges: entries of
+ * all adjacency lists.  Any out pointer may be NULL. */
+int vt_hnsw_memory(const vt_hnsw *index, size_t *rows, size_t *row_capacity, size_t *dead_rows, size_t *edges);
 
 /* ------------------------------------------- MUVERA (fixed-dimensional encoding)
  * muvera_encode_query/7, muvera_encode_document/7, nifs.rs:430-476 -> muvera.rs:26-74, for `count` sets of

@@ -27,6 +27,14 @@ static void flat_dtor(ErlNifEnv *env, void *obj) {
   vt_flat_free(((flat_res *)obj)->h); /* ResourceArc drop: HBM, streams, pinned staging */
 }
 
+static ErlNifResourceType *HNSW;
+typedef struct { vt_hnsw *h; } hnsw_res;
+
+static void hnsw_dtor(ErlNifEnv *env, void *obj) {
+  (void)env;
+  vt_hnsw_free(((hnsw_res *)obj)->h);
+}
+
 /* ---------------------------------------------------------------- terms */
 static ERL_NIF_TERM mk_atom(ErlNifEnv *env, const char *a) { return enif_make_atom(env, a); }
 
@@ -766,12 +774,102 @@ static ERL_NIF_TERM muvera_encode_document(ErlNifEnv *env, int argc, const ERL_N
   return muvera_encode(env, argv, 1);
 }
 
+/* ------------------------------------------------------------------ HNSW */
+/* hnsw_new_l2 / _cosine / _inner_product(m, m0, ef_construction, ef_search, max_level, device)
+ *   -> {:ok, reference} | {:error, binary}                                          nifs.rs:311-374
+ * (the reference's five arguments and the device ordinal; HnswParams::validate's strings come back as they are) */
+static hnsw_res *get_hnsw(ErlNifEnv *env, ERL_NIF_TERM t) {
+  hnsw_res *r;
+  return enif_get_resource(env, t, HNSW, (void **)&r) ? r : NULL;
+}
+
+static ERL_NIF_TERM hnsw_new(ErlNifEnv *env, const ERL_NIF_TERM argv[], int metric) {
+  size_t p[5];
+  int device;
+  for (int i = 0; i < 5; ++i)
+    if (!get_size(env, argv[i], &p[i])) return enif_make_badarg(env);
+  if (!enif_get_int(env, argv[5], &device) || device < 0) return enif_make_badarg(env);
+  vt_hnsw *h;
+  int st = vt_hnsw_new(metric, device, p[0], p[1], p[2], p[3], p[4], &h);
+  if (st != VT_OK) return mk_error(env, st);
+  hnsw_res *r = (hnsw_res *)enif_alloc_resource(HNSW, sizeof *r);
+  r->h = h;
+  ERL_NIF_TERM t = enif_make_resource(env, r);
+  enif_release_resource(r);
+  return enif_make_tuple2(env, mk_atom(env, "ok"), t);
+}
+static ERL_NIF_TERM hnsw_new_l2(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return hnsw_new(env, argv, VT_L2);
+}
+static ERL_NIF_TERM hnsw_new_cosine(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return hnsw_new(env, argv, VT_COSINE);
+}
+static ERL_NIF_TERM hnsw_new_inner_product(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return hnsw_new(env, argv, VT_INNER_PRODUCT);
+}
+
+/* hnsw_insert(ref, id, [float]) -> {:ok, {}} | {:error, binary}                     nifs.rs:376-388 */
+static ERL_NIF_TERM hnsw_insert(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  ErlNifBinary id;
+  float *v;
+  size_t n;
+  (void)argc;
+  if (!r || !enif_inspect_binary(env, argv[1], &id) || !get_f32_list(env, argv[2], &v, &n)) return enif_make_badarg(env);
+  int st = vt_hnsw_insert(r->h, (const char *)id.data, id.size, v, n);
+  free(v);
+  return st == VT_OK ? mk_ok_unit(env) : mk_error(env, st);
+}
+
+/* hnsw_insert_many(ref, [{id, [float]}]) -> {:ok, {}} | {:error, binary}            nifs.rs:390-401
+ * (every vector is validated before the first insert; earlier inserts stay when a later one fails, hnsw.rs:249-260) */
+static ERL_NIF_TERM hnsw_insert_many(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  ragged g;
+  (void)argc;
+  if (!r) return enif_make_badarg(env);
+  if (!get_ragged(env, argv[1], 0, &g)) {
+    ragged_free(&g);
+    return enif_make_badarg(env);
+  }
+  int st = vt_hnsw_insert_many(r->h, g.count, g.ids, g.id_off, (const float *)g.vals, g.val_off);
+  ragged_free(&g);
+  return st == VT_OK ? mk_ok_unit(env) : mk_error(env, st);
+}
+
+/* hnsw_delete(ref, id) -> {:ok, {}} | {:error, binary}                              nifs.rs:403-412 */
+static ERL_NIF_TERM hnsw_delete(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  ErlNifBinary id;
+  (void)argc;
+  if (!r || !enif_inspect_binary(env, argv[1], &id)) return enif_make_badarg(env);
+  int st = vt_hnsw_delete(r->h, (const char *)id.data, id.size);
+  return st == VT_OK ? mk_ok_unit(env) : mk_error(env, st);
+}
+
+/* hnsw_search(ref, [float], limit) -> {:ok, [{id, raw}]} | {:error, binary}         nifs.rs:414-426 */
+static ERL_NIF_TERM hnsw_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  float *q;
+  size_t n, limit;
+  (void)argc;
+  if (!r || !get_f32_list(env, argv[1], &q, &n) || !get_size(env, argv[2], &limit)) return enif_make_badarg(env);
+  vt_hits *h;
+  int st = vt_hnsw_search(r->h, q, n, limit, &h);
+  free(q);
+  return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
+}
+
 static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   (void)priv; (void)info;
   /* a libvettore_hip.so built from another header would be handed structs of the wrong size */
   if (vt_abi_version() != VT_ABI_VERSION) return 1;
   FLAT = enif_open_resource_type(env, NULL, "vettore_gpu_flat", flat_dtor, ERL_NIF_RT_CREATE, NULL);
-  return FLAT ? 0 : 1;
+  HNSW = enif_open_resource_type(env, NULL, "vettore_gpu_hnsw", hnsw_dtor, ERL_NIF_RT_CREATE, NULL);
+  return FLAT && HNSW ? 0 : 1;
 }
 
 static ErlNifFunc funcs[] = {
@@ -795,6 +893,13 @@ static ErlNifFunc funcs[] = {
   {"multi_vector_top_k", 4, multi_vector_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"muvera_encode_query", 7, muvera_encode_query, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"muvera_encode_document", 7, muvera_encode_document, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_new_l2", 6, hnsw_new_l2, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_new_cosine", 6, hnsw_new_cosine, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_new_inner_product", 6, hnsw_new_inner_product, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_insert", 3, hnsw_insert, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_insert_many", 2, hnsw_insert_many, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_delete", 2, hnsw_delete, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_search", 3, hnsw_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(Elixir.Vettore.Gpu.Nifs, funcs, load, NULL, NULL, NULL)

@@ -49,4 +49,11 @@ defmodule Vettore.Gpu.Nifs do
   def multi_vector_top_k(_documents, _query_vectors, _metric_code, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def muvera_encode_query(_vectors, _dimension, _num_repetitions, _num_simhash_projections, _seed, _projection_dimension, _final_projection_dimension), do: :erlang.nif_error(:nif_not_loaded)
   def muvera_encode_document(_vectors, _dimension, _num_repetitions, _num_simhash_projections, _seed, _projection_dimension, _final_projection_dimension), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_new_l2(_m, _m0, _ef_construction, _ef_search, _max_level, _device), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_new_cosine(_m, _m0, _ef_construction, _ef_search, _max_level, _device), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_new_inner_product(_m, _m0, _ef_construction, _ef_search, _max_level, _device), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_insert(_ref, _id, _vector), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_insert_many(_ref, _entries), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_delete(_ref, _id), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_search(_ref, _query, _limit), do: :erlang.nif_error(:nif_not_loaded)
 end

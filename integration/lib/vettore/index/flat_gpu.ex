@@ -182,6 +182,16 @@ defmodule Vettore.Index.FlatGpu do
   defdelegate muvera_encode_query(vectors, dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension), to: Nifs
   defdelegate muvera_encode_document(vectors, dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension), to: Nifs
 
+  # The HNSW NIFs on the device (Vettore.Nifs.hnsw_*, nifs.rs:311-426, with the device ordinal as the constructors' last
+  # argument): same terms in and out.  Vettore.Index.HnswGpu (hnsw_gpu.ex) is the index module built on them.
+  defdelegate hnsw_new_l2(m, m0, ef_construction, ef_search, max_level, device), to: Nifs
+  defdelegate hnsw_new_cosine(m, m0, ef_construction, ef_search, max_level, device), to: Nifs
+  defdelegate hnsw_new_inner_product(m, m0, ef_construction, ef_search, max_level, device), to: Nifs
+  defdelegate hnsw_insert(ref, id, vector), to: Nifs
+  defdelegate hnsw_insert_many(ref, entries), to: Nifs
+  defdelegate hnsw_delete(ref, id), to: Nifs
+  defdelegate hnsw_search(ref, query, limit), to: Nifs
+
   # collection.ex:510 / :547
   defp max_candidates(limit) when is_integer(limit), do: max(limit * 10, limit)
   defp max_candidates(_), do: 0

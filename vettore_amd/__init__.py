@@ -6,4 +6,4 @@ from . import _lib
 
 _lib.load()  # fails loudly when the HIP library is missing: there is no fallback
 
-__all__ = ["_lib", "nifs", "index_flat", "collection", "sharded"]
+__all__ = ["_lib", "nifs", "index_flat", "index_hnsw", "collection", "sharded"]

@@ -35,6 +35,8 @@ SYMBOLS = [
     "vt_multi_vector_score", "vt_multi_vector_top_k", "vt_muvera_encode", "vt_muvera_fde_dimension",
     "vt_mv_new", "vt_mv_free", "vt_mv_put_many", "vt_mv_delete", "vt_mv_len", "vt_mv_dimension", "vt_mv_top_k", "vt_mv_top_k_ids",
     "vt_mv_memory", "vt_mv_top_k_batch", "vt_mv_top_k_ids_batch", "vt_mv_counters",
+    "vt_hnsw_new", "vt_hnsw_free", "vt_hnsw_insert", "vt_hnsw_insert_many", "vt_hnsw_delete", "vt_hnsw_search", "vt_hnsw_search_batch",
+    "vt_hnsw_len", "vt_hnsw_dimension", "vt_hnsw_node", "vt_hnsw_neighbors", "vt_hnsw_counters", "vt_hnsw_memory",
     "vt_flat_set_profiling", "vt_flat_get_profile", "vt_flat_get_profile_sized",
     "vt_flat_set_batch_shadow", "vt_flat_batch_shadow", "vt_flat_set_single_nominate", "vt_flat_single_nominate",
 ]
@@ -185,6 +187,22 @@ def load() -> C.CDLL:
     L.vt_mv_top_k_ids_batch.argtypes = [vp, C.c_size_t, szp, C.c_char_p, szp, szp, f32p, szp, C.c_int, C.c_size_t,
                                         C.POINTER(vp), C.POINTER(C.c_int)]
     L.vt_mv_counters.argtypes = [vp, u64p, u64p]
+    L.vt_hnsw_new.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.vt_hnsw_free.restype = None
+    L.vt_hnsw_free.argtypes = [vp]
+    L.vt_hnsw_insert.argtypes = [vp, C.c_char_p, C.c_size_t, f32p, C.c_size_t]
+    L.vt_hnsw_insert_many.argtypes = [vp, C.c_size_t, C.c_char_p, szp, f32p, szp]
+    L.vt_hnsw_delete.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.vt_hnsw_search.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.vt_hnsw_search_batch.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_int)]
+    L.vt_hnsw_len.restype = C.c_size_t
+    L.vt_hnsw_len.argtypes = [vp]
+    L.vt_hnsw_dimension.restype = C.c_long
+    L.vt_hnsw_dimension.argtypes = [vp]
+    L.vt_hnsw_node.argtypes = [vp, C.c_char_p, C.c_size_t, u64p, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+    L.vt_hnsw_neighbors.argtypes = [vp, C.c_uint64, C.c_uint32, u64p, C.c_size_t, szp]
+    L.vt_hnsw_counters.argtypes = [vp, u64p, u64p, u64p]
+    L.vt_hnsw_memory.argtypes = [vp, szp, szp, szp, szp]
     L.vt_muvera_fde_dimension.restype = C.c_size_t
     L.vt_muvera_fde_dimension.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.vt_flat_set_profiling.argtypes = [vp, C.c_int]

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import nifs
 from .index_flat import FlatGpu, Result, result_values, MAX_NIF_USIZE
+from .index_hnsw import HnswGpu
 from .mv_store import ResidentMultiVector
 
 F32_MAX = 3.4028234663852886e38  # collection.ex:61
@@ -72,7 +73,7 @@ class Collection:
             return ("error", "invalid_normalization")               # zscore/minmax: out of scope
         if score not in ("raw", "similarity"):
             return ("error", "invalid_score_mode")
-        index_mod = FlatGpu if index in ("flat", "flat_gpu") else index
+        index_mod = FlatGpu if index in ("flat", "flat_gpu") else HnswGpu if index in ("hnsw", "hnsw_gpu") else index
         for cb in ("new", "put", "put_many", "delete", "search"):
             if not hasattr(index_mod, cb):
                 return ("error", "invalid_index")

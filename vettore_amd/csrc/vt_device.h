@@ -645,6 +645,48 @@ hipError_t launch_muvera_encode(const MuveraArgs &a, hipStream_t s);
 hipError_t launch_muvera_sketch(const float *full, size_t out_size, uint32_t nsets, uint32_t final_dim, const uint32_t *off,
                                 const uint32_t *list, float *out, int *status, hipStream_t s);
 
+// ---- K11 (vt_hnsw.hip): HNSW traversals, one wave each (hnsw.rs:292-434) ----------------------------------------------
+// The device mirror of a graph (host/vt_hnswgraph.h): nodes are named by their slab rows.  The list of row r on layer 0
+// is adj0[r * (m0 + 1)] = its length, then its rows; on layer l >= 1 (level[r] >= l) the same at
+// upper[upoff[r] + (l - 1) * (m + 1)].
+struct HnswDev {
+  const float *X;         // the slab: `stride` floats a row (a multiple of 4), the pad zero and never read
+  size_t stride;
+  uint32_t d;
+  const uint32_t *adj0;
+  const uint32_t *level, *upoff, *upper;
+  uint32_t m, m0;
+};
+constexpr int kHnswRetry = 100;           // internal: the traversal outgrew its scratch, run it again with more
+constexpr uint32_t kHnswLdsDim = 4096;    // rows up to this long are staged through LDS, the query beside them
+struct HnswTravArgs {
+  HnswDev g;
+  int metric, order;      // VT_L2, VT_COSINE (the f32 dot, rank 1 - raw) or VT_INNER_PRODUCT
+  int mode;               // 0: search, 1: an insert's descent
+  const float *Q;         // traversal t's query: Q + query(t) * q_stride, 16-byte aligned; query(t) = qmap ? qmap[t] : t
+  uint32_t q_stride;
+  const uint32_t *qmap;
+  uint32_t entry, top;    // the graph's entry row and its level
+  uint32_t node_level;    // insert: the new node's level
+  uint32_t ef;            // of the search_layer calls, already cut to the node count
+  uint32_t cap, hshift;   // scratch entries per slot (a power of two >= 2) and 32 - log2(2 * cap)
+  uint64_t *scratch;      // [slots][3 * cap]
+  // per query `out_stride` words: {status, n}, then -- search -- n results (row, raw bits), or -- insert -- n layers,
+  // layer l at word 2 + l * (1 + 2 * ef): its count, then (row, rank distance bits) each
+  uint32_t *out;
+  uint32_t out_stride;
+  uint32_t tt, ld;        // hnsw_tile_plan: rows of the LDS tile (0: nothing is staged) and floats between them
+};
+void hnsw_tile_plan(uint32_t d, uint32_t stride, uint32_t *tt, uint32_t *ld);
+size_t hnsw_lds_bytes(uint32_t d, uint32_t tt, uint32_t ld);
+hipError_t launch_hnsw_traverse(const HnswTravArgs &a, uint32_t nslots, hipStream_t s);
+struct HnswPatch {
+  uint64_t dst;      // index into the array `target` names: 0 adj0, 1 upper, 2 level, 3 upoff
+  uint32_t val, target;
+};
+hipError_t launch_hnsw_patch(const HnswPatch *p, uint32_t n, uint32_t *adj0, uint32_t *upper, uint32_t *level, uint32_t *upoff,
+                             hipStream_t s);
+
 // normalize_l2 (distances.rs:350-361) on rows: out = (x / sqrt(f64 sum x^2)) as f32.
 hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *out, hipStream_t s);
 

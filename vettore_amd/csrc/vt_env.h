@@ -102,7 +102,8 @@ enum Parse {
   X(TEST_FOREIGN_ROWS, "test_foreign_rows", P_FLAG, 0, "device-resident rows are treated as living on another GPU (they reach a mapped slab through a staging block)") \
   X(TEST_REFUSE_SPARE_SCRATCH, "test_refuse_spare_scratch", P_FLAG, 0, "the second context of a pipelined batch call cannot get its scratch: the call must go on in series on the first") \
   X(TEST_COALESCE_HOLD_UNTIL, "test_coalesce_hold_until", P_INT, 0, "an idle handle's first caller keeps its slot until this many callers have queued (callers MEET: `vt_callers_meet`)") \
-  X(TEST_MV_K9, "test_mv_k9", P_FLAG, 0, "a resident multi-vector store's searches launch K9 over its slab where K9r would serve (`tools/maxsim_resident_probe.py` times one against the other)")
+  X(TEST_MV_K9, "test_mv_k9", P_FLAG, 0, "a resident multi-vector store's searches launch K9 over its slab where K9r would serve (`tools/maxsim_resident_probe.py` times one against the other)") \
+  X(TEST_HNSW_SCRATCH_CAP, "test_hnsw_scratch_cap", P_INT, 0, "entries of an HNSW traversal's heaps and visited set (default: a few thousand by ef, never more than the nodes need); a few entries make small traversals outgrow them and run again with full-size scratch")
 
 enum Key : int {
 #define VT_ENV_ENUM(key, name, parse, dflt, doc) key,

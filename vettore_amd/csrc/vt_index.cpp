@@ -37,6 +37,7 @@
 #include "host/vt_sketch5.h"
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
+#include "host/vt_hnswgraph.h"
 #include "host/vt_concurrency.h"
 #include "host/vt_base.h"
 #include "host/vt_types.h"
@@ -52,6 +53,7 @@
 #include "host/vt_maxsim.h"
 #include "host/vt_muvera.h"
 #include "host/vt_mvsearch.h"
+#include "host/vt_hnsw.h"
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
 
@@ -80,6 +82,14 @@ const char *vt_strerror(int status) {
     case VT_ERR_FDE_OVERFLOW: return "fde dimension overflow";
     case VT_ERR_FDE_LIMIT: return "fde dimension exceeds safety limit";
     case VT_ERR_ENCODING_OVERFLOW: return "encoding overflow";
+    case VT_ERR_HNSW_M: return "m must be positive";
+    case VT_ERR_HNSW_M0: return "m0 must be positive";
+    case VT_ERR_HNSW_DEGREE: return "invalid hnsw degree";
+    case VT_ERR_HNSW_EF_CONSTRUCTION: return "ef_construction must be >= m";
+    case VT_ERR_HNSW_EF_LIMIT: return "ef_construction exceeds safety limit";
+    case VT_ERR_HNSW_EF_SEARCH: return "ef_search must be positive";
+    case VT_ERR_HNSW_MAX_LEVEL: return "max_level must be positive";
+    case VT_ERR_HNSW_POISONED: return "hnsw lock poisoned";
     case VT_ERR_NOMEM: return "out of memory";
     case VT_ERR_DEVICE: return "device error";
     case VT_ERR_UNSUPPORTED: return "unsupported on device";
@@ -962,6 +972,166 @@ int vt_mv_memory(const vt_mv *s, size_t *vectors, size_t *row_capacity, size_t *
   if (dead_rows) *dead_rows = (size_t)s->table.dead_rows();
   if (uploaded_bytes) *uploaded_bytes = s->uploaded_bytes;
   if (compactions) *compactions = s->table.compactions();
+  return VT_OK;
+}
+
+int vt_hnsw_new(int metric_code, int device, size_t m, size_t m0, size_t ef_construction, size_t ef_search, size_t max_level,
+                vt_hnsw **out) {
+  return guarded([&]() -> int {
+  if (!out) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  if (metric_code != VT_L2 && metric_code != VT_COSINE && metric_code != VT_INNER_PRODUCT)
+    return fail(VT_ERR_UNSUPPORTED, "hnsw supports the l2, cosine and inner_product metrics only");
+  VT_TRY(hnsw_check_params(m, m0, ef_construction, ef_search, max_level));
+  auto h = std::make_unique<vt_hnsw>(m, m0, max_level);
+  VT_TRY(h->ctx.init(device));  // (no CPU fallback)
+  h->metric = metric_code;
+  h->order = default_order();
+  h->m = m;
+  h->m0 = m0;
+  h->ef_construction = ef_construction;
+  h->ef_search = ef_search;
+  *out = h.release();
+  return VT_OK;
+  });
+}
+
+void vt_hnsw_free(vt_hnsw *h) {
+  if (!h) return;
+  (void)guarded([&]() -> int {
+    (void)h->ctx.bind();
+    delete h;
+    return VT_OK;
+  });
+}
+
+int vt_hnsw_insert(vt_hnsw *h, const char *id, size_t id_len, const float *vector, size_t n) {
+  return guarded([&]() -> int {
+  if (!h || (id_len && !id) || (n && !vector)) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(h->mu);
+  if (h->poisoned) return VT_ERR_HNSW_POISONED;
+  VT_TRY(validate_vector(vector, n, h->graph.dimension()));
+  bool mutated = false;
+  const int st = no_throw([&]() { return hnsw_insert_one(h, id, id_len, vector, n, &mutated); });
+  return hnsw_settle(h, st, mutated);
+  });
+}
+
+int vt_hnsw_insert_many(vt_hnsw *h, size_t count, const char *ids, const size_t *id_off, const float *values,
+                        const size_t *value_off) {
+  return guarded([&]() -> int {
+  if (!h || (count && (!id_off || !value_off))) return VT_ERR_ARGUMENT;
+  if (count && ((id_off[count] > id_off[0] && !ids) || (value_off[count] > value_off[0] && !values))) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(h->mu);
+  return hnsw_insert_many(h, count, ids, id_off, values, value_off);
+  });
+}
+
+int vt_hnsw_delete(vt_hnsw *h, const char *id, size_t id_len) {
+  return guarded([&]() -> int {
+  if (!h || (id_len && !id)) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(h->mu);
+  return hnsw_delete(h, id, id_len);
+  });
+}
+
+int vt_hnsw_search(vt_hnsw *h, const float *query, size_t n, size_t limit, vt_hits **out) {
+  return guarded([&]() -> int {
+  if (!h || !out || (n && !query)) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(h->mu);
+  int status = VT_OK;
+  VT_TRY(hnsw_search_many(h, query, 1, n, limit, out, &status));
+  return status;
+  });
+}
+
+int vt_hnsw_search_batch(vt_hnsw *h, const float *queries, size_t nq, size_t d, size_t limit, vt_hits **out,
+                         int *query_status) {
+  return guarded([&]() -> int {
+  if (!h || (nq && !out) || (nq && d && !queries)) return VT_ERR_ARGUMENT;
+  for (size_t i = 0; i < nq; ++i) out[i] = nullptr;
+  if (nq == 0) return VT_OK;
+  std::vector<int> status(nq, VT_OK);
+  auto drop = [&]() {  // a call that fails leaves every out[i] NULL
+    for (size_t i = 0; i < nq; ++i) {
+      delete out[i];
+      out[i] = nullptr;
+    }
+  };
+  int rc;
+  try {
+    std::lock_guard<std::mutex> g(h->mu);
+    rc = hnsw_search_many(h, queries, nq, d, limit, out, status.data());
+  } catch (...) {
+    drop();
+    throw;
+  }
+  // without query_status the first failing query, in batch order, fails the call (vt_mv_top_k_batch's convention)
+  for (size_t i = 0; i < nq && rc == VT_OK && !query_status; ++i) rc = status[i];
+  if (rc != VT_OK) {
+    drop();
+    return rc;
+  }
+  for (size_t i = 0; i < nq && query_status; ++i) query_status[i] = status[i];
+  return VT_OK;
+  });
+}
+
+size_t vt_hnsw_len(const vt_hnsw *h) {
+  if (!h) return 0;
+  std::lock_guard<std::mutex> g(const_cast<vt_hnsw *>(h)->mu);
+  return h->graph.len();
+}
+
+long vt_hnsw_dimension(const vt_hnsw *h) {
+  if (!h) return -1;
+  std::lock_guard<std::mutex> g(const_cast<vt_hnsw *>(h)->mu);
+  return h->graph.dimension();
+}
+
+int vt_hnsw_node(const vt_hnsw *h, const char *id, size_t id_len, uint64_t *internal_id, uint32_t *level, int *is_entry) {
+  return guarded([&]() -> int {
+  if (!h || (id_len && !id)) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(const_cast<vt_hnsw *>(h)->mu);
+  const uint64_t iid = h->graph.find(std::string(id_len ? id : "", id_len));
+  if (iid == vt_host::HnswGraph::kNoEntry) return VT_ERR_ARGUMENT;
+  if (internal_id) *internal_id = iid;
+  if (level) *level = h->graph.node(iid)->level;
+  if (is_entry) *is_entry = h->graph.entry() == iid ? 1 : 0;
+  return VT_OK;
+  });
+}
+
+int vt_hnsw_neighbors(const vt_hnsw *h, uint64_t internal_id, uint32_t layer, uint64_t *out, size_t cap, size_t *count) {
+  return guarded([&]() -> int {
+  if (!h || !count || (cap && !out)) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(const_cast<vt_hnsw *>(h)->mu);
+  const vt_host::HnswNode *n = h->graph.node(internal_id);
+  if (!n || layer >= n->conn.size()) return VT_ERR_ARGUMENT;
+  const std::vector<vt_host::HnswEdge> &l = n->conn[layer];
+  *count = l.size();
+  for (size_t i = 0; i < l.size() && i < cap; ++i) out[i] = l[i].id;
+  return VT_OK;
+  });
+}
+
+int vt_hnsw_counters(const vt_hnsw *h, uint64_t *traversal_launches, uint64_t *traversals, uint64_t *reruns) {
+  if (!h) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(const_cast<vt_hnsw *>(h)->mu);
+  if (traversal_launches) *traversal_launches = h->launches;
+  if (traversals) *traversals = h->traversals;
+  if (reruns) *reruns = h->reruns;
+  return VT_OK;
+}
+
+int vt_hnsw_memory(const vt_hnsw *h, size_t *rows, size_t *row_capacity, size_t *dead_rows, size_t *edges) {
+  if (!h) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(const_cast<vt_hnsw *>(h)->mu);
+  if (rows) *rows = (size_t)h->rows_used;
+  if (row_capacity) *row_capacity = (size_t)h->capacity;
+  if (dead_rows) *dead_rows = (size_t)h->dead_rows;
+  if (edges) *edges = h->graph.edges();
   return VT_OK;
 }
 

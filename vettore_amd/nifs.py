@@ -575,6 +575,140 @@ def mv_memory(store: MvRef) -> dict:
 # ------------------------------------------------------------------ MUVERA
 MUVERA_QUERY, MUVERA_DOCUMENT = 0, 1
 U64_MAX = (1 << 64) - 1
+# ---------------------------------------------- HNSW index (hnsw_* NIFs, nifs.rs:311-426; vt_hnsw_*)
+class HnswRef:
+    """The `reference()` returned by hnsw_new_*: owns a vt_hnsw handle, freed with the object."""
+
+    def __init__(self, handle, metric: int):
+        self.handle = handle
+        self.metric = metric
+
+    def __del__(self):
+        try:
+            if self.handle:
+                _lib.load().vt_hnsw_free(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def __len__(self):
+        return _lib.load().vt_hnsw_len(self.handle)
+
+    @property
+    def dimension(self):
+        d = _lib.load().vt_hnsw_dimension(self.handle)
+        return None if d < 0 else d
+
+
+def _hnsw_new(metric: int, m, m0, ef_construction, ef_search, max_level, device=None):
+    """nifs.rs:311-374: ("ok", ref) | ("error", HnswParams::validate's string); no device: RuntimeError."""
+    for v in (m, m0, ef_construction, ef_search, max_level):
+        if not isinstance(v, int) or isinstance(v, bool) or not 0 <= v <= USIZE_MAX:
+            raise TypeError("badarg: hnsw parameters are usize")
+    h = C.c_void_p()
+    st = _lib.load().vt_hnsw_new(metric, DEVICE if device is None else device, m, m0, ef_construction, ef_search, max_level,
+                                 C.byref(h))
+    if 29 <= st <= 35:
+        return _err(st)
+    if st != 0:
+        raise RuntimeError("hnsw_new: " + _lib.error_text(st))
+    return ("ok", HnswRef(h, metric))
+
+
+def hnsw_new_l2(m, m0, ef_construction, ef_search, max_level, device=None):
+    return _hnsw_new(0, m, m0, ef_construction, ef_search, max_level, device)
+
+
+def hnsw_new_cosine(m, m0, ef_construction, ef_search, max_level, device=None):
+    return _hnsw_new(2, m, m0, ef_construction, ef_search, max_level, device)
+
+
+def hnsw_new_inner_product(m, m0, ef_construction, ef_search, max_level, device=None):
+    return _hnsw_new(3, m, m0, ef_construction, ef_search, max_level, device)
+
+
+def hnsw_insert(index: HnswRef, id_, vector):
+    """nifs.rs:376-388."""
+    b, v = _bytes(id_), _f32_list(vector)
+    st = _lib.load().vt_hnsw_insert(index.handle, b, len(b), _fp(v), v.size)
+    return ("ok", ()) if st == 0 else _err(st)
+
+
+def hnsw_insert_many(index: HnswRef, vectors: Sequence[Tuple[object, Sequence[float]]]):
+    """nifs.rs:390-401."""
+    vectors = list(vectors)
+    ids, ioff = _pack_ids(i for i, _ in vectors)
+    vals, voff = _pack_ragged([_f32_list(v) for _, v in vectors], np.float32)
+    st = _lib.load().vt_hnsw_insert_many(index.handle, len(vectors), ids, _szp(ioff), _fp(vals), _szp(voff))
+    return ("ok", ()) if st == 0 else _err(st)
+
+
+def hnsw_delete(index: HnswRef, id_):
+    """nifs.rs:403-412."""
+    b = _bytes(id_)
+    st = _lib.load().vt_hnsw_delete(index.handle, b, len(b))
+    return ("ok", ()) if st == 0 else _err(st)
+
+
+def hnsw_search(index: HnswRef, query, limit: int, with_keys: bool = False):
+    """nifs.rs:414-426 -> [(id, raw)] ascending by (rank, id)."""
+    if not isinstance(limit, int) or limit < 0 or limit > USIZE_MAX:
+        raise TypeError("badarg: limit must fit usize")
+    q = _f32_list(query)
+    h = C.c_void_p()
+    st = _lib.load().vt_hnsw_search(index.handle, _fp(q), q.size, limit, C.byref(h))
+    return ("ok", _export_hits(h, with_keys)) if st == 0 else _err(st)
+
+
+def hnsw_search_batch(index: HnswRef, queries, limit: int, with_keys: bool = False):
+    """Extension: `queries` is an [nq][d] matrix, one traversal launch for all of them: [("ok", hits) | ("error",
+    reason)] per query, each exactly what hnsw_search returns for that query alone."""
+    if not isinstance(limit, int) or limit < 0 or limit > USIZE_MAX:
+        raise TypeError("badarg: limit must fit usize")
+    q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+    if q.ndim != 2:
+        raise TypeError("badarg: queries must be a matrix")
+    nq, d = q.shape
+    outs, status = (C.c_void_p * max(nq, 1))(), (C.c_int * max(nq, 1))()
+    st = _lib.load().vt_hnsw_search_batch(index.handle, _fp(q.reshape(-1)), nq, d, limit, outs, status)
+    return _mv_batch_results(st, outs, status, nq, with_keys)
+
+
+def hnsw_node(index: HnswRef, id_):
+    """(internal id, level, is_entry) of a live id, None when there is none (inspection: tests compare graphs)."""
+    b = _bytes(id_)
+    iid, level, entry = C.c_uint64(), C.c_uint32(), C.c_int()
+    st = _lib.load().vt_hnsw_node(index.handle, b, len(b), C.byref(iid), C.byref(level), C.byref(entry))
+    return (iid.value, level.value, bool(entry.value)) if st == 0 else None
+
+
+def hnsw_neighbors(index: HnswRef, internal_id: int, layer: int):
+    """The internal ids of a node's list on one layer, in list order; None: no such node or layer."""
+    L = _lib.load()
+    n = C.c_size_t()
+    if L.vt_hnsw_neighbors(index.handle, internal_id, layer, None, 0, C.byref(n)) != 0:
+        return None
+    out = (C.c_uint64 * max(n.value, 1))()
+    L.vt_hnsw_neighbors(index.handle, internal_id, layer, out, n.value, C.byref(n))
+    return [int(out[i]) for i in range(n.value)]
+
+
+def hnsw_counters(index: HnswRef) -> dict:
+    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    st = _lib.load().vt_hnsw_counters(index.handle, C.byref(a), C.byref(b), C.byref(c))
+    if st != 0:
+        raise RuntimeError("hnsw_counters: " + _lib.error_text(st))
+    return {"traversal_launches": a.value, "traversals": b.value, "reruns": c.value}
+
+
+def hnsw_memory(index: HnswRef) -> dict:
+    a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+    st = _lib.load().vt_hnsw_memory(index.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    if st != 0:
+        raise RuntimeError("hnsw_memory: " + _lib.error_text(st))
+    return {"rows": a.value, "row_capacity": b.value, "dead_rows": c.value, "edges": d.value}
+
+
 _MUVERA_SET_ERRORS = (2, 3, 20, 28)  # dimension mismatch, non-finite, "empty vectors", "encoding overflow"
 
 
