@@ -24,7 +24,7 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_hnsw
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_hnsw vt_mmr
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -70,6 +70,8 @@ EXTRA_vt_sketch5          := $(EXTRA_vt_sketch6)
 # K11 (HNSW traversals): the distance chains are K9's with the recovery by value; heaps and visited set live in the
 # slot's global scratch, nothing is indexed dynamically in registers -- no scratch segment
 NOSCRATCH_vt_hnsw         := hnsw_traverse_kernel
+# K12 (MMR steps): one lane's chain per pair, K9's, with the recovery by value -- no scratch segment behind any of a call's launches
+NOSCRATCH_vt_mmr          := mmr_step_kernel
 NOSPILL_vt_batch_bf16     := bf16_scores_kernel
 NOSPILL_vt_batch_shadow   := shadow_scores_kernel
 
@@ -83,8 +85,8 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 # (what the sketch units share)
 $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o: $(CSRC)/vt_sketch.cuh
 
-# (the pass K9r and K9rb share; K11 takes its finish_raw)
-$(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o: $(CSRC)/vt_maxsim_pair.cuh
+# (the pass K9r and K9rb share; K11 and K12 take its finish_raw)
+$(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_maxsim_pair.cuh
 
 HOSTHDR := $(wildcard $(CSRC)/host/*.h)
 $(LIBDIR)/vt_index.o: $(CSRC)/vt_index.cpp $(HOSTHDR) $(CSRC)/vt_device.h $(CSRC)/vt_env.h include/vettore_flat.h

@@ -93,7 +93,10 @@ enum {
   VT_ERR_HNSW_EF_LIMIT = 33,        /* "ef_construction exceeds safety limit" */
   VT_ERR_HNSW_EF_SEARCH = 34,       /* "ef_search must be positive" */
   VT_ERR_HNSW_MAX_LEVEL = 35,       /* "max_level must be positive" */
-  VT_ERR_HNSW_POISONED = 36         /* "hnsw lock poisoned"                          nifs.rs:376-426 */
+  VT_ERR_HNSW_POISONED = 36,        /* "hnsw lock poisoned"                          nifs.rs:376-426 */
+  /* mmr_rerank/5, lib/vettore_distance.ex:334-405 */
+  /* (37 stays unassigned: vt_strerror(37) is "unknown status") */
+  VT_ERR_MMR_ARGS = 38              /* "invalid mmr args"  (:invalid_mmr_args) */
 };
 
 /* Lane order of wide::f32x8::reduce_add used for every 8-float chunk
@@ -529,6 +532,50 @@ int vt_hnsw_counters(const vt_hnsw *index, uint64_t *traversal_launches, uint64_
 /* rows: slab rows handed out; row_capacity: rows the slab holds; dead_rows: rows of deleted nodes; edges: entries of
  * all adjacency lists.  Any out pointer may be NULL. */
 int vt_hnsw_memory(const vt_hnsw *index, size_t *rows, size_t *row_capacity, size_t *dead_rows, size_t *edges);
+
+/* ------------------------------------------- MMR reranking and diversified search
+ * Vettore.Distance.mmr_rerank/5 (lib/vettore_distance.ex:334-519) and Vettore.rerank/4 (lib/vettore.ex:622-640): from an
+ * initial list of (candidate, relevance score) the call chooses up to final_k candidates, each round the one with the
+ * largest alpha * score - (1 - alpha) * (its largest pair_similarity to those chosen so far), the first such in list
+ * order -- f32 metric values in the lane order in force, f64 combination, never fused.  The answer is `order`: indices
+ * into the initial list in order of choice, min(final_k, count) of them (*order_len; `order` has room for that many);
+ * the selection is the reference's for every input, and so is "metric overflow" (VT_ERR_OVERFLOW): a pair fails the call
+ * in the round that scores it, a round that never runs fails nothing.  The rounds run on the device, one step launch
+ * each (csrc/vt_mmr.hip), with one wait at the end; no vector comes back to the host.
+ * vt_mmr_rerank: the candidates' vectors come with the call, row i of values ([count][d]) belonging to entry i.
+ * Checked in this order: alpha outside [0, 1] (or NaN), final_k == 0 or a score outside the f32 range (or NaN) is
+ * VT_ERR_MMR_ARGS; then the metric (VT_ERR_UNKNOWN_METRIC), d == 0 (VT_ERR_EMPTY), a non-finite value
+ * (VT_ERR_NON_FINITE); only then the device (VT_ERR_DEVICE without one: no CPU fallback).  count == 0 is VT_OK with an
+ * empty order.
+ * vt_flat_mmr_rerank: the candidates are ids of a one-shard index, the metric and lane order the handle's, the rows read
+ * where they lie in the slab.  After the checks on alpha, final_k and the scores, an id that is not in the index, or
+ * occurs twice, is VT_ERR_MMR_ARGS.  A read: it shares the handle with searches.  A sharded handle returns
+ * VT_ERR_UNSUPPORTED (vt_last_error says so), as do the two calls below.
+ * vt_flat_mmr_search / _batch: vt_flat_search / vt_flat_search_batch with limit = candidates -- *out receives exactly
+ * their hits, the candidate list --, then MMR over those hits under the same lease.  The initial scores are
+ * result_values/3's (lib/vettore_distance.ex:525-546) for score_mode 0 (raw) or 1 (similarity), computed in f64 from the
+ * hits' f32 raw values; any other score_mode is VT_ERR_MMR_ARGS, like a bad alpha or final_k.  `order` has room for
+ * min(final_k, candidates) indices per query (query i's at order + i * that), order_len one entry per query.  All
+ * queries of a batch are one chain of step launches.  A search error fails the call; a query's own MMR error follows
+ * vt_hnsw_search_batch's convention: with query_status it lands in query_status[i] with out[i] NULL and the call
+ * returns VT_OK, without it the first failing query's status is returned and every out[i] is NULL. */
+int vt_mmr_rerank(int device, int metric_code, size_t count, size_t d, const float *values, const double *scores /* count */,
+                  double alpha, size_t final_k, uint32_t *order, size_t *order_len);
+int vt_flat_mmr_rerank(vt_flat *index, size_t count, const char *ids, const size_t *id_off /* count + 1 */,
+                       const double *scores /* count */, double alpha, size_t final_k, uint32_t *order, size_t *order_len);
+/* vt_flat_mmr_rerank for nprob problems in one chain of step launches: problem p owns entries [prob_off[p], prob_off[p + 1])
+ * of ids (id_off is indexed by entry), scores and order, and has its own alpha[p] and final_k[p].  A problem's own error
+ * (VT_ERR_MMR_ARGS, VT_ERR_OVERFLOW) lands in prob_status[p] with order_len[p] = 0 while the call returns VT_OK; without
+ * prob_status the first failing problem's status is returned.  Every order equals the lone call's. */
+int vt_flat_mmr_rerank_batch(vt_flat *index, size_t nprob, const size_t *prob_off /* nprob + 1 */, const char *ids,
+                             const size_t *id_off /* entries + 1 */, const double *scores, const double *alpha /* nprob */,
+                             const size_t *final_k /* nprob */, uint32_t *order, size_t *order_len /* nprob */,
+                             int *prob_status /* nprob, may be NULL */);
+int vt_flat_mmr_search(vt_flat *index, const float *query, size_t n, size_t candidates, size_t final_k, double alpha,
+                       int score_mode, vt_hits **out, uint32_t *order, size_t *order_len);
+int vt_flat_mmr_search_batch(vt_flat *index, const float *queries, size_t nq, size_t d, size_t candidates, size_t final_k,
+                             double alpha, int score_mode, vt_hits **out /* nq */, uint32_t *order, size_t *order_len /* nq */,
+                             int *query_status /* nq, may be NULL */);
 
 /* ------------------------------------------- MUVERA (fixed-dimensional encoding)
  * muvera_encode_query/7, muvera_encode_document/7, nifs.rs:430-476 -> muvera.rs:26-74, for `count` sets of

@@ -863,6 +863,173 @@ static ERL_NIF_TERM hnsw_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
   return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
 }
 
+/* ------------------------------------------------------- MMR reranking
+ * Vettore.Distance.mmr_rerank/5 and Vettore.rerank/4 on the device.  The Elixir layer validates in the reference's
+ * order and converts numbers with `/ 1` (flat_gpu.ex); what crosses here is floats, and what comes back is the chosen
+ * entries' indices into the initial list, in order of choice. */
+static int get_f64_list(ErlNifEnv *env, ERL_NIF_TERM list, double **out, size_t *n) {
+  unsigned len;
+  if (!enif_get_list_length(env, list, &len)) return 0;
+  double *v = (double *)malloc((len ? len : 1) * sizeof(double));
+  if (!v) return 0;
+  ERL_NIF_TERM head, tail = list;
+  for (unsigned i = 0; i < len; ++i) {
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !enif_get_double(env, head, &v[i])) { free(v); return 0; }
+  }
+  *out = v;
+  *n = len;
+  return 1;
+}
+
+static ERL_NIF_TERM index_list(ErlNifEnv *env, const uint32_t *order, size_t n) {
+  ERL_NIF_TERM list = enif_make_list(env, 0);
+  for (size_t i = n; i-- > 0;) list = enif_make_list_cell(env, enif_make_uint64(env, order[i]), list);
+  return list;
+}
+
+/* mmr_rerank(metric_code, [[float]], [float], alpha, final_k) -> {:ok, [index]} | {:error, binary}
+ * row i of the matrix is the vector of initial entry i, scores[i] its relevance */
+static ERL_NIF_TERM mmr_rerank(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  int code, st;
+  unsigned count;
+  float *rows = NULL;
+  double *scores = NULL, alpha;
+  size_t d = 0, ns, final_k, got = 0;
+  (void)argc;
+  if (!enif_get_int(env, argv[0], &code) || !enif_get_list_length(env, argv[1], &count) ||
+      !get_f64_list(env, argv[2], &scores, &ns) || !enif_get_double(env, argv[3], &alpha) || !get_size(env, argv[4], &final_k)) {
+    free(scores);
+    return enif_make_badarg(env);
+  }
+  if (ns != count || !get_f32_matrix(env, argv[1], count, &rows, &d, &st)) { free(scores); return enif_make_badarg(env); }
+  if (st != VT_OK) { free(scores); return mk_error(env, st); }
+  uint32_t *order = (uint32_t *)malloc((count ? count : 1) * sizeof(uint32_t));
+  st = order ? vt_mmr_rerank(0, code, count, count ? d : 1, rows, scores, alpha, final_k, order, &got) : VT_ERR_NOMEM;
+  free(rows);
+  free(scores);
+  ERL_NIF_TERM res = st == VT_OK ? enif_make_tuple2(env, mk_atom(env, "ok"), index_list(env, order, got)) : mk_error(env, st);
+  free(order);
+  return res;
+}
+
+/* flat_mmr_rerank(ref, [{id, score}], alpha, final_k) -> {:ok, [index]} | {:error, binary}: the rows are the index's own */
+static ERL_NIF_TERM flat_mmr_rerank(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  flat_res *r = get_flat(env, argv[0]);
+  unsigned count;
+  double alpha;
+  size_t final_k, got = 0;
+  (void)argc;
+  if (!r || !enif_get_list_length(env, argv[1], &count) || !enif_get_double(env, argv[2], &alpha) ||
+      !get_size(env, argv[3], &final_k))
+    return enif_make_badarg(env);
+  size_t *off = (size_t *)calloc((size_t)count + 1, sizeof(size_t));
+  double *scores = (double *)malloc((count ? count : 1) * sizeof(double));
+  uint32_t *order = (uint32_t *)malloc((count ? count : 1) * sizeof(uint32_t));
+  char *ids = NULL;
+  size_t cap = 0;
+  int ok = off && scores && order;
+  ERL_NIF_TERM head, tail = argv[1];
+  for (unsigned i = 0; ok && i < count; ++i) {
+    const ERL_NIF_TERM *pair;
+    int arity;
+    ErlNifBinary id;
+    ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_tuple(env, head, &arity, &pair) && arity == 2 &&
+         enif_inspect_binary(env, pair[0], &id) && enif_get_double(env, pair[1], &scores[i]);
+    if (!ok) break;
+    if (off[i] + id.size > cap) {
+      cap = (off[i] + id.size) * 2 + 64;
+      char *grown = (char *)realloc(ids, cap);
+      if (!grown) { ok = 0; break; }
+      ids = grown;
+    }
+    memcpy(ids + off[i], id.data, id.size);
+    off[i + 1] = off[i] + id.size;
+  }
+  ERL_NIF_TERM res;
+  if (!ok) {
+    res = enif_make_badarg(env);
+  } else {
+    int st = vt_flat_mmr_rerank(r->h, count, ids ? ids : "", off, scores, alpha, final_k, order, &got);
+    res = st == VT_OK ? enif_make_tuple2(env, mk_atom(env, "ok"), index_list(env, order, got)) : mk_error(env, st);
+  }
+  free(ids);
+  free(off);
+  free(scores);
+  free(order);
+  return res;
+}
+
+/* flat_mmr_search(ref, [float], candidates, limit, alpha, score_mode) -> {:ok, {[{id, raw}], [index]}} | {:error, binary}
+ * flat_search(limit = candidates), its hits unchanged, then MMR over them; score_mode 0 :raw, 1 :similarity */
+static ERL_NIF_TERM flat_mmr_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  flat_res *r = get_flat(env, argv[0]);
+  float *q;
+  size_t n, candidates, limit, got = 0;
+  double alpha;
+  int mode;
+  (void)argc;
+  if (!r || !get_size(env, argv[2], &candidates) || !get_size(env, argv[3], &limit) || !enif_get_double(env, argv[4], &alpha) ||
+      !enif_get_int(env, argv[5], &mode) || !get_f32_list(env, argv[1], &q, &n))
+    return enif_make_badarg(env);
+  const size_t cap = limit < candidates ? limit : candidates;
+  uint32_t *order = (uint32_t *)malloc((cap ? cap : 1) * sizeof(uint32_t));
+  vt_hits *h = NULL;
+  int st = order ? vt_flat_mmr_search(r->h, q, n, candidates, limit, alpha, mode, &h, order, &got) : VT_ERR_NOMEM;
+  free(q);
+  ERL_NIF_TERM res = st == VT_OK ? enif_make_tuple2(env, mk_atom(env, "ok"),
+                                                    enif_make_tuple2(env, hits_to_list(env, h), index_list(env, order, got)))
+                                 : mk_error(env, st);
+  free(order);
+  return res;
+}
+
+/* flat_mmr_search_batch(ref, [[float]], candidates, limit, alpha, score_mode)
+ *   -> {:ok, [{:ok, {[{id, raw}], [index]}} | {:error, binary}]} | {:error, binary}: all queries one chain of launches */
+static ERL_NIF_TERM flat_mmr_search_batch(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  flat_res *r = get_flat(env, argv[0]);
+  unsigned nq;
+  size_t candidates, limit, d;
+  double alpha;
+  int mode, st;
+  float *qs = NULL;
+  (void)argc;
+  if (!r || !enif_get_list_length(env, argv[1], &nq) || !get_size(env, argv[2], &candidates) || !get_size(env, argv[3], &limit) ||
+      !enif_get_double(env, argv[4], &alpha) || !enif_get_int(env, argv[5], &mode))
+    return enif_make_badarg(env);
+  if (nq == 0) return enif_make_tuple2(env, mk_atom(env, "ok"), enif_make_list(env, 0));
+  if (!get_f32_matrix(env, argv[1], nq, &qs, &d, &st)) return enif_make_badarg(env);
+  if (st != VT_OK) return mk_error(env, st);
+  const size_t cap = limit < candidates ? limit : candidates;
+  vt_hits **out = (vt_hits **)calloc(nq, sizeof(vt_hits *));
+  const size_t slots = (size_t)nq * cap;
+  uint32_t *order = (uint32_t *)malloc((slots > 0 ? slots : 1) * sizeof(uint32_t));
+  size_t *lens = (size_t *)calloc(nq, sizeof(size_t));
+  int *status = (int *)calloc(nq, sizeof(int));
+  st = out && order && lens && status
+           ? vt_flat_mmr_search_batch(r->h, qs, nq, d, candidates, limit, alpha, mode, out, order, lens, status)
+           : VT_ERR_NOMEM;
+  free(qs);
+  ERL_NIF_TERM res;
+  if (st != VT_OK) {
+    res = mk_error(env, st);
+  } else {
+    ERL_NIF_TERM list = enif_make_list(env, 0);
+    for (unsigned i = nq; i-- > 0;) {
+      ERL_NIF_TERM one = status[i] == VT_OK
+                             ? enif_make_tuple2(env, mk_atom(env, "ok"),
+                                                enif_make_tuple2(env, hits_to_list(env, out[i]), index_list(env, order + (size_t)i * cap, lens[i])))
+                             : mk_error(env, status[i]);
+      list = enif_make_list_cell(env, one, list);
+    }
+    res = enif_make_tuple2(env, mk_atom(env, "ok"), list);
+  }
+  free(out);
+  free(order);
+  free(lens);
+  free(status);
+  return res;
+}
+
 static int load(ErlNifEnv *env, void **priv, ERL_NIF_TERM info) {
   (void)priv; (void)info;
   /* a libvettore_hip.so built from another header would be handed structs of the wrong size */
@@ -900,6 +1067,10 @@ static ErlNifFunc funcs[] = {
   {"hnsw_insert_many", 2, hnsw_insert_many, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_delete", 2, hnsw_delete, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_search", 3, hnsw_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"mmr_rerank", 5, mmr_rerank, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"flat_mmr_rerank", 4, flat_mmr_rerank, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"flat_mmr_search", 6, flat_mmr_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"flat_mmr_search_batch", 6, flat_mmr_search_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 ERL_NIF_INIT(Elixir.Vettore.Gpu.Nifs, funcs, load, NULL, NULL, NULL)

@@ -192,6 +192,74 @@ defmodule Vettore.Index.FlatGpu do
   defdelegate hnsw_delete(ref, id), to: Nifs
   defdelegate hnsw_search(ref, query, limit), to: Nifs
 
+  # ---- MMR reranking and diversified search on the resident rows (DESIGN 4.15)
+  @doc """
+  `Vettore.rerank/4` (vettore.ex:622-640) without `all/1`: MMR over `initial = [{id, score}]` under the collection's
+  metric, the rows read where they lie in the index.  Options `limit:` (10) and `alpha:` (0.5), anything else
+  `{:error, :invalid_options}`.  The selection, its order and its errors are `Vettore.Distance.mmr_rerank/5`'s.
+  """
+  def rerank(%Collection{} = collection, initial, opts \\ []) when is_list(initial) and is_list(opts) do
+    limit = Keyword.get(opts, :limit, 10)
+    alpha = Keyword.get(opts, :alpha, 0.5)
+
+    cond do
+      not (Keyword.keyword?(opts) and Enum.all?(Keyword.keys(opts), &(&1 in [:limit, :alpha]))) ->
+        {:error, :invalid_options}
+
+      not mmr_guards?(alpha, limit) or not Enum.all?(initial, &mmr_entry?/1) ->
+        {:error, :invalid_mmr_args}
+
+      true ->
+        pairs = Enum.map(initial, fn {id, score} -> {id, score / 1} end)
+
+        case Nifs.flat_mmr_rerank(collection.index_state, pairs, alpha / 1, min(limit, @max_nif_usize)) do
+          {:ok, order} -> {:ok, Enum.map(order, &Enum.at(initial, &1))}
+          {:error, reason} -> {:error, mmr_atom(reason)}
+        end
+    end
+  end
+
+  @doc """
+  Diversified search: `search(limit: candidates)` followed by `rerank(limit: limit, alpha: alpha)` over its
+  `{id, score}` pairs, as one NIF call under one lease.  Options `limit:` (10), `candidates:` (`max(limit * 10, limit)`,
+  collection.ex:510), `alpha:` (0.5).  Results come back in MMR order.
+  """
+  def mmr_search(%Collection{} = collection, query, opts \\ []) do
+    limit = Keyword.get(opts, :limit, 10)
+    candidates = Keyword.get(opts, :candidates, max_candidates(limit))
+    alpha = Keyword.get(opts, :alpha, 0.5)
+    mode = if collection.score == :similarity, do: 1, else: 0
+
+    with :ok <- validate_limit(limit),
+         :ok <- validate_candidates(candidates, limit),
+         :ok <- if(mmr_guards?(alpha, limit), do: :ok, else: {:error, :invalid_mmr_args}),
+         {:ok, prepared} <- Collection.prepare_query(collection, query) do
+      case Nifs.flat_mmr_search(collection.index_state, prepared, candidates, limit, alpha / 1, mode) do
+        {:ok, {hits, order}} -> {:ok, Enum.flat_map(order, &to_result(collection, Enum.at(hits, &1)))}
+        {:error, reason} -> {:error, mmr_atom(reason)}
+      end
+    end
+  end
+
+  # The raw MMR NIFs (DESIGN 4.15): indices into the initial list / the hit list come back, in order of choice.
+  defdelegate mmr_rerank(metric_code, rows, scores, alpha, final_k), to: Nifs
+  defdelegate flat_mmr_rerank(ref, initial, alpha, final_k), to: Nifs
+  defdelegate flat_mmr_search(ref, query, candidates, limit, alpha, score_mode), to: Nifs
+  defdelegate flat_mmr_search_batch(ref, queries, candidates, limit, alpha, score_mode), to: Nifs
+
+  # vettore_distance.ex:334-336, :407-414
+  defp mmr_guards?(alpha, final_k),
+    do: is_number(alpha) and alpha >= 0 and alpha <= 1 and is_integer(final_k) and final_k > 0
+
+  defp mmr_entry?({id, score}) when is_binary(id) and id != "" and is_number(score),
+    do: score >= -3.402_823_466_385_288_6e38 and score <= 3.402_823_466_385_288_6e38
+
+  defp mmr_entry?(_entry), do: false
+
+  defp mmr_atom("invalid mmr args"), do: :invalid_mmr_args
+  defp mmr_atom("metric overflow"), do: :metric_overflow
+  defp mmr_atom(reason), do: reason
+
   # collection.ex:510 / :547
   defp max_candidates(limit) when is_integer(limit), do: max(limit * 10, limit)
   defp max_candidates(_), do: 0

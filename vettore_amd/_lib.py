@@ -37,6 +37,7 @@ SYMBOLS = [
     "vt_mv_memory", "vt_mv_top_k_batch", "vt_mv_top_k_ids_batch", "vt_mv_counters",
     "vt_hnsw_new", "vt_hnsw_free", "vt_hnsw_insert", "vt_hnsw_insert_many", "vt_hnsw_delete", "vt_hnsw_search", "vt_hnsw_search_batch",
     "vt_hnsw_len", "vt_hnsw_dimension", "vt_hnsw_node", "vt_hnsw_neighbors", "vt_hnsw_counters", "vt_hnsw_memory",
+    "vt_mmr_rerank", "vt_flat_mmr_rerank", "vt_flat_mmr_rerank_batch", "vt_flat_mmr_search", "vt_flat_mmr_search_batch",
     "vt_flat_set_profiling", "vt_flat_get_profile", "vt_flat_get_profile_sized",
     "vt_flat_set_batch_shadow", "vt_flat_batch_shadow", "vt_flat_set_single_nominate", "vt_flat_single_nominate",
 ]
@@ -203,6 +204,13 @@ def load() -> C.CDLL:
     L.vt_hnsw_neighbors.argtypes = [vp, C.c_uint64, C.c_uint32, u64p, C.c_size_t, szp]
     L.vt_hnsw_counters.argtypes = [vp, u64p, u64p, u64p]
     L.vt_hnsw_memory.argtypes = [vp, szp, szp, szp, szp]
+    f64p = C.POINTER(C.c_double)
+    L.vt_mmr_rerank.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, f32p, f64p, C.c_double, C.c_size_t, u32p, szp]
+    L.vt_flat_mmr_rerank.argtypes = [vp, C.c_size_t, C.c_char_p, szp, f64p, C.c_double, C.c_size_t, u32p, szp]
+    L.vt_flat_mmr_rerank_batch.argtypes = [vp, C.c_size_t, szp, C.c_char_p, szp, f64p, f64p, szp, u32p, szp, C.POINTER(C.c_int)]
+    L.vt_flat_mmr_search.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.c_int, C.POINTER(vp), u32p, szp]
+    L.vt_flat_mmr_search_batch.argtypes = [vp, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_double, C.c_int,
+                                           C.POINTER(vp), u32p, szp, C.POINTER(C.c_int)]
     L.vt_muvera_fde_dimension.restype = C.c_size_t
     L.vt_muvera_fde_dimension.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
     L.vt_flat_set_profiling.argtypes = [vp, C.c_int]

@@ -367,6 +367,88 @@ class Collection:
         return ("ok", [Result(id=i, value=self.store[i].value, score=float(score), distance=None, metric=metric,
                               metadata=self.store[i].metadata) for i, score in res[1] if i in self.store])
 
+    # -- lib/vettore.ex:622-640: rerank/4 -> Vettore.Distance.mmr_rerank/5 --------------------------
+    def rerank(self, initial, opts=None):
+        """MMR over `initial` = [(id, score)] under the collection's metric: ("ok", the chosen entries in order of
+        choice).  Options: limit (10), alpha (0.5).  A FlatGpu index reads the rows where they are resident; any other
+        index module goes through the stateless call with the vectors of the initial entries from the store (the
+        reference hands mmr_rerank/5 the whole table; the stored vectors it would validate are valid by construction)."""
+        opts = {} if opts is None else opts
+        if not isinstance(initial, list) or not isinstance(opts, dict):
+            return ("error", "invalid_arguments")                          # vettore.ex:642
+        if any(k not in ("limit", "alpha") for k in opts):
+            return ("error", "invalid_options")                            # vettore.ex:628, :638
+        limit, alpha = opts.get("limit", 10), opts.get("alpha", 0.5)
+        fn = getattr(self.index_mod, "rerank", None)
+        if fn is not None:
+            res = fn(self, initial, alpha, limit)
+            if res is not None:
+                return res
+        conv, pairs, seen = [], [], set()
+        for entry in initial:
+            if isinstance(entry, tuple) and len(entry) == 2 and isinstance(entry[0], (str, bytes)):
+                idb = nifs._bytes(entry[0])
+                conv.append((idb, entry[1]))
+                if idb in self.store and idb not in seen:
+                    seen.add(idb)
+                    pairs.append((idb, [float(x) for x in self.store[idb].vector]))
+            else:
+                conv.append(entry)
+        res = nifs.mmr_rerank(conv, pairs, self.metric, alpha, limit)
+        if res[0] != "ok":
+            return res
+        place = {id(e): i for i, e in enumerate(conv)}
+        return ("ok", [initial[place[id(e)]] for e in res[1]])
+
+    def _mmr_composed(self, query, opts):
+        """mmr_search as its definition: search(limit: candidates), then rerank over the results' (id, score)."""
+        lc = FlatGpu._mmr_options(opts)
+        if lc[0] != "ok":
+            return lc
+        found = self.search(query, {"limit": lc[2]})
+        if found[0] != "ok":
+            return found
+        res = self.rerank([(r.id, r.score) for r in found[1]], {"limit": lc[1], "alpha": lc[3]})
+        if res[0] != "ok":
+            return res
+        by_id = {r.id: r for r in found[1]}
+        return ("ok", [by_id[i] for i, _ in res[1]])
+
+    def mmr_search(self, query, opts=None):
+        """Diversified search (an extension of the adapter): Results in MMR order, equal to search(limit: candidates)
+        followed by rerank(limit: limit, alpha: alpha).  Options: limit (10), candidates (max(limit * 10, limit)), alpha (0.5)."""
+        opts = {} if opts is None else opts
+        if not isinstance(opts, dict):
+            return ("error", "invalid_options")
+        bad = [k for k in opts if k not in ("limit", "candidates", "alpha")]
+        if bad:
+            return ("error", ("unsupported_option", bad[0]))
+        fn = getattr(self.index_mod, "mmr_search", None)
+        if fn is not None:
+            res = fn(self, query, opts)
+            if res is not None:
+                return res
+        return self._mmr_composed(query, opts)
+
+    def mmr_search_batch(self, queries, opts=None):
+        """mmr_search for a list of queries: ("ok", [("ok", [Result]) | ("error", reason) per query]); with a FlatGpu
+        index all of them are one call and one chain of step launches."""
+        opts = {} if opts is None else opts
+        if not isinstance(opts, dict):
+            return ("error", "invalid_options")
+        bad = [k for k in opts if k not in ("limit", "candidates", "alpha")]
+        if bad:
+            return ("error", ("unsupported_option", bad[0]))
+        fn = getattr(self.index_mod, "mmr_search_batch", None)
+        if fn is not None:
+            res = fn(self, queries, opts)
+            if res is not None:
+                return res
+        lc = FlatGpu._mmr_options(opts)
+        if lc[0] != "ok":
+            return lc
+        return ("ok", [self._mmr_composed(q, opts) for q in queries])
+
     # (extensions of the adapter: lists of queries, one call)
     def search_batch(self, queries, opts=None):
         return self._staged("search_batch", ("limit",), queries, opts)

@@ -111,6 +111,35 @@ inline vt::MuveraArgs muvera_args(size_t d, size_t R, size_t k, size_t pd, int m
   return a;
 }
 
+// K12 over the rows of `r` (d coordinates used), the context's MMR buffers as they are NOW (every ensure comes first).
+// The two test hooks are read here and nowhere else: candidates per block and pass, and the staging limit.
+inline uint32_t mmr_block_rows() {
+  const long v = vt::env::get(vt::env::TEST_MMR_BLOCK_ROWS);
+  return v >= 1 && v <= (long)vt::kMmrBlockRows ? (uint32_t)v : vt::kMmrBlockRows;
+}
+inline vt::MmrArgs mmr_args(const RowSet &r, Ctx &c, uint32_t d, uint32_t block_rows) {
+  vt::MmrArgs a{};
+  a.X = r.X;
+  a.stride = r.stride;
+  a.d = d;
+  a.metric = r.metric;
+  a.order = r.order;
+  a.prob = c.dMmrProb.p;
+  a.rows = c.dMmrRows.p;
+  a.rel = c.dMmrRel.p;
+  a.red = c.dMmrRed.p;
+  a.norm = c.dMmrNorm.p;
+  a.live = c.dMmrLive.p;
+  a.partial = c.dMmrPartial.p;
+  a.order_out = c.dMmrOrder.p;
+  a.count = c.dMmrCount.p;
+  a.status = c.dMmrStatus.p;
+  a.block_rows = block_rows;
+  const long ldim = vt::env::get(vt::env::TEST_MMR_LDS_DIM);
+  a.lds_dim = ldim >= 1 && ldim <= (long)vt::kMmrLdsDim ? (uint32_t)ldim : vt::kMmrLdsDim;
+  return a;
+}
+
 // ------------------------------------------------------------------ gather lists
 // One stage's output as the next stage's gather list: the first row index and the u32 words from one to the next.
 struct GatherList {

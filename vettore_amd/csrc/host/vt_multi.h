@@ -783,8 +783,12 @@ int store_validated(vt_flat *h, size_t count, const char *ids, const size_t *id_
   return st;
 }
 
+// What a caller may run behind its search, on the same shard and context, still under the search's lease (the MMR calls,
+// vt_mmr.h): the hits are then exactly the search's, whatever the search's path becomes.  One-shard handles only.
+using AfterSearch = std::function<int(Shard *, Ctx &)>;
+
 // flat_search as one caller runs it (nifs.rs:297-309).
-int search_direct(vt_flat *h, const float *query, size_t n, size_t limit, vt_hits **out) {
+int search_direct(vt_flat *h, const float *query, size_t n, size_t limit, vt_hits **out, const AfterSearch &after = nullptr) {
   if (h->multi()) {
     std::shared_lock<std::shared_mutex> rl(h->rw);
     if (h->poisoned) return poisoned_status();
@@ -795,7 +799,14 @@ int search_direct(vt_flat *h, const float *query, size_t n, size_t limit, vt_hit
   // (and the int8 sketch where sketch_wanted says a lone search reads it: the first such search builds it)
   const unsigned need = NEED_RANKS | NEED_NZBITS | NEED_SKETCH |
                         (s0->single_nominate && limit <= (size_t)vt::kMaxFusedK ? NEED_NORMS | NEED_STRICT_RANKS : 0u);
-  return read_single(h, need, limit, [&](Shard *ix, Ctx &c) -> int { return search_ready(ix, c, query, n, limit, out, true); });
+  return read_single(h, need, limit, [&](Shard *ix, Ctx &c) -> int {
+    if (after) {  // (a second run after an escalation starts clean)
+      delete *out;
+      *out = nullptr;
+    }
+    const int st = search_ready(ix, c, query, n, limit, out, true);
+    return st == VT_OK && after ? after(ix, c) : st;
+  });
 }
 
 // quantized_search as one caller runs it (collection.ex:276-295).
@@ -877,7 +888,8 @@ int funnel_batch_direct(vt_flat *h, const float *queries, size_t nq, size_t d, c
 }
 
 // flat_search_batch: nq queries of d floats, one hit list each, or one status for all.
-int batch_direct(vt_flat *h, const float *queries, size_t nq, size_t d, size_t limit, vt_hits **out) {
+int batch_direct(vt_flat *h, const float *queries, size_t nq, size_t d, size_t limit, vt_hits **out,
+                 const AfterSearch &after = nullptr) {
   for (size_t i = 0; i < nq; ++i) out[i] = nullptr;
   int st;
   if (h->multi()) {
@@ -896,7 +908,8 @@ int batch_direct(vt_flat *h, const float *queries, size_t nq, size_t d, size_t l
         out[i] = nullptr;
       }
       if (ix->n && batch_uses_mfma(ix, nq, limit) && shard_stale(ix, NEED_NORMS, limit)) return kEscalate;
-      return batch_ready(ix, c, queries, nq, d, limit, out);
+      const int rs = batch_ready(ix, c, queries, nq, d, limit, out);
+      return rs == VT_OK && after ? after(ix, c) : rs;
     });
   }
   if (st != VT_OK)

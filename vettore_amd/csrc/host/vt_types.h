@@ -58,6 +58,14 @@ struct Ctx {
   DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
   DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
   DevBuf<uint32_t> dSk5Rows;  // K1f (sketch5_search): its candidate list, a row for every retained slot
+  // K12 (vt_mmr.h, mmr_run): a call's problems, per-candidate arrays and block partials; what goes up and what comes back
+  // travel through the two pinned blocks (grow, never shrink: no allocation per call)
+  DevBuf<vt::MmrProblem> dMmrProb;
+  DevBuf<uint32_t> dMmrRows, dMmrLive, dMmrOrder, dMmrCount;
+  DevBuf<double> dMmrRel, dMmrRed, dMmrNorm;
+  DevBuf<vt::MmrPartial> dMmrPartial;
+  DevBuf<int> dMmrStatus;
+  PinnedBuf<unsigned char> hMmrUp, hMmrDown;
   // grouped quantized searches: one stage-1 block per query
   DevBuf<ResultBlock> dStageB;
   PinnedBuf<float> hBQ, hBTau;

@@ -687,6 +687,57 @@ struct HnswPatch {
 hipError_t launch_hnsw_patch(const HnswPatch *p, uint32_t n, uint32_t *adj0, uint32_t *upper, uint32_t *level, uint32_t *upoff,
                              hipStream_t s);
 
+// ---- K12 (vt_mmr.hip): MMR reranking (vettore_distance.ex:416-519), one step kernel queued once per round ------------
+// A call solves `nprob` problems over one row matrix.  Problem p owns entries [off, off + n) of the per-candidate arrays;
+// candidate i of it is row rows[off + i] of X with the f64 relevance rel[off + i].  launch_mmr_step(a, t, ...) is queued
+// for t = 0 .. max_p(kk_p), kk_p = min(k_p, n_p), back to back on one stream; the grid is (blocks, nprob), nothing waits
+// inside a launch.  Launch t of problem p:
+//   phase A (1 <= t <= kk): every block reduces the blocks' partials of launch t - 1 -- the largest score, the smallest
+//     candidate on a tie (Enum.max_by keeps the first maximum), and the smallest candidate whose pair failed.  A failed
+//     pair makes the problem's status kErrOverflow for good (the blocks hand the failure on through their partials);
+//     otherwise block 0 appends the winner to order[off + t - 1] and sets count[p] = t;
+//   phase B (t < kk, nothing failed): the winner's row is staged in LDS (rows longer than lds_dim floats are read where
+//     they lie); every live candidate is scored against it by one lane -- compute(metric, candidate, winner) in the
+//     reference's f32 order for `order`, f64 recovery included, then pair_similarity's f64 value --, its running
+//     maximum red[off + i] updated (the first similarity replaces it), its score alpha * rel - (1 - alpha) * red formed
+//     in f64 without contraction; the block's best (score, candidate) and first failed candidate go to
+//     partial[t & 1][p][block].  At t = 0 there is no winner: the redundancy is 0.0, the candidates come alive and --
+//     cosine -- their f64 norms are filed.
+// Partials alternate by launch parity: no block of a launch reads what another block of the same launch writes.
+constexpr uint32_t kMmrNone = 0xffffffffu;
+constexpr uint32_t kMmrLdsDim = 4096;        // winners up to this long are staged in LDS (as K11's rows)
+constexpr uint32_t kMmrBlockRows = 256;      // candidates a block takes per pass: one per thread
+constexpr uint32_t kMmrMaxBlocks = 64;       // blocks per problem at most (one wave reduces their partials)
+struct MmrProblem {
+  uint32_t off, n, kk, pad;
+  double alpha;
+};
+struct MmrPartial {
+  double score;
+  uint32_t best, failed;  // candidates, kMmrNone: none
+};
+static_assert(sizeof(MmrProblem) == 24 && sizeof(MmrPartial) == 16, "layout");
+struct MmrArgs {
+  const float *X;          // rows `stride` floats apart, 16-byte aligned (stride % 4 == 0)
+  size_t stride;
+  uint32_t d;
+  int metric, order;
+  const MmrProblem *prob;  // [nprob]
+  const uint32_t *rows;    // per candidate
+  const double *rel;       // per candidate
+  double *red;             // per candidate: the running maximum similarity to the chosen
+  double *norm;            // per candidate (cosine): sqrt(f64 x.x)
+  uint32_t *live;          // per candidate: 1 until chosen
+  MmrPartial *partial;     // [2][nprob][blocks]
+  uint32_t *order_out;     // per candidate slot: problem p's choices at off ..
+  uint32_t *count;         // [nprob] choices made
+  int *status;             // [nprob] 0 or kErrOverflow
+  uint32_t block_rows;     // candidates per block and pass (<= kMmrBlockRows)
+  uint32_t lds_dim;        // staging limit in floats
+};
+size_t mmr_lds_bytes(uint32_t d, uint32_t lds_dim);
+hipError_t launch_mmr_step(const MmrArgs &a, uint32_t t, uint32_t blocks, uint32_t nprob, hipStream_t s);
+
 // normalize_l2 (distances.rs:350-361) on rows: out = (x / sqrt(f64 sum x^2)) as f32.
 hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *out, hipStream_t s);
 

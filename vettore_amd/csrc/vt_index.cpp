@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -38,6 +39,7 @@
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
+#include "host/vt_mmrplan.h"
 #include "host/vt_concurrency.h"
 #include "host/vt_base.h"
 #include "host/vt_types.h"
@@ -56,6 +58,7 @@
 #include "host/vt_hnsw.h"
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
+#include "host/vt_mmr.h"
 
 // =============================================================== C ABI
 extern "C" {
@@ -90,6 +93,7 @@ const char *vt_strerror(int status) {
     case VT_ERR_HNSW_EF_SEARCH: return "ef_search must be positive";
     case VT_ERR_HNSW_MAX_LEVEL: return "max_level must be positive";
     case VT_ERR_HNSW_POISONED: return "hnsw lock poisoned";
+    case VT_ERR_MMR_ARGS: return "invalid mmr args";
     case VT_ERR_NOMEM: return "out of memory";
     case VT_ERR_DEVICE: return "device error";
     case VT_ERR_UNSUPPORTED: return "unsupported on device";
@@ -1154,6 +1158,52 @@ size_t vt_muvera_fde_dimension(size_t num_repetitions, size_t num_simhash_projec
   size_t out_size = 0, fde = 0;
   if (muvera_check_config(m) != VT_OK || muvera_check_sizes(m, &out_size, &fde) != VT_OK) return 0;
   return fde;
+}
+
+int vt_mmr_rerank(int device, int metric_code, size_t count, size_t d, const float *values, const double *scores, double alpha,
+                  size_t final_k, uint32_t *order, size_t *order_len) {
+  return guarded([&]() -> int {
+  if (!order_len || (count && (!scores || !order || (d && !values)))) return VT_ERR_ARGUMENT;
+  *order_len = 0;
+  return mmr_rerank_stateless(device, metric_code, count, d, values, scores, alpha, final_k, order, order_len);
+  });
+}
+
+int vt_flat_mmr_rerank(vt_flat *h, size_t count, const char *ids, const size_t *id_off, const double *scores, double alpha,
+                       size_t final_k, uint32_t *order, size_t *order_len) {
+  return guarded([&]() -> int {
+  if (!h || !order_len || (count && (!id_off || !scores || !order))) return VT_ERR_ARGUMENT;
+  *order_len = 0;
+  return flat_mmr_rerank(h, count, ids ? ids : "", id_off, scores, alpha, final_k, order, order_len);
+  });
+}
+
+int vt_flat_mmr_rerank_batch(vt_flat *h, size_t nprob, const size_t *prob_off, const char *ids, const size_t *id_off,
+                             const double *scores, const double *alpha, const size_t *final_k, uint32_t *order, size_t *order_len,
+                             int *prob_status) {
+  return guarded([&]() -> int {
+  if (!h || (nprob && (!prob_off || !alpha || !final_k || !order_len))) return VT_ERR_ARGUMENT;
+  if (nprob && prob_off[nprob] > prob_off[0] && (!id_off || !scores || !order)) return VT_ERR_ARGUMENT;
+  return flat_mmr_rerank_batch(h, nprob, prob_off, ids ? ids : "", id_off, scores, alpha, final_k, order, order_len, prob_status);
+  });
+}
+
+int vt_flat_mmr_search(vt_flat *h, const float *query, size_t n, size_t candidates, size_t final_k, double alpha, int score_mode,
+                       vt_hits **out, uint32_t *order, size_t *order_len) {
+  return guarded([&]() -> int {
+  if (!h || !out || !order_len || (!query && n) || (candidates && !order)) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  *order_len = 0;
+  return flat_mmr_search(h, query, n, candidates, final_k, alpha, score_mode, out, order, order_len);
+  });
+}
+
+int vt_flat_mmr_search_batch(vt_flat *h, const float *queries, size_t nq, size_t d, size_t candidates, size_t final_k, double alpha,
+                             int score_mode, vt_hits **out, uint32_t *order, size_t *order_len, int *query_status) {
+  return guarded([&]() -> int {
+  if (!h || (nq && (!out || !order_len || (candidates && !order))) || (nq && d && !queries)) return VT_ERR_ARGUMENT;
+  return flat_mmr_search_batch(h, queries, nq, d, candidates, final_k, alpha, score_mode, out, order, order_len, query_status);
+  });
 }
 
 int vt_binary_top_k(int device, size_t count, const char *ids, const size_t *id_off, const uint64_t *words,

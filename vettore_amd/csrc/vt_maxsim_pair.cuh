@@ -13,7 +13,7 @@ namespace {
 
 constexpr int kQB = 8;                       // query vectors per lane pass (as in K9)
 constexpr size_t kResidentLds = 128 * 1024;  // LDS of a block: the query panel and four tiles
-enum { MS_COS = 6 };                         // beside OP_DOT / OP_L2 / OP_L1 / OP_LINF
+enum { MS_COS = 6, MS_COUNT = 7 };           // beside OP_DOT / OP_L2 / OP_L1 / OP_LINF
 
 // compute() (distances.rs:42-68) after the f32 chain, and similarity_value (distances.rs:122-128): K9's, word for word
 template <int OP>
@@ -28,6 +28,29 @@ __device__ __forceinline__ float similarity(int metric, float raw) {
   if (metric == M_COS || metric == M_IP) return raw;
   if (metric == M_NIP) return -raw;
   return 1.0f / (1.0f + raw);
+}
+
+// One pair, one lane, outside the f32 families (K12; K9 and the pass below run the same steps eight query vectors wide):
+// cosine() (distances.rs:160-177) over the two vectors' f64 norms -- fma(q, x, acc) == acc + q*x, a product of two f32 is
+// exact in f64; NaN: "metric overflow" --
+__device__ __forceinline__ float pair_cosine_raw(const float *q, const float *x, uint32_t d, double qn, double xn) {
+  double dot = 0.0;
+  for (uint32_t e = 0; e < d; ++e) dot = __builtin_fma((double)q[e], (double)x[e], dot);
+  if (qn == 0.0 || xn == 0.0) return 0.0f;
+  const double sim = dot / (qn * xn);
+  return isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
+}
+// and hamming() / jaccard() (distances.rs:319-347) over truthiness: integer counts, exact for any d
+__device__ __forceinline__ float pair_count_raw(int metric, const float *q, const float *x, uint32_t d) {
+  uint32_t ham = 0, inter = 0, uni = 0;
+  for (uint32_t e = 0; e < d; ++e) {
+    const bool ql = q[e] != 0.0f, xr = x[e] != 0.0f;
+    ham += ql != xr;
+    inter += ql && xr;
+    uni += ql || xr;
+  }
+  if (metric == M_HAM) return (float)ham;
+  return uni == 0 ? 0.0f : 1.0f - (float)inter / (float)uni;
 }
 
 // A wave's view of the slab and of its LDS tile: wave-uniform but for the lane's own place in the staging walk.

@@ -318,6 +318,73 @@ class FlatGpu:
         return collection._multi_vector_results(qv[1], candidates, metric, limit)
 
 
+    # ---- MMR on the resident rows (flat_gpu.ex: rerank/3, mmr_search/3).  None: this handle does not serve it (its rows
+    # are spread over several devices) and the collection composes the call itself.
+    _MMR_ATOMS = {"invalid mmr args": "invalid_mmr_args", "metric overflow": "metric_overflow"}
+
+    @staticmethod
+    def _mmr_error(res):
+        return ("error", FlatGpu._MMR_ATOMS.get(res[1], res[1]))
+
+    @staticmethod
+    def rerank(collection, initial, alpha, limit):
+        """Vettore.rerank/4 (lib/vettore.ex:622-640) without all/1: the initial list's rows are read where they lie."""
+        if nifs.flat_shard_count(collection.index_state) > 1:
+            return None
+        res = nifs.flat_mmr_rerank(collection.index_state, initial, alpha, limit)
+        return res if res[0] == "ok" else FlatGpu._mmr_error(res)
+
+    @staticmethod
+    def _mmr_options(opts):
+        lc = FlatGpu._limit_and_candidates(opts)
+        if lc[0] != "ok":
+            return lc
+        alpha = opts.get("alpha", 0.5)
+        if not (isinstance(alpha, (int, float)) and not isinstance(alpha, bool) and 0 <= alpha <= 1):
+            return ("error", "invalid_mmr_args")                              # vettore_distance.ex:334-345
+        return ("ok", lc[1], lc[2], alpha)
+
+    @staticmethod
+    def _mmr_results(collection, hits, order):
+        out: List[Result] = []
+        for i in order:
+            out.extend(_to_result(collection, hits[i][0], hits[i][1]))
+        return out
+
+    @staticmethod
+    def mmr_search(collection, query, opts=None):
+        """search(limit: candidates), then rerank(limit: limit, alpha: alpha) over its (id, score) pairs, as one call."""
+        if nifs.flat_shard_count(collection.index_state) > 1:
+            return None
+        mo = FlatGpu._mmr_options({} if opts is None else opts)
+        if mo[0] != "ok":
+            return mo
+        q = collection.prepare_query(query)
+        if q[0] != "ok":
+            return q
+        res = nifs.flat_mmr_search(collection.index_state, q[1], mo[2], mo[1], mo[3], collection.score)
+        return FlatGpu._mmr_error(res) if res[0] != "ok" else ("ok", FlatGpu._mmr_results(collection, *res[1]))
+
+    @staticmethod
+    def mmr_search_batch(collection, queries, opts=None):
+        """mmr_search for a list of queries, one call: ("ok", [("ok", [Result]) | ("error", reason) per query])."""
+        if nifs.flat_shard_count(collection.index_state) > 1:
+            return None
+        mo = FlatGpu._mmr_options({} if opts is None else opts)
+        if mo[0] != "ok":
+            return mo
+        prepared = FlatGpu._prepare_all(collection, queries)
+        if prepared[0] != "ok":
+            return prepared
+        if not prepared[1]:
+            return ("ok", [])
+        res = nifs.flat_mmr_search_batch(collection.index_state, prepared[1], mo[2], mo[1], mo[3], collection.score)
+        if res[0] != "ok":
+            return FlatGpu._mmr_error(res)
+        return ("ok", [("ok", FlatGpu._mmr_results(collection, *r[1])) if r[0] == "ok" else FlatGpu._mmr_error(r)
+                       for r in res[1]])
+
+
 def _valid_size(v):
     return isinstance(v, int) and not isinstance(v, bool) and 0 < v <= MAX_NIF_USIZE
 

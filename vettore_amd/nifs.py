@@ -981,6 +981,187 @@ def flat_batch_shadow(index: FlatRef) -> str:
     return _lib.SHADOW_STATE.get(int(_lib.load().vt_flat_batch_shadow(index.handle)), "?")
 
 
+# ----------------------------------------------------------------- MMR reranking
+_MMR_INVALID = ("error", "invalid_mmr_args")
+_MMR_ARGS = 38  # VT_ERR_MMR_ARGS
+_SCORE_MODE = {"raw": 0, "similarity": 1}
+
+
+def _is_number(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def _finite_number(v) -> bool:
+    """finite_number?/1 (lib/vettore_distance.ex:407-414): an integer or a float within the f32 range."""
+    return _is_number(v) and -_F32_MAX <= v <= _F32_MAX
+
+
+def _is_binary(v) -> bool:
+    return isinstance(v, (bytes, bytearray, str))
+
+
+def _mmr_guards(alpha, final_k) -> bool:
+    return (_is_number(alpha) and 0 <= alpha <= 1 and isinstance(final_k, int) and not isinstance(final_k, bool)
+            and final_k > 0)
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def mmr_rerank(initial, embeddings, metric, alpha, final_k):
+    """`Vettore.Distance.mmr_rerank/5` (lib/vettore_distance.ex:334-519) with the reference's validation order and atoms:
+    ("ok", [(id, score)]) -- the chosen entries of `initial`, the caller's own objects, in order of choice --,
+    ("error", "invalid_mmr_args"), ("error", ("unknown_metric", metric)) or ("error", "metric_overflow").  The rounds run
+    on the device (vt_mmr_rerank): the vectors of the initial entries go up once, nothing but the order comes back."""
+    if not (isinstance(initial, list) and isinstance(embeddings, list) and _mmr_guards(alpha, final_k)):
+        return _MMR_INVALID
+    if not (isinstance(metric, str) and metric in METRIC_CODE):
+        return ("error", ("unknown_metric", metric))
+    vectors, expected = {}, None
+    for embedding in embeddings:  # validate_mmr_embeddings (:347-387)
+        if not (isinstance(embedding, tuple) and len(embedding) == 2):
+            return _MMR_INVALID
+        id_, vector = embedding
+        if not (_is_binary(id_) and len(id_) > 0 and isinstance(vector, list) and vector != []):
+            return _MMR_INVALID
+        if id_ in vectors or expected not in (None, len(vector)) or not all(_finite_number(v) for v in vector):
+            return _MMR_INVALID
+        vectors[id_] = vector
+        expected = expected or len(vector)
+    seen = set()
+    for entry in initial:  # validate_mmr_initial (:389-405)
+        if not (isinstance(entry, tuple) and len(entry) == 2 and _is_binary(entry[0]) and len(entry[0]) > 0):
+            return _MMR_INVALID
+        id_, score = entry
+        if not (_finite_number(score) and id_ in vectors and id_ not in seen):
+            return _MMR_INVALID
+        seen.add(id_)
+    n = len(initial)
+    if n == 0:
+        return ("ok", [])
+    rows = np.ascontiguousarray(np.array([[float(v) for v in vectors[id_]] for id_, _ in initial], dtype=np.float64)
+                                .astype(np.float32))
+    scores = np.ascontiguousarray(np.array([float(s) for _, s in initial], dtype=np.float64))
+    order = np.zeros(n, dtype=np.uint32)
+    count = C.c_size_t()
+    st = _lib.load().vt_mmr_rerank(DEVICE, METRIC_CODE[metric], n, rows.shape[1], _fp(rows.reshape(-1)), _f64p(scores),
+                                   float(alpha), min(final_k, n), _u32p(order), C.byref(count))
+    if st == 4:
+        return ("error", "metric_overflow")
+    if st != 0:
+        return _err(st)
+    return ("ok", [initial[int(i)] for i in order[:count.value]])
+
+
+def flat_mmr_rerank(index: FlatRef, initial, alpha, final_k):
+    """mmr_rerank over the rows resident in `index` (one shard), under its metric: `initial` is [(id, score)];
+    ("ok", [(id, score)]) -- the caller's entries in order of choice --, or ("error", reason) with the library's strings
+    ("invalid mmr args": a bad alpha, final_k or score, an id that is not in the index or occurs twice; "metric
+    overflow")."""
+    if not (isinstance(initial, list) and _mmr_guards(alpha, final_k)
+            and all(isinstance(e, tuple) and len(e) == 2 and _is_binary(e[0]) and _finite_number(e[1]) for e in initial)):
+        return _err(_MMR_ARGS)
+    n = len(initial)
+    ids, off = _pack_ids(e[0] for e in initial)
+    scores = np.ascontiguousarray(np.array([float(e[1]) for e in initial], dtype=np.float64))
+    order = np.zeros(max(n, 1), dtype=np.uint32)
+    count = C.c_size_t()
+    st = _lib.load().vt_flat_mmr_rerank(index.handle, n, ids, _szp(off), _f64p(scores), float(alpha), min(final_k, max(n, 1)),
+                                        _u32p(order), C.byref(count))
+    if st != 0:
+        return _err(st)
+    return ("ok", [initial[int(i)] for i in order[:count.value]])
+
+
+def flat_mmr_rerank_batch(index: FlatRef, problems):
+    """Extension: flat_mmr_rerank for every (initial, alpha, final_k) of `problems` in one call, all of them one chain
+    of step launches: [("ok", [(id, score)]) | ("error", reason)] per problem, each what flat_mmr_rerank returns for it
+    alone; ("error", reason) when the call itself fails."""
+    results = [None] * len(problems)
+    live = []
+    for p, (initial, alpha, final_k) in enumerate(problems):
+        if not (isinstance(initial, list) and _mmr_guards(alpha, final_k)
+                and all(isinstance(e, tuple) and len(e) == 2 and _is_binary(e[0]) and _finite_number(e[1]) for e in initial)):
+            results[p] = _err(_MMR_ARGS)
+        else:
+            live.append(p)
+    entries = [e for p in live for e in problems[p][0]]
+    prob_off = np.zeros(len(live) + 1, dtype=np.uintp)
+    if live:
+        prob_off[1:] = np.cumsum([len(problems[p][0]) for p in live])
+    ids, off = _pack_ids(e[0] for e in entries)
+    scores = np.ascontiguousarray(np.array([float(e[1]) for e in entries] or [0.0], dtype=np.float64))
+    alphas = np.ascontiguousarray(np.array([float(problems[p][1]) for p in live] or [0.0], dtype=np.float64))
+    ks = np.array([min(problems[p][2], max(len(problems[p][0]), 1)) for p in live] or [1], dtype=np.uintp)
+    order = np.zeros(max(len(entries), 1), dtype=np.uint32)
+    counts = np.zeros(max(len(live), 1), dtype=np.uintp)
+    status = (C.c_int * max(len(live), 1))()
+    st = _lib.load().vt_flat_mmr_rerank_batch(index.handle, len(live), _szp(prob_off), ids, _szp(off), _f64p(scores),
+                                              _f64p(alphas), _szp(ks), _u32p(order), _szp(counts), status)
+    if st != 0:
+        return _err(st)
+    for j, p in enumerate(live):
+        base = int(prob_off[j])
+        results[p] = (("ok", [problems[p][0][int(i)] for i in order[base:base + int(counts[j])]]) if status[j] == 0
+                      else _err(status[j]))
+    return results
+
+
+def _mmr_search_args(candidates, limit, alpha, score_mode):
+    if not isinstance(candidates, int) or candidates < 0 or candidates > USIZE_MAX:
+        raise TypeError("badarg: candidates must fit usize")
+    if score_mode not in _SCORE_MODE:
+        raise TypeError("badarg: score_mode must be \"raw\" or \"similarity\"")
+    return _mmr_guards(alpha, limit)
+
+
+def flat_mmr_search(index: FlatRef, query, candidates: int, limit: int, alpha, score_mode: str = "raw"):
+    """Extension: flat_search(query, candidates), then MMR over its hits -- scored by result_values/3 for `score_mode` --
+    down to `limit`, in one call under one lease: ("ok", (hits, order)) with `hits` exactly flat_search's and `order`
+    the chosen hits' indices in order of choice; or ("error", reason)."""
+    if not _mmr_search_args(candidates, limit, alpha, score_mode):
+        return _err(_MMR_ARGS)
+    q = _f32_list(query)
+    cap = max(1, min(limit, candidates))
+    order = np.zeros(cap, dtype=np.uint32)
+    count = C.c_size_t()
+    h = C.c_void_p()
+    st = _lib.load().vt_flat_mmr_search(index.handle, _fp(q), q.size, candidates, min(limit, USIZE_MAX), float(alpha),
+                                        _SCORE_MODE[score_mode], C.byref(h), _u32p(order), C.byref(count))
+    if st != 0:
+        return _err(st)
+    return ("ok", (_take_hits(h), [int(i) for i in order[:count.value]]))
+
+
+def flat_mmr_search_batch(index: FlatRef, queries, candidates: int, limit: int, alpha, score_mode: str = "raw"):
+    """flat_mmr_search for every row of the [nq][d] matrix `queries` in one call, all queries one chain of step
+    launches: ("ok", [("ok", (hits, order)) | ("error", reason) per query]), or ("error", reason) when the call itself
+    fails (a search error, bad arguments)."""
+    if not _mmr_search_args(candidates, limit, alpha, score_mode):
+        return _err(_MMR_ARGS)
+    q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+    if q.ndim != 2:
+        raise TypeError("badarg: queries must be a matrix")
+    nq, d = q.shape
+    cap = max(1, min(limit, candidates))
+    outs, status = (C.c_void_p * max(nq, 1))(), (C.c_int * max(nq, 1))()
+    order = np.zeros(max(nq, 1) * cap, dtype=np.uint32)
+    counts = np.zeros(max(nq, 1), dtype=np.uintp)
+    st = _lib.load().vt_flat_mmr_search_batch(index.handle, _fp(q.reshape(-1)), nq, d, candidates, min(limit, USIZE_MAX),
+                                              float(alpha), _SCORE_MODE[score_mode], outs, _u32p(order), _szp(counts), status)
+    lists = [_take_hits(C.c_void_p(outs[b])) if outs[b] else None for b in range(nq)]
+    if st != 0:
+        return _err(st)
+    cap = min(limit, candidates)
+    return ("ok", [("ok", (lists[b], [int(i) for i in order[b * cap:b * cap + int(counts[b])]])) if status[b] == 0
+                   else _err(status[b]) for b in range(nq)])
+
+
 def set_default_reduce_order(order: int):
     st = _lib.load().vt_set_default_reduce_order(order)
     return "ok" if st == 0 else _err(st)
