@@ -51,9 +51,9 @@ NOSCRATCH_vt_maxsim_resident := maxsim_resident_kernel
 NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 # K10 (MUVERA): one lane's f64 chain per dot product, nothing indexed dynamically in registers
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
-# K1q, K1s and K1f (the int8, 6-bit and 5-bit sketch passes): the register ring must stay in registers; its tail (one block behind every pass) likewise
-# carries no scratch segment
-NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel
+# K1q, K1s and K1f (the int8, 6-bit and 5-bit sketch passes): the register ring must stay in registers; K1q's tail and the
+# threshold and collect kernels behind the other two likewise carry no scratch segment
+NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_thresh_kernel sketch_collect_kernel
 NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
 NOSCRATCH_vt_sketch5      := sketch5_scan_kernel
 # K1s's pass branches three ways per run on wave-uniform cursors.  By default the CFG structurizer lays the three arms out in

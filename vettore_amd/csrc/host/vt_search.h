@@ -341,8 +341,9 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   return VT_OK;
 }
 
-// K1s, one host wait: blit, the 6-bit pass, the tail in its certify-only mode, the gathered K1 over the candidate rows it
-// left (the count read on the device: none when the pass did not certify) and K1's select, all queued before the wait.
+// K1s, one host wait: blit, the 6-bit pass, the certification spread over the card (the threshold kernel, the collect
+// kernel), the gathered K1 over the candidate rows they left (the count read on the device: none when the pass did not
+// certify) and K1's select, all queued before the wait.
 // *done as sketch_search has it; a pass that does not certify counts towards the shard's miss limit.
 // `five`: K1f, the same chain over the 5-bit sketch (its pass, its bound of the level kept off the L plane, its longer
 // candidate list, more blocks for the gathered K1, its own counters and misses).
@@ -381,6 +382,9 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   DevBuf<uint32_t> &cand_rows = five ? c.dSk5Rows : c.dSk6Rows;
   VT_TRY(cand_rows.ensure(cand_cap));
   VT_TRY(c.dSkCount.ensure(1));
+  const uint32_t thresh_blocks = vt::sketch_thresh_blocks(blocks, kp);
+  VT_TRY(c.dSkParts.ensure((size_t)thresh_blocks * (k + 1)));
+  VT_TRY(c.dSkSync.ensure(4));
   VT_TRY(c.hSkInfo.ensure(4));
   VT_TRY(c.ensure_part_lists((size_t)rescore_blocks * k));
   uint32_t *info = c.hSkInfo.mapped();
@@ -417,29 +421,22 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   VT_TRY(c.mark_begin());
   VT_HIP((five ? vt::launch_sketch5_scan : vt::launch_sketch6_scan)(a, blocks, c.stream));
   VT_TRY(c.mark_end());
-  vt::SketchTailArgs ta{};
-  ta.keys = c.dSkKeys.p;
+  vt::SketchSpreadArgs ta{};
+  ta.lo_words = c.dSkLoWords.p;
+  ta.hi_words = c.dSkHiWords.p;
   ta.pay = c.dSkPay.p;
   ta.lists = blocks;
   ta.kp = kp;
   ta.k = k;
   ta.cap = cand_cap;
+  ta.parts = c.dSkParts.p;
+  ta.live = c.dSkParts.p + (size_t)thresh_blocks * k;
+  ta.sync = c.dSkSync.p;
   ta.rows = cand_rows.p;
   ta.count = c.dSkCount.p;
   ta.info = info;
-  ta.X = ix->dX;
-  ta.stride = ld;
-  ta.q = c.qsrc;
-  ta.id_rank = ix->dRank.p;
-  ta.d = d;
-  ta.metric = ix->metric;
-  ta.order = ix->order;
-  ta.status = c.dStatus.p;
-  ta.out = c.dResMapped;
-  ta.certify_only = 1;
-  ta.lo_words = c.dSkLoWords.p;
-  ta.hi_words = c.dSkHiWords.p;
-  VT_HIP(vt::launch_sketch_tail(ta, c.stream));
+  VT_HIP(vt::launch_sketch_thresh(ta, c.stream));
+  VT_HIP(vt::launch_sketch_collect(ta, c.stream));
   vt::ScanArgs sa = scan_args(ix, c, d);
   set_gather(sa, gather_of(cand_rows.p), cand_cap);  // (the list's room: the count is batch_counts[0])
   sa.k = k;
@@ -482,7 +479,7 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   return VT_OK;
 }
 
-// K1f: blit, the 5-bit pass, the certify-only tail, the gathered K1 and its select behind one host wait.
+// K1f: blit, the 5-bit pass, the threshold and collect kernels, the gathered K1 and its select behind one host wait.
 int sketch5_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
   return sketch6_search(ix, c, query, limit, done, out, true);
 }

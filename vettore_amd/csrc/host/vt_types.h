@@ -57,6 +57,8 @@ struct Ctx {
   std::vector<double> hSkResid;
   DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
   DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
+  DevBuf<uint32_t> dSkParts;  // K1s / K1f: the threshold kernel's k smallest words per block, then its live counts
+  DevBuf<uint32_t> dSkSync;   // the collect kernel's claim, fail and ticket words (16 bytes, zeroed by the threshold kernel)
   DevBuf<uint32_t> dSk5Rows;  // K1f (sketch5_search): its candidate list, a row for every retained slot
   // K12 (vt_mmr.h, mmr_run): a call's problems, per-candidate arrays and block partials; what goes up and what comes back
   // travel through the two pinned blocks (grow, never shrink: no allocation per call)

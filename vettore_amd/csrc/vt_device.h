@@ -784,7 +784,7 @@ hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStrea
 
 // One block over the lists of launch_sketch_scan: Kt = the k-th smallest key(lo) retained; every retained row whose
 // key(hi) <= Kt is a candidate; certified iff they number at most `cap` and no list consists of candidates alone (a
-// full list whose largest key(hi) is <= Kt).  info = {outcome, candidates, Kt bits, 1 if the word arrays were read} (host-mapped), outcome
+// full list whose largest key(hi) is <= Kt).  K1q's tail.  info = {outcome, candidates, Kt bits, 0} (host-mapped), outcome
 //   1: certified, and the block rescored the candidates itself with K1's arithmetic (X, q, order, metric; *status
 //      raised like K1's) and wrote the k best, sorted, with the status word into *out like launch_select -- taken when
 //      they are few enough for its LDS (at most 256);
@@ -806,16 +806,31 @@ struct SketchTailArgs {
   int *status;
   ResultBlock *out;
   uint32_t ld, ss, lds_words;  // set by the launcher
-  // certify only: Kt, the candidate rows, their count and the full-list check as ever, but the block never rescores
-  // (outcome 2 or 0): the caller has queued the gathered K1 and its select behind this kernel already (K1s)
-  uint32_t certify_only;
-  // launch_sketch6_scan's word arrays ([lists][kp] each; kp even), or both null: the sweeps then read keys and pay.  With
-  // them the first sweep reads lo_words alone and stages their upper halves in LDS, the filing sweep compares the staged
-  // halves and reads again only the words it files, the collect reads hi_words and a candidate's pay[i].row.  Taken when
-  // the halves fit the block's LDS (info[3] = 1 then); Kt, the candidates and the full-list check are the ones the lists give.
-  const uint32_t *lo_words, *hi_words;
 };
 hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s);
+
+// The same certification behind K1s's and K1f's passes, spread over the card in two launches (vt_sketch.hip): Kt, the
+// candidates, their count and the full-list check are the ones launch_sketch_tail would give; nothing is rescored (the
+// caller queues the gathered K1 and its select behind).  launch_sketch_thresh: every block's k smallest key(lo) words
+// to parts[], its live words to live[], and the three words of sync[] to zero.  launch_sketch_collect: Kt from parts[],
+// the rows of the candidates (key(hi) <= Kt) to rows[] in no particular order, and from the block that finishes last
+// *count (0 unless certified) and info = {2 if certified else 0, candidates, Kt bits, 1}.  Both take the same arguments.
+struct SketchSpreadArgs {
+  // launch_sketch6_scan's / launch_sketch5_scan's word arrays and payloads ([lists][kp] each)
+  const uint32_t *lo_words, *hi_words;
+  const Payload *pay;
+  uint32_t lists, kp, k, cap;
+  uint32_t *parts;          // [sketch_thresh_blocks(lists, kp)][k]
+  uint32_t *live;           // [sketch_thresh_blocks(lists, kp)]
+  uint32_t *sync;           // {claim, fail, ticket, -}: a 16-byte block of its own
+  uint32_t *rows;           // [cap]
+  uint32_t *count;
+  uint32_t *info;           // [4] (host-mapped)
+  uint32_t thresh_blocks, collect_blocks, collect_lists;  // set by the launchers
+};
+uint32_t sketch_thresh_blocks(uint32_t lists, uint32_t kp);
+hipError_t launch_sketch_thresh(SketchSpreadArgs a, hipStream_t s);
+hipError_t launch_sketch_collect(SketchSpreadArgs a, hipStream_t s);
 
 // ---- K1s (vt_sketch.hip): the same search over a 6-bit sketch in two planes -- 0.755 of K1q's bytes ------------------
 // Row r is kept as X_r = round(x_r / s_r) in [-31, 31] with s_r = max_i |x_ri| / 31, split as X = 4 H + L: H = X >> 2
@@ -852,10 +867,10 @@ struct Sketch6ScanArgs {
   // w3 = 1.5 t3 ||Q3||_1 to e_r; both products are exact in f64.
   double c3, w3;
   uint32_t k;               // entries per block list
-  uint64_t *part_keys;      // [blocks][k], as launch_sketch_scan writes them: launch_sketch_tail reads either
+  uint64_t *part_keys;      // [blocks][k], as launch_sketch_scan writes them
   Payload *part_pay;
   // [blocks][k] each, beside the lists: a slot's orderable key(lo) word and its orderable key(hi) word, 0xffffffff in both
-  // for an empty slot -- what launch_sketch_tail's certify-only sweeps read in place of the lists themselves
+  // for an empty slot -- what launch_sketch_thresh and launch_sketch_collect read in place of the lists themselves
   uint32_t *lo_words, *hi_words;
 };
 // k <= kSmallK and ld8 >= 256 (a tile of ld8 = 128 is shorter than the load ring: K1q serves those); 0: not supported

@@ -197,25 +197,17 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch_scan_kernel(cons
   if (wib == 0) tk.store(a.part_keys + (size_t)blockIdx.x * a.k, a.part_pay + (size_t)blockIdx.x * a.k, lane);
 }
 
-// ---- the tail: certification and, for a short candidate list, the exact rescoring and the final select ---------------
-// One block.  Kt is the k-th smallest retained key(lo), exactly DESIGN 4.10's threshold.  One sweep of independent
-// loads stages the key(lo) words in LDS when lists * k' of them fit (104 KB at the headline; otherwise later sweeps read
+// ---- K1q's tail: certification and, for a short candidate list, the exact rescoring and the final select -------------
+// One block (K1s and K1f spread the same certification over the card: sketch_thresh_kernel and sketch_collect_kernel
+// below).  Kt is the k-th smallest retained key(lo), exactly DESIGN 4.10's threshold.  One sweep of independent loads stages the key(lo) words in LDS when lists * k' of them fit (104 KB at the headline; otherwise later sweeps read
 // global memory again) and leaves every thread the smallest of its own; an empty slot counts as 0xffffffff.  The k-th
 // smallest of those 1 024 minima is located to its top 16 bits by two 8-bit radix passes over one word per thread; U is
 // that bin's upper end.  k distinct entries are <= U, so the entries <= U hold the k smallest of all: they are filed and
 // Kt is their k-th smallest by counting (at most 1 024; when more tie around the k-th, Kt is found by four radix passes
-// over every word instead).  With k or fewer live entries
-// Kt is the maximum.  The collect is one more sweep of independent loads over the 64-bit keys, its counters (all the
+// over every word instead).  With k or fewer live entries Kt is the maximum.  The collect is one more sweep of independent loads over the 64-bit keys, its counters (all the
 // candidates; each list's own, exact) raised once per wave, not once per candidate; a list is refused when
 // every one of its k' slots is a candidate (it is full and its largest key(hi) is <= Kt: it may have dropped a row that
 // matters).
-// Behind K1s's pass the lists' words arrive a second time as two plain arrays (SketchTailArgs::lo_words / hi_words), and
-// the sweeps read those: the first the key(lo) words alone, staging their upper halves (two a dword: lists * k' / 2
-// dwords of LDS, 128 KB at the headline); U ends in 0xffff, so the filing sweep compares the staged halves and reads
-// again only the words it files; the collect reads the key(hi) words and a candidate's pay[i].row.  Kt, the candidate set,
-// the count and the full-list check are the ones the lists give.  (A thread owns the slot pairs
-// (2 i, 2 i + 1) here, not the slots tid + 1024 j, so the 1 024 minima, U and the entries <= U are other ones; Kt is not.)
-// info[3] says which path ran (1: the word arrays).
 // Up to kTailFuseMax candidates whose chunk sums fit the same LDS are then rescored here with K1's arithmetic: a wave
 // per row, a lane pair per 8-float chunk (elem4 / chunk_sum of vt_scan.cuh in the index's reduce order), the sums to an
 // LDS row, and one thread per candidate walks its row's sums in order -- the reference's sequential chain -- then the
@@ -256,6 +248,39 @@ __device__ __forceinline__ uint32_t wave_claim(uint32_t *counter, bool on, int l
   return base + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
 }
 
+// Wave 0 of a block, after a radix digit's histogram (256 bins): the bin that holds the *remaining-th smallest of this
+// digit joins *prefix_out, and *remaining becomes the rank inside that bin (four bins per lane, one wave scan).
+__device__ __forceinline__ void radix_pick_bin(const uint32_t *hist, uint32_t *prefix_out, uint32_t *remaining, uint32_t prefix,
+                                               int shift, int lane) {
+  const uint32_t krem = *remaining;
+  const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
+  const uint32_t sum = h0 + h1 + h2 + h3;
+  uint32_t incl = sum;
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const uint32_t t = (uint32_t)__shfl_up((int)incl, o, kWave);
+    if (lane >= o) incl += t;
+  }
+  uint32_t cum = incl - sum;
+  if (cum < krem && krem <= incl) {
+    uint32_t b = 0;
+    if (cum + h0 < krem) {
+      cum += h0;
+      b = 1;
+      if (cum + h1 < krem) {
+        cum += h1;
+        b = 2;
+        if (cum + h2 < krem) {
+          cum += h2;
+          b = 3;
+        }
+      }
+    }
+    *remaining = krem - cum;
+    *prefix_out = prefix | ((4u * (uint32_t)lane + b) << shift);
+  }
+}
+
 __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchTailArgs a) {
   extern __shared__ __align__(16) uint32_t dyn[];  // the key(lo) words; once Kt is known: per-list counts, chunk sums
   __shared__ uint32_t hist[256];
@@ -279,90 +304,31 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   }
   __syncthreads();
   constexpr uint32_t kUnroll = 8;
-  // the scan's word arrays in place of its lists (SketchTailArgs): dyn holds the key(lo) words' upper halves, two a dword
-  const bool words = a.lo_words && a.hi_words && !(m & 1u) && m / 2 <= a.lds_words;
-  const uint32_t m2 = m / 2;
   uint32_t mine = 0xffffffffu;  // the smallest key(lo) word among this thread's entries
-  if (words) {
-    uint32_t live = 0;
-    const uint2 *lo2 = reinterpret_cast<const uint2 *>(a.lo_words);
-    for (uint32_t b = tid; b < m2; b += kUnroll * kTailThreads) {
-      uint2 v[kUnroll];
+  uint32_t live = 0;
+  for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
+    uint64_t key[kUnroll];
+    float raw[kUnroll];
 #pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = b + u * kTailThreads;
-        v[u] = i < m2 ? lo2[i] : make_uint2(0xffffffffu, 0xffffffffu);
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = b + u * kTailThreads;
-        live += (v[u].x != 0xffffffffu ? 1u : 0u) + (v[u].y != 0xffffffffu ? 1u : 0u);
-        const uint32_t lo = v[u].x < v[u].y ? v[u].x : v[u].y;
-        mine = lo < mine ? lo : mine;
-        if (i < m2) dyn[i] = (v[u].x >> 16) | (v[u].y & 0xffff0000u);
-      }
+    for (uint32_t u = 0; u < kUnroll; ++u) {
+      const uint32_t i = b + u * kTailThreads;
+      key[u] = i < m ? a.keys[i] : kEmptyKey;
+      raw[u] = i < m ? a.pay[i].raw : 0.0f;  // (an empty slot's payload was never written: loaded, not used)
     }
-    live = wave_sum_u(live);
-    if (lane == 0 && live) atomicAdd(&s_total, live);
-  } else {
-    uint32_t live = 0;
-    for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
-      uint64_t key[kUnroll];
-      float raw[kUnroll];
 #pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = b + u * kTailThreads;
-        key[u] = i < m ? a.keys[i] : kEmptyKey;
-        raw[u] = i < m ? a.pay[i].raw : 0.0f;  // (an empty slot's payload was never written: loaded, not used)
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = b + u * kTailThreads;
-        const uint32_t v = key[u] == kEmptyKey ? 0xffffffffu : orderable(raw[u]);
-        live += key[u] != kEmptyKey ? 1u : 0u;
-        mine = v < mine ? v : mine;
-        if (i < m && in_lds) dyn[i] = v;
-      }
+    for (uint32_t u = 0; u < kUnroll; ++u) {
+      const uint32_t i = b + u * kTailThreads;
+      const uint32_t v = key[u] == kEmptyKey ? 0xffffffffu : orderable(raw[u]);
+      live += key[u] != kEmptyKey ? 1u : 0u;
+      mine = v < mine ? v : mine;
+      if (i < m && in_lds) dyn[i] = v;
     }
-    live = wave_sum_u(live);
-    if (lane == 0 && live) atomicAdd(&s_total, live);
   }
+  live = wave_sum_u(live);
+  if (lane == 0 && live) atomicAdd(&s_total, live);
   // U = the upper end of the 16-bit bin that holds the k-th smallest of the 1 024 threads' minima (k <= 256): k distinct
   // entries are <= U, so Kt <= U, and the entries <= U -- a few more than k unless hundreds tie -- hold the k smallest
   // of all.  Two radix passes over one word per thread, in place of four over all lists * k' words.
-  // wave 0, after a digit's histogram: the bin that holds the s_remaining-th smallest of this digit joins s_prefix (four
-  // bins per lane, one wave scan)
-  auto pick_bin = [&](uint32_t prefix, int shift) {
-    {  // (wave 0)
-      const uint32_t krem = s_remaining;
-      const uint32_t h0 = hist[4 * lane], h1 = hist[4 * lane + 1], h2 = hist[4 * lane + 2], h3 = hist[4 * lane + 3];
-      const uint32_t sum = h0 + h1 + h2 + h3;
-      uint32_t incl = sum;
-#pragma unroll
-      for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o, kWave);
-        if (lane >= o) incl += t;
-      }
-      uint32_t cum = incl - sum;
-      if (cum < krem && krem <= incl) {
-        uint32_t b = 0;
-        if (cum + h0 < krem) {
-          cum += h0;
-          b = 1;
-          if (cum + h1 < krem) {
-            cum += h1;
-            b = 2;
-            if (cum + h2 < krem) {
-              cum += h2;
-              b = 3;
-            }
-          }
-        }
-        s_remaining = krem - cum;
-        s_prefix = prefix | ((4u * (uint32_t)lane + b) << shift);
-      }
-    }
-  };
   uint32_t mask = 0;
   for (int pass = 0; pass < 2; ++pass) {
     const int shift = 24 - 8 * pass;
@@ -371,7 +337,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
     const uint32_t prefix = s_prefix;
     hist_add(hist, (mine & mask) == prefix, (mine >> shift) & 255u, lane);
     __syncthreads();
-    if (w == 0) pick_bin(prefix, shift);
+    if (w == 0) radix_pick_bin(hist, &s_prefix, &s_remaining, prefix, shift, lane);
     mask |= 255u << shift;
     __syncthreads();
   }
@@ -379,29 +345,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   uint32_t kt = 0xffffffffu;  // (k or fewer entries in all: every one is a candidate)
   if (s_total > a.k) {
     const uint32_t ub = s_prefix | 0xffffu;
-    // (ub ends in 0xffff: a word's upper half decides; only the words filed are read again)
-    for (uint32_t b = tid; words && b < m2; b += kUnroll * kTailThreads) {
-      uint32_t h[kUnroll];
-#pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = b + u * kTailThreads;
-        h[u] = i < m2 ? dyn[i] : 0xffffffffu;
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < kUnroll; ++u) {
-        const uint32_t i = b + u * kTailThreads;
-#pragma unroll
-        for (uint32_t e = 0; e < 2; ++e) {
-          const uint32_t half = e ? h[u] >> 16 : h[u] & 0xffffu;
-          if (i < m2 && half <= (ub >> 16)) {
-            const uint32_t v = a.lo_words[2 * i + e];
-            const uint32_t pos = atomicAdd(&s_nsv, 1u);
-            if (pos < kTailSurvivors) sv[pos] = v;
-          }
-        }
-      }
-    }
-    for (uint32_t b = tid; !words && b < m; b += kUnroll * kTailThreads) {
+    for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
       uint32_t v[kUnroll];
 #pragma unroll
       for (uint32_t u = 0; u < kUnroll; ++u) {
@@ -433,13 +377,11 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
         __syncthreads();
         const uint32_t prefix = s_prefix;
         for (uint32_t i = tid; i < m; i += kTailThreads) {
-          uint32_t v;
-          if (words) v = a.lo_words[i];
-          else v = in_lds ? dyn[i] : (a.keys[i] == kEmptyKey ? 0xffffffffu : orderable(a.pay[i].raw));
+          const uint32_t v = in_lds ? dyn[i] : (a.keys[i] == kEmptyKey ? 0xffffffffu : orderable(a.pay[i].raw));
           hist_add(hist, (v & rmask) == prefix, (v >> shift) & 255u, lane);
         }
         __syncthreads();
-        if (w == 0) pick_bin(prefix, shift);
+        if (w == 0) radix_pick_bin(hist, &s_prefix, &s_remaining, prefix, shift, lane);
         rmask |= 255u << shift;
         __syncthreads();
       }
@@ -462,27 +404,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   const uint32_t lists4 = (a.lists + 3u) & ~3u;
   for (uint32_t l = tid; l < a.lists; l += kTailThreads) dyn[l] = 0;
   __syncthreads();
-  for (uint32_t b = tid; words && b < m; b += kUnroll * kTailThreads) {
-    uint32_t h[kUnroll];
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint32_t i = b + u * kTailThreads;
-      h[u] = i < m ? a.hi_words[i] : 0xffffffffu;
-    }
-#pragma unroll
-    for (uint32_t u = 0; u < kUnroll; ++u) {
-      const uint32_t i = b + u * kTailThreads;
-      const bool cand = h[u] != 0xffffffffu && h[u] <= kt;
-      const uint32_t pos = wave_claim(&s_count, cand, lane);
-      if (cand) {
-        const uint32_t row = a.pay[i].row;
-        if (pos < a.cap) a.rows[pos] = row;
-        if (pos < kTailFuseMax) c_row[pos] = row;
-      }
-      hist_add(dyn, cand, i / a.kp, lane);
-    }
-  }
-  for (uint32_t b = tid; !words && b < m; b += kUnroll * kTailThreads) {
+  for (uint32_t b = tid; b < m; b += kUnroll * kTailThreads) {
     uint64_t key[kUnroll];
 #pragma unroll
     for (uint32_t u = 0; u < kUnroll; ++u) {
@@ -508,14 +430,14 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
   __syncthreads();
   const uint32_t cnt = s_count;
   const bool ok = !s_fail && cnt <= a.cap;
-  const bool fused = ok && !a.certify_only && cnt <= kTailFuseMax && lists4 + cnt * a.ss <= a.lds_words;
+  const bool fused = ok && cnt <= kTailFuseMax && lists4 + cnt * a.ss <= a.lds_words;
   if (!fused) {
     if (tid == 0) {
       *a.count = ok ? cnt : 0u;
       a.info[0] = ok ? 2u : 0u;
       a.info[1] = cnt;
       a.info[2] = kt;
-      a.info[3] = words ? 1u : 0u;
+      a.info[3] = 0u;
     }
     return;
   }
@@ -612,7 +534,181 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
     a.info[0] = 1u;
     a.info[1] = cnt;
     a.info[2] = kt;
-    a.info[3] = words ? 1u : 0u;
+    a.info[3] = 0u;
+  }
+}
+
+// ---- the tail of K1s and K1f, spread over the card: two kernels, Kt across the boundary between them ------------------
+// Behind these passes nothing is rescored by the certifying block (hundreds to tens of thousands of candidates: the
+// gathered K1 and its select are queued behind), and the lists' words arrive a second time as two plain arrays
+// (SketchSpreadArgs::lo_words / hi_words).  One block sweeping lists * k' words three times left the other CUs idle for
+// its whole duration; here every block owns a slice, and nothing waits inside a kernel.
+//   sketch_thresh_kernel   block b: the k smallest key(lo) words of slots [b * kThreshSlots, + kThreshSlots), with
+//                          multiplicity, to parts[b][0..k) in any order, and the slice's live words to live[b].  An empty
+//                          slot (and a slot past the end) counts as 0xffffffff, so a slice with fewer than k live words
+//                          pads with that word.  Four 8-bit radix passes over the thread's own words find the slice's k-th
+//                          smallest word v and how many copies of it belong to the k: the words < v are filed by wave_claim,
+//                          v is written as often as is left.  The k smallest of all the slots are among the slices' k
+//                          smallest, so Kt = the k-th smallest word of parts[], exactly.  Block 0 zeroes the three words
+//                          the collect shares (claim, fail, ticket): every call starts from zero whatever the last one did.
+//   sketch_collect_kernel  every block finds Kt for itself from parts[] (at most a few thousand words, staged in LDS; four
+//                          radix passes; 0xffffffff when k or fewer words are live) -- cheaper than a third kernel --, then
+//                          sweeps the key(hi) words of its own whole lists: a slot is a candidate iff h != 0xffffffff and
+//                          h <= Kt.  The candidates' rows are staged in LDS at places wave_claim hands out on an LDS
+//                          counter; the block then takes ONE returning atomic on the claim word for all of them and
+//                          copies them to rows[base ..) (pos < cap).  One word takes about 88 atomics a us: one per wave
+//                          of the sweep (1 024) would queue for over 10 us, one per block for under 3.  A list whose k'
+//                          slots are all candidates raises the fail word (per-list counts exact, through hist_add).
+// The one exchange inside a launch (kernel guide, Guideline 16): count and info[] need every block's claim.  Each block,
+// its atomics and stores drained by every wave and behind a block barrier, has one lane issue an agent-scope release and
+// draw a ticket with a returning atomic; the block that draws the last one reads the claim total and the fail word through
+// returning agent-scope atomics alone (never a plain load, never the scalar path) and writes *count = ok ? cnt : 0 and
+// info = {ok ? 2 : 0, cnt, Kt, 1}, ok = !fail && cnt <= cap.  Nothing polls: a block that is not last just ends.  The
+// order of rows[] across blocks is whatever the claims make it; the gathered K1 keeps per-block lists and the select
+// orders by (rank key, id rank), so it reaches no result.
+constexpr int kSpreadThreads = 256;
+constexpr uint32_t kThreshSlots = 1024;                                  // a threshold block's slice
+constexpr uint32_t kThreshPer = kThreshSlots / (uint32_t)kSpreadThreads;  // words per thread
+constexpr uint32_t kCollectLists = 16;                                   // whole lists per collect block (more when over kCollectMaxBlocks)
+constexpr uint32_t kCollectMaxBlocks = 256;
+
+__device__ __forceinline__ uint32_t agent_add(uint32_t *p, uint32_t v) {
+  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(kSpreadThreads) void sketch_thresh_kernel(const SketchSpreadArgs a) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_prefix, s_remaining, s_live, s_out;
+  const uint32_t m = a.lists * a.kp;
+  const uint32_t tid = threadIdx.x, base = blockIdx.x * kThreshSlots;
+  const int lane = tid & (kWave - 1), w = tid / kWave;
+  if (blockIdx.x == 0 && tid < 3) __hip_atomic_store(a.sync + tid, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) {
+    s_prefix = 0;
+    s_remaining = a.k;
+    s_live = 0;
+    s_out = 0;
+  }
+  uint32_t v[kThreshPer];
+  uint32_t live = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < kThreshPer; ++u) {
+    const uint32_t i = base + u * kSpreadThreads + tid;
+    v[u] = i < m ? a.lo_words[i] : 0xffffffffu;
+  }
+#pragma unroll
+  for (uint32_t u = 0; u < kThreshPer; ++u) live += v[u] != 0xffffffffu ? 1u : 0u;
+  live = wave_sum_u(live);
+  __syncthreads();
+  if (lane == 0 && live) atomicAdd(&s_live, live);
+  uint32_t mask = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    hist[tid] = 0;
+    __syncthreads();
+    const uint32_t prefix = s_prefix;
+#pragma unroll
+    for (uint32_t u = 0; u < kThreshPer; ++u) hist_add(hist, (v[u] & mask) == prefix, (v[u] >> shift) & 255u, lane);
+    __syncthreads();
+    if (w == 0) radix_pick_bin(hist, &s_prefix, &s_remaining, prefix, shift, lane);
+    mask |= 255u << shift;
+    __syncthreads();
+  }
+  // vk: the slice's k-th smallest word; `need` of its copies belong to the k (k - need words are smaller)
+  const uint32_t vk = s_prefix, need = s_remaining;
+  uint32_t *out = a.parts + (size_t)blockIdx.x * a.k;
+#pragma unroll
+  for (uint32_t u = 0; u < kThreshPer; ++u) {
+    const bool below = v[u] < vk;
+    const uint32_t pos = wave_claim(&s_out, below, lane);
+    if (below && pos < a.k) out[pos] = v[u];
+  }
+  if (tid < need && need <= a.k) out[a.k - need + tid] = vk;
+  if (tid == 0) a.live[blockIdx.x] = s_live;
+}
+
+__global__ __launch_bounds__(kSpreadThreads) void sketch_collect_kernel(const SketchSpreadArgs a) {
+  extern __shared__ __align__(16) uint32_t dyn[];  // parts[] | the block's candidate rows | its lists' candidate counts
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_prefix, s_remaining, s_live, s_n, s_base;
+  const uint32_t tid = threadIdx.x;
+  const int lane = tid & (kWave - 1), w = tid / kWave;
+  const uint32_t np = a.thresh_blocks * a.k;
+  const uint32_t l0 = blockIdx.x * a.collect_lists;
+  const uint32_t nl = a.lists - l0 < a.collect_lists ? a.lists - l0 : a.collect_lists;
+  const uint32_t slots = nl * a.kp, first = l0 * a.kp;
+  uint32_t *pw = dyn, *stage = dyn + ((np + 3u) & ~3u), *lcnt = stage + a.collect_lists * a.kp;
+  if (tid == 0) {
+    s_prefix = 0;
+    s_remaining = a.k;
+    s_live = 0;
+    s_n = 0;
+    s_base = 0;
+  }
+  for (uint32_t l = tid; l < nl; l += kSpreadThreads) lcnt[l] = 0;
+  // Kt from the partial thresholds (plain loads: the kernel boundary has published them)
+  for (uint32_t i = tid; i < np; i += kSpreadThreads) pw[i] = a.parts[i];
+  uint32_t live = 0;
+  for (uint32_t i = tid; i < a.thresh_blocks; i += kSpreadThreads) live += a.live[i];
+  live = wave_sum_u(live);
+  __syncthreads();
+  if (lane == 0 && live) atomicAdd(&s_live, live);
+  __syncthreads();
+  uint32_t kt = 0xffffffffu;  // (k or fewer entries in all: every one is a candidate)
+  if (s_live > a.k) {
+    uint32_t mask = 0;
+    for (int pass = 0; pass < 4; ++pass) {
+      const int shift = 24 - 8 * pass;
+      hist[tid] = 0;
+      __syncthreads();
+      const uint32_t prefix = s_prefix;
+      for (uint32_t b = 0; b < np; b += kSpreadThreads) {  // (whole waves: hist_add votes)
+        const uint32_t i = b + tid;
+        const uint32_t x = i < np ? pw[i] : 0u;
+        hist_add(hist, i < np && (x & mask) == prefix, (x >> shift) & 255u, lane);
+      }
+      __syncthreads();
+      if (w == 0) radix_pick_bin(hist, &s_prefix, &s_remaining, prefix, shift, lane);
+      mask |= 255u << shift;
+      __syncthreads();
+    }
+    kt = s_prefix;
+  }
+  // the block's own lists: candidates' rows to LDS, each list's count
+  for (uint32_t b = 0; b < slots; b += kSpreadThreads) {  // (whole waves: wave_claim and hist_add vote)
+    const uint32_t i = b + tid;
+    const uint32_t h = i < slots ? a.hi_words[first + i] : 0xffffffffu;
+    const bool cand = h != 0xffffffffu && h <= kt;
+    const uint32_t pos = wave_claim(&s_n, cand, lane);
+    if (cand) stage[pos] = a.pay[first + i].row;
+    hist_add(lcnt, cand, i / a.kp, lane);
+  }
+  __syncthreads();
+  const uint32_t n = s_n;
+  if (tid == 0 && n) s_base = agent_add(a.sync + 0, n);  // the block's one claim
+  for (uint32_t l = tid; l < nl; l += kSpreadThreads)
+    if (lcnt[l] == a.kp) __hip_atomic_fetch_or(a.sync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  const uint32_t base = s_base;
+  for (uint32_t j = tid; j < n; j += kSpreadThreads)
+    if (base + j < a.cap) a.rows[base + j] = stage[j];
+  // the ticket: every wave's atomics and stores drained, the barrier, one lane's release, then its draw
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t ticket = agent_add(a.sync + 2, 1u);
+    if (ticket == gridDim.x - 1) {  // every other block has claimed and flagged before it drew
+      const uint32_t cnt = agent_add(a.sync + 0, 0u);
+      const uint32_t fail = __hip_atomic_fetch_or(a.sync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const bool ok = !fail && cnt <= a.cap;
+      *a.count = ok ? cnt : 0u;
+      a.info[0] = ok ? 2u : 0u;
+      a.info[1] = cnt;
+      a.info[2] = kt;
+      a.info[3] = 1u;
+    }
   }
 }
 
@@ -753,6 +849,34 @@ hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s) {
   hipError_t e = allow_lds(sketch_tail_kernel, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sketch_tail_kernel, dim3(1), dim3(kTailThreads), lds, s, a);
+  return hipGetLastError();
+}
+
+uint32_t sketch_thresh_blocks(uint32_t lists, uint32_t kp) { return (lists * kp + kThreshSlots - 1) / kThreshSlots; }
+
+// (the grids and the collect's slice: filled in here, for both launchers alike)
+static bool sketch_spread_shape(SketchSpreadArgs &a, size_t *collect_lds) {
+  if (a.lists == 0 || a.kp == 0 || a.k == 0 || a.k > a.kp || a.k > (uint32_t)kSpreadThreads || !a.lo_words || !a.hi_words || !a.pay ||
+      !a.parts || !a.live || !a.sync || !a.rows || !a.count || !a.info)
+    return false;
+  a.thresh_blocks = sketch_thresh_blocks(a.lists, a.kp);
+  a.collect_lists = std::max(kCollectLists, (a.lists + kCollectMaxBlocks - 1) / kCollectMaxBlocks);
+  a.collect_blocks = (a.lists + a.collect_lists - 1) / a.collect_lists;
+  *collect_lds = ((((size_t)a.thresh_blocks * a.k + 3) & ~(size_t)3) + (size_t)a.collect_lists * a.kp + a.collect_lists) * 4;
+  return *collect_lds <= 48 * 1024;
+}
+
+hipError_t launch_sketch_thresh(SketchSpreadArgs a, hipStream_t s) {
+  size_t lds = 0;
+  if (!sketch_spread_shape(a, &lds)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sketch_thresh_kernel, dim3(a.thresh_blocks), dim3(kSpreadThreads), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sketch_collect(SketchSpreadArgs a, hipStream_t s) {
+  size_t lds = 0;
+  if (!sketch_spread_shape(a, &lds)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(sketch_collect_kernel, dim3(a.collect_blocks), dim3(kSpreadThreads), lds, s, a);
   return hipGetLastError();
 }
 
