@@ -1,5 +1,5 @@
 # Builds the product library (HIP, gfx950 only) and the CPU oracle (tests only).
-#   make            -> vettore_amd/lib/libvettore_hip.so + oracle/libvt_oracle.so
+#   make            -> vettore_amd/lib/libvettore_hip.so + oracle/libvt_oracle.so (+ the tests' own libraries)
 # hipcc cross-compiles for gfx950 without a GPU present.
 ROCM    ?= /opt/rocm
 HIPCC   ?= $(ROCM)/bin/hipcc
@@ -28,7 +28,7 @@ DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_bat
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -118,6 +118,16 @@ $(LIBDIR)/libvt_callers.so: tools/callers_native.cpp include/vettore_flat.h $(LI
 # the same callers bound to the hooks build (tests that force callers to meet: vt_callers_meet with `hold`)
 $(LIBDIR)/libvt_callers_hooks.so: tools/callers_native.cpp include/vettore_flat.h $(LIBDIR)/libvettore_hip_hooks.so
 	g++ -O2 -std=c++17 -fPIC -shared tools/callers_native.cpp -Iinclude -L$(LIBDIR) -lvettore_hip_hooks -lpthread -Wl,-rpath,'$$ORIGIN' -o $@
+
+# The sketch kernels on their own behind a probe (tests/sketch_probe.cpp: builders, passes and the spread certification
+# launched one at a time on a test's arrays; tests/test_gpu_sketch_kernels.py loads it with ctypes): test infrastructure.
+# The three sketch units and the probe, nothing else of the library, and no export map; the package never loads it.
+$(LIBDIR)/sketch_probe.o: tests/sketch_probe.cpp $(CSRC)/vt_device.h $(CSRC)/host/vt_sketch5.h $(CSRC)/host/vt_sketch6.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/sketch_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:
 	$(MAKE) -C oracle -s

@@ -117,3 +117,16 @@ def intervals(X, s, rho, nu, q, split=True):
     tiny = (d + 16.0) * 2.0 ** -125
     e = (qn * rho + eta * nu + kerr * qn * (nu + rho) + 2.0 ** -40 * nu * (qn + eta) + s64 * w3) * ref6.SLACK + tiny
     return a, e
+
+
+def level_bound(Q3, t3):
+    """c3, w3 as host/vt_sketch5.h sketch5_level_bound forms them: 0.5 t3 (P3 + N3) and 0.5 t3 ||Q3||_1."""
+    pos, neg, l1 = level_sums(Q3)
+    half = 0.5 * np.float64(np.float32(t3))
+    return half * float(pos + neg), half * float(l1)
+
+
+def pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3):
+    """sketch5_scan_kernel's two words per row, bit for bit (sketch6_ref.split_pass_words says how); `intervals` above adds
+    c3 in another association and stays the model of the bound, not of the bits."""
+    return ref6.split_pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3, 1)

@@ -126,3 +126,66 @@ def intervals(X, s, rho, nu, q, levels=LEVELS):
     tiny = (d + 16.0) * 2.0 ** -125
     e = (qn * rho + eta * nu + kerr * qn * (nu + rho) + 2.0 ** -40 * nu * (qn + eta)) * SLACK + tiny
     return a, e
+
+
+# ---- the pass's own arithmetic, operation by operation ------------------------------------------------------------------
+# What sketch6_scan_kernel, sketch5_scan_kernel and sketch_scan_kernel do once a row's integer dots are complete, in the
+# kernels' order of operations.  numpy's float64 and float32 are the IEEE formats the device uses and the units are built
+# without contraction, so the words below are the pass's words bit for bit (tests/test_gpu_sketch_kernels.py).
+M_COS, M_IP, M_NIP = 2, 3, 4
+
+
+def f32_up_v(v):
+    """f64 -> f32 towards +inf, element-wise (f32_up of vt_sketch.cuh)."""
+    v = np.asarray(v, np.float64)
+    with np.errstate(over="ignore"):
+        f = v.astype(np.float32)
+    return np.where(f.astype(np.float64) < v, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+
+
+def f32_down_v(v):
+    v = np.asarray(v, np.float64)
+    with np.errstate(over="ignore"):
+        f = v.astype(np.float32)
+    return np.where(f.astype(np.float64) > v, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def orderable(f):
+    """f32::total_cmp as an order-preserving u32 (vt_common.cuh)."""
+    u = np.ascontiguousarray(f, np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def pass_error(d, s, rho, nu, qn, eta, kerr, w3=None):
+    """e_r as the kernels write it: the four terms left to right, s_r w3 behind them where the pass has one, the slack, tiny."""
+    s, rho, nu = (np.asarray(v, np.float32).astype(np.float64) for v in (s, rho, nu))
+    qn, eta, kerr = np.float64(qn), np.float64(eta), np.float64(kerr)
+    tiny = (np.float64(d) + 16.0) * 2.0 ** -125
+    e = qn * rho + eta * nu + kerr * qn * (nu + rho) + 2.0 ** -40 * nu * (qn + eta)
+    if w3 is not None:
+        e = e + s * np.float64(w3)
+    return e * SLACK + tiny
+
+
+def interval_words(metric, av, e):
+    """(orderable key(hi_r) word -- the high half of the list's key --, orderable key(lo_r) word -- the payload's --) from
+    a_r and e_r: f32_up / f32_down, then 1.0f - x or -x in f32."""
+    hi, lo = f32_up_v(av + e), f32_down_v(av - e)
+    if metric == M_COS:
+        first, second = np.float32(1.0) - hi, np.float32(1.0) - lo
+    else:
+        first, second = -hi, -lo
+    return orderable(first), orderable(second)
+
+
+def split_pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3, shift):
+    """The 6-bit (shift = 2) and 5-bit (shift = 1) passes for any integer levels Q [3][d] with scales t:
+    sum = t1 (2^shift H.Q1 + L.Q1) + t2 (2^shift H.Q2 + L.Q2) + t3 (2^shift H.Q3) + c3, left to right; a_r = s_r sum."""
+    X, Q = np.asarray(X, np.int64), np.asarray(Q, np.int64)
+    H = X >> shift
+    t = np.asarray(t, np.float32).astype(np.float64)
+    full = X @ Q[:2].T                                     # 2^shift accH_j + accL_j: the whole of X . Q_j
+    top = (H @ Q[2]) << shift
+    total = t[0] * full[:, 0].astype(np.float64) + t[1] * full[:, 1].astype(np.float64) + t[2] * top.astype(np.float64) + np.float64(c3)
+    av = np.asarray(s, np.float32).astype(np.float64) * total
+    return interval_words(metric, av, pass_error(X.shape[1], s, rho, nu, qn, eta, kerr, w3))

@@ -40,6 +40,19 @@ def intervals(X, s, rho, nu, q):
     return a, e
 
 
+def level_bound(Q3, t3):
+    """c3, w3 as host/vt_search.h forms them for the 6-bit pass: 1.5 t3 (P3 + N3) and 1.5 t3 ||Q3||_1."""
+    pos, neg, l1 = level_sums(Q3)
+    t15 = 1.5 * np.float64(np.float32(t3))
+    return t15 * float(pos + neg), t15 * float(l1)
+
+
+def pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3):
+    """sketch6_scan_kernel's two words per row, bit for bit (sketch6_ref.split_pass_words says how); `intervals` above adds
+    c3 in another association and stays the model of the bound, not of the bits."""
+    return ref.split_pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3, 2)
+
+
 def adversarial_rows(q, n, seed, mirror=False, scale=2.0 ** -9):
     """n rows x = scale * X with X in [-31, 31] chosen so that, for the query q, the term the pass drops sits at an end of
     its range: L = X mod 4 is 3 exactly where Q3 > 0 and 0 where Q3 < 0 (Q3.L = 3 P3, the upper end), or the mirror image
