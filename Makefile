@@ -24,11 +24,11 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_hnsw vt_mmr
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_hnsw vt_mmr
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -51,11 +51,12 @@ NOSCRATCH_vt_maxsim_resident := maxsim_resident_kernel
 NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 # K10 (MUVERA): one lane's f64 chain per dot product, nothing indexed dynamically in registers
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
-# K1q, K1s and K1f (the int8, 6-bit and 5-bit sketch passes): the register ring must stay in registers; K1q's tail and the
-# threshold and collect kernels behind the other two likewise carry no scratch segment
-NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_thresh_kernel sketch_collect_kernel
+# K1q, K1s, K1f and K1n (the int8, 6-bit, 5-bit and 4-bit sketch passes): the register ring must stay in registers; K1q's
+# tail and the threshold, refine and collect kernels behind the other three likewise carry no scratch segment
+NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_thresh_kernel sketch_refine_kernel sketch_collect_kernel
 NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
 NOSCRATCH_vt_sketch5      := sketch5_scan_kernel
+NOSCRATCH_vt_sketch4      := sketch4_scan_kernel
 # K1s's pass branches three ways per run on wave-uniform cursors.  By default the CFG structurizer lays the three arms out in
 # a row behind flags, as it must for divergent branches, and every sum then lives across all arms and is copied in each
 # (about 400 v_mov_b32 per tile at d = 768, profiles/sketch6_loop/isa_counts.txt); told to leave wave-uniform regions as
@@ -67,6 +68,8 @@ NOSCRATCH_vt_sketch5      := sketch5_scan_kernel
 EXTRA_vt_sketch6          := -mllvm -structurizecfg-skip-uniform-regions=true
 # (K1f's pass, the 5-bit sketch: the same loop with another L plane)
 EXTRA_vt_sketch5          := $(EXTRA_vt_sketch6)
+# (K1n's pass, the 4-bit sketch: the same loop with two arms, data and metadata)
+EXTRA_vt_sketch4          := $(EXTRA_vt_sketch6)
 # K11 (HNSW traversals): the distance chains are K9's with the recovery by value; heaps and visited set live in the
 # slot's global scratch, nothing is indexed dynamically in registers -- no scratch segment
 NOSCRATCH_vt_hnsw         := hnsw_traverse_kernel
@@ -83,7 +86,7 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
 
 # (what the sketch units share)
-$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o: $(CSRC)/vt_sketch.cuh
+$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/vt_sketch4.o: $(CSRC)/vt_sketch.cuh
 
 # (the pass K9r and K9rb share; K11 and K12 take its finish_raw)
 $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_maxsim_pair.cuh
@@ -127,6 +130,15 @@ $(LIBDIR)/sketch_probe.o: tests/sketch_probe.cpp $(CSRC)/vt_device.h $(CSRC)/hos
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/sketch_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# K1n's kernels behind a probe of their own (tests/sketch4_probe.cpp; tests/test_gpu_sketch4_kernels.py loads it): the
+# builders, the pass, and the threshold, refine and collect launches on a test's arrays.  Test infrastructure, as above.
+$(LIBDIR)/sketch4_probe.o: tests/sketch4_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch4_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch4.o $(LIBDIR)/sketch4_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

@@ -665,6 +665,14 @@ typedef struct vt_profile {
   uint64_t sketch5_fallbacks;        /* passes the bound could not certify (the 6-bit sketch, the int8 sketch or the f32 rows then served) */
   uint64_t sketch5_builds;           /* whole builds of the 5-bit sketch */
   uint64_t sketch5_patched_rows;     /* rows re-quantised in place after mutations */
+  /* K1n: lone searches nominated from the 4-bit sketch (its passes count as scan_launches / scan_ms / scan_bytes too) */
+  uint64_t sketch4_launches;         /* passes over the 4-bit sketch */
+  double sketch4_ms;
+  uint64_t sketch4_bytes;            /* what the passes read: whole tiles and their metadata */
+  uint64_t sketch4_candidates;       /* rows handed to the gathered K1, summed over passes */
+  uint64_t sketch4_fallbacks;        /* passes the bound could not certify (the 5-bit sketch and what lies behind it then served) */
+  uint64_t sketch4_builds;           /* whole builds of the 4-bit sketch */
+  uint64_t sketch4_patched_rows;     /* rows re-quantised in place after mutations */
 } vt_profile;
 int vt_flat_set_profiling(vt_flat *index, int enabled);
 int vt_flat_get_profile(vt_flat *index, vt_profile *out, int reset);

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """tools/sketch_candidates.py OUT.json [--queries 300] [--limit 10] [--seed S] -- candidates per lone search of the
 bench's 10 M x 768 cosine corpus: bench.py's generator for rows and queries (the queries from another seed), profiling
-on, one search at a time.  Per query the growth of `sketch5_candidates` (the limit's path: K1f up to 10, else
-`sketch6_candidates`) and whether the pass certified; OUT.json holds min / max / mean / median, the passes that did not
-certify and the per-query list, so two builds can be compared query by query (`profiles/sketch_tail_spread/`)."""
+on, one search at a time.  Per query the growth of the path's `_candidates` counter (the limit's path: K1n up to 10 --
+K1f where `VT_SKETCH6=3` switches K1n off --, else `sketch6_candidates`) and whether the pass certified; OUT.json holds
+min / max / mean / median, the passes that did not certify, the queries' seed and the per-query list, so two builds can be
+compared query by query (`profiles/sketch_tail_spread/`, `profiles/sketch4/`)."""
 import argparse
 import ctypes as C
 import json
@@ -52,7 +53,7 @@ def main():
 
     search(qs[0])  # (builds the columns)
     nifs.flat_set_profiling(ref, True)
-    name = "sketch5" if a.limit <= 10 else "sketch6"
+    name = "sketch6" if a.limit > 10 else "sketch5" if os.environ.get("VT_SKETCH6") == "3" else "sketch4"
     per, missed = [], 0
     prev = nifs.flat_get_profile(ref)
     for q in qs:

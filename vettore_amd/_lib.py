@@ -70,6 +70,9 @@ class Profile(C.Structure):
         ("sketch5_launches", C.c_uint64), ("sketch5_ms", C.c_double), ("sketch5_bytes", C.c_uint64),
         ("sketch5_candidates", C.c_uint64), ("sketch5_fallbacks", C.c_uint64), ("sketch5_builds", C.c_uint64),
         ("sketch5_patched_rows", C.c_uint64),
+        ("sketch4_launches", C.c_uint64), ("sketch4_ms", C.c_double), ("sketch4_bytes", C.c_uint64),
+        ("sketch4_candidates", C.c_uint64), ("sketch4_fallbacks", C.c_uint64), ("sketch4_builds", C.c_uint64),
+        ("sketch4_patched_rows", C.c_uint64),
     ]
 
 

@@ -124,6 +124,7 @@ int shard_delete(Shard *ix, const char *id, size_t id_len, bool *began) {
     ix->sketch.release();  // (an emptied index gives the sketch's room back)
     ix->sketch6.release();
     ix->sketch5.release();
+    ix->sketch4.release();
   }
   return VT_OK;
 }

@@ -114,16 +114,84 @@ constexpr uint32_t kSketch5CandCap = 65536;       // every retained slot: 1 024 
 constexpr uint32_t kSketch5RescoreBlocks = 512;
 constexpr uint32_t kSketch5MissLimit = 4;
 bool sketch5_wanted(const Shard *ix, size_t limit) {
-  if (!sketch6_wanted(ix, limit) || limit > kSketch5MaxLimit || vt::env::get(vt::env::SKETCH6) != 1 || ix->sketch5.refused) return false;
+  if (!sketch6_wanted(ix, limit) || limit > kSketch5MaxLimit || vt::env::get(vt::env::SKETCH6) == 2 || ix->sketch5.refused) return false;
   if (vt::sketch5_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
   return vt::env::get(vt::env::FORCE_SKETCH6) >= 2 || (double)ix->n * ix->ld * 4.0 >= kSketch5MinBytes;
 }
 size_t sketch5_elems(const Shard *ix) { return vt::sketch5_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
+// K1n (vt_sketch4.hip; its tail: vt_sketch.hip): where K1f applies, limits up to kSketch4MaxLimit over f32 rows
+// of at least kSketch4MinBytes read the 4-bit sketch first -- 0.806 of the 5-bit sketch's bytes.  Its intervals are twice
+// K1f's again: under the sketch's own threshold Kt a quarter of the corpus would be a candidate.  The threshold is therefore
+// taken from the exact keys of the k rows with the smallest key(lo) (launch_sketch_refine, between the threshold and the
+// collect kernels): the band is then one interval wide, not two, and leaves what K1f leaves behind Kt (tens of thousands
+// of 10 M uniform unit rows at d = 768), over a wider spread -- so the pass leaves two lists a block, the candidate list
+// has a row for every slot of those and the gathered K1 runs on kSketch4RescoreBlocks blocks.  K1f is its fallback, on
+// K1f's own terms; after kSketch4MissLimit passes in a row that did not certify the shard stops taking K1n until the
+// column is built anew.  The settings are K1s's, one value further still (the product's list of settings stays as long
+// as it was): VT_SKETCH6=3 keeps K1s and K1f and switches K1n off -- the chain as it was without this column --;
+// force_sketch6 = 1 / 2 select what they did, force_sketch6 = 3 forces all three.
+// kSketch4MinBytes: the sweep over sizes has not been run for any of the three cuts; this one stays at the one size the
+// path has been measured at, which is K1s's and K1f's.
+constexpr double kSketch4MinBytes = 16.0 * 1024 * (1 << 20);
+constexpr size_t kSketch4MaxLimit = 10;
+constexpr uint32_t kSketch4CandCap = 131072;      // every retained slot: 2 048 lists of 64
+constexpr uint32_t kSketch4RescoreBlocks = 1024;
+constexpr uint32_t kSketch4MissLimit = 4;
+bool sketch4_wanted(const Shard *ix, size_t limit) {
+  if (!sketch5_wanted(ix, limit) || limit > kSketch4MaxLimit || vt::env::get(vt::env::SKETCH6) == 3 || ix->sketch4.refused) return false;
+  if (vt::sketch4_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
+  return vt::env::get(vt::env::FORCE_SKETCH6) >= 3 || (double)ix->n * ix->ld * 4.0 >= kSketch4MinBytes;
+}
+size_t sketch4_elems(const Shard *ix) { return vt::sketch4_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
+
+// What tells the sketch columns apart, by bits per element (8: K1q, 6: K1s, 5: K1f, 4: K1n): the column and what is kept
+// beside it, its builders and pass, its counters, and the shape of the chain behind the pass.  index_ensure_sketch and
+// sketch6_search go by this one table.
+struct SketchKind {
+  DerivedColumn<unsigned char> Shard::*col;
+  double Shard::*max_norm;
+  std::atomic<uint32_t> Shard::*misses;  // (null: K1q counts none)
+  size_t (*bytes)(uint32_t rows, uint32_t d);
+  hipError_t (*build)(const float *, size_t, uint32_t, uint32_t, uint32_t, void *, unsigned long long *, hipStream_t);
+  hipError_t (*rows)(const float *, size_t, const uint32_t *, uint32_t, uint32_t, uint32_t, void *, unsigned long long *, hipStream_t);
+  hipError_t (*scan)(const vt::Sketch6ScanArgs &, uint32_t, hipStream_t);  // (null: K1q's pass takes other arguments)
+  uint64_t vt_profile::*launches;
+  double vt_profile::*ms;
+  uint64_t vt_profile::*bytes_read, vt_profile::*candidates, vt_profile::*fallbacks, vt_profile::*builds, vt_profile::*patched_rows;
+  vt::env::Key refuse_hook;
+  uint32_t block_lists, cand_cap, rescore_blocks;  // lists a block of the pass leaves; the candidate list; the gathered K1's grid
+  DevBuf<uint32_t> Ctx::*cand_rows;
+  bool exact_threshold;  // Kt' from launch_sketch_refine
+};
+const SketchKind &sketch_kind(int bits) {
+  static const SketchKind k8{&Shard::sketch, &Shard::sketch_max_norm, nullptr, vt::sketch_bytes, vt::launch_sketch_build, vt::launch_sketch_rows,
+                             nullptr, &vt_profile::sketch_launches, &vt_profile::sketch_ms, &vt_profile::sketch_bytes,
+                             &vt_profile::sketch_candidates, &vt_profile::sketch_fallbacks, &vt_profile::sketch_builds,
+                             &vt_profile::sketch_patched_rows, vt::env::TEST_REFUSE_SKETCH, 1, kSketchCandCap, kSketchRescoreBlocks,
+                             &Ctx::dSkRows, false};
+  static const SketchKind k6{&Shard::sketch6, &Shard::sketch6_max_norm, &Shard::sketch6_misses, vt::sketch6_bytes, vt::launch_sketch6_build,
+                             vt::launch_sketch6_rows, vt::launch_sketch6_scan, &vt_profile::sketch6_launches, &vt_profile::sketch6_ms,
+                             &vt_profile::sketch6_bytes, &vt_profile::sketch6_candidates, &vt_profile::sketch6_fallbacks,
+                             &vt_profile::sketch6_builds, &vt_profile::sketch6_patched_rows, vt::env::TEST_REFUSE_SKETCH6, 1,
+                             kSketch6CandCap, kSketch6RescoreBlocks, &Ctx::dSk6Rows, false};
+  static const SketchKind k5{&Shard::sketch5, &Shard::sketch5_max_norm, &Shard::sketch5_misses, vt::sketch5_bytes, vt::launch_sketch5_build,
+                             vt::launch_sketch5_rows, vt::launch_sketch5_scan, &vt_profile::sketch5_launches, &vt_profile::sketch5_ms,
+                             &vt_profile::sketch5_bytes, &vt_profile::sketch5_candidates, &vt_profile::sketch5_fallbacks,
+                             &vt_profile::sketch5_builds, &vt_profile::sketch5_patched_rows, vt::env::TEST_REFUSE_SKETCH5, 1,
+                             kSketch5CandCap, kSketch5RescoreBlocks, &Ctx::dSk5Rows, false};
+  static const SketchKind k4{&Shard::sketch4, &Shard::sketch4_max_norm, &Shard::sketch4_misses, vt::sketch4_bytes, vt::launch_sketch4_build,
+                             vt::launch_sketch4_rows, vt::launch_sketch4_scan, &vt_profile::sketch4_launches, &vt_profile::sketch4_ms,
+                             &vt_profile::sketch4_bytes, &vt_profile::sketch4_candidates, &vt_profile::sketch4_fallbacks,
+                             &vt_profile::sketch4_builds, &vt_profile::sketch4_patched_rows, vt::env::TEST_REFUSE_SKETCH4,
+                             vt::kSketch4BlockLists, kSketch4CandCap, kSketch4RescoreBlocks, &Ctx::dSk4Rows, true};
+  return bits == 4 ? k4 : bits == 5 ? k5 : bits == 6 ? k6 : k8;
+}
+
 // The derived columns a reader with `need` / `limit` wants current, as the elements each must hold (0: not wanted).
 // shard_stale and shard_prepare both go by this one answer.  (A shard with rows.)
 struct ColumnsWanted {
-  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0, sketch6 = 0, sketch5 = 0;
+  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0, sketch6 = 0, sketch5 = 0, sketch4 = 0;
 };
 ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   ColumnsWanted w;
@@ -136,6 +204,7 @@ ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   if ((need & NEED_SKETCH) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
   if ((need & NEED_SKETCH) && sketch6_wanted(ix, limit)) w.sketch6 = sketch6_elems(ix);
   if ((need & NEED_SKETCH) && sketch5_wanted(ix, limit)) w.sketch5 = sketch5_elems(ix);
+  if ((need & NEED_SKETCH) && sketch4_wanted(ix, limit)) w.sketch4 = sketch4_elems(ix);
   return w;
 }
 
@@ -150,7 +219,7 @@ bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
   return (w.bits && !ix->bits.current(w.bits)) || (w.nz_bits && !ix->nz_bits.current(w.nz_bits)) ||
          (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow)) ||
          (w.sketch && !ix->sketch.current(w.sketch)) || (w.sketch6 && !ix->sketch6.current(w.sketch6)) ||
-         (w.sketch5 && !ix->sketch5.current(w.sketch5));
+         (w.sketch5 && !ix->sketch5.current(w.sketch5)) || (w.sketch4 && !ix->sketch4.current(w.sketch4));
 }
 
 int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords);
@@ -173,6 +242,7 @@ int shard_prepare(Shard *ix, unsigned need, size_t limit) {
   if (w.sketch) VT_TRY(index_ensure_sketch(ix, w.sketch));
   if (w.sketch6) VT_TRY(index_ensure_sketch(ix, w.sketch6, 6));
   if (w.sketch5) VT_TRY(index_ensure_sketch(ix, w.sketch5, 5));
+  if (w.sketch4) VT_TRY(index_ensure_sketch(ix, w.sketch4, 4));
   return VT_OK;
 }
 
@@ -345,16 +415,20 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
 // kernel), the gathered K1 over the candidate rows they left (the count read on the device: none when the pass did not
 // certify) and K1's select, all queued before the wait.
 // *done as sketch_search has it; a pass that does not certify counts towards the shard's miss limit.
-// `five`: K1f, the same chain over the 5-bit sketch (its pass, its bound of the level kept off the L plane, its longer
-// candidate list, more blocks for the gathered K1, its own counters and misses).
-int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, bool five = false) {
+// `bits` 5: K1f, the same chain over the 5-bit sketch (its pass, its bound of the level kept off the L plane, its longer
+// candidate list, more blocks for the gathered K1, its own counters and misses).  `bits` 4: K1n, over the 4-bit sketch
+// (one plane: no such level bound; two lists a block), with launch_sketch_refine between the threshold and the collect
+// kernels: the collect takes the exact threshold it publishes.
+int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, int bits = 6) {
+  const SketchKind &kind = sketch_kind(bits);
+  const bool five = bits == 5;
   *done = false;
   const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d);
   double qq = 0.0;
   for (uint32_t i = 0; i < d; ++i) qq += (double)query[i] * (double)query[i];
   const double up = 1.0 + 0x1p-30;
   const double qn = std::sqrt(qq) * up;
-  if (!(qn * (five ? ix->sketch5_max_norm : ix->sketch6_max_norm) * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
+  if (!(qn * ix->*kind.max_norm * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
   const uint32_t lw = vt_host::sketch6_level_words(d);
   const size_t total = (size_t)ld + (size_t)vt::kSketch6Levels * lw;
   VT_TRY(c.dQ.ensure(total));
@@ -372,25 +446,25 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   VT_HIP(hipMemcpyAsync(c.dQ.p, c.hQ.p, total * sizeof(float), hipMemcpyHostToDevice, c.stream));
 
   const uint32_t kp = kSketch6ListK, k = (uint32_t)limit;
-  const uint32_t blocks = (uint32_t)c.num_cus * 4u;
-  VT_TRY(c.dSkKeys.ensure((size_t)blocks * kp));
-  VT_TRY(c.dSkPay.ensure((size_t)blocks * kp));
-  VT_TRY(c.dSkLoWords.ensure((size_t)blocks * kp));
-  VT_TRY(c.dSkHiWords.ensure((size_t)blocks * kp));
-  const uint32_t cand_cap = five ? kSketch5CandCap : kSketch6CandCap;
-  const uint32_t rescore_blocks = five ? kSketch5RescoreBlocks : kSketch6RescoreBlocks;
-  DevBuf<uint32_t> &cand_rows = five ? c.dSk5Rows : c.dSk6Rows;
+  const uint32_t blocks = (uint32_t)c.num_cus * 4u, lists = blocks * kind.block_lists;
+  VT_TRY(c.dSkKeys.ensure((size_t)lists * kp));
+  VT_TRY(c.dSkPay.ensure((size_t)lists * kp));
+  VT_TRY(c.dSkLoWords.ensure((size_t)lists * kp));
+  VT_TRY(c.dSkHiWords.ensure((size_t)lists * kp));
+  const uint32_t cand_cap = kind.cand_cap, rescore_blocks = kind.rescore_blocks;
+  DevBuf<uint32_t> &cand_rows = c.*kind.cand_rows;
   VT_TRY(cand_rows.ensure(cand_cap));
   VT_TRY(c.dSkCount.ensure(1));
-  const uint32_t thresh_blocks = vt::sketch_thresh_blocks(blocks, kp);
-  VT_TRY(c.dSkParts.ensure((size_t)thresh_blocks * (k + 1)));
+  const uint32_t thresh_blocks = vt::sketch_thresh_blocks(lists, kp);
+  // (parts[thresh_blocks][k] | live[thresh_blocks] | K1n: slots[thresh_blocks][k] | the exact threshold's word)
+  VT_TRY(c.dSkParts.ensure((size_t)thresh_blocks * (2 * k + 1) + 1));
   VT_TRY(c.dSkSync.ensure(4));
   VT_TRY(c.hSkInfo.ensure(4));
   VT_TRY(c.ensure_part_lists((size_t)rescore_blocks * k));
   uint32_t *info = c.hSkInfo.mapped();
   if (!info) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch status)");
   vt::Sketch6ScanArgs a{};
-  a.img = five ? ix->sketch5.buf.p : ix->sketch6.buf.p;
+  a.img = (ix->*kind.col).buf.p;
   a.id_rank = ix->dRank.p;
   a.qimg = reinterpret_cast<const uint32_t *>(c.dQ.p + ld);
   a.n = ix->n;
@@ -404,7 +478,9 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   {  // the last level stays off the L plane: its share there is c3 -+ w3 per unit of s_r (exact: 25 bits times 19)
     int64_t pos = 0, neg = 0, l1 = 0;
     const uint32_t *last = reinterpret_cast<const uint32_t *>(hq + ld) + (size_t)(vt::kSketch6Levels - 1) * lw;
-    if (five) {  // (0 <= L <= 1: half of t3 where the 6-bit plane has 1.5)
+    if (bits == 4) {  // (one plane: every level meets every bit)
+      a.c3 = a.w3 = 0.0;
+    } else if (five) {  // (0 <= L <= 1: half of t3 where the 6-bit plane has 1.5)
       vt_host::sketch5_level_bound(last, lw, t[vt::kSketch6Levels - 1], &a.c3, &a.w3);
     } else {
       vt_host::sketch6_level_sums(last, lw, &pos, &neg, &l1);
@@ -419,13 +495,13 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   a.lo_words = c.dSkLoWords.p;
   a.hi_words = c.dSkHiWords.p;
   VT_TRY(c.mark_begin());
-  VT_HIP((five ? vt::launch_sketch5_scan : vt::launch_sketch6_scan)(a, blocks, c.stream));
+  VT_HIP(kind.scan(a, blocks, c.stream));
   VT_TRY(c.mark_end());
   vt::SketchSpreadArgs ta{};
   ta.lo_words = c.dSkLoWords.p;
   ta.hi_words = c.dSkHiWords.p;
   ta.pay = c.dSkPay.p;
-  ta.lists = blocks;
+  ta.lists = lists;
   ta.kp = kp;
   ta.k = k;
   ta.cap = cand_cap;
@@ -435,7 +511,27 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   ta.rows = cand_rows.p;
   ta.count = c.dSkCount.p;
   ta.info = info;
+  if (kind.exact_threshold) ta.slots = ta.live + thresh_blocks;
   VT_HIP(vt::launch_sketch_thresh(ta, c.stream));
+  if (kind.exact_threshold) {
+    vt::SketchRefineArgs ra{};
+    ra.parts = ta.parts;
+    ra.slots = ta.slots;
+    ra.live = ta.live;
+    ra.thresh_blocks = thresh_blocks;
+    ra.k = k;
+    ra.pay = c.dSkPay.p;
+    ra.slots_total = lists * kp;
+    ra.X = ix->dX;
+    ra.stride = ld;
+    ra.q = c.qsrc;
+    ra.d = d;
+    ra.metric = ix->metric;
+    ra.order = ix->order;
+    ra.kt_out = ta.slots + (size_t)thresh_blocks * k;
+    VT_HIP(vt::launch_sketch_refine(ra, c.stream));
+    ta.kt_word = ra.kt_out;
+  }
   VT_HIP(vt::launch_sketch_collect(ta, c.stream));
   vt::ScanArgs sa = scan_args(ix, c, d);
   set_gather(sa, gather_of(cand_rows.p), cand_cap);  // (the list's room: the count is batch_counts[0])
@@ -451,24 +547,17 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   if (c.profiling) {
     float ms = 0.f;
     VT_TRY(c.span_ms(&ms));
-    const uint64_t bytes = (uint64_t)(five ? vt::sketch5_bytes(ix->n, d) : vt::sketch6_bytes(ix->n, d));
-    if (five) {
-      c.prof.sketch5_launches += 1;
-      c.prof.sketch5_ms += ms;
-      c.prof.sketch5_bytes += bytes;
-      c.prof.sketch5_candidates += c.hSkInfo.p[1];
-    } else {
-      c.prof.sketch6_launches += 1;
-      c.prof.sketch6_ms += ms;
-      c.prof.sketch6_bytes += bytes;
-      c.prof.sketch6_candidates += c.hSkInfo.p[1];
-      c.prof.sketch6_tail_words += c.hSkInfo.p[3] == 1u ? 1 : 0;
-    }
+    const uint64_t bytes = (uint64_t)kind.bytes(ix->n, d);
+    c.prof.*kind.launches += 1;
+    c.prof.*kind.ms += ms;
+    c.prof.*kind.bytes_read += bytes;
+    c.prof.*kind.candidates += c.hSkInfo.p[1];
+    if (bits == 6) c.prof.sketch6_tail_words += c.hSkInfo.p[3] == 1u ? 1 : 0;
     VT_TRY(c.book_scan(1, ix->n, bytes));
   }
-  std::atomic<uint32_t> &misses = five ? ix->sketch5_misses : ix->sketch6_misses;
+  std::atomic<uint32_t> &misses = ix->*kind.misses;
   if (!certified) {
-    (five ? c.prof.sketch5_fallbacks : c.prof.sketch6_fallbacks) += 1;
+    c.prof.*kind.fallbacks += 1;
     misses.fetch_add(1, std::memory_order_relaxed);
     return VT_OK;
   }
@@ -481,7 +570,12 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
 
 // K1f: blit, the 5-bit pass, the threshold and collect kernels, the gathered K1 and its select behind one host wait.
 int sketch5_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
-  return sketch6_search(ix, c, query, limit, done, out, true);
+  return sketch6_search(ix, c, query, limit, done, out, 5);
+}
+
+// K1n: blit, the 4-bit pass, the threshold, refine and collect kernels, the gathered K1 and its select behind one host wait.
+int sketch4_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
+  return sketch6_search(ix, c, query, limit, done, out, 4);
 }
 
 // flat.rs:96-124 on a shard whose rank column shard_prepare has brought up to date --
@@ -492,6 +586,12 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
   if (limit == 0) return empty_hits(out);
   VT_TRY(validate_vector(query, n, ix->dim));
   if (ix->n == 0) return empty_hits(out);
+  if (lone && sketch4_wanted(ix, limit) && ix->sketch4.current(sketch4_elems(ix)) &&
+      ix->sketch4_misses.load(std::memory_order_relaxed) < kSketch4MissLimit) {
+    bool done = false;
+    VT_TRY(sketch4_search(ix, c, query, limit, &done, out));
+    if (done) return VT_OK;
+  }
   if (lone && sketch5_wanted(ix, limit) && ix->sketch5.current(sketch5_elems(ix)) &&
       ix->sketch5_misses.load(std::memory_order_relaxed) < kSketch5MissLimit) {
     bool done = false;
@@ -857,18 +957,16 @@ int index_ensure_shadow(Shard *ix, size_t elems) {
 // its last use are re-quantised in place; a first use, a slab that outgrew it or more than kMaxDerivedDirty mutations
 // rebuild it (one pass over the rows); without room for it -- a quarter of the card must stay free -- it is refused and
 // lone searches keep scanning the f32 rows.  The bound on every row's norm comes back with it (the overflow guard).
-// `bits` 6 / 5: the 6-bit / 5-bit sketch on the same terms (its own bound, its own counters); a whole build starts its
-// misses over.
+// `bits` 6 / 5 / 4: the 6-bit / 5-bit / 4-bit sketch on the same terms (its own bound, its own counters: sketch_kind); a
+// whole build starts its misses over.
 int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
   Ctx &c = ix->ctx;
-  const bool six = bits_per == 6, five = bits_per == 5;
-  DerivedColumn<unsigned char> &col = five ? ix->sketch5 : six ? ix->sketch6 : ix->sketch;
-  double &max_norm = five ? ix->sketch5_max_norm : six ? ix->sketch6_max_norm : ix->sketch_max_norm;
+  const SketchKind &kind = sketch_kind(bits_per);
+  DerivedColumn<unsigned char> &col = ix->*kind.col;
+  double &max_norm = ix->*kind.max_norm;
   if (col.current(bytes)) return VT_OK;
   const uint32_t d = (uint32_t)ix->dim;
-  const size_t tile_bytes = five  ? vt::sketch5_bytes(vt::kSketchTileRows, d)
-                            : six ? vt::sketch6_bytes(vt::kSketchTileRows, d)
-                                  : vt::sketch_bytes(vt::kSketchTileRows, d);
+  const size_t tile_bytes = kind.bytes(vt::kSketchTileRows, d);
   VT_TRY(c.dBNorm.ensure(1));
   unsigned long long bits = 0;
   if (col.patchable(bytes)) {
@@ -877,9 +975,8 @@ int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
     std::memcpy(&bits, &max_norm, sizeof(double));
     VT_HIP(hipMemcpyAsync(c.dBNorm.p, &bits, sizeof(bits), hipMemcpyHostToDevice, c.stream));
     const uint32_t rows_img = (uint32_t)(col.buf.count / tile_bytes * vt::kSketchTileRows);
-    VT_HIP((five ? vt::launch_sketch5_rows : six ? vt::launch_sketch6_rows : vt::launch_sketch_rows)(
-        ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
-    (five ? c.prof.sketch5_patched_rows : six ? c.prof.sketch6_patched_rows : c.prof.sketch_patched_rows) += count;
+    VT_HIP(kind.rows(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    c.prof.*kind.patched_rows += count;
   } else {
     col.forget();
     if (col.buf.count < bytes) {
@@ -896,7 +993,7 @@ int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
       }
 #ifdef VT_TEST_HOOKS
       // (libvettore_hip_hooks.so only: the allocation "fails", tests/test_gpu_sketch.py checks what follows)
-      refused = refused || vt::env::on(five ? vt::env::TEST_REFUSE_SKETCH5 : six ? vt::env::TEST_REFUSE_SKETCH6 : vt::env::TEST_REFUSE_SKETCH);
+      refused = refused || vt::env::on(kind.refuse_hook);
 #endif
       if (refused) {
         col.refuse();
@@ -905,11 +1002,9 @@ int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
     }
     const uint32_t rows_img = (uint32_t)(bytes / tile_bytes * vt::kSketchTileRows);
     VT_HIP(hipMemsetAsync(c.dBNorm.p, 0, sizeof(unsigned long long), c.stream));
-    VT_HIP((five ? vt::launch_sketch5_build : six ? vt::launch_sketch6_build : vt::launch_sketch_build)(
-        ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
-    (five ? c.prof.sketch5_builds : six ? c.prof.sketch6_builds : c.prof.sketch_builds) += 1;
-    if (six) ix->sketch6_misses.store(0, std::memory_order_relaxed);
-    if (five) ix->sketch5_misses.store(0, std::memory_order_relaxed);
+    VT_HIP(kind.build(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    c.prof.*kind.builds += 1;
+    if (kind.misses) (ix->*kind.misses).store(0, std::memory_order_relaxed);
   }
   VT_HIP(hipMemcpyAsync(&bits, c.dBNorm.p, sizeof(bits), hipMemcpyDeviceToHost, c.stream));
   // current from here on, for readers on other streams too: the build has finished before the exclusive lock can drop

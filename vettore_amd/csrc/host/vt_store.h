@@ -10,9 +10,14 @@ int index_reserve_once(Shard *ix, uint32_t want_rows);
 // The rows come first: when the slab cannot grow and the shard keeps a bf16 shadow (an accelerator
 // of the batch pass, half the slab's size), the shadow goes and the growth is tried once more; then
 // the int8 sketch of lone searches.  The 6-bit sketch goes before either: the int8 one serves in its place; and the
-// 5-bit sketch before that one, which serves in its place.
+// 5-bit sketch before that one, which serves in its place; and the 4-bit sketch first of all.
 int index_reserve(Shard *ix, uint32_t want_rows) {
   int st = index_reserve_once(ix, want_rows);
+  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch4.buf.p) {
+    (void)hipStreamSynchronize(ix->ctx.stream);
+    ix->sketch4.refuse();
+    st = index_reserve_once(ix, want_rows);
+  }
   if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch5.buf.p) {
     (void)hipStreamSynchronize(ix->ctx.stream);
     ix->sketch5.refuse();

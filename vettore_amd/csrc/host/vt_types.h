@@ -60,6 +60,7 @@ struct Ctx {
   DevBuf<uint32_t> dSkParts;  // K1s / K1f: the threshold kernel's k smallest words per block, then its live counts
   DevBuf<uint32_t> dSkSync;   // the collect kernel's claim, fail and ticket words (16 bytes, zeroed by the threshold kernel)
   DevBuf<uint32_t> dSk5Rows;  // K1f (sketch5_search): its candidate list, a row for every retained slot
+  DevBuf<uint32_t> dSk4Rows;  // K1n (sketch4_search): likewise, over twice the lists
   // K12 (vt_mmr.h, mmr_run): a call's problems, per-candidate arrays and block partials; what goes up and what comes back
   // travel through the two pinned blocks (grow, never shrink: no allocation per call)
   DevBuf<vt::MmrProblem> dMmrProb;
@@ -351,6 +352,12 @@ struct Shard {
   DerivedColumn<unsigned char> sketch5;
   double sketch5_max_norm = 0.0;
   std::atomic<uint32_t> sketch5_misses{0};
+  // K1n: the rows in four bits, one plane with its own scale (vt_device.h, above launch_sketch4_scan) -- 0.806 of the 5-bit
+  // sketch's bytes, read first by the largest lone searches (vt_search.h, sketch4_search) with the other three behind it.
+  // Kept on the 5-bit sketch's terms, misses included (kSketch4MissLimit); the first column to go when the slab needs room.
+  DerivedColumn<unsigned char> sketch4;
+  double sketch4_max_norm = 0.0;
+  std::atomic<uint32_t> sketch4_misses{0};
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
   // ids
@@ -414,6 +421,7 @@ struct Shard {
       sketch.touch(rows[i]);
       sketch6.touch(rows[i]);
       sketch5.touch(rows[i]);
+      sketch4.touch(rows[i]);
     }
   }
   void forget_derived() {
@@ -424,6 +432,7 @@ struct Shard {
     sketch.forget();
     sketch6.forget();
     sketch5.forget();
+    sketch4.forget();
   }
   // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
   // shadow gives its room back.
@@ -439,6 +448,8 @@ struct Shard {
     sketch6.buf.release();
     sketch5.reset();
     sketch5.buf.release();
+    sketch4.reset();
+    sketch4.buf.release();
   }
 };
 

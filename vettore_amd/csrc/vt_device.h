@@ -827,10 +827,38 @@ struct SketchSpreadArgs {
   uint32_t *count;
   uint32_t *info;           // [4] (host-mapped)
   uint32_t thresh_blocks, collect_blocks, collect_lists;  // set by the launchers
+  // K1n's exact threshold (launch_sketch_refine below); null: both launches behave as they did without these
+  uint32_t *slots = nullptr;          // [thresh_blocks][k]: launch_sketch_thresh files beside every word of parts[] the
+                                      // slot of lo_words[] it came from -- distinct slots that hold that word
+  const uint32_t *kt_word = nullptr;  // launch_sketch_collect takes this word for the Kt it would derive from parts[]
 };
 uint32_t sketch_thresh_blocks(uint32_t lists, uint32_t kp);
 hipError_t launch_sketch_thresh(SketchSpreadArgs a, hipStream_t s);
 hipError_t launch_sketch_collect(SketchSpreadArgs a, hipStream_t s);
+
+// Between the two, behind K1n's pass: the threshold from exact rescoring.  One block takes the k smallest
+// (word, slot) pairs of parts[] / slots[] -- Kt is the largest of those words --, reads the rows pay[slot].row and rescores
+// each with K1's arithmetic in the index's reduce order (a wave per row: elem4 / chunk_sum of vt_scan.cuh, the sequential
+// chain over the chunk sums, the scalar tail; the rank value formed as K1 forms it).  *kt_out = min(Kt, the largest of the
+// k exact key words): the exact key of k real rows, so at least k rows have a key <= it, and it is never above Kt.  Plain
+// Kt (0xffffffff with k or fewer live words) when fewer than k + 1 words are live, when any of the k values is not finite,
+// or when the rows' chunk sums do not fit the block's LDS.  picked[0..k) (optional): the rows it rescored, 0xffffffff
+// where it rescored none.
+struct SketchRefineArgs {
+  const uint32_t *parts, *slots, *live;  // launch_sketch_thresh's, [thresh_blocks][k] / [thresh_blocks]
+  uint32_t thresh_blocks, k;
+  const Payload *pay;       // [slots_total]
+  uint32_t slots_total;     // lists * kp
+  const float *X;           // the f32 rows, `stride` floats apart
+  size_t stride;
+  const float *q;           // the query padded with zeros to padded_dim(d) floats (device)
+  uint32_t d;
+  int metric, order;
+  uint32_t *kt_out;
+  uint32_t *picked;
+  uint32_t ld, ss, np4;     // set by the launcher
+};
+hipError_t launch_sketch_refine(SketchRefineArgs a, hipStream_t s);
 
 // ---- K1s (vt_sketch.hip): the same search over a 6-bit sketch in two planes -- 0.755 of K1q's bytes ------------------
 // Row r is kept as X_r = round(x_r / s_r) in [-31, 31] with s_r = max_i |x_ri| / 31, split as X = 4 H + L: H = X >> 2
@@ -898,5 +926,26 @@ hipError_t launch_sketch5_rows(const float *X, size_t stride, const uint32_t *li
 // + 2 t3 accH_3 + c3).  k <= kSmallK and ld8 >= 256; 0: not supported
 size_t sketch5_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_sketch5_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
+
+// ---- K1n (vt_sketch4.hip): the same search over a 4-bit sketch in one plane -- 0.806 of K1f's bytes -------------------
+// Row r is kept as X_r = round(x_r / s_r) in [-7, 7] with s_r = max_i |x_ri| / 7, one signed nibble per element; rho_r and
+// nu_r as K1q has them.  Layout, per tile of 64 rows, in 1-KiB runs of 16 bytes per row: ld8 / 32 runs in K1s's H layout
+// (nibble i of dword j of run c is element 32 c + 8 j + i), then one run of {s, rho, nu, 0}: ld8 / 32 + 1 KiB per tile.
+constexpr uint32_t kSketch4BlockLists = 2;  // lists a block of the pass leaves: launch_sketch4_scan writes blocks * 2 of them
+__host__ __device__ inline uint32_t sketch4_runs(uint32_t d) { return sketch_ld8(d) / 32 + 1; }  // per tile
+inline size_t sketch4_bytes(uint32_t rows, uint32_t d) {
+  const size_t tiles = ((size_t)rows + kSketchTileRows - 1) / kSketchTileRows;
+  return tiles * sketch4_runs(d) * 1024;
+}
+// (as launch_sketch_build / launch_sketch_rows; a run's place in the image: sketch6_offset with sketch4_runs)
+hipError_t launch_sketch4_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                                unsigned long long *max_norm, hipStream_t s);
+hipError_t launch_sketch4_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                               void *img, unsigned long long *max_norm, hipStream_t s);
+// The pass takes Sketch6ScanArgs as K1s's does (img: the 4-bit column; c3 and w3 are not read): a_r = s_r sum_j t_j acc_j.
+// part_keys, part_pay, lo_words and hi_words hold [blocks * kSketch4BlockLists][k].  k <= kSmallK and ld8 >= 256; 0: not
+// supported
+size_t sketch4_scan_lds_bytes(uint32_t d, uint32_t k);
+hipError_t launch_sketch4_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
 
 }  // namespace vt

@@ -1303,6 +1303,13 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch5_fallbacks += p.sketch5_fallbacks;
       t.sketch5_builds += p.sketch5_builds;
       t.sketch5_patched_rows += p.sketch5_patched_rows;
+      t.sketch4_launches += p.sketch4_launches;
+      t.sketch4_ms += p.sketch4_ms;
+      t.sketch4_bytes += p.sketch4_bytes;
+      t.sketch4_candidates += p.sketch4_candidates;
+      t.sketch4_fallbacks += p.sketch4_fallbacks;
+      t.sketch4_builds += p.sketch4_builds;
+      t.sketch4_patched_rows += p.sketch4_patched_rows;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

@@ -578,7 +578,7 @@ __device__ __forceinline__ uint32_t agent_add(uint32_t *p, uint32_t v) {
 
 __global__ __launch_bounds__(kSpreadThreads) void sketch_thresh_kernel(const SketchSpreadArgs a) {
   __shared__ uint32_t hist[256];
-  __shared__ uint32_t s_prefix, s_remaining, s_live, s_out;
+  __shared__ uint32_t s_prefix, s_remaining, s_live, s_out, s_eq;
   const uint32_t m = a.lists * a.kp;
   const uint32_t tid = threadIdx.x, base = blockIdx.x * kThreshSlots;
   const int lane = tid & (kWave - 1), w = tid / kWave;
@@ -588,6 +588,7 @@ __global__ __launch_bounds__(kSpreadThreads) void sketch_thresh_kernel(const Ske
     s_remaining = a.k;
     s_live = 0;
     s_out = 0;
+    s_eq = 0;
   }
   uint32_t v[kThreshPer];
   uint32_t live = 0;
@@ -622,9 +623,178 @@ __global__ __launch_bounds__(kSpreadThreads) void sketch_thresh_kernel(const Ske
     const bool below = v[u] < vk;
     const uint32_t pos = wave_claim(&s_out, below, lane);
     if (below && pos < a.k) out[pos] = v[u];
+    if (a.slots && below && pos < a.k) a.slots[(size_t)blockIdx.x * a.k + pos] = base + u * kSpreadThreads + tid;
   }
   if (tid < need && need <= a.k) out[a.k - need + tid] = vk;
+  if (a.slots && need <= a.k) {
+    // the copies of vk: `need` distinct slots that hold it (a padded slice files empty slots, past the end included:
+    // their word says so)
+    uint32_t *sl = a.slots + (size_t)blockIdx.x * a.k + (a.k - need);
+#pragma unroll
+    for (uint32_t u = 0; u < kThreshPer; ++u) {
+      const bool eq = v[u] == vk;
+      const uint32_t pos = wave_claim(&s_eq, eq, lane);
+      if (eq && pos < need) sl[pos] = base + u * kSpreadThreads + tid;
+    }
+  }
   if (tid == 0) a.live[blockIdx.x] = s_live;
+}
+
+// ---- K1n's threshold from exact rescoring (vt_device.h, SketchRefineArgs) ---------------------------------
+// One block between the two kernels.  Kt and the k smallest (word, slot) pairs of parts[]: four radix passes over the
+// words staged in LDS as the collect has them, the words below Kt filed by wave_claim, Kt's copies as often as are left.
+// Then sketch_tail_kernel's rescoring on those k rows: a wave per row, a lane pair per 8-float chunk, the sums to an LDS
+// row, one thread per row down the reference's sequential chain and the scalar tail.  Nothing waits for another block.
+__global__ __launch_bounds__(kTailThreads) void sketch_refine_kernel(const SketchRefineArgs a) {
+  extern __shared__ __align__(16) uint32_t dyn[];  // parts[] | slots[] | the k rows' chunk sums
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_prefix, s_remaining, s_live, s_lt, s_eq, s_bad, s_max;
+  __shared__ uint32_t sel_slot[kSpreadThreads], sel_row[kSpreadThreads];
+  const uint32_t tid = threadIdx.x;
+  const int lane = tid & (kWave - 1), w = tid / kWave;
+  const uint32_t np = a.thresh_blocks * a.k;
+  uint32_t *pw = dyn, *ps = dyn + a.np4;
+  if (tid == 0) {
+    s_prefix = 0;
+    s_remaining = a.k;
+    s_live = 0;
+    s_lt = 0;
+    s_eq = 0;
+    s_bad = 0;
+    s_max = 0;
+  }
+  if (tid < a.k) sel_slot[tid] = 0xffffffffu;
+  for (uint32_t i = tid; i < np; i += kTailThreads) {
+    pw[i] = a.parts[i];
+    ps[i] = a.slots[i];
+  }
+  uint32_t live = 0;
+  for (uint32_t i = tid; i < a.thresh_blocks; i += kTailThreads) live += a.live[i];
+  live = wave_sum_u(live);
+  __syncthreads();
+  if (lane == 0 && live) atomicAdd(&s_live, live);
+  __syncthreads();
+  if (s_live <= a.k || a.ss == 0) {  // (k or fewer live words: every one is a candidate, as the collect has it)
+    uint32_t kt = 0xffffffffu;
+    if (s_live > a.k) {
+      // the rows do not fit: Kt itself, by the same four passes
+      uint32_t mask = 0;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        const uint32_t prefix = s_prefix;
+        for (uint32_t b = 0; b < np; b += kTailThreads) {
+          const uint32_t i = b + tid;
+          const uint32_t x = i < np ? pw[i] : 0u;
+          hist_add(hist, i < np && (x & mask) == prefix, (x >> shift) & 255u, lane);
+        }
+        __syncthreads();
+        if (w == 0) radix_pick_bin(hist, &s_prefix, &s_remaining, prefix, shift, lane);
+        mask |= 255u << shift;
+        __syncthreads();
+      }
+      kt = s_prefix;
+    }
+    if (tid == 0) *a.kt_out = kt;
+    if (a.picked && tid < a.k) a.picked[tid] = 0xffffffffu;
+    return;
+  }
+  uint32_t mask = 0;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    const uint32_t prefix = s_prefix;
+    for (uint32_t b = 0; b < np; b += kTailThreads) {  // (whole waves: hist_add votes)
+      const uint32_t i = b + tid;
+      const uint32_t x = i < np ? pw[i] : 0u;
+      hist_add(hist, i < np && (x & mask) == prefix, (x >> shift) & 255u, lane);
+    }
+    __syncthreads();
+    if (w == 0) radix_pick_bin(hist, &s_prefix, &s_remaining, prefix, shift, lane);
+    mask |= 255u << shift;
+    __syncthreads();
+  }
+  // kt: the k-th smallest word (live: more than k words are); `need` of its copies belong to the k
+  const uint32_t kt = s_prefix, need = s_remaining;
+  for (uint32_t b = 0; b < np; b += kTailThreads) {  // (whole waves: wave_claim votes)
+    const uint32_t i = b + tid;
+    const uint32_t x = i < np ? pw[i] : 0xffffffffu;
+    const bool below = i < np && x < kt, eq = i < np && x == kt;
+    const uint32_t pl = wave_claim(&s_lt, below, lane);
+    if (below && pl < a.k) sel_slot[pl] = ps[i];
+    const uint32_t pe = wave_claim(&s_eq, eq, lane);
+    if (eq && pe < need && need <= a.k) sel_slot[a.k - need + pe] = ps[i];
+  }
+  __syncthreads();
+  if (tid < a.k) {
+    const uint32_t slot = sel_slot[tid];
+    uint32_t row = 0xffffffffu;
+    if (slot < a.slots_total) row = a.pay[slot].row;
+    else s_bad = 1;  // (cannot be: a word below 0xffffffff came from a live slot)
+    sel_row[tid] = row;
+  }
+  __syncthreads();
+  // K1 on the k rows: wave w takes rows w, w + 16, ...; lane l the floats [256 s + 4 l, + 4) of segment s
+  float *S = reinterpret_cast<float *>(dyn + 2 * a.np4);  // [k][ss]
+  const int odd = lane & 1;
+  const uint32_t cfull = a.d / 8, tail = a.d % 8, tail_base = a.ss - 12;
+  for (uint32_t c = (uint32_t)w; c < a.k; c += kTailThreads / kWave) {
+    if (sel_row[c] == 0xffffffffu) continue;
+    const float *x = a.X + (size_t)sel_row[c] * a.stride;
+    float *Srow = S + (size_t)c * a.ss;
+    for (uint32_t s0 = 0; s0 < a.ld; s0 += 4 * 256) {
+      f32x4 xv[4], qv[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t col = s0 + u * 256 + (uint32_t)lane * 4;
+        const bool in = col < a.ld;
+        xv[u] = in ? *reinterpret_cast<const f32x4 *>(x + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+        qv[u] = in ? *reinterpret_cast<const f32x4 *>(a.q + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const uint32_t col = s0 + u * 256 + (uint32_t)lane * 4;
+        const f32x4 pr = elem4<OP_DOT>(OP_DOT, qv[u], xv[u]);
+        const float sum = chunk_sum<OP_DOT, -1>(OP_DOT, a.order, pr.x, pr.y, pr.z, pr.w, odd);
+        const uint32_t ch = col >> 3;
+        if (col < a.ld) {
+          if (ch < cfull) {
+            if (!odd) Srow[ch] = sum;
+          } else if (ch == cfull) {  // the tail chunk: the reference adds these products one by one
+            *reinterpret_cast<f32x4 *>(Srow + tail_base + odd * 4) = pr;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < a.k && sel_row[tid] != 0xffffffffu) {
+    const float *Sr = S + (size_t)tid * a.ss;
+    float acc = 0.0f;
+    uint32_t c = 0;
+    for (; c + 4 <= cfull; c += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4 *>(Sr + c);
+      acc = acc + v.x;
+      acc = acc + v.y;
+      acc = acc + v.z;
+      acc = acc + v.w;
+    }
+    for (; c < cfull; ++c) acc = acc + Sr[c];
+    for (uint32_t j = 0; j < tail; ++j) acc = acc + Sr[tail_base + j];
+    // the value and its rank as scan_topk_kernel forms them; a value that is not finite goes through K1's f64 recovery
+    // there: here it only means that this call keeps the sketch's own threshold
+    const float raw = a.metric == M_NIP ? -acc : acc;
+    float rank = raw;
+    if (a.metric == M_COS) rank = 1.0f - raw;
+    else if (a.metric == M_IP) rank = -raw;
+    if (!finite_f32(raw) || !finite_f32(rank)) s_bad = 1;
+    else atomicMax(&s_max, orderable(rank));
+  }
+  __syncthreads();
+  if (tid == 0) *a.kt_out = s_bad ? kt : (s_max < kt ? s_max : kt);
+  if (a.picked && tid < a.k) a.picked[tid] = sel_row[tid];
 }
 
 __global__ __launch_bounds__(kSpreadThreads) void sketch_collect_kernel(const SketchSpreadArgs a) {
@@ -647,15 +817,19 @@ __global__ __launch_bounds__(kSpreadThreads) void sketch_collect_kernel(const Sk
   }
   for (uint32_t l = tid; l < nl; l += kSpreadThreads) lcnt[l] = 0;
   // Kt from the partial thresholds (plain loads: the kernel boundary has published them)
-  for (uint32_t i = tid; i < np; i += kSpreadThreads) pw[i] = a.parts[i];
   uint32_t live = 0;
-  for (uint32_t i = tid; i < a.thresh_blocks; i += kSpreadThreads) live += a.live[i];
+  if (!a.kt_word) {
+    for (uint32_t i = tid; i < np; i += kSpreadThreads) pw[i] = a.parts[i];
+    for (uint32_t i = tid; i < a.thresh_blocks; i += kSpreadThreads) live += a.live[i];
+  }
   live = wave_sum_u(live);
   __syncthreads();
   if (lane == 0 && live) atomicAdd(&s_live, live);
   __syncthreads();
   uint32_t kt = 0xffffffffu;  // (k or fewer entries in all: every one is a candidate)
-  if (s_live > a.k) {
+  if (a.kt_word) {
+    kt = *a.kt_word;  // (K1n: launch_sketch_refine's word, published by the kernel boundary; never above the Kt of parts[])
+  } else if (s_live > a.k) {
     uint32_t mask = 0;
     for (int pass = 0; pass < 4; ++pass) {
       const int shift = 24 - 8 * pass;
@@ -877,6 +1051,25 @@ hipError_t launch_sketch_collect(SketchSpreadArgs a, hipStream_t s) {
   size_t lds = 0;
   if (!sketch_spread_shape(a, &lds)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(sketch_collect_kernel, dim3(a.collect_blocks), dim3(kSpreadThreads), lds, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sketch_refine(SketchRefineArgs a, hipStream_t s) {
+  if (a.thresh_blocks == 0 || a.k == 0 || a.k > (uint32_t)kSpreadThreads || !a.parts || !a.slots || !a.live || !a.pay || !a.X || !a.q ||
+      !a.kt_out || a.d == 0)
+    return hipErrorInvalidValue;
+  a.ld = padded_dim(a.d);
+  a.ss = a.ld / 8 + 12;  // (K1's panel row: 4 * odd dwords, the eight tail products behind the sums)
+  a.np4 = (a.thresh_blocks * a.k + 3u) & ~3u;
+  size_t lds = ((size_t)2 * a.np4 + (size_t)a.k * a.ss) * 4;
+  if (lds > 96 * 1024) {  // rows too long for the block: the kernel publishes the sketch's own Kt
+    a.ss = 0;
+    lds = (size_t)2 * a.np4 * 4;
+    if (lds > 96 * 1024) return hipErrorInvalidValue;
+  }
+  hipError_t e = allow_lds(sketch_refine_kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sketch_refine_kernel, dim3(1), dim3(kTailThreads), lds, s, a);
   return hipGetLastError();
 }
 
