@@ -24,7 +24,7 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_hnsw vt_mmr
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_hnsw vt_mmr vt_prepare
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -75,6 +75,8 @@ EXTRA_vt_sketch4          := $(EXTRA_vt_sketch6)
 NOSCRATCH_vt_hnsw         := hnsw_traverse_kernel
 # K12 (MMR steps): one lane's chain per pair, K9's, with the recovery by value -- no scratch segment behind any of a call's launches
 NOSCRATCH_vt_mmr          := mmr_step_kernel
+# K14 (prepare rows): a lane's chain accumulators and a batch of loaded runs, all indexed statically -- no scratch segment
+NOSCRATCH_vt_prepare      := prepare_rows_kernel
 NOSPILL_vt_batch_bf16     := bf16_scores_kernel
 NOSPILL_vt_batch_shadow   := shadow_scores_kernel
 

@@ -407,6 +407,41 @@ int vt_normalize_l2(int device, size_t count, size_t d, const float *in,
 int vt_compress_sign_bits(int device, size_t count, size_t d, const float *in,
                           uint64_t *out);
 
+/* ---- prepare rows: the collection's four normalizations (collection.ex:50), for batches
+ * The arithmetic is the reference's, bit for bit (distances.rs:350-410): l2 divides by sqrt of the f64 sum of squares,
+ * zscore subtracts the f64 mean and divides by the population standard deviation, minmax maps [min, max] to [0, 1]
+ * (a zero norm / deviation / range gives a row of zeros); every sum is a serial f64 chain in index order, every
+ * division a true f64 division.  One thing the reference leaves open: f32::min / max do not say which zero wins
+ * between +0.0 and -0.0, so under minmax the sign of a zero result is unspecified for a row whose minimum is a zero
+ * and that holds zeros of both signs. */
+enum { VT_NORM_NONE = 0, VT_NORM_L2 = 1, VT_NORM_ZSCORE = 2, VT_NORM_MINMAX = 3 };
+/* normalize_zscore/1, normalize_minmax/1, nifs.rs:113-123 -> distances.rs:363-410: the shape of vt_normalize_l2
+ * (vt_prepare_rows without words). */
+int vt_normalize_zscore(int device, size_t count, size_t d, const float *in, float *out);
+int vt_normalize_minmax(int device, size_t count, size_t d, const float *in, float *out);
+/* What Collection.prepare_embedding does per record (collection.ex:921-946), for the rows of a [count][d] matrix in one
+ * call: every value finite, else VT_ERR_NON_FINITE; `mode` (VT_NORM_*, anything else: VT_ERR_ARGUMENT) applied to each
+ * row into out[count][d]; words != NULL: compress_sign_bits of each NORMALIZED row into words[count][(d + 63) / 64].
+ * Finiteness is checked on the host before any device is touched: on refusal nothing is written and *first_refused
+ * (may be NULL) is the smallest refused row; it is `count` when every row was accepted.  Empty batches and empty rows
+ * are VT_OK and write nothing.  Large inputs stream through pooled buffers in chunks (upload, kernel and download
+ * overlap); after the first call of a size no device or pinned memory is allocated or freed. */
+int vt_prepare_rows(int device, int mode, size_t count, size_t d, const float *in,
+                    float *out, uint64_t *words, size_t *first_refused);
+/* The same for rows already in this device's HBM (what feeds vt_flat_load_device_matrix): `in` is a row-major f32
+ * matrix whose rows lie ld_in floats apart and whose first d columns count (ld_in >= d; columns past d are neither read
+ * nor written), `out` likewise with ld_out, `words` (device, may be NULL) is [count][(d + 63) / 64] u64.  `out` may be
+ * `in` itself (then ld_out == ld_in); any other overlap is not supported.  Validation happens in the kernel: a row
+ * holding a non-finite value is left UNWRITTEN, values and words, every other row is written, and the call returns
+ * VT_ERR_NON_FINITE with *first_refused (may be NULL) the smallest such row -- in place the matrix is then partly
+ * normalized: the caller must discard it.
+ * Ordering: the call waits for everything queued on the device before it starts (the producer of `in` may have used
+ * any stream) and returns after its own work has finished: whatever the caller queues afterwards, on any stream, sees
+ * the complete result. */
+int vt_prepare_device_rows(int device, int mode, size_t count, size_t d, size_t ld_in,
+                           const void *in, size_t ld_out, void *out, void *words,
+                           size_t *first_refused);
+
 /* ------------------------------------------------- MaxSim (late interaction)
  * Vectors are ragged: vector j of a list is values[value_off[j] .. value_off[j + 1]), and a
  * length that differs from the query's is the reference's "dimension mismatch".  Validation

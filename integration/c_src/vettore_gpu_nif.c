@@ -485,6 +485,82 @@ static ERL_NIF_TERM normalize_l2(ErlNifEnv *env, int argc, const ERL_NIF_TERM ar
   return res;
 }
 
+/* normalize_zscore([float]) / normalize_minmax([float]) -> {:ok, [float]} | {:error, binary}   nifs.rs:113-123 */
+static ERL_NIF_TERM f32_list_term(ErlNifEnv *env, const float *v, size_t n) {
+  ERL_NIF_TERM list = enif_make_list(env, 0);
+  for (size_t i = n; i-- > 0;) list = enif_make_list_cell(env, enif_make_double(env, (double)v[i]), list);
+  return list;
+}
+
+static ERL_NIF_TERM normalize_with(ErlNifEnv *env, ERL_NIF_TERM vector, int mode) {
+  float *v;
+  size_t n;
+  if (!get_f32_list(env, vector, &v, &n)) return enif_make_badarg(env);
+  float *out = (float *)malloc((n ? n : 1) * sizeof(float));
+  int st = out ? vt_prepare_rows(0, mode, 1, n, v, out, NULL, NULL) : VT_ERR_NOMEM;
+  ERL_NIF_TERM res = st != VT_OK ? mk_error(env, st) : enif_make_tuple2(env, mk_atom(env, "ok"), f32_list_term(env, out, n));
+  free(v); free(out);
+  return res;
+}
+
+static ERL_NIF_TERM normalize_zscore(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return normalize_with(env, argv[0], VT_NORM_ZSCORE);
+}
+
+static ERL_NIF_TERM normalize_minmax(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return normalize_with(env, argv[0], VT_NORM_MINMAX);
+}
+
+/* prepare_rows(:none | :l2 | :zscore | :minmax, [[float]]) -> {:ok, [{[float], [u64]}]} | {:error, binary}
+ * Extension: what Collection.prepare_embedding does to a record's vector (collection.ex:921-946 -- validate,
+ * normalize, compress_sign_bits of the result), for a batch in one call.  Vectors of one length; any other atom, a
+ * ragged batch or a non-float is badarg. */
+static ERL_NIF_TERM prepare_rows(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  static const char *names[] = {"none", "l2", "zscore", "minmax"};
+  int mode = -1;
+  unsigned count;
+  (void)argc;
+  for (int m = 0; m < 4; ++m)
+    if (argv[0] == enif_make_atom(env, names[m])) mode = m;
+  if (mode < 0 || !enif_get_list_length(env, argv[1], &count)) return enif_make_badarg(env);
+  if (count == 0) return enif_make_tuple2(env, mk_atom(env, "ok"), enif_make_list(env, 0));
+  float *in = NULL;
+  size_t d = 0;
+  ERL_NIF_TERM head, tail = argv[1];
+  for (unsigned i = 0; i < count; ++i) {
+    float *v;
+    size_t n;
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !get_f32_list(env, head, &v, &n)) { free(in); return enif_make_badarg(env); }
+    if (i == 0) {
+      d = n;
+      in = (float *)malloc(((size_t)count * d + 1) * sizeof(float));
+    }
+    if (!in || n != d) { free(v); free(in); return enif_make_badarg(env); }
+    memcpy(in + (size_t)i * d, v, d * sizeof(float));
+    free(v);
+  }
+  const size_t W = (d + 63) / 64;
+  float *out = (float *)malloc(((size_t)count * d + 1) * sizeof(float));
+  uint64_t *words = (uint64_t *)calloc((size_t)count * W + 1, sizeof(uint64_t));
+  int st = out && words ? vt_prepare_rows(0, mode, count, d, in, out, words, NULL) : VT_ERR_NOMEM;
+  ERL_NIF_TERM res;
+  if (st != VT_OK) {
+    res = mk_error(env, st);
+  } else {
+    ERL_NIF_TERM list = enif_make_list(env, 0);
+    for (size_t i = count; i-- > 0;) {
+      ERL_NIF_TERM bits = enif_make_list(env, 0);
+      for (size_t w = W; w-- > 0;) bits = enif_make_list_cell(env, enif_make_uint64(env, (ErlNifUInt64)words[i * W + w]), bits);
+      list = enif_make_list_cell(env, enif_make_tuple2(env, f32_list_term(env, out + i * d, d), bits), list);
+    }
+    res = enif_make_tuple2(env, mk_atom(env, "ok"), list);
+  }
+  free(in); free(out); free(words);
+  return res;
+}
+
 /* compress_sign_bits([float]) -> [u64]   (bare list, as the reference returns it) nifs.rs:113-129 */
 static ERL_NIF_TERM compress_sign_bits(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
   float *v;
@@ -1054,6 +1130,9 @@ static ErlNifFunc funcs[] = {
   {"flat_hybrid_search", 4, flat_hybrid_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"normalize_l2", 1, normalize_l2, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"compress_sign_bits", 1, compress_sign_bits, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"normalize_zscore", 1, normalize_zscore, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"normalize_minmax", 1, normalize_minmax, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"prepare_rows", 2, prepare_rows, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"vector_top_k", 5, vector_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"binary_top_k", 4, binary_top_k, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"multi_vector_score", 3, multi_vector_score, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -43,6 +43,9 @@ defmodule Vettore.Gpu.Nifs do
   def flat_hybrid_search(_ref, _query, _generators, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def normalize_l2(_vector), do: :erlang.nif_error(:nif_not_loaded)
   def compress_sign_bits(_vector), do: :erlang.nif_error(:nif_not_loaded)
+  def normalize_zscore(_vector), do: :erlang.nif_error(:nif_not_loaded)
+  def normalize_minmax(_vector), do: :erlang.nif_error(:nif_not_loaded)
+  def prepare_rows(_mode, _vectors), do: :erlang.nif_error(:nif_not_loaded)
   def vector_top_k(_vectors, _query, _metric_code, _dimensions, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def binary_top_k(_vectors, _query, _dimensions, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def multi_vector_score(_query_vectors, _document_vectors, _metric_code), do: :erlang.nif_error(:nif_not_loaded)

@@ -171,6 +171,12 @@ defmodule Vettore.Index.FlatGpu do
   # candidate lists: same terms in and out.
   defdelegate normalize_l2(vector), to: Nifs
   defdelegate compress_sign_bits(vector), to: Nifs
+  # the other two normalizations of Vettore.Distance.normalize/2 (nifs.rs:113-123), and Collection.prepare_embedding's
+  # vector work (collection.ex:921-946) for a batch: mode is :none | :l2 | :zscore | :minmax, the answer
+  # {:ok, [{normalized_vector, sign_words}]} in the vectors' order
+  defdelegate normalize_zscore(vector), to: Nifs
+  defdelegate normalize_minmax(vector), to: Nifs
+  defdelegate prepare_rows(mode, vectors), to: Nifs
   defdelegate vector_top_k(vectors, query, metric_code, dimensions, limit), to: Nifs
   defdelegate binary_top_k(vectors, query, dimensions, limit), to: Nifs
   # MaxSim (late interaction) on the device: Vettore.Nifs.multi_vector_score/3 and multi_vector_top_k/4

@@ -32,6 +32,7 @@ SYMBOLS = [
     "vt_flat_load_matrix", "vt_flat_load_device_matrix", "vt_flat_quantized_search", "vt_flat_quantized_search_batch", "vt_flat_funnel_search", "vt_flat_funnel_search_batch", "vt_flat_hybrid_search",
     "vt_rank_ids", "vt_flat_set_id_ranks", "vt_flat_stream", "vt_flat_search_begin", "vt_flat_merge_gathered",
     "vt_vector_top_k", "vt_binary_top_k", "vt_normalize_l2", "vt_compress_sign_bits",
+    "vt_normalize_zscore", "vt_normalize_minmax", "vt_prepare_rows", "vt_prepare_device_rows",
     "vt_multi_vector_score", "vt_multi_vector_top_k", "vt_muvera_encode", "vt_muvera_fde_dimension",
     "vt_mv_new", "vt_mv_free", "vt_mv_put_many", "vt_mv_delete", "vt_mv_len", "vt_mv_dimension", "vt_mv_top_k", "vt_mv_top_k_ids",
     "vt_mv_memory", "vt_mv_top_k_batch", "vt_mv_top_k_ids_batch", "vt_mv_counters",
@@ -170,6 +171,10 @@ def load() -> C.CDLL:
                                   C.c_size_t, C.POINTER(vp)]
     L.vt_normalize_l2.argtypes = [C.c_int, C.c_size_t, C.c_size_t, f32p, f32p]
     L.vt_compress_sign_bits.argtypes = [C.c_int, C.c_size_t, C.c_size_t, f32p, u64p]
+    L.vt_normalize_zscore.argtypes = [C.c_int, C.c_size_t, C.c_size_t, f32p, f32p]
+    L.vt_normalize_minmax.argtypes = [C.c_int, C.c_size_t, C.c_size_t, f32p, f32p]
+    L.vt_prepare_rows.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, f32p, f32p, u64p, szp]
+    L.vt_prepare_device_rows.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp, vp, szp]
     L.vt_multi_vector_score.argtypes = [C.c_int, f32p, szp, C.c_size_t, f32p, szp, C.c_size_t, C.c_int, f32p]
     L.vt_multi_vector_top_k.argtypes = [C.c_int, C.c_size_t, C.c_char_p, szp, szp, f32p, szp, f32p, szp, C.c_size_t,
                                         C.c_int, C.c_size_t, C.POINTER(vp)]

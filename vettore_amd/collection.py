@@ -69,8 +69,8 @@ class Collection:
             return ("error", "invalid_metric")
         if normalize is None:
             normalize = "l2" if metric == "cosine" else "none"     # collection.ex:1317-1319
-        if normalize not in ("none", "l2"):
-            return ("error", "invalid_normalization")               # zscore/minmax: out of scope
+        if normalize not in ("none", "l2", "zscore", "minmax"):      # collection.ex:50
+            return ("error", "invalid_normalization")
         if score not in ("raw", "similarity"):
             return ("error", "invalid_score_mode")
         index_mod = FlatGpu if index in ("flat", "flat_gpu") else HnswGpu if index in ("hnsw", "hnsw_gpu") else index
@@ -128,7 +128,8 @@ class Collection:
     def _normalize(self, vector):
         if self.normalize == "none":
             return ("ok", [float(x) / 1 for x in vector])
-        res = nifs.normalize_l2([float(x) for x in vector])    # vettore_distance.ex:62-66
+        fn = {"l2": nifs.normalize_l2, "zscore": nifs.normalize_zscore, "minmax": nifs.normalize_minmax}[self.normalize]
+        res = fn([float(x) for x in vector])                    # vettore_distance.ex:62-66
         if res[0] != "ok":
             return ("error", "invalid_vector")
         return ("ok", res[1])
@@ -149,7 +150,9 @@ class Collection:
         return ("ok", out)
 
     # -- collection.ex:921-937, :993-1017 -------------------------------------
-    def _prepare_embedding(self, emb):
+    @staticmethod
+    def _check_embedding(emb):
+        """The checks that come before any vector is looked at: ("ok", Embedding) or the error."""
         if isinstance(emb, dict):
             emb = Embedding(id=emb.get("id"), value=emb.get("value"), vector=emb.get("vector"),
                             metadata=emb.get("metadata"), vectors=emb.get("vectors"))
@@ -157,6 +160,13 @@ class Collection:
             return ("error", "invalid_embedding")
         if not isinstance(emb.id, (str, bytes)) or len(emb.id) == 0:
             return ("error", "missing_id")
+        return ("ok", emb)
+
+    def _prepare_embedding(self, emb):
+        checked = self._check_embedding(emb)
+        if checked[0] != "ok":
+            return checked
+        emb = checked[1]
         vectors = None
         if emb.vectors is not None:
             pv = self._prepare_vectors(emb.vectors)
@@ -201,12 +211,40 @@ class Collection:
     def put_many(self, embs):
         if not isinstance(embs, list):
             return ("error", "invalid_embeddings")
-        prepared = []
+        # Every embedding is checked in order and the first error is the answer, as in a loop of _prepare_embedding; the
+        # ones that carry `vectors` are prepared right there, the plain `vector`s of the batch wait for ONE prepare_rows
+        # call (normalization and sign bits of all of them: a checked vector cannot be refused any more).
+        prepared, plain = [], []
         for emb in embs:
-            p = self._prepare_embedding(emb)
-            if p[0] != "ok":
-                return p
-            prepared.append(p[1])
+            checked = self._check_embedding(emb)
+            if checked[0] != "ok":
+                return checked
+            emb = checked[1]
+            if emb.vectors is not None:
+                p = self._prepare_embedding(emb)
+                if p[0] != "ok":
+                    return p
+                prepared.append(p[1])
+                continue
+            ok = _validate_vector(emb.vector, self.dimensions)
+            if ok != "ok":
+                return ok
+            plain.append((len(prepared), emb))
+            prepared.append(None)
+        if plain:
+            rows = [[float(x) for x in emb.vector] for _, emb in plain]
+            with np.errstate(over="ignore"):
+                matrix = np.asarray(rows, dtype=np.float64).astype(np.float32)
+            res = nifs.prepare_rows(matrix, self.normalize)
+            if res[0] != "ok":
+                return ("error", "invalid_vector")
+            normalized, words = res[1]
+            for k, (at, emb) in enumerate(plain):
+                # (normalize: none keeps the caller's numbers as they came, like _normalize)
+                vec = [x / 1 for x in rows[k]] if self.normalize == "none" else np.array(normalized[k])
+                idb = nifs._bytes(emb.id)
+                prepared[at] = Embedding(id=idb, value=emb.value if emb.value is not None else idb, vector=vec,
+                                         binary_vector=[int(w) for w in words[k]], metadata=emb.metadata, vectors=None)
         ids = [e.id for e in prepared]
         if len(set(ids)) != len(ids) or any(i in self.store for i in ids):
             return ("error", "duplicate_id")

@@ -77,13 +77,48 @@ struct MuveraState {
   PinnedBuf<int> hStatus;
 };
 
+// Prepare rows (K14, vt_prepare.h): two chunks in flight, each with a pinned block and a device buffer for its rows
+// (normalized in place on the device, so the block that went up is the block that comes down) and the same for its sign
+// words; a stream per direction beside the context's; the first-refused word.  Everything grows and stays.
+struct PrepareState {
+  hipStream_t up = nullptr, down = nullptr;
+  hipEvent_t uploaded[2] = {nullptr, nullptr}, computed[2] = {nullptr, nullptr}, landed[2] = {nullptr, nullptr};
+  PinnedBuf<float> hX[2];
+  PinnedBuf<uint64_t> hW[2];
+  DevBuf<float> dX[2];
+  DevBuf<uint64_t> dW[2];
+  DevBuf<uint32_t> dFirst;
+  PinnedBuf<uint32_t> hFirst;
+  int open() {
+    if (!up) VT_HIP(hipStreamCreateWithFlags(&up, hipStreamNonBlocking));
+    if (!down) VT_HIP(hipStreamCreateWithFlags(&down, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b)
+      for (hipEvent_t *e : {&uploaded[b], &computed[b], &landed[b]})
+        if (!*e) VT_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    // nothing of an earlier call (one that failed between two chunks) is in flight
+    VT_HIP(hipStreamSynchronize(up));
+    VT_HIP(hipStreamSynchronize(down));
+    VT_TRY(dFirst.ensure(1));
+    return hFirst.ensure(1);
+  }
+  ~PrepareState() {
+    for (hipStream_t s : {up, down})
+      if (s) (void)hipStreamSynchronize(s);
+    for (hipEvent_t e : {uploaded[0], uploaded[1], computed[0], computed[1], landed[0], landed[1]})
+      if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : {up, down})
+      if (s) (void)hipStreamDestroy(s);
+  }
+};
+
 // What the stateless calls keep on one device (the ring and the states after the context: gone before its stream).
 struct Stateless {
   Ctx ctx;
   UploadRing ring;
   MaxSimState maxsim;
   MuveraState muvera;
-  // (pooled buffers of the four dense helpers would live here: today each call allocates and frees its own)
+  PrepareState prepare;
+  // (vector_top_k, binary_top_k, normalize_l2 and compress_sign_bits still allocate and free their own buffers per call)
 };
 
 // One session per device, one lock over all of them: a lease is the only way to a session and holds the lock while it lives.

@@ -741,6 +741,30 @@ hipError_t launch_mmr_step(const MmrArgs &a, uint32_t t, uint32_t blocks, uint32
 // normalize_l2 (distances.rs:350-361) on rows: out = (x / sqrt(f64 sum x^2)) as f32.
 hipError_t launch_normalize_l2(const float *in, uint32_t n, uint32_t d, float *out, hipStream_t s);
 
+// ---- K14 (vt_prepare.hip): prepare rows -- finite check, normalization and sign bits of a matrix in one launch ---------
+// Row r of `in` (rows ld_in floats apart, the first d columns count) is checked for non-finite values, normalized as
+// `mode` says (distances.rs:350-410, the reference's order of operations: serial f64 sums in index order, true f64
+// divisions) and written to row r of `out` (rows ld_out floats apart; columns past d are not touched); `out` may be `in`
+// when ld_out == ld_in.  words != nullptr: the sign bits of the written values (compress_sign_bits, :413-423) go to
+// words[r][(d + 63) / 64].  A row holding a non-finite value is left unwritten, values and words, and *first_refused
+// (set to kPrepNoRow by the caller beforehand) is lowered to its index by atomicMin; all other rows are written.
+constexpr uint32_t kPrepWaveRows = 64;    // rows of a wave's tile: one lane owns one row's serial chains
+constexpr uint32_t kPrepPanel = 64;       // columns a tile passes through LDS at a time
+constexpr uint32_t kPrepBlockRows = 128;  // rows per block = threads per block: two waves, each with its own LDS image
+constexpr int kPrepInFlight = 32;         // 256-byte runs a wave loads before it converts and stores them
+constexpr uint32_t kPrepNoRow = 0xffffffffu;
+enum { kPrepNone = 0, kPrepL2 = 1, kPrepZscore = 2, kPrepMinmax = 3 };  // = VT_NORM_* (include/vettore_flat.h)
+struct PrepareArgs {
+  const float *in;
+  size_t ld_in;
+  float *out;
+  size_t ld_out;
+  uint64_t *words;          // [n][(d + 63) / 64], or nullptr
+  uint32_t *first_refused;  // one word
+  uint32_t n, d;
+};
+hipError_t launch_prepare_rows(const PrepareArgs &a, int mode, hipStream_t s);
+
 // ---- K1q (vt_sketch.hip): a lone dot-family search over an int8 sketch of the rows -----------------------------------
 // Row r is kept as X_r = round(x_r / s_r) in int8 with s_r = max_i |x_ri| / 127, beside two f32 bounds rounded up:
 // rho_r >= ||x_r - s_r X_r|| (the residual, summed in f64) and nu_r >= s_r ||X_r||.  Layout, per tile of 64 rows: the

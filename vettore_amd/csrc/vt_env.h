@@ -106,7 +106,8 @@ enum Parse {
   X(TEST_MV_K9, "test_mv_k9", P_FLAG, 0, "a resident multi-vector store's searches launch K9 over its slab where K9r would serve (`tools/maxsim_resident_probe.py` times one against the other)") \
   X(TEST_HNSW_SCRATCH_CAP, "test_hnsw_scratch_cap", P_INT, 0, "entries of an HNSW traversal's heaps and visited set (default: a few thousand by ef, never more than the nodes need); a few entries make small traversals outgrow them and run again with full-size scratch") \
   X(TEST_MMR_BLOCK_ROWS, "test_mmr_block_rows", P_INT, 0, "candidates an MMR step block takes per pass (default 256, one per thread); a few make short lists span several blocks with a ragged last one") \
-  X(TEST_MMR_LDS_DIM, "test_mmr_lds_dim", P_INT, 0, "longest chosen row an MMR step stages in LDS, in floats (default 4 096); a few make short rows take the unstaged walk")
+  X(TEST_MMR_LDS_DIM, "test_mmr_lds_dim", P_INT, 0, "longest chosen row an MMR step stages in LDS, in floats (default 4 096); a few make short rows take the unstaged walk") \
+  X(TEST_PREPARE_CHUNK_ROWS, "test_prepare_chunk_rows", P_INT, 0, "rows per upload chunk of a `vt_prepare_rows` call (default: 32 MiB of rows); a few make small calls cross many chunks")
 
 enum Key : int {
 #define VT_ENV_ENUM(key, name, parse, dflt, doc) key,

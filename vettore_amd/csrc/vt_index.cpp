@@ -52,6 +52,7 @@
 #include "host/vt_funnel.h"
 #include "host/vt_hybrid.h"
 #include "host/vt_stateless.h"
+#include "host/vt_prepare.h"
 #include "host/vt_maxsim.h"
 #include "host/vt_muvera.h"
 #include "host/vt_mvsearch.h"
@@ -1227,6 +1228,30 @@ int vt_compress_sign_bits(int device, size_t count, size_t d, const float *in, u
   return guarded([&]() -> int {
   if ((count && d) && (!in || !out)) return VT_ERR_ARGUMENT;
   return compress_sign_bits(device, count, d, in, out);
+  });
+}
+
+int vt_normalize_zscore(int device, size_t count, size_t d, const float *in, float *out) {
+  return vt_prepare_rows(device, VT_NORM_ZSCORE, count, d, in, out, nullptr, nullptr);
+}
+
+int vt_normalize_minmax(int device, size_t count, size_t d, const float *in, float *out) {
+  return vt_prepare_rows(device, VT_NORM_MINMAX, count, d, in, out, nullptr, nullptr);
+}
+
+int vt_prepare_rows(int device, int mode, size_t count, size_t d, const float *in, float *out, uint64_t *words,
+                    size_t *first_refused) {
+  return guarded([&]() -> int {
+  if (mode < VT_NORM_NONE || mode > VT_NORM_MINMAX) return VT_ERR_ARGUMENT;
+  if ((count && d) && (!in || !out)) return VT_ERR_ARGUMENT;
+  return prepare_rows(device, mode, count, d, in, out, words, first_refused);
+  });
+}
+
+int vt_prepare_device_rows(int device, int mode, size_t count, size_t d, size_t ld_in, const void *in, size_t ld_out,
+                           void *out, void *words, size_t *first_refused) {
+  return guarded([&]() -> int {
+  return prepare_device_rows(device, mode, count, d, ld_in, in, ld_out, out, words, first_refused);
   });
 }
 

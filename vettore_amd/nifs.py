@@ -813,6 +813,66 @@ def compress_sign_bits(vector):
     return [int(w) for w in words]
 
 
+def normalize_zscore(vector):
+    """nifs.rs:113-117."""
+    v = _f32_list(vector)
+    out = np.empty_like(v)
+    st = _lib.load().vt_normalize_zscore(DEVICE, 1, v.size, _fp(v), _fp(out))
+    return ("ok", out) if st == 0 else _err(st)
+
+
+def normalize_minmax(vector):
+    """nifs.rs:119-123."""
+    v = _f32_list(vector)
+    out = np.empty_like(v)
+    st = _lib.load().vt_normalize_minmax(DEVICE, 1, v.size, _fp(v), _fp(out))
+    return ("ok", out) if st == 0 else _err(st)
+
+
+NORM_MODES = {"none": 0, "l2": 1, "zscore": 2, "minmax": 3}   # VT_NORM_*
+
+
+def _norm_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in NORM_MODES:
+            raise TypeError("badarg: unknown normalization")
+        return NORM_MODES[mode]
+    return int(mode)
+
+
+def prepare_rows(matrix, mode):
+    """Extension: Collection.prepare_embedding's vector work (collection.ex:921-946) for every row of a [count][d]
+    matrix in one call -- finite check, normalization `mode` ("none" | "l2" | "zscore" | "minmax", or VT_NORM_*), sign
+    bits of the normalized rows.  ("ok", (normalized float32 [count][d], words uint64 [count][(d + 63) // 64])), or
+    ("error", reason, first_refused) with the smallest refused row (None when the call was refused as a whole)."""
+    m = np.ascontiguousarray(matrix, dtype=np.float32)
+    if m.ndim != 2:
+        raise TypeError("badarg: matrix must be two-dimensional")
+    count, d = m.shape
+    out = np.empty_like(m)
+    words = np.zeros((count, (d + 63) // 64), dtype=np.uint64)
+    first = C.c_size_t(count)
+    st = _lib.load().vt_prepare_rows(DEVICE, _norm_mode(mode), count, d, _fp(m.reshape(-1)), _fp(out.reshape(-1)),
+                                     _up(words.reshape(-1)), C.byref(first))
+    if st != 0:
+        return ("error", _lib.error_text(st), int(first.value) if first.value < count else None)
+    return ("ok", (out, words))
+
+
+def prepare_device_rows(mode, count: int, d: int, in_ptr: int, ld_in: int, out_ptr: int, ld_out: int, words_ptr: int = 0):
+    """Extension: prepare_rows on rows already resident in this device's HBM (raw device pointers, like
+    flat_load_device_matrix): row-major f32 at `in_ptr` with rows `ld_in` floats apart, normalized into `out_ptr`
+    (`ld_out`; may be `in_ptr` itself), sign words into `words_ptr` (0: none).  ("ok", ()) or
+    ("error", reason, first_refused): refused rows are unwritten, every other row is written."""
+    first = C.c_size_t(count)
+    st = _lib.load().vt_prepare_device_rows(DEVICE, _norm_mode(mode), count, d, ld_in, C.c_void_p(in_ptr), ld_out,
+                                            C.c_void_p(out_ptr), C.c_void_p(words_ptr) if words_ptr else None,
+                                            C.byref(first))
+    if st != 0:
+        return ("error", _lib.error_text(st), int(first.value) if first.value < count else None)
+    return ("ok", ())
+
+
 # -------------------------------------------- bulk / device-side extensions
 def flat_load_matrix(index: FlatRef, ids: Sequence, matrix: np.ndarray):
     """insert_many of equal-length rows from one dense host matrix."""
