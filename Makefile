@@ -24,11 +24,11 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_hnsw vt_mmr vt_prepare
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_hnsw vt_mmr vt_prepare
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -36,7 +36,7 @@ all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/lib
 #   EXTRA_<unit>      compiler flags of that unit alone
 # K1's instantiation units: no scratch at all (r05: the overflow recovery returns its value by value; every launch of a
 # kernel with a scratch segment has it set up)
-K1_UNITS := vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather
+K1_UNITS := vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter
 $(foreach u,$(K1_UNITS),$(eval NOSCRATCH_$(u) := scan_topk_kernel))
 NOSCRATCH_vt_scan_multi   := scan_multi_kernel
 NOSCRATCH_vt_prefix_multi := prefix_multi_kernel
@@ -141,6 +141,15 @@ $(LIBDIR)/sketch4_probe.o: tests/sketch4_probe.cpp $(CSRC)/vt_device.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch4_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch4.o $(LIBDIR)/sketch4_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# The kernel that finishes K1n's chain behind a probe (tests/sketch4_finish_probe.cpp; tests/test_gpu_sketch4_finish_kernels.py
+# loads it): the gathered K1 in filter mode on a test's arrays.  Test infrastructure, as above.
+$(LIBDIR)/sketch4_finish_probe.o: tests/sketch4_finish_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch4_finish_probe.so: $(LIBDIR)/vt_scan_filter.o $(LIBDIR)/sketch4_finish_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

@@ -708,6 +708,7 @@ typedef struct vt_profile {
   uint64_t sketch4_fallbacks;        /* passes the bound could not certify (the 5-bit sketch and what lies behind it then served) */
   uint64_t sketch4_builds;           /* whole builds of the 4-bit sketch */
   uint64_t sketch4_patched_rows;     /* rows re-quantised in place after mutations */
+  uint64_t sketch4_finished;         /* searches whose result the filtered K1 behind the pass wrote itself (no select, one wait) */
 } vt_profile;
 int vt_flat_set_profiling(vt_flat *index, int enabled);
 int vt_flat_get_profile(vt_flat *index, vt_profile *out, int reset);

@@ -54,7 +54,7 @@ def main():
     search(qs[0])  # (builds the columns)
     nifs.flat_set_profiling(ref, True)
     name = "sketch6" if a.limit > 10 else "sketch5" if os.environ.get("VT_SKETCH6") == "3" else "sketch4"
-    per, missed = [], 0
+    per, missed, delivered = [], 0, 0  # (delivered: K1n searches whose result the filtered K1 wrote itself)
     prev = nifs.flat_get_profile(ref)
     for q in qs:
         search(q)
@@ -65,11 +65,14 @@ def main():
             per.append(None)
         else:
             per.append(int(cur[name + "_candidates"] - prev[name + "_candidates"]))
+            delivered += int(cur.get("sketch4_finished", 0) - prev.get("sketch4_finished", 0))
         prev = cur
     ok = [c for c in per if c is not None]
     out = {"rows": a.rows, "dim": a.dim, "queries": a.queries, "limit": a.limit, "seed": a.seed, "path": name, "corpus_checksum": checksum,
            "fallbacks": missed, "candidates_min": min(ok), "candidates_max": max(ok), "candidates_mean": float(np.mean(ok)),
            "candidates_median": float(np.median(ok)), "per_query": per}
+    if name == "sketch4":  # (certified searches the filtered K1 did not deliver took the lists and the select behind a second wait)
+        out["delivered"], out["second_wait"] = delivered, len(ok) - delivered
     json.dump(out, open(a.out, "w"))
     print(json.dumps({k: v for k, v in out.items() if k != "per_query"}))
 

@@ -73,7 +73,7 @@ class Profile(C.Structure):
         ("sketch5_patched_rows", C.c_uint64),
         ("sketch4_launches", C.c_uint64), ("sketch4_ms", C.c_double), ("sketch4_bytes", C.c_uint64),
         ("sketch4_candidates", C.c_uint64), ("sketch4_fallbacks", C.c_uint64), ("sketch4_builds", C.c_uint64),
-        ("sketch4_patched_rows", C.c_uint64),
+        ("sketch4_patched_rows", C.c_uint64), ("sketch4_finished", C.c_uint64),
     ]
 
 

@@ -418,7 +418,9 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
 // `bits` 5: K1f, the same chain over the 5-bit sketch (its pass, its bound of the level kept off the L plane, its longer
 // candidate list, more blocks for the gathered K1, its own counters and misses).  `bits` 4: K1n, over the 4-bit sketch
 // (one plane: no such level bound; two lists a block), with launch_sketch_refine between the threshold and the collect
-// kernels: the collect takes the exact threshold it publishes.
+// kernels: the collect takes the exact threshold it publishes, and the gathered K1 runs in filter mode
+// (launch_scan_filter): it keeps the rows under that threshold and writes the sorted result itself, no select behind it.
+// A search whose survivors overflow its short list queues the lists and the select behind a second wait.
 int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, int bits = 6) {
   const SketchKind &kind = sketch_kind(bits);
   const bool five = bits == 5;
@@ -430,7 +432,11 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   const double qn = std::sqrt(qq) * up;
   if (!(qn * ix->*kind.max_norm * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
   const uint32_t lw = vt_host::sketch6_level_words(d);
-  const size_t total = (size_t)ld + (size_t)vt::kSketch6Levels * lw;
+  const size_t qwords = (size_t)ld + (size_t)vt::kSketch6Levels * lw;
+  // K1n: zero words ride behind the query's image in the same blit -- the filtered K1's count, overflow and ticket words
+  // (4 KiB: a line per ticket) start every call from zero whatever the last one did, at no launch's cost
+  const size_t chain_zeros = vt::kScanFilterSyncWords;
+  const size_t total = qwords + (kind.exact_threshold ? chain_zeros : 0);
   VT_TRY(c.dQ.ensure(total));
   VT_TRY(c.hQ.ensure(total));
   if (c.hSkResid.size() < d) c.hSkResid.resize(d);
@@ -441,6 +447,8 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   double ee = 0.0;
   static_assert(vt::kSketch6Levels == vt_host::kSketch6Levels, "one number of query levels on both sides");
   vt_host::sketch6_query_levels(query, d, reinterpret_cast<uint32_t *>(hq + ld), c.hSkResid.data(), t, &ee);
+  if (kind.exact_threshold) std::memset(hq + qwords, 0, chain_zeros * sizeof(float));
+  uint32_t *chain_words = reinterpret_cast<uint32_t *>(c.dQ.p + qwords);  // (ScanArgs::fsync)
   c.qbits_kind = 0;
   c.qsrc = c.dQ.p;
   VT_HIP(hipMemcpyAsync(c.dQ.p, c.hQ.p, total * sizeof(float), hipMemcpyHostToDevice, c.stream));
@@ -460,7 +468,7 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   VT_TRY(c.dSkParts.ensure((size_t)thresh_blocks * (2 * k + 1) + 1));
   VT_TRY(c.dSkSync.ensure(4));
   VT_TRY(c.hSkInfo.ensure(4));
-  VT_TRY(c.ensure_part_lists((size_t)rescore_blocks * k));
+  VT_TRY(c.ensure_part_lists(std::max<size_t>((size_t)rescore_blocks * k, vt::kScanFilterCap)));  // (K1n: the survivors lie there)
   uint32_t *info = c.hSkInfo.mapped();
   if (!info) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch status)");
   vt::Sketch6ScanArgs a{};
@@ -539,11 +547,33 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   use_part_lists(sa, c);
   sa.batch_counts = c.dSkCount.p;
   sa.batch_cap = cand_cap;
-  VT_HIP(vt::launch_scan_batch(sa, rescore_blocks, 1, c.stream));
-  VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, rescore_blocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
-                           c.dSelKeys.p, c.dSelPay.p, c.stream));
-  VT_HIP(hipStreamSynchronize(c.stream));
-  const bool certified = c.hSkInfo.p[0] == 2u && c.hRes.p->status == 0;
+  bool delivered = false;
+  if (kind.exact_threshold) {
+    // K1n: the gathered K1 keeps the rows whose rank word is <= Kt' -- the k hits and what ties the k-th -- and its last
+    // block sorts them into the result block: no lists, no select (the survivors lie where the lists would)
+    vt::ScanArgs fa = sa;
+    fa.hi_word = ta.kt_word;
+    fa.surv_keys = c.dPartKeys.p;
+    fa.surv_pay = c.dPartPay.p;
+    fa.surv_cap = vt::kScanFilterCap;
+    fa.fsync = chain_words;
+    fa.out = c.dResMapped;
+    fa.info = info;
+    VT_HIP(vt::launch_scan_filter(fa, rescore_blocks, c.stream));
+    VT_HIP(hipStreamSynchronize(c.stream));
+    delivered = c.hSkInfo.p[0] == vt::kScanFilterDelivered;
+  }
+  if (!delivered && (!kind.exact_threshold || c.hSkInfo.p[0] == 2u)) {
+    // (K1n, certified but not delivered -- more survivors than the short list holds: thousands of rows tie the k-th key,
+    // or the refine kept the sketch's own Kt: the lists and their select over the candidates still on the device, behind
+    // a second wait.  Not a fallback.)
+    VT_HIP(vt::launch_scan_batch(sa, rescore_blocks, 1, c.stream));
+    VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, rescore_blocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
+                             c.dSelKeys.p, c.dSelPay.p, c.stream));
+    VT_HIP(hipStreamSynchronize(c.stream));
+  }
+  const bool certified = (delivered || c.hSkInfo.p[0] == 2u) && c.hRes.p->status == 0;
+  if (delivered && certified) c.prof.sketch4_finished += 1;
   if (c.profiling) {
     float ms = 0.f;
     VT_TRY(c.span_ms(&ms));
@@ -573,7 +603,7 @@ int sketch5_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   return sketch6_search(ix, c, query, limit, done, out, 5);
 }
 
-// K1n: blit, the 4-bit pass, the threshold, refine and collect kernels, the gathered K1 and its select behind one host wait.
+// K1n: blit, the 4-bit pass, the threshold, refine and collect kernels and the filtered K1 that finishes behind one host wait.
 int sketch4_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
   return sketch6_search(ix, c, query, limit, done, out, 4);
 }

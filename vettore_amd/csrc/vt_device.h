@@ -72,7 +72,24 @@ struct ScanArgs {
   // position i writes key_out[i] (kEmptyKey if the row is excluded) and, if given, pay_out[i].
   uint64_t *key_out;
   Payload *pay_out;
+  // Filter mode (launch_scan_filter alone; null / zero everywhere else): a row is kept iff it is valid by the rules above
+  // and its rank word is <= *hi_word.  The kept rows go to surv_keys / surv_pay[0 .. surv_cap) at places claimed on
+  // fsync[0]; a place past surv_cap raises fsync[1]; fsync[2] is the top ticket and fsync[kScanFilterLine * (1 + g)] the
+  // ticket of block group g < kScanFilterGroups.  The caller hands fsync[0 .. kScanFilterSyncWords) over zeroed.  The block that draws the last ticket sorts the survivors and writes the k best to *out (status taken from
+  // *status and cleared), then info[0] = kScanFilterDelivered; on overflow, or with no rows to scan, it leaves info alone.
+  const uint32_t *hi_word;
+  uint64_t *surv_keys;
+  Payload *surv_pay;
+  uint32_t surv_cap;
+  uint32_t *fsync;
+  ResultBlock *out;
+  uint32_t *info;
 };
+constexpr uint32_t kScanFilterCap = 1024;       // the survivor list's room: select_topk_kernel's short-list bound
+constexpr uint32_t kScanFilterGroups = 32;      // ticket words below the top one: a thousand blocks queue on none of them
+constexpr uint32_t kScanFilterLine = 32;        // words between them: a 128-byte line each
+constexpr uint32_t kScanFilterSyncWords = kScanFilterLine * (1 + kScanFilterGroups);
+constexpr uint32_t kScanFilterDelivered = 3u;   // info[0] once the filtered K1 has written the result itself
 
 // Rows per wave tile for a scan of n rows of dimension d on `resident_waves` waves:
 // 32 when there is plenty of work per wave; 16 or 8 when there are few tiles per
@@ -116,6 +133,10 @@ int scan_multi_blocks_per_cu(uint32_t d, uint32_t k, int metric);  // 3 for the 
 hipError_t launch_scan_multi(const MultiScanArgs &a, uint32_t blocks, hipStream_t s);
 // Batch mode: `blocks` per query x `nq` queries.
 hipError_t launch_scan_batch(const ScanArgs &a, uint32_t blocks, uint32_t nq, hipStream_t s);
+// K1n's last link (vt_scan_filter.hip): launch_scan_batch for ONE query in filter mode (ScanArgs::hi_word and the fields
+// behind it).  No partial lists and no select behind it: the launch leaves the sorted result in *out itself whenever at
+// most kScanFilterCap rows pass the filter.  dot-family metrics only (cosine, dot, negative dot).
+hipError_t launch_scan_filter(const ScanArgs &a, uint32_t blocks, hipStream_t s);
 
 // K3: selects the k smallest of keys[0..m) (kEmptyKey ignored) by radix select,
 // writes them sorted ascending with their payloads to out->e, out->count;

@@ -1335,6 +1335,7 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch4_fallbacks += p.sketch4_fallbacks;
       t.sketch4_builds += p.sketch4_builds;
       t.sketch4_patched_rows += p.sketch4_patched_rows;
+      t.sketch4_finished += p.sketch4_finished;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

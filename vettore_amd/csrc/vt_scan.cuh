@@ -208,6 +208,102 @@ __device__ __noinline__ static float recover_overflow(int metric, const float *q
   }
 }
 
+// ---- filter mode (FILTER below): the survivor list and the finish ------------------------------
+__device__ __forceinline__ uint32_t filter_agent_add(uint32_t *p, uint32_t v) {
+  return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A place in the survivor list for each lane with `on`: the wave's lanes are counted by ballot and the counter takes one
+// returning agent-scope atomic per wave (wave_claim's form, vt_sketch.hip).  Called by whole waves.
+__device__ __forceinline__ uint32_t filter_claim(uint32_t *counter, bool on, int lane) {
+  const uint64_t act = __ballot(on);
+  if (!act) return 0u;
+  const int leader = __ffsll((long long)act) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = filter_agent_add(counter, (uint32_t)__popcll(act));
+  base = (uint32_t)__shfl((int)base, leader, kWave);
+  return base + (uint32_t)__popcll(act & ((1ull << lane) - 1ull));
+}
+
+// (a block's flag: some row of it passed the filter -- static LDS of the filter-mode kernels alone)
+__device__ __forceinline__ uint32_t *filter_stored_flag() {
+  __shared__ uint32_t f_stored;
+  return &f_stored;
+}
+
+// The end of a filter-mode block: the collect's exchange (vt_sketch.hip) -- every wave's stores and atomics drained, the
+// block barrier, one lane's agent-scope release and its draw of a ticket with a returning atomic.  A block that is not
+// last ends; nothing polls.  One word takes about 88 atomics a us and this grid is a thousand blocks that end together
+// (a queue of 12 us, measured: profiles/sketch4_tail/), so the tickets are drawn in two levels: block b draws on the word
+// of its group b % kScanFilterGroups -- a cache line of its own --, and the last of a group draws on the top word for
+// it.  A block none of whose rows passed has stored nothing and skips the release (`stored`: an LDS flag its waves raise).
+// The block that draws the last top ticket reads what the others wrote -- the survivor count, the overflow word, the
+// entries -- through agent-scope atomics alone, never a plain load and never the scalar path; it rank-sorts the survivors
+// by their full u64 key as select_topk_kernel's short-list branch does (smaller first, equal keys by position) and
+// writes the first k into the host-mapped result block.  With more survivors than the list holds, or no rows scanned (the
+// collect refused), info[] stays as the collect wrote it and the caller queues today's scan and select.
+__device__ __forceinline__ void filter_finish(const ScanArgs &a, uint32_t nrows, uint32_t nblocks, const uint32_t *stored) {
+  __shared__ uint64_t f_keys[kScanFilterCap], f_pay[kScanFilterCap];
+  __shared__ uint32_t f_last, f_n;
+  const uint32_t tid = threadIdx.x;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    if (*stored) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    const uint32_t groups = nblocks < kScanFilterGroups ? nblocks : kScanFilterGroups;
+    const uint32_t g = blockIdx.x % groups, members = (nblocks - g + groups - 1) / groups;
+    uint32_t last = 0, n = 0;
+    if (filter_agent_add(a.fsync + kScanFilterLine * (1 + g), 1u) == members - 1)  // the group's last: every member drew before it
+      last = filter_agent_add(a.fsync + 2, 1u) == groups - 1 ? 1u : 0u;
+    if (last) {  // every other block has claimed, stored and flagged before its group's last drew
+      n = filter_agent_add(a.fsync + 0, 0u);
+      const uint32_t over = __hip_atomic_fetch_or(a.fsync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (nrows == 0) {  // nothing was handed over: an empty result, info untouched
+        a.out->count = 0;
+        last = 0;
+      } else if (over || n > a.surv_cap) {
+        last = 0;
+      }
+    }
+    f_last = last;
+    f_n = n;
+  }
+  __syncthreads();
+  if (!f_last) return;
+  const uint32_t n = f_n;
+  for (uint32_t i = tid; i < n; i += blockDim.x) {
+    f_keys[i] = __hip_atomic_load(a.surv_keys + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    f_pay[i] = __hip_atomic_load(reinterpret_cast<const uint64_t *>(a.surv_pay + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  for (uint32_t i = tid; i < n; i += blockDim.x) {
+    const uint64_t key = f_keys[i];
+    uint32_t pos = 0;
+    for (uint32_t x = 0; x < n; ++x) {
+      const uint64_t kx = f_keys[x];
+      pos += (kx < key || (kx == key && x < i)) ? 1u : 0u;
+    }
+    if (pos < a.k) {
+      const uint64_t pv = f_pay[i];
+      Entry e;
+      e.key = key;
+      e.row = (uint32_t)pv;                          // (Payload: row, then raw)
+      e.raw = __uint_as_float((uint32_t)(pv >> 32));
+      a.out->e[pos] = e;
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    a.out->count = n < a.k ? n : a.k;
+    a.out->status = atomicExch(a.status, 0);  // (every block's atomicMax is behind its ticket)
+    a.info[0] = kScanFilterDelivered;
+  }
+}
+
 // Position of a wave in its stream of 1-KiB segments: tile t, column panel p,
 // segment s of that panel (all wave-uniform), and this lane's (row in tile,
 // column in panel) of the 4 floats it loads there.
@@ -223,7 +319,10 @@ struct Cursor {
 // property: a query pointer that may be either is a generic pointer, its loads are flat_load, a
 // flat_load counts against vmcnt as well as lgkmcnt, and the wait for the query fragment then
 // drains the whole register ring at every segment (r03, measured: gathered scans ran one load deep).
-template <int OP, int ORDER, int CAP, bool GENERAL, bool PADDED, bool QGLOBAL = false>
+// FILTER (gathered scans of one query, vt_scan_filter.hip): no lists -- the rows whose rank word is <= *a.hi_word go to the
+// survivor list, and the last block to finish sorts them and writes the result (filter_finish above).  Every FILTER
+// branch is `if constexpr`: the other instantiations are what they were.
+template <int OP, int ORDER, int CAP, bool GENERAL, bool PADDED, bool QGLOBAL = false, bool FILTER = false>
 __global__ __launch_bounds__(kWavesPerBlock *kWave) void scan_topk_kernel(const ScanDev sd) {
   extern __shared__ __align__(16) float lds[];
   const ScanArgs &a = sd.a;
@@ -251,6 +350,9 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void scan_topk_kernel(const 
   }
   if (!QGLOBAL)
     for (uint32_t i = threadIdx.x; i < p.ld; i += blockDim.x) lds[i] = qsrc[i];
+  if constexpr (FILTER) {
+    if (threadIdx.x == 0) *filter_stored_flag() = 0;
+  }
   __syncthreads();
 
   const int op_rt = metric_op(a.metric);
@@ -259,7 +361,9 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void scan_topk_kernel(const 
   const uint32_t ntiles = GENERAL ? (nrows + p.tr - 1) / p.tr : p.ntiles;
 
   WaveTopK<CAP> tk;
-  tk.init(tkbuf, a.k);
+  if constexpr (!FILTER) tk.init(tkbuf, a.k);
+  uint32_t hi_word = 0;
+  if constexpr (FILTER) hi_word = *a.hi_word;  // (an earlier launch's word: a plain load)
 
   if (wave_global < ntiles) {
     const uint32_t last_tile = wave_global + ((ntiles - 1 - wave_global) / total_waves) * total_waves;
@@ -465,7 +569,22 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void scan_topk_kernel(const 
       else if (metric == M_IP) rank = -raw;
       const uint64_t key = ((uint64_t)orderable(rank) << 32) | my_rank;
       if (a.has_lo) valid = valid && key > a.lo_key;
-      if (a.key_out) {  // key-column mode (wave-uniform)
+      if constexpr (FILTER) {
+        const bool keep = valid && (uint32_t)(key >> 32) <= hi_word;
+        const uint32_t pos = filter_claim(a.fsync + 0, keep, lane);
+        if (keep) {
+          if (pos < a.surv_cap) {
+            *filter_stored_flag() = 1;
+            a.surv_keys[pos] = key;
+            Payload pv;
+            pv.row = src_row;
+            pv.raw = raw;
+            a.surv_pay[pos] = pv;
+          } else {
+            __hip_atomic_fetch_or(a.fsync + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+        }
+      } else if (a.key_out) {  // key-column mode (wave-uniform)
         if (row_valid) {
           a.key_out[grow] = valid ? key : kEmptyKey;
           if (a.pay_out) {
@@ -480,13 +599,17 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void scan_topk_kernel(const 
       }
     }
   }
-  // one list per block: wave 0 absorbs the other waves' buffers
-  if (a.key_out) return;
-  __shared__ uint32_t s_counts[kWavesPerBlock];
-  tk.merge_block(wib, kWavesPerBlock, s_counts, lane);
-  if (wib == 0)
-    tk.store(a.part_keys + (size_t)(list_base + blockIdx.x) * a.k, a.part_pay + (size_t)(list_base + blockIdx.x) * a.k,
-             lane);
+  if constexpr (FILTER) {
+    filter_finish(a, nrows, gridDim.x, filter_stored_flag());
+  } else {
+    // one list per block: wave 0 absorbs the other waves' buffers
+    if (a.key_out) return;
+    __shared__ uint32_t s_counts[kWavesPerBlock];
+    tk.merge_block(wib, kWavesPerBlock, s_counts, lane);
+    if (wib == 0)
+      tk.store(a.part_keys + (size_t)(list_base + blockIdx.x) * a.k, a.part_pay + (size_t)(list_base + blockIdx.x) * a.k,
+               lane);
+  }
 }
 
 constexpr size_t kMaxLds = 160 * 1024;
@@ -498,9 +621,9 @@ inline hipError_t allow_lds(K kernel, size_t bytes) {
                              (int)bytes);
 }
 
-template <int OP, int ORDER, int CAP, bool GENERAL, bool PADDED, bool QGLOBAL = false>
+template <int OP, int ORDER, int CAP, bool GENERAL, bool PADDED, bool QGLOBAL = false, bool FILTER = false>
 inline hipError_t launch_scan_t(const ScanDev &sd, uint32_t blocks, size_t lds, hipStream_t s, uint32_t nq = 1) {
-  auto kern = scan_topk_kernel<OP, ORDER, CAP, GENERAL, PADDED, QGLOBAL>;
+  auto kern = scan_topk_kernel<OP, ORDER, CAP, GENERAL, PADDED, QGLOBAL, FILTER>;
   hipError_t e = allow_lds(kern, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(blocks, nq), dim3(kWavesPerBlock * kWave), lds, s, sd);
@@ -514,6 +637,7 @@ hipError_t launch_scan_misc(const ScanDev &sd, uint32_t blocks, size_t lds, bool
 hipError_t launch_scan_l1(const ScanDev &sd, uint32_t blocks, size_t lds, bool padded, hipStream_t s);
 hipError_t launch_scan_general(const ScanDev &sd, uint32_t blocks, uint32_t nq, size_t lds, hipStream_t s);
 hipError_t launch_scan_gather(const ScanDev &sd, uint32_t blocks, uint32_t nq, size_t lds, hipStream_t s);
+hipError_t launch_scan_filter_t(const ScanDev &sd, uint32_t blocks, size_t lds, hipStream_t s);
 constexpr int kDefaultReduceOrder = 3;  // VT_ORDER_SSE2 (include/vettore_flat.h)
 
 // order (0..3) x candidate buffer (k <= kSmallK -> small) x padded
