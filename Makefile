@@ -50,7 +50,7 @@ NOSCRATCH_vt_maxsim_resident := maxsim_resident_kernel
 # K9rb (K9r over many query sets): the same pass (vt_maxsim_pair.cuh), the sets' totals in registers -- no scratch segment
 NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 # K10 (MUVERA): one lane's f64 chain per dot product, nothing indexed dynamically in registers
-NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_sketch_kernel muvera_table_kernel
+NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_encode_slab_kernel muvera_sketch_kernel muvera_table_kernel
 # K1q, K1s, K1f and K1n (the int8, 6-bit, 5-bit and 4-bit sketch passes): the register ring must stay in registers; K1q's
 # tail and the threshold, refine and collect kernels behind the other three likewise carry no scratch segment
 NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_thresh_kernel sketch_refine_kernel sketch_collect_kernel

@@ -636,6 +636,60 @@ int vt_muvera_encode(int device, int mode, size_t count, const size_t *set_vec_o
 size_t vt_muvera_fde_dimension(size_t num_repetitions, size_t num_simhash_projections, size_t projection_dimension,
                                size_t final_projection_dimension, int final_is_some);
 
+/* ------------------------------------------- MUVERA retrieval over a resident multi-vector store
+ * The reference's four steps (README, "MUVERA": encode the query, encode every document, search the encodings with
+ * inner product, rerank the candidates with exact MaxSim -- muvera.rs:26-74, flat.rs:98-135, multi_vector.rs:40-122)
+ * joined over documents that are already in device memory.  The configuration is vt_muvera_encode's seven trailing
+ * arguments.  `index` is a flat handle that holds one row per encodable document, its document-mode encoding:
+ * single-shard (else VT_ERR_UNSUPPORTED, vt_last_error says so), on the store's device (else VT_ERR_ARGUMENT), with
+ * metric VT_INNER_PRODUCT (else VT_ERR_ARGUMENT), and, when it is not empty, of the encoding's dimension (else
+ * VT_ERR_DIMENSION, before anything changes).  A NULL handle is VT_ERR_ARGUMENT.
+ *
+ * vt_mv_encode_documents: row i of `out` is what vt_muvera_encode(mode 1) returns for the vectors of document ids[i], bit
+ * for bit, read from the store's rows (no upload).  The call's own checks, in order: NULL arguments, the configuration
+ * (muvera.rs:81-95), the sizes (:29-42), VT_ERR_DIMENSION when the store has a dimension other than `dimension`.  A
+ * listed id that is not live, or a live document without vectors, is VT_ERR_EMPTY_SET (muvera.rs:79) with a zero row;
+ * "encoding overflow" on the device (muvera.rs:175, :195) likewise.  With doc_status NULL, or count 1, the first failing
+ * document's status is returned (vt_muvera_encode's convention).
+ *
+ * vt_mv_fde_sync brings `index` in line with the store for the listed ids (count 0 with ids NULL: every live document,
+ * in store order).  After VT_OK `index` holds a listed id, with exactly the row above, if the store holds it live with a
+ * vector and its encoding succeeded, and does not hold it otherwise; every other id of `index` is untouched; a duplicate
+ * counts once.  doc_status: VT_OK for a document stored and for an id that is not live (removed from `index`),
+ * VT_ERR_EMPTY_SET for a live document without vectors (removed), VT_ERR_ENCODING_OVERFLOW (removed); with doc_status
+ * NULL the first failing document's status is returned, the index synced for every listed id all the same.  The
+ * encodings never visit the host.  The store's mutex is held for the whole call and the index is changed through its own
+ * entry points under its own lock: a search of `index` that runs meanwhile may see the sync half applied.  A device
+ * failure half-way leaves the store untouched and the index possibly partly synced; calling again repairs it.
+ *
+ * vt_mv_fde_top_k answers exactly vt_mv_top_k_ids(store, ids of H, query, metric, limit) -- ids, order, score bits, rank
+ * keys -- where H = vt_flat_search(index, the query-mode encoding of `query`, candidates), under one hold of the store's
+ * mutex.  Statuses arise in this order: NULL arguments; the index requirements; vt_mv_top_k's validation up to the device
+ * (metric, the query vectors on their own, their length against the store's dimension); vt_muvera_encode(mode 0, count
+ * 1)'s (no query vector: VT_ERR_EMPTY_SET); vt_flat_search's; the rerank's.  limit 0 still does all the work and returns
+ * an empty list; candidates 0 or an empty index returns an empty list.
+ *
+ * vt_mv_fde_top_k_batch: out[b] and set_status[b] are vt_mv_fde_top_k's for set b on the same state, in one encoding
+ * call, one vt_flat_search_batch and one batched rerank; NULL set_status, call-level failures and nsets == 0 follow
+ * vt_mv_top_k_ids_batch. */
+int vt_mv_encode_documents(vt_mv *store, size_t count, const char *ids, const size_t *id_off, size_t dimension,
+                           size_t num_repetitions, size_t num_simhash_projections, uint64_t seed, size_t projection_dimension,
+                           size_t final_projection_dimension, int final_is_some, float *out /* [count][fde] */,
+                           int *doc_status /* count, may be NULL */);
+int vt_mv_fde_sync(vt_mv *store, vt_flat *index, size_t count, const char *ids, const size_t *id_off, size_t dimension,
+                   size_t num_repetitions, size_t num_simhash_projections, uint64_t seed, size_t projection_dimension,
+                   size_t final_projection_dimension, int final_is_some, int *doc_status /* count, may be NULL */);
+int vt_mv_fde_top_k(vt_mv *store, vt_flat *index, size_t dimension, size_t num_repetitions, size_t num_simhash_projections,
+                    uint64_t seed, size_t projection_dimension, size_t final_projection_dimension, int final_is_some,
+                    const float *query, const size_t *query_off, size_t nquery, size_t candidates, int metric_code,
+                    size_t limit, vt_hits **out);
+int vt_mv_fde_top_k_batch(vt_mv *store, vt_flat *index, size_t dimension, size_t num_repetitions,
+                          size_t num_simhash_projections, uint64_t seed, size_t projection_dimension,
+                          size_t final_projection_dimension, int final_is_some, size_t nsets,
+                          const size_t *set_vec_off /* nsets + 1 */, const float *query, const size_t *query_off,
+                          size_t candidates, int metric_code, size_t limit, vt_hits **out /* nsets */,
+                          int *set_status /* nsets, may be NULL */);
+
 /* ------------------------------------------------------------ profiling
  * Device-side timing of the dominant kernels with HIP events on the stream the
  * kernels are launched on (bench.py's roofline figure). */

@@ -36,6 +36,7 @@ SYMBOLS = [
     "vt_multi_vector_score", "vt_multi_vector_top_k", "vt_muvera_encode", "vt_muvera_fde_dimension",
     "vt_mv_new", "vt_mv_free", "vt_mv_put_many", "vt_mv_delete", "vt_mv_len", "vt_mv_dimension", "vt_mv_top_k", "vt_mv_top_k_ids",
     "vt_mv_memory", "vt_mv_top_k_batch", "vt_mv_top_k_ids_batch", "vt_mv_counters",
+    "vt_mv_encode_documents", "vt_mv_fde_sync", "vt_mv_fde_top_k", "vt_mv_fde_top_k_batch",
     "vt_hnsw_new", "vt_hnsw_free", "vt_hnsw_insert", "vt_hnsw_insert_many", "vt_hnsw_delete", "vt_hnsw_search", "vt_hnsw_search_batch",
     "vt_hnsw_len", "vt_hnsw_dimension", "vt_hnsw_node", "vt_hnsw_neighbors", "vt_hnsw_counters", "vt_hnsw_memory",
     "vt_mmr_rerank", "vt_flat_mmr_rerank", "vt_flat_mmr_rerank_batch", "vt_flat_mmr_search", "vt_flat_mmr_search_batch",
@@ -196,6 +197,12 @@ def load() -> C.CDLL:
     L.vt_mv_top_k_ids_batch.argtypes = [vp, C.c_size_t, szp, C.c_char_p, szp, szp, f32p, szp, C.c_int, C.c_size_t,
                                         C.POINTER(vp), C.POINTER(C.c_int)]
     L.vt_mv_counters.argtypes = [vp, u64p, u64p]
+    cfg = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64, C.c_size_t, C.c_size_t, C.c_int]  # vt_muvera_encode's seven
+    L.vt_mv_encode_documents.argtypes = [vp, C.c_size_t, C.c_char_p, szp] + cfg + [f32p, C.POINTER(C.c_int)]
+    L.vt_mv_fde_sync.argtypes = [vp, vp, C.c_size_t, C.c_char_p, szp] + cfg + [C.POINTER(C.c_int)]
+    L.vt_mv_fde_top_k.argtypes = [vp, vp] + cfg + [f32p, szp, C.c_size_t, C.c_size_t, C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.vt_mv_fde_top_k_batch.argtypes = [vp, vp] + cfg + [C.c_size_t, szp, f32p, szp, C.c_size_t, C.c_int, C.c_size_t,
+                                                         C.POINTER(vp), C.POINTER(C.c_int)]
     L.vt_hnsw_new.argtypes = [C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]
     L.vt_hnsw_free.restype = None
     L.vt_hnsw_free.argtypes = [vp]

@@ -17,6 +17,7 @@ from . import nifs
 from .index_flat import FlatGpu, Result, result_values, MAX_NIF_USIZE
 from .index_hnsw import HnswGpu
 from .mv_store import ResidentMultiVector
+from . import muvera as muvera_mod
 
 F32_MAX = 3.4028234663852886e38  # collection.ex:61
 METRIC_ALIASES = {"euclidean": "l2", "dot": "inner_product", "dot_product": "inner_product"}  # :1300-1304
@@ -85,6 +86,18 @@ class Collection:
             resident = index_options.pop("resident_multi_vector")
             if not isinstance(resident, bool):
                 return ("error", "invalid_index_options")
+        # `muvera: {...}` (the collection's own as well, only beside resident_multi_vector: true): the resident documents'
+        # fixed-dimensional encodings are kept in a second, inner-product flat handle that muvera_search draws candidates from
+        muvera_cfg = None
+        if isinstance(index_options, dict) and "muvera" in index_options:
+            index_options = dict(index_options)
+            given = muvera_mod._keyword(index_options.pop("muvera"))
+            if given is None or not resident:
+                return ("error", "invalid_index_options")
+            normalized = muvera_mod._normalize_config(given, dimensions)   # (defaults: muvera.ex:83-94)
+            if isinstance(normalized, str):
+                return ("error", "invalid_index_options")
+            muvera_cfg = muvera_mod._args(normalized)
         made = index_mod.new(metric, index_options or [])
         if made[0] != "ok":
             return made
@@ -95,8 +108,15 @@ class Collection:
                 mv_store = ResidentMultiVector(device)
             except RuntimeError as e:
                 return ("error", str(e))
+        fde_index = None
+        if muvera_cfg is not None:
+            try:
+                fde_index = nifs.flat_new_sharded(nifs.METRIC_CODE["inner_product"], [device])
+            except RuntimeError as e:
+                return ("error", str(e))
         self = object.__new__(cls)
         self.mv_store = mv_store
+        self.muvera_config, self.fde_index = muvera_cfg, fde_index
         self.name, self.dimensions, self.metric = name, dimensions, metric
         self.normalize, self.score = normalize, score
         self.index_mod, self.index_state = index_mod, made[1]
@@ -264,6 +284,15 @@ class Collection:
             if self.mv_store is not None:
                 self.mv_store.delete(e.id)
             self.store.pop(e.id, None)
+        self._fde_follow([e.id for e in embs])
+
+    def _fde_follow(self, ids):
+        """The FDE index follows the resident store for the ids a call touched.  A document whose encoding overflows is
+        simply absent from it (the put stands); only a failure of the call itself is an error."""
+        if self.fde_index is None or not ids:
+            return "ok"
+        res = self.mv_store.fde_sync(self.fde_index, ids, self.muvera_config)
+        return "ok" if res[0] == "ok" else res
 
     _MV_ERRORS = {"score overflow": "score_overflow", "dimension mismatch": "dimension_mismatch",
                   "vector contains a non-finite value": "invalid_multi_vector"}
@@ -274,7 +303,9 @@ class Collection:
         if self.mv_store is None:
             return "ok"
         res = self.mv_store.put_many([(e.id, e.vectors if e.vectors else [e.vector]) for e in embs])
-        return res if res == "ok" else ("error", self._MV_ERRORS.get(res[1], res[1]))
+        if res != "ok":
+            return ("error", self._MV_ERRORS.get(res[1], res[1]))
+        return self._fde_follow([e.id for e in embs])
 
     def delete(self, id_):
         if not isinstance(id_, (str, bytes)):
@@ -284,6 +315,7 @@ class Collection:
         if res == "ok":
             if self.mv_store is not None:
                 self.mv_store.delete(idb)
+                self._fde_follow([idb])
             self.store.pop(idb, None)
         return res
 
@@ -367,6 +399,61 @@ class Collection:
         out = [self._prepare_vectors(q) for q in query_vector_lists]
         valid = [i for i, qv in enumerate(out) if qv[0] == "ok"]
         res = self.mv_store.top_k_batch([out[i][1] for i in valid], nifs.METRIC_CODE[metric], limit)
+        if not isinstance(res, list):   # the call itself failed: every entry's answer
+            res = [res] * len(valid)
+        for i, r in zip(valid, res):
+            out[i] = self._resident_answer(r, metric)
+        return out
+
+    # -- the reference's MUVERA flow (README: encode, search the encodings by inner product, rerank with MaxSim) over
+    # the resident store and its FDE index
+    def _muvera_options(self, opts):
+        """("ok", metric, limit, candidates), or the error every search with these options returns."""
+        opts = {} if opts is None else opts
+        if not isinstance(opts, dict):
+            return ("error", "invalid_options")
+        bad = [k for k in opts if k not in ("limit", "candidates", "metric")]
+        if bad:
+            return ("error", ("unsupported_option", bad[0]))
+        parsed = self._multi_vector_options({k: v for k, v in opts.items() if k != "candidates"})
+        if parsed[0] != "ok":
+            return parsed
+        _, metric, limit = parsed
+        candidates = opts.get("candidates", max(limit * 10, limit))      # candidate_count, collection.ex:510
+        if not (isinstance(candidates, int) and not isinstance(candidates, bool) and limit <= candidates <= MAX_NIF_USIZE):
+            return ("error", "invalid_candidates")                          # collection.ex:889-895
+        return ("ok", metric, limit, candidates)
+
+    def muvera_search(self, query_vectors, opts=None):
+        """multi_vector_search over the `candidates` stored embeddings whose encodings score highest against the
+        query's: Results carry the exact MaxSim score."""
+        if self.fde_index is None:
+            return ("error", "muvera_not_configured")
+        parsed = self._muvera_options(opts)
+        if parsed[0] != "ok":
+            return parsed
+        _, metric, limit, candidates = parsed
+        qv = self._prepare_vectors(query_vectors)
+        if qv[0] != "ok":
+            return qv
+        res = self.mv_store.fde_top_k(self.fde_index, self.muvera_config, qv[1], candidates, nifs.METRIC_CODE[metric], limit)
+        return self._resident_answer(res, metric)
+
+    def muvera_search_batch(self, query_vector_lists, opts=None):
+        """muvera_search for every entry of a list of query-vector lists: element-wise what muvera_search returns, the
+        valid entries in one batched call."""
+        if self.fde_index is None:
+            return ("error", "muvera_not_configured")
+        if not isinstance(query_vector_lists, (list, tuple)):
+            return ("error", "invalid_multi_vector")
+        parsed = self._muvera_options(opts)
+        if parsed[0] != "ok":
+            return [parsed for _ in query_vector_lists]
+        _, metric, limit, candidates = parsed
+        out = [self._prepare_vectors(q) for q in query_vector_lists]
+        valid = [i for i, qv in enumerate(out) if qv[0] == "ok"]
+        res = self.mv_store.fde_top_k_batch(self.fde_index, self.muvera_config, [out[i][1] for i in valid], candidates,
+                                            nifs.METRIC_CODE[metric], limit)
         if not isinstance(res, list):   # the call itself failed: every entry's answer
             res = [res] * len(valid)
         for i, r in zip(valid, res):

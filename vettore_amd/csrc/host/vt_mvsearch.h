@@ -46,6 +46,9 @@ struct vt_mv {
   PinnedBuf<unsigned long long> hBFirst;
   // vt_mv_counters: launches of a MaxSim scoring kernel (K9, K9r, K9rb) and query sets scored by K9rb, since vt_mv_new
   uint64_t scoring_launches = 0, batched_sets = 0;
+  // the documents' MUVERA encodings (host/vt_fde.h): a call's table and slot lists, a chunk's rows, first rows and counts
+  MuveraState F;
+  DevBuf<uint32_t> dFdeDoc;
 };
 
 namespace {

@@ -661,6 +661,18 @@ uint32_t muvera_reps_per_wave(uint32_t R, uint32_t k, uint32_t C, int mode);
 size_t muvera_lds_bytes(const MuveraArgs &a);
 hipError_t launch_muvera_table(uint64_t seed, uint32_t R, uint32_t d, uint32_t k, uint32_t C, float *table, hipStream_t s);
 hipError_t launch_muvera_encode(const MuveraArgs &a, hipStream_t s);
+// K10s: K10 over the slab of a resident multi-vector store (vt_mv_encode_documents, vt_mv_fde_sync).  Set i is the
+// doc_cnt[i] rows from row doc_first[i] on of a.X, `stride` floats apart (a multiple of 4 >= a.d, so every row starts on
+// 16 bytes; the pad is zero and never enters a sum); a.set_off is not read.  Only the addressing and the load of a vector
+// into LDS differ from K10: the arithmetic behind it is the one device function both kernels call, so the bits are K10's.
+struct MuveraSlabArgs {
+  MuveraArgs a;
+  const uint32_t *doc_first;  // [nsets]
+  const uint32_t *doc_cnt;    // [nsets]  (0: the set keeps its zero row)
+  uint32_t stride;
+};
+size_t muvera_slab_lds_bytes(const MuveraSlabArgs &a);
+hipError_t launch_muvera_encode_slab(const MuveraSlabArgs &a, hipStream_t s);
 // out[set][s] = the sequential f32-rounded signed sum of full[set][i] over list[off[s] .. off[s + 1]) (low 31 bits: i,
 // increasing; bit 31: sign -1)   muvera.rs:180-200
 hipError_t launch_muvera_sketch(const float *full, size_t out_size, uint32_t nsets, uint32_t final_dim, const uint32_t *off,

@@ -40,6 +40,7 @@
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
 #include "host/vt_mmrplan.h"
+#include "host/vt_fdeplan.h"
 #include "host/vt_concurrency.h"
 #include "host/vt_base.h"
 #include "host/vt_types.h"
@@ -60,6 +61,7 @@
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
 #include "host/vt_mmr.h"
+#include "host/vt_fde.h"
 
 // =============================================================== C ABI
 extern "C" {
@@ -1160,6 +1162,52 @@ size_t vt_muvera_fde_dimension(size_t num_repetitions, size_t num_simhash_projec
   if (muvera_check_config(m) != VT_OK || muvera_check_sizes(m, &out_size, &fde) != VT_OK) return 0;
   return fde;
 }
+
+#define VT_MUVERA_CFG_PARAMS                                                                                          \
+  size_t dimension, size_t num_repetitions, size_t num_simhash_projections, uint64_t seed, size_t projection_dimension, \
+      size_t final_projection_dimension, int final_is_some
+#define VT_MUVERA_CFG \
+  MuveraConfig { dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension, final_is_some != 0 }
+
+int vt_mv_encode_documents(vt_mv *s, size_t count, const char *ids, const size_t *id_off, VT_MUVERA_CFG_PARAMS, float *out,
+                           int *doc_status) {
+  return guarded([&]() -> int {
+  if (!s || (count && (!id_off || !ids))) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(s->mu);
+  return mv_encode_documents(s, count, ids, id_off, VT_MUVERA_CFG, out, doc_status);
+  });
+}
+
+int vt_mv_fde_sync(vt_mv *s, vt_flat *index, size_t count, const char *ids, const size_t *id_off, VT_MUVERA_CFG_PARAMS,
+                   int *doc_status) {
+  return guarded([&]() -> int {
+  if (!s || !index || (count && (!id_off || !ids))) return VT_ERR_ARGUMENT;
+  std::lock_guard<std::mutex> g(s->mu);
+  return mv_fde_sync(s, index, count, ids, id_off, VT_MUVERA_CFG, doc_status);
+  });
+}
+
+int vt_mv_fde_top_k(vt_mv *s, vt_flat *index, VT_MUVERA_CFG_PARAMS, const float *query, const size_t *query_off, size_t nquery,
+                    size_t candidates, int metric_code, size_t limit, vt_hits **out) {
+  return guarded([&]() -> int {
+  if (!s || !index || !out || (nquery && !query_off)) return VT_ERR_ARGUMENT;
+  *out = nullptr;
+  std::lock_guard<std::mutex> g(s->mu);
+  return mv_fde_top_k(s, index, VT_MUVERA_CFG, query, query_off, nquery, candidates, metric_code, limit, out);
+  });
+}
+
+int vt_mv_fde_top_k_batch(vt_mv *s, vt_flat *index, VT_MUVERA_CFG_PARAMS, size_t nsets, const size_t *set_vec_off,
+                          const float *query, const size_t *query_off, size_t candidates, int metric_code, size_t limit,
+                          vt_hits **out, int *set_status) {
+  return guarded([&]() -> int {
+  if (!s || !index || !out || !set_vec_off || (set_vec_off[nsets] && !query_off)) return VT_ERR_ARGUMENT;
+  return mv_fde_batch_call(s, index, VT_MUVERA_CFG, nsets, set_vec_off, query, query_off, candidates, metric_code, limit, out,
+                           set_status);
+  });
+}
+#undef VT_MUVERA_CFG_PARAMS
+#undef VT_MUVERA_CFG
 
 int vt_mmr_rerank(int device, int metric_code, size_t count, size_t d, const float *values, const double *scores, double alpha,
                   size_t final_k, uint32_t *order, size_t *order_len) {

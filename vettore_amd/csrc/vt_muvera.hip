@@ -1,4 +1,5 @@
-// vt_muvera.hip -- K10: MUVERA fixed-dimensional encoding of multi-vector sets (gfx950).
+// vt_muvera.hip -- K10 / K10s: MUVERA fixed-dimensional encoding of multi-vector sets (gfx950), from a dense chunk of
+// uploaded vectors (K10) or from the slab of a resident multi-vector store (K10s).
 //
 // Replaces encode (native/vettore/src/muvera.rs:26-74) under muvera_encode_query / _document, for a chunk of
 // sets at once.  Layout and launch shape: MuveraArgs in vt_device.h.  The result is the reference's bit for bit:
@@ -73,81 +74,133 @@ __device__ __forceinline__ uint32_t partition_of(uint64_t mask, uint32_t g, uint
   return (uint32_t)(__brevll(field) >> (64 - k));
 }
 
-// ---------------------------------------------------------------- the encode kernel
+// ---------------------------------------------------------------- the encode kernels
 // One wave per (set, group of a.rg repetitions).  Lane l serves repetition r0 + l / C and table column l % C when
 // the columns of a.rg repetitions fit in one wave; a repetition with more than 64 columns takes the wave alone and
 // its lanes walk the columns in passes of 64 (the SimHash columns, fewer than 31, are all in the first pass).
+// K10 (muvera_encode_kernel) and K10s (muvera_encode_slab_kernel) differ in where a set's vectors lie and in how one is
+// loaded into LDS; what a wave is (encode_wave) and everything it does with a loaded vector (encode_vector) is shared.
+struct EncodeWave {
+  uint32_t lane, r0, rga;   // the first repetition this wave serves and how many
+  uint32_t g, c1;           // this lane's repetition within the group and its column in the first pass
+  bool live1, wide;
+  float *out;               // the set's row of a.full
+  uint32_t *cnt;            // [rga][P] partition counts (document mode; LDS or device memory), else null
+};
+
+// `lcnt`: the wave's counts in LDS, zeroed here when they are the ones in use (the barrier before the first vector's
+// load stands between that and their first reader).
+__device__ __forceinline__ EncodeWave encode_wave(const MuveraArgs &a, uint32_t *lcnt) {
+  EncodeWave w;
+  w.lane = threadIdx.x;
+  const uint32_t set = (uint32_t)(blockIdx.x / a.groups);
+  w.r0 = (uint32_t)(blockIdx.x % a.groups) * a.rg;
+  w.rga = min(a.rg, a.R - w.r0);
+  const uint32_t C = a.C, P = 1u << a.k;
+  w.out = a.full + (size_t)set * a.out_size;
+  w.cnt = nullptr;
+  if (a.mode == 1) {
+    if (a.counts) {
+      w.cnt = a.counts + ((size_t)set * a.R + w.r0) * P;                  // (zeroed by the host; rg == 1)
+    } else {
+      w.cnt = lcnt;
+      for (uint32_t i = w.lane; i < w.rga * P; i += kWave) w.cnt[i] = 0;
+    }
+  }
+  w.wide = C > (uint32_t)kWave;
+  w.g = w.wide || C == 0 ? 0u : w.lane / C;
+  w.c1 = w.wide || C == 0 ? w.lane : w.lane - w.g * C;
+  w.live1 = C != 0 && w.g < w.rga && w.c1 < C;
+  return w;
+}
+
+// One vector, staged in xs[0 .. d) and visible to the whole wave: its dot products, the sign ballot, the partition
+// counts and the slots it is accumulated into.  true: some slot answered "encoding overflow".
+__device__ __forceinline__ bool encode_vector(const MuveraArgs &a, const EncodeWave &w, const float *xs) {
+  const uint32_t lane = w.lane, r0 = w.r0, rga = w.rga, g = w.g, c1 = w.c1;
+  const uint32_t d = a.d, C = a.C, k = a.k, pd = a.pd;
+  const uint32_t P = 1u << k;
+  const bool live1 = w.live1;
+  float *out = w.out;
+  uint32_t *cnt = w.cnt;
+  bool failed = false;
+
+  // first pass: every SimHash column and the first projection columns
+  double dot = 0.0;
+  if (live1) {
+    const float *t = a.table + (size_t)(r0 + g) * d * C + c1;
+    for (uint32_t j = 0; j < d; ++j) dot += (double)xs[j] * (double)t[(size_t)j * C];
+  }
+  const uint64_t mask = __ballot(live1 && c1 < k && dot >= 0.0);
+  const uint32_t part = partition_of(mask, g, C, k);
+
+  if (a.mode == 1) {  // counts[count_index] += 1 (muvera.rs:55): one lane per repetition of the group
+    if (lane < rga) {
+      uint32_t *slot = cnt + (size_t)lane * P + partition_of(mask, lane, C, k);
+      *slot = *slot + 1;
+    }
+    __syncthreads();
+  }
+
+  if (a.identity) {
+    // muvera.rs:141-146: the coordinates themselves, lanes over (repetition, coordinate)
+    for (uint32_t i = lane; i < rga * d; i += kWave) {
+      const uint32_t gi = i / d, q = i - gi * d;
+      const uint32_t pi = partition_of(mask, gi, C, k);
+      const uint32_t count = a.mode == 1 ? cnt[(size_t)gi * P + pi] : 1u;
+      if (!accumulate(out + (size_t)(r0 + gi) * a.rep_size + (size_t)pi * pd + q, (double)xs[q], a.mode, count)) failed = true;
+    }
+  } else {
+    const uint32_t count = a.mode == 1 && g < rga ? cnt[(size_t)g * P + part] : 1u;
+    float *base = out + (size_t)(r0 + g) * a.rep_size + (size_t)part * pd;
+    if (live1 && c1 >= k && !accumulate(base + (c1 - k), dot, a.mode, count)) failed = true;
+    if (w.wide) {
+      for (uint32_t c = lane + kWave; c < C; c += kWave) {
+        const float *t = a.table + (size_t)r0 * d * C + c;
+        double val = 0.0;
+        for (uint32_t j = 0; j < d; ++j) val += (double)xs[j] * (double)t[(size_t)j * C];
+        if (!accumulate(base + (c - k), val, a.mode, count)) failed = true;
+      }
+    }
+  }
+  return failed;
+}
+
+// K10: set s is rows [set_off[s], set_off[s + 1]) of a dense matrix, d floats apart.
 __global__ __launch_bounds__(kWave) void muvera_encode_kernel(const MuveraArgs a) {
   extern __shared__ __align__(16) float lds[];
   float *xs = lds;                                                        // [d] the current vector
-  uint32_t *lcnt = reinterpret_cast<uint32_t *>(lds + a.d);               // [rg][P] partition counts (document mode)
-  const uint32_t lane = threadIdx.x;
+  const EncodeWave w = encode_wave(a, reinterpret_cast<uint32_t *>(lds + a.d));
   const uint32_t set = (uint32_t)(blockIdx.x / a.groups);
-  const uint32_t r0 = (uint32_t)(blockIdx.x % a.groups) * a.rg;
-  const uint32_t rga = min(a.rg, a.R - r0);                               // repetitions this wave serves
-  const uint32_t d = a.d, C = a.C, k = a.k, pd = a.pd;
-  const uint32_t P = 1u << k;
   const uint32_t v0 = a.set_off[set], v1 = a.set_off[set + 1];
-  float *out = a.full + (size_t)set * a.out_size;
-  uint32_t *cnt = nullptr;
-  if (a.mode == 1) {
-    if (a.counts) {
-      cnt = a.counts + ((size_t)set * a.R + r0) * P;                      // (zeroed by the host; rg == 1)
-    } else {
-      cnt = lcnt;
-      for (uint32_t i = lane; i < rga * P; i += kWave) cnt[i] = 0;
-    }
-  }
-  const bool wide = C > (uint32_t)kWave;
-  const uint32_t g = wide || C == 0 ? 0u : lane / C;                      // this lane's repetition within the group
-  const uint32_t c1 = wide || C == 0 ? lane : lane - g * C;               // ... and its column in the first pass
-  const bool live1 = C != 0 && g < rga && c1 < C;
   bool failed = false;
-
   for (uint32_t v = v0; v < v1; ++v) {
-    const float *x = a.X + (size_t)v * d;
+    const float *x = a.X + (size_t)v * a.d;
     __syncthreads();  // the last vector's readers are done (and the counts are zeroed)
-    for (uint32_t j = lane; j < d; j += kWave) xs[j] = x[j];
+    for (uint32_t j = w.lane; j < a.d; j += kWave) xs[j] = x[j];
     __syncthreads();
+    if (encode_vector(a, w, xs)) failed = true;
+  }
+  if (failed) a.status[set] = kErrEncodingOverflow;
+}
 
-    // first pass: every SimHash column and the first projection columns
-    double dot = 0.0;
-    if (live1) {
-      const float *t = a.table + (size_t)(r0 + g) * d * C + c1;
-      for (uint32_t j = 0; j < d; ++j) dot += (double)xs[j] * (double)t[(size_t)j * C];
-    }
-    const uint64_t mask = __ballot(live1 && c1 < k && dot >= 0.0);
-    const uint32_t part = partition_of(mask, g, C, k);
-
-    if (a.mode == 1) {  // counts[count_index] += 1 (muvera.rs:55): one lane per repetition of the group
-      if (lane < rga) {
-        uint32_t *slot = cnt + (size_t)lane * P + partition_of(mask, lane, C, k);
-        *slot = *slot + 1;
-      }
-      __syncthreads();
-    }
-
-    if (a.identity) {
-      // muvera.rs:141-146: the coordinates themselves, lanes over (repetition, coordinate)
-      for (uint32_t i = lane; i < rga * d; i += kWave) {
-        const uint32_t gi = i / d, q = i - gi * d;
-        const uint32_t pi = partition_of(mask, gi, C, k);
-        const uint32_t count = a.mode == 1 ? cnt[(size_t)gi * P + pi] : 1u;
-        if (!accumulate(out + (size_t)(r0 + gi) * a.rep_size + (size_t)pi * pd + q, (double)xs[q], a.mode, count)) failed = true;
-      }
-    } else {
-      const uint32_t count = a.mode == 1 && g < rga ? cnt[(size_t)g * P + part] : 1u;
-      float *base = out + (size_t)(r0 + g) * a.rep_size + (size_t)part * pd;
-      if (live1 && c1 >= k && !accumulate(base + (c1 - k), dot, a.mode, count)) failed = true;
-      if (wide) {
-        for (uint32_t c = lane + kWave; c < C; c += kWave) {
-          const float *t = a.table + (size_t)r0 * d * C + c;
-          double val = 0.0;
-          for (uint32_t j = 0; j < d; ++j) val += (double)xs[j] * (double)t[(size_t)j * C];
-          if (!accumulate(base + (c - k), val, a.mode, count)) failed = true;
-        }
-      }
-    }
+// K10s: set s is doc_cnt[s] rows from row doc_first[s] on of a store's slab, `stride` floats apart.  A row starts on 16
+// bytes and its pad is zero, so it is staged whole, four floats a lane (xs holds `stride` floats; the pad is never read).
+__global__ __launch_bounds__(kWave) void muvera_encode_slab_kernel(const MuveraSlabArgs s) {
+  extern __shared__ __align__(16) float lds[];
+  const MuveraArgs &a = s.a;
+  float *xs = lds;                                                        // [stride] the current row
+  const EncodeWave w = encode_wave(a, reinterpret_cast<uint32_t *>(lds + s.stride));
+  const uint32_t set = (uint32_t)(blockIdx.x / a.groups);
+  const uint32_t first = s.doc_first[set], n = s.doc_cnt[set];
+  const uint32_t quads = s.stride / 4;
+  bool failed = false;
+  for (uint32_t v = 0; v < n; ++v) {
+    const float4 *x = reinterpret_cast<const float4 *>(a.X + ((size_t)first + v) * s.stride);
+    __syncthreads();  // the last vector's readers are done (and the counts are zeroed)
+    for (uint32_t j = w.lane; j < quads; j += kWave) reinterpret_cast<float4 *>(xs)[j] = x[j];
+    __syncthreads();
+    if (encode_vector(a, w, xs)) failed = true;
   }
   if (failed) a.status[set] = kErrEncodingOverflow;
 }
@@ -212,6 +265,24 @@ hipError_t launch_muvera_encode(const MuveraArgs &a, hipStream_t s) {
   hipError_t e = dev::allow_lds(dev::muvera_encode_kernel, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(dev::muvera_encode_kernel, dim3((uint32_t)((size_t)a.nsets * a.groups)), dim3(dev::kWave), lds, s, a);
+  return hipGetLastError();
+}
+
+size_t muvera_slab_lds_bytes(const MuveraSlabArgs &s) {
+  size_t bytes = (size_t)s.stride * sizeof(float);
+  if (s.a.mode == 1 && !s.a.counts) bytes += ((size_t)s.a.rg << s.a.k) * sizeof(uint32_t);
+  return std::max<size_t>(bytes, 16);
+}
+
+hipError_t launch_muvera_encode_slab(const MuveraSlabArgs &s, hipStream_t stream) {
+  const MuveraArgs &a = s.a;
+  if (a.nsets == 0) return hipSuccess;
+  const size_t lds = muvera_slab_lds_bytes(s);
+  if (lds > dev::kMaxLds || a.rg == 0 || a.groups == 0 || (size_t)a.nsets * a.groups > 0x7fffffffull) return hipErrorInvalidValue;
+  if (s.stride < a.d || s.stride % 4 != 0 || !s.doc_first || !s.doc_cnt) return hipErrorInvalidValue;
+  hipError_t e = dev::allow_lds(dev::muvera_encode_slab_kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(dev::muvera_encode_slab_kernel, dim3((uint32_t)((size_t)a.nsets * a.groups)), dim3(dev::kWave), lds, stream, s);
   return hipGetLastError();
 }
 

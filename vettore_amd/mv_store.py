@@ -34,6 +34,23 @@ class ResidentMultiVector:
         """top_k_ids for every (id list, query set) pair in one call."""
         return nifs.mv_top_k_ids_batch(self.ref, id_lists, query_sets, metric_code, limit)
 
+    # MUVERA retrieval: `config` is (dimension, num_repetitions, num_simhash_projections, seed, projection_dimension,
+    # final_projection_dimension | None); `index` a single-shard inner-product FlatRef on the store's device
+    def encode_documents(self, ids, config):
+        """The listed documents' document-mode encodings, computed from the resident rows (K10s)."""
+        return nifs.mv_encode_documents(self.ref, ids, config)
+
+    def fde_sync(self, index, ids, config):
+        """Brings `index` in line with the store for `ids` (None: every live document)."""
+        return nifs.mv_fde_sync(self.ref, index, ids, config)
+
+    def fde_top_k(self, index, config, query_vectors, candidates, metric_code, limit):
+        """Candidates from `index` by the query's encoding, reranked with exact MaxSim."""
+        return nifs.mv_fde_top_k(self.ref, index, config, query_vectors, candidates, metric_code, limit)
+
+    def fde_top_k_batch(self, index, config, query_sets, candidates, metric_code, limit):
+        return nifs.mv_fde_top_k_batch(self.ref, index, config, query_sets, candidates, metric_code, limit)
+
     def counters(self):
         """{"scoring_launches", "batched_sets"}: MaxSim kernel launches and query sets scored by K9rb since the store was made."""
         return nifs.mv_counters(self.ref)

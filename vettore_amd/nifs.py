@@ -710,6 +710,7 @@ def hnsw_memory(index: HnswRef) -> dict:
 
 
 _MUVERA_SET_ERRORS = (2, 3, 20, 28)  # dimension mismatch, non-finite, "empty vectors", "encoding overflow"
+_FDE_DOC_ERRORS = (20, 28)           # what a resident document can answer: "empty vectors", "encoding overflow"
 
 
 def _usize(v, what):
@@ -782,6 +783,89 @@ def muvera_encode_batch(sets, mode: int, dimension: int, num_repetitions: int, n
     elif st != 0:
         return _err(st)
     return ("ok", (out, [None if s == 0 else _lib.error_text(int(s)) for s in status]))
+
+
+# ---------------------------------------------- MUVERA retrieval over a resident store (vt_mv_encode_documents, vt_mv_fde_*)
+def _muvera_cfg(config):
+    """(dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension | None)
+    -> vt_muvera_encode's seven trailing arguments."""
+    dimension, num_repetitions, num_simhash_projections, seed, projection_dimension, final_projection_dimension = config
+    for name, v in (("dimension", dimension), ("num_repetitions", num_repetitions),
+                    ("num_simhash_projections", num_simhash_projections), ("projection_dimension", projection_dimension)):
+        _usize(v, name)
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed <= U64_MAX:
+        raise TypeError("badarg: seed is a u64")
+    some = final_projection_dimension is not None
+    if some:
+        _usize(final_projection_dimension, "final_projection_dimension")
+    return (dimension, num_repetitions, num_simhash_projections, seed, projection_dimension,
+            final_projection_dimension if some else 0, 1 if some else 0)
+
+
+def mv_encode_documents(store: MvRef, ids, config):
+    """The document-mode encoding of every listed resident document, read from the store's rows:
+    ("ok", (matrix [count][fde] float32, [reason or None per document])) -- a document with a reason keeps a zero row --,
+    or ("error", reason) when the call itself is refused."""
+    cfg = _muvera_cfg(config)
+    idb, ioff = _pack_ids(ids)
+    n = ioff.size - 1
+    fde = muvera_fde_dimension(config[1], config[2], config[4], config[5])
+    out = np.zeros((n, fde), dtype=np.float32)
+    status = np.zeros(max(n, 1), dtype=np.intc)
+    st = _lib.load().vt_mv_encode_documents(store.handle, n, idb, _szp(ioff), *cfg, _fp(out.reshape(-1)) if out.size else None,
+                                            status.ctypes.data_as(C.POINTER(C.c_int)))
+    if st != 0 and n == 1 and st in _FDE_DOC_ERRORS:
+        status = [st]   # (one document: its own error is the call's status)
+    elif st != 0:
+        return _err(st)
+    return ("ok", (out, [None if s == 0 else _lib.error_text(int(s)) for s in status[:n]]))
+
+
+def mv_fde_sync(store: MvRef, index: FlatRef, ids, config):
+    """Brings `index` in line with the store for the listed ids (None: every live document).  ("ok", [reason or None per
+    listed id]) -- a reason means the id is absent from `index` --, or ("error", reason)."""
+    cfg = _muvera_cfg(config)
+    if ids is None:
+        st = _lib.load().vt_mv_fde_sync(store.handle, index.handle, 0, None, None, *cfg, None)
+        return ("ok", []) if st == 0 or st in _FDE_DOC_ERRORS else _err(st)
+    idb, ioff = _pack_ids(ids)
+    n = ioff.size - 1
+    status = np.zeros(max(n, 1), dtype=np.intc)
+    st = _lib.load().vt_mv_fde_sync(store.handle, index.handle, n, idb, _szp(ioff), *cfg, status.ctypes.data_as(C.POINTER(C.c_int)))
+    if st != 0 and n == 1 and st in _FDE_DOC_ERRORS:
+        status = [st]
+    elif st != 0:
+        return _err(st)
+    return ("ok", [None if s == 0 else _lib.error_text(int(s)) for s in status[:n]])
+
+
+def mv_fde_top_k(store: MvRef, index: FlatRef, config, query_vectors, candidates: int, metric_code: int, limit: int,
+                 with_keys: bool = False):
+    """mv_top_k_ids over the `candidates` documents whose encodings in `index` have the largest inner product with the
+    query's encoding."""
+    _mv_search_args(metric_code, limit)
+    _usize(candidates, "candidates")
+    cfg = _muvera_cfg(config)
+    qv, qoff = _vector_list(query_vectors)
+    h = C.c_void_p()
+    st = _lib.load().vt_mv_fde_top_k(store.handle, index.handle, *cfg, _fp(qv), _szp(qoff), qoff.size - 1, candidates, metric_code,
+                                     limit, C.byref(h))
+    return ("ok", _export_hits(h, with_keys)) if st == 0 else _err(st)
+
+
+def mv_fde_top_k_batch(store: MvRef, index: FlatRef, config, sets, candidates: int, metric_code: int, limit: int,
+                       with_keys: bool = False):
+    """mv_fde_top_k for every query set in one call: [("ok", hits) | ("error", reason)] per set; ("error", reason) when
+    the call itself fails."""
+    _mv_search_args(metric_code, limit)
+    _usize(candidates, "candidates")
+    cfg = _muvera_cfg(config)
+    qv, qoff, set_off = _pack_sets(sets)
+    n = len(set_off) - 1
+    outs, status = (C.c_void_p * max(n, 1))(), (C.c_int * max(n, 1))()
+    st = _lib.load().vt_mv_fde_top_k_batch(store.handle, index.handle, *cfg, n, _szp(set_off), _fp(qv), _szp(qoff), candidates,
+                                           metric_code, limit, outs, status)
+    return _mv_batch_results(st, outs, status, n, with_keys)
 
 
 def binary_top_k(vectors, query, dimensions: int, limit: int):
