@@ -24,11 +24,11 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_hnsw vt_mmr vt_prepare
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_sketch4_rescore vt_hnsw vt_mmr vt_prepare
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -70,6 +70,9 @@ EXTRA_vt_sketch6          := -mllvm -structurizecfg-skip-uniform-regions=true
 EXTRA_vt_sketch5          := $(EXTRA_vt_sketch6)
 # (K1n's pass, the 4-bit sketch: the same loop with two arms, data and metadata)
 EXTRA_vt_sketch4          := $(EXTRA_vt_sketch6)
+# K1n's last link (candidates rescored from the pass's lists): a round of loaded rows indexed statically, the recovery by
+# value as in K1 -- no scratch segment, no spill
+NOSCRATCH_vt_sketch4_rescore := sketch4_rescore_kernel
 # K11 (HNSW traversals): the distance chains are K9's with the recovery by value; heaps and visited set live in the
 # slot's global scratch, nothing is indexed dynamically in registers -- no scratch segment
 NOSCRATCH_vt_hnsw         := hnsw_traverse_kernel
@@ -150,6 +153,15 @@ $(LIBDIR)/sketch4_finish_probe.o: tests/sketch4_finish_probe.cpp $(CSRC)/vt_devi
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch4_finish_probe.so: $(LIBDIR)/vt_scan_filter.o $(LIBDIR)/sketch4_finish_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# K1n's last link behind a probe (tests/sketch4_rescore_probe.cpp; tests/test_gpu_sketch4_rescore_kernels.py loads it): the
+# rescoring kernel on a test's hand-made lists.  Test infrastructure, as above.
+$(LIBDIR)/sketch4_rescore_probe.o: tests/sketch4_rescore_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch4_rescore_probe.so: $(LIBDIR)/vt_sketch4_rescore.o $(LIBDIR)/sketch4_rescore_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

@@ -417,10 +417,11 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
 // *done as sketch_search has it; a pass that does not certify counts towards the shard's miss limit.
 // `bits` 5: K1f, the same chain over the 5-bit sketch (its pass, its bound of the level kept off the L plane, its longer
 // candidate list, more blocks for the gathered K1, its own counters and misses).  `bits` 4: K1n, over the 4-bit sketch
-// (one plane: no such level bound; two lists a block), with launch_sketch_refine between the threshold and the collect
-// kernels: the collect takes the exact threshold it publishes, and the gathered K1 runs in filter mode
-// (launch_scan_filter): it keeps the rows under that threshold and writes the sorted result itself, no select behind it.
-// A search whose survivors overflow its short list queues the lists and the select behind a second wait.
+// (one plane: no such level bound; two lists a block), with launch_sketch_refine behind the threshold kernel and one kernel
+// behind that (launch_sketch4_rescore): it takes the candidates under the exact threshold straight from the pass's lists,
+// rescores them, keeps the rows under that threshold and writes the sorted result itself, no select behind it.  (Rows too
+// long for its block: the collect with that threshold and the gathered K1 in filter mode, launch_scan_filter, as before.)
+// A search whose survivors overflow its short list queues the collect, the lists and the select behind a second wait.
 int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, int bits = 6) {
   const SketchKind &kind = sketch_kind(bits);
   const bool five = bits == 5;
@@ -540,7 +541,12 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
     VT_HIP(vt::launch_sketch_refine(ra, c.stream));
     ta.kt_word = ra.kt_out;
   }
-  VT_HIP(vt::launch_sketch_collect(ta, c.stream));
+  // K1n, wherever its launcher takes the shape: the candidates are rescored straight from the pass's lists by one kernel
+  // (launch_sketch4_rescore) that certifies as the collect does and finishes as the filtered K1 does; no candidate array
+  const bool dot_metric = ix->metric == VT_COSINE || ix->metric == VT_INNER_PRODUCT || ix->metric == VT_NEG_INNER_PRODUCT;
+  const bool from_lists = kind.exact_threshold && dot_metric && k <= (uint32_t)vt::kSmallK && ta.kt_word &&
+                          vt::sketch4_rescore_lds_bytes(d, kp) != 0;
+  if (!from_lists) VT_HIP(vt::launch_sketch_collect(ta, c.stream));
   vt::ScanArgs sa = scan_args(ix, c, d);
   set_gather(sa, gather_of(cand_rows.p), cand_cap);  // (the list's room: the count is batch_counts[0])
   sa.k = k;
@@ -549,8 +555,8 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   sa.batch_cap = cand_cap;
   bool delivered = false;
   if (kind.exact_threshold) {
-    // K1n: the gathered K1 keeps the rows whose rank word is <= Kt' -- the k hits and what ties the k-th -- and its last
-    // block sorts them into the result block: no lists, no select (the survivors lie where the lists would)
+    // K1n: the rows whose rank word is <= Kt' are kept -- the k hits and what ties the k-th -- and the last block sorts
+    // them into the result block: no lists, no select (the survivors lie where the lists would)
     vt::ScanArgs fa = sa;
     fa.hi_word = ta.kt_word;
     fa.surv_keys = c.dPartKeys.p;
@@ -559,14 +565,28 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
     fa.fsync = chain_words;
     fa.out = c.dResMapped;
     fa.info = info;
-    VT_HIP(vt::launch_scan_filter(fa, rescore_blocks, c.stream));
+    if (from_lists) {
+      vt::Sketch4RescoreArgs ra{};
+      ra.s = fa;
+      ra.s.gather = nullptr;
+      ra.s.batch_counts = nullptr;
+      ra.hi_words = ta.hi_words;
+      ra.pay = ta.pay;
+      ra.kp = kp;
+      ra.cap = cand_cap;
+      VT_HIP(vt::launch_sketch4_rescore(ra, blocks, c.stream));
+    } else {
+      VT_HIP(vt::launch_scan_filter(fa, rescore_blocks, c.stream));
+    }
     VT_HIP(hipStreamSynchronize(c.stream));
     delivered = c.hSkInfo.p[0] == vt::kScanFilterDelivered;
   }
   if (!delivered && (!kind.exact_threshold || c.hSkInfo.p[0] == 2u)) {
     // (K1n, certified but not delivered -- more survivors than the short list holds: thousands of rows tie the k-th key,
-    // or the refine kept the sketch's own Kt: the lists and their select over the candidates still on the device, behind
-    // a second wait.  Not a fallback.)
+    // or the refine kept the sketch's own Kt: the lists and their select over the candidates, behind a second wait.  The
+    // rescoring kernel left no candidate array: the collect, over the lists still on the device, goes first.  Not a
+    // fallback.)
+    if (from_lists) VT_HIP(vt::launch_sketch_collect(ta, c.stream));
     VT_HIP(vt::launch_scan_batch(sa, rescore_blocks, 1, c.stream));
     VT_HIP(vt::launch_select(c.dPartKeys.p, c.dPartPay.p, rescore_blocks * k, k, 0, 0, c.dStatus.p, c.dResMapped,
                              c.dSelKeys.p, c.dSelPay.p, c.stream));
@@ -603,7 +623,7 @@ int sketch5_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   return sketch6_search(ix, c, query, limit, done, out, 5);
 }
 
-// K1n: blit, the 4-bit pass, the threshold, refine and collect kernels and the filtered K1 that finishes behind one host wait.
+// K1n: blit, the 4-bit pass, the threshold and refine kernels and the rescoring kernel that finishes behind one host wait.
 int sketch4_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
   return sketch6_search(ix, c, query, limit, done, out, 4);
 }

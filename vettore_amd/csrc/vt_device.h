@@ -1005,4 +1005,25 @@ hipError_t launch_sketch4_rows(const float *X, size_t stride, const uint32_t *li
 size_t sketch4_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_sketch4_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
 
+// K1n's last link (vt_sketch4_rescore.hip), behind launch_sketch_refine: launch_sketch_collect and launch_scan_filter in one
+// launch on the pass's grid, with no candidate array between them.  Block b takes the slots of the pass's lists
+// [b * kSketch4BlockLists, + kSketch4BlockLists) whose key(hi) word is live and <= *s.hi_word -- the collect's candidates, and
+// its certificate: ok = no list of candidates alone && candidates <= cap --, rescores their rows with K1's arithmetic and
+// keeps the valid ones whose rank word is <= *s.hi_word as launch_scan_filter keeps them (s.surv_keys / surv_pay / surv_cap,
+// s.fsync[0 .. kScanFilterSyncWords) handed over zeroed: word 1 of a group's ticket line counts the group's candidates, bit
+// 1 of fsync[1] is the certificate's fail bit).  The block that draws the last ticket writes info = {outcome, candidates,
+// the word, 1}: kScanFilterDelivered with the sorted result in *s.out when ok and at most surv_cap rows were kept, else 2
+// when ok (the caller queues launch_sketch_collect, launch_scan_batch and launch_select over the lists) and 0 when not.
+// Of `s` it reads X, stride, q, id_rank, d, metric (cosine, dot, negative dot), order, k <= kSmallK, status and the
+// filter-mode fields; d is bounded by the block's LDS (sketch4_rescore_lds_bytes, 0: not supported).
+struct Sketch4RescoreArgs {
+  ScanArgs s;
+  const uint32_t *hi_words;  // [blocks * kSketch4BlockLists][kp], launch_sketch4_scan's
+  const Payload *pay;        // [blocks * kSketch4BlockLists][kp]
+  uint32_t kp, cap;
+  uint32_t ld, ss;           // set by the launcher
+};
+size_t sketch4_rescore_lds_bytes(uint32_t d, uint32_t kp);
+hipError_t launch_sketch4_rescore(Sketch4RescoreArgs a, uint32_t blocks, hipStream_t s);
+
 }  // namespace vt

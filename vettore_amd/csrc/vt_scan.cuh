@@ -32,6 +32,8 @@
 #pragma once
 #include "vt_common.cuh"
 
+#include <type_traits>
+
 namespace vt {
 namespace dev {
 
@@ -242,7 +244,13 @@ __device__ __forceinline__ uint32_t *filter_stored_flag() {
 // by their full u64 key as select_topk_kernel's short-list branch does (smaller first, equal keys by position) and
 // writes the first k into the host-mapped result block.  With more survivors than the list holds, or no rows scanned (the
 // collect refused), info[] stays as the collect wrote it and the caller queues today's scan and select.
-__device__ __forceinline__ void filter_finish(const ScanArgs &a, uint32_t nrows, uint32_t nblocks, const uint32_t *stored) {
+// `decide` (K1n's rescoring kernel, vt_sketch4_rescore.hip, which has no collect in front of it; FilterAsCollected: none):
+// called by the one lane that has drawn the last ticket IN PLACE of the reads and the rule above -- it reads what it needs
+// in one trip, the same way, says how many survivors there are and whether the block delivers.
+struct FilterAsCollected {};
+template <typename Decide>
+__device__ __forceinline__ void filter_finish(const ScanArgs &a, uint32_t nrows, uint32_t nblocks, const uint32_t *stored,
+                                              Decide decide) {
   __shared__ uint64_t f_keys[kScanFilterCap], f_pay[kScanFilterCap];
   __shared__ uint32_t f_last, f_n;
   const uint32_t tid = threadIdx.x;
@@ -258,15 +266,19 @@ __device__ __forceinline__ void filter_finish(const ScanArgs &a, uint32_t nrows,
     uint32_t last = 0, n = 0;
     if (filter_agent_add(a.fsync + kScanFilterLine * (1 + g), 1u) == members - 1)  // the group's last: every member drew before it
       last = filter_agent_add(a.fsync + 2, 1u) == groups - 1 ? 1u : 0u;
-    if (last) {  // every other block has claimed, stored and flagged before its group's last drew
-      n = filter_agent_add(a.fsync + 0, 0u);
-      const uint32_t over = __hip_atomic_fetch_or(a.fsync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (nrows == 0) {  // nothing was handed over: an empty result, info untouched
-        a.out->count = 0;
-        last = 0;
-      } else if (over || n > a.surv_cap) {
-        last = 0;
+    if constexpr (std::is_same<Decide, FilterAsCollected>::value) {
+      if (last) {  // every other block has claimed, stored and flagged before its group's last drew
+        n = filter_agent_add(a.fsync + 0, 0u);
+        const uint32_t over = __hip_atomic_fetch_or(a.fsync + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (nrows == 0) {  // nothing was handed over: an empty result, info untouched
+          a.out->count = 0;
+          last = 0;
+        } else if (over || n > a.surv_cap) {
+          last = 0;
+        }
       }
+    } else {
+      if (last) last = decide(&n) ? 1u : 0u;
     }
     f_last = last;
     f_n = n;
@@ -302,6 +314,10 @@ __device__ __forceinline__ void filter_finish(const ScanArgs &a, uint32_t nrows,
     a.out->status = atomicExch(a.status, 0);  // (every block's atomicMax is behind its ticket)
     a.info[0] = kScanFilterDelivered;
   }
+}
+
+__device__ __forceinline__ void filter_finish(const ScanArgs &a, uint32_t nrows, uint32_t nblocks, const uint32_t *stored) {
+  filter_finish(a, nrows, nblocks, stored, FilterAsCollected{});
 }
 
 // Position of a wave in its stream of 1-KiB segments: tile t, column panel p,
