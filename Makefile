@@ -28,7 +28,7 @@ DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_bat
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -162,6 +162,16 @@ $(LIBDIR)/sketch4_rescore_probe.o: tests/sketch4_rescore_probe.cpp $(CSRC)/vt_de
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch4_rescore_probe.so: $(LIBDIR)/vt_sketch4_rescore.o $(LIBDIR)/sketch4_rescore_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# The int8 sketch's L2 family behind a probe (tests/sketch_l2_probe.cpp; tests/test_gpu_sketch_l2_kernels.py loads it): the
+# builders with and without xx, the pass in either metric family and the one-block tail on a test's arrays.  vt_sketch.o and
+# the probe, nothing else of the library.  Test infrastructure, as above.
+$(LIBDIR)/sketch_l2_probe.o: tests/sketch_l2_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch_l2_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/sketch_l2_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

@@ -50,24 +50,33 @@ bool shadow_wanted(const Shard *ix) {
 size_t shadow_elems(const Shard *ix) { return vt::shadow_elems((uint32_t)std::max<size_t>(ix->cap, ix->n), ix->ld); }
 bool shadow_current(const Shard *ix) { return ix->shadow.current(shadow_elems(ix)); }
 
-// K1q (vt_sketch.hip): a lone cosine / inner-product search over rows of at least kSketchMinBytes reads the
+// K1q (vt_sketch.hip): a lone cosine / inner-product / L2 search over rows of at least kSketchMinBytes reads the
 // int8 sketch -- a quarter of the bytes -- and the exact K1 rescores the rows it cannot rule out.  Only on strictly
 // ranked shards (lazy searches after trickle inserts keep K1), and only while each block's list of k' = max(2k, k + 16)
 // fits one wave buffer.  NEED_SKETCH asks for the column and means nothing where this says no.
 // f32 rows below this take K1.  (With the pass's tail in one kernel the two paths meet near 130 MB of f32 rows, DESIGN 5;
 // the cut stays where the suite's launch counters on mid-size corpora were written against it.)
 constexpr double kSketchMinBytes = 256.0 * (1 << 20);
+// The L2 family's own cut.  The family has been measured at 5 M and 10 M rows of d = 768 and in a sweep down to 256 MB
+// (DESIGN 5); the cut does not sit at the measured meeting point but at 1 GiB, above the 461-MB shards whose lone L2
+// searches the two-rank rehearsal of config 4 prices as scans of the f32 rows.  L2 rows below it are served as before.
+constexpr double kSketchL2MinBytes = 1024.0 * (1 << 20);
 constexpr uint32_t kSketchCandCap = 4096;              // candidates the gathered K1 rescores at most (more: not certified)
 constexpr uint32_t kSketchRescoreBlocks = 32;
 inline uint32_t sketch_list_k(size_t limit) { return (uint32_t)std::max<size_t>(2 * limit, limit + 16); }
-bool sketch_metric(int metric) { return metric == VT_COSINE || metric == VT_INNER_PRODUCT || metric == VT_NEG_INNER_PRODUCT; }
+// The L2 family (L2, squared L2) reads the int8 sketch alone -- its column keeps ||x_r||^2 beside the dot's bounds (DESIGN
+// 4.10); the 6-, 5- and 4-bit tiers stay with the dot family (sketch_dot_metric: their passes have no such epilogue).
+bool sketch_dot_metric(int metric) { return metric == VT_COSINE || metric == VT_INNER_PRODUCT || metric == VT_NEG_INNER_PRODUCT; }
+bool sketch_l2_metric(int metric) { return metric == VT_L2 || metric == VT_L2_SQUARED; }
+bool sketch_metric(int metric) { return sketch_dot_metric(metric) || sketch_l2_metric(metric); }
 bool sketch_wanted(const Shard *ix, size_t limit) {
   if (!vt::env::on(vt::env::SKETCH) || ix->sketch.refused || !sketch_metric(ix->metric) || ix->single_nominate) return false;
   if (!ix->ranks_clean || ix->n == 0 || ix->dim <= 0 || (uint32_t)ix->dim > vt::kSketchMaxDim) return false;
   if (limit == 0 || sketch_list_k(limit) > (size_t)vt::kMaxFusedK || vt::sketch_scan_lds_bytes((uint32_t)ix->dim, sketch_list_k(limit)) == 0)
     return false;
   // (force_sketch6 brings the int8 sketch with it: it is the 6-bit pass's fallback, and serves the limits that pass declines)
-  return vt::env::on(vt::env::FORCE_SKETCH) || vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= kSketchMinBytes;
+  const double cut = sketch_l2_metric(ix->metric) ? kSketchL2MinBytes : kSketchMinBytes;
+  return vt::env::on(vt::env::FORCE_SKETCH) || vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= cut;
 }
 size_t sketch_elems(const Shard *ix) { return vt::sketch_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
@@ -89,7 +98,9 @@ constexpr uint32_t kSketch6CandCap = 32768;       // ~100 MB of f32 rows at d = 
 constexpr uint32_t kSketch6RescoreBlocks = 256;
 constexpr uint32_t kSketch6MissLimit = 4;
 bool sketch6_wanted(const Shard *ix, size_t limit) {
-  if (!sketch_wanted(ix, limit) || limit > kSketch6MaxLimit || !vt::env::on(vt::env::SKETCH6) || ix->sketch6.refused) return false;
+  if (!sketch_wanted(ix, limit) || !sketch_dot_metric(ix->metric) || limit > kSketch6MaxLimit || !vt::env::on(vt::env::SKETCH6) ||
+      ix->sketch6.refused)
+    return false;
   if (vt::sketch6_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
   return vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= kSketch6MinBytes;
 }
@@ -301,7 +312,8 @@ void sketch_query_image(Ctx &c, const float *query, uint32_t d, uint32_t ld, uin
 // for that block (up to kSketchCandCap) goes through the gathered K1 and its select after a second wait.  *done: the
 // hits in *out are the exact top `limit`; otherwise the caller scans the f32 rows -- the bound could not certify
 // (counted), or it declined before any launch because a dot of these rows could reach the f32 overflow K1 must see for
-// itself.
+// itself.  The L2 family: the same chain over the column with xx (the pass's L2 epilogue, kerr = 0, ||q||^2 between its two
+// ends), declined where a squared difference could overflow f32.
 int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
   *done = false;
   const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d), nch = ld8 / 16;
@@ -314,7 +326,14 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   }
   const double up = 1.0 + 0x1p-30;
   const double qn = std::sqrt(qq) * up;
-  if (!(qn * ix->sketch_max_norm * up < 0x1p126)) return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
+  const bool l2 = sketch_l2_metric(ix->metric);
+  if (l2) {
+    // (||q - x|| <= ||q|| + ||x||: below 2^62 no square of K1's can overflow; at or past it the plain scan recomputes in
+    // f64 or reports "metric overflow" for itself.  A column built without xx never serves the family.)
+    if (!ix->sketch_xx || !((qn + ix->sketch_max_norm) * up < 0x1p62)) return VT_OK;
+  } else if (!(qn * ix->sketch_max_norm * up < 0x1p126)) {
+    return VT_OK;  // (K1's overflow flag depends on every row: its scan decides)
+  }
   const size_t total = (size_t)ld + 2 * (size_t)ld8 / 4;
   VT_TRY(c.dQ.ensure(total));
   VT_TRY(c.hQ.ensure(total));
@@ -347,7 +366,11 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   a.t2 = t2;
   a.qn = qn;
   a.eta = std::sqrt(ee) * up;
-  a.kerr = 8.0 * d * 0x1p-24;  // K1's summation error per unit of ||q|| ||x_r|| (DESIGN_APPENDIX A.5)
+  // K1's summation error per unit of ||q|| ||x_r|| (DESIGN_APPENDIX A.5); the L2 family bounds the real dot and carries
+  // K1's rounding as a relative term of the distance (A.5b)
+  a.kerr = l2 ? 0.0 : 8.0 * d * 0x1p-24;
+  a.qq_lo = qq / up;
+  a.qq_hi = qq * up;
   a.k = kp;
   a.part_keys = c.dSkKeys.p;
   a.part_pay = c.dSkPay.p;
@@ -1008,7 +1031,8 @@ int index_ensure_shadow(Shard *ix, size_t elems) {
 // rebuild it (one pass over the rows); without room for it -- a quarter of the card must stay free -- it is refused and
 // lone searches keep scanning the f32 rows.  The bound on every row's norm comes back with it (the overflow guard).
 // `bits` 6 / 5 / 4: the 6-bit / 5-bit / 4-bit sketch on the same terms (its own bound, its own counters: sketch_kind); a
-// whole build starts its misses over.
+// whole build starts its misses over.  The int8 column of an L2 / squared-L2 handle is built and patched with xx_r in the
+// metadata run's fourth dword (Shard::sketch_xx); every other column's image is what it was.
 int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
   Ctx &c = ix->ctx;
   const SketchKind &kind = sketch_kind(bits_per);
@@ -1020,12 +1044,14 @@ int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
   VT_TRY(c.dBNorm.ensure(1));
   unsigned long long bits = 0;
   if (col.patchable(bytes)) {
+    const bool with_xx = bits_per == 8 && ix->sketch_xx;  // (the patch writes what the build wrote)
     uint32_t count = 0;
     VT_TRY(upload_row_list(ix, col.dirty, &count));
     std::memcpy(&bits, &max_norm, sizeof(double));
     VT_HIP(hipMemcpyAsync(c.dBNorm.p, &bits, sizeof(bits), hipMemcpyHostToDevice, c.stream));
     const uint32_t rows_img = (uint32_t)(col.buf.count / tile_bytes * vt::kSketchTileRows);
-    VT_HIP(kind.rows(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    VT_HIP((with_xx ? vt::launch_sketch_rows_xx : kind.rows)(ix->dX, ix->ld, c.dRankPairs.p, count, rows_img, d, col.buf.p, c.dBNorm.p,
+                                                             c.stream));
     c.prof.*kind.patched_rows += count;
   } else {
     col.forget();
@@ -1052,7 +1078,9 @@ int index_ensure_sketch(Shard *ix, size_t bytes, int bits_per) {
     }
     const uint32_t rows_img = (uint32_t)(bytes / tile_bytes * vt::kSketchTileRows);
     VT_HIP(hipMemsetAsync(c.dBNorm.p, 0, sizeof(unsigned long long), c.stream));
-    VT_HIP(kind.build(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
+    if (bits_per == 8) ix->sketch_xx = sketch_l2_metric(ix->metric);  // (a handle's metric never changes: fixed with the column)
+    const bool with_xx = bits_per == 8 && ix->sketch_xx;
+    VT_HIP((with_xx ? vt::launch_sketch_build_xx : kind.build)(ix->dX, ix->ld, ix->n, rows_img, d, col.buf.p, c.dBNorm.p, c.stream));
     c.prof.*kind.builds += 1;
     if (kind.misses) (ix->*kind.misses).store(0, std::memory_order_relaxed);
   }

@@ -333,11 +333,14 @@ struct Shard {
   DerivedColumn<uint16_t> shadow;
   int shadow_mode = default_shadow();  // VT_SHADOW_*
   // K1q: the rows once more in int8 with a per-row scale and error bounds (vt_device.h, SketchScanArgs) -- a quarter of
-  // the bytes a lone cosine / dot search reads (vt_search.h, sketch_search).  Optional, like the shadow: refused when the
+  // the bytes a lone cosine / dot / L2 search reads (vt_search.h, sketch_search).  Optional, like the shadow: refused when the
   // card has no room, given back when the slab needs it (index_reserve) and when the index is emptied.
   // sketch_max_norm: an upper bound of every row's norm (a value only while the column is valid; patches only raise it).
+  // sketch_xx: the column carries xx_r >= ||x_r||^2 in the metadata run's fourth dword -- an L2 / squared-L2 handle's,
+  // fixed when the column is built (a handle's metric never changes) and kept by every patch.
   DerivedColumn<unsigned char> sketch;
   double sketch_max_norm = 0.0;
+  bool sketch_xx = false;
   // K1s: the rows in six bits, two planes (vt_device.h, Sketch6ScanArgs) -- 0.755 of the int8 sketch's bytes, read by the
   // largest lone searches (vt_search.h, sketch6_search) with the int8 sketch as its fallback.  Kept on the int8 sketch's
   // terms; the first column to go when the slab needs room.  sketch6_misses: consecutive passes the bound could not

@@ -798,11 +798,14 @@ struct PrepareArgs {
 };
 hipError_t launch_prepare_rows(const PrepareArgs &a, int mode, hipStream_t s);
 
-// ---- K1q (vt_sketch.hip): a lone dot-family search over an int8 sketch of the rows -----------------------------------
+// ---- K1q (vt_sketch.hip): a lone dot-family or L2-family search over an int8 sketch of the rows ----------------------
 // Row r is kept as X_r = round(x_r / s_r) in int8 with s_r = max_i |x_ri| / 127, beside two f32 bounds rounded up:
 // rho_r >= ||x_r - s_r X_r|| (the residual, summed in f64) and nu_r >= s_r ||X_r||.  Layout, per tile of 64 rows: the
 // rows' 16-byte chunk c is one 1-KiB run ((tile * (nch + 1) + c) * 1024 + (r % 64) * 16), c < nch = ld8 / 16, and the
 // tile ends with one more run of {s, rho, nu, 0} per row -- a wave streams a tile, metadata included, in whole 1-KiB loads.
+// The column of an L2 / squared-L2 handle keeps xx_r >= ||x_r||^2 in that fourth dword (f32, rounded up, of the f64 sum
+// times 1 + 2^-30; launch_sketch_build_xx / launch_sketch_rows_xx): ||q - x||^2 = ||q||^2 + ||x||^2 - 2 q.x turns the dot's
+// interval into the distance's.  Every other handle's fourth dword stays zero.
 constexpr uint32_t kSketchTileRows = 64;
 constexpr uint32_t kSketchMaxDim = 32768;  // (K1q's query image sits in LDS; and d * 127^2 stays far below 2^31)
 __host__ __device__ inline uint32_t sketch_ld8(uint32_t d) { return (d + 127) / 128 * 128; }
@@ -821,20 +824,27 @@ hipError_t launch_sketch_build(const float *X, size_t stride, uint32_t n_src, ui
 // the same for the rows of a list
 hipError_t launch_sketch_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
                               void *img, unsigned long long *max_norm, hipStream_t s);
+// the same two with xx_r in the metadata run's fourth dword (the L2 family's column)
+hipError_t launch_sketch_build_xx(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                                  unsigned long long *max_norm, hipStream_t s);
+hipError_t launch_sketch_rows_xx(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                                 void *img, unsigned long long *max_norm, hipStream_t s);
 
 struct SketchScanArgs {
   const void *img;
   const uint32_t *id_rank;
   const int8_t *qimg;       // [2][ld8]: the query's two int8 levels, q ~ t1 Q1 + t2 Q2
   uint32_t n, d, nch;       // nch = ld8 / 16
-  int metric;               // VT_COSINE / VT_INNER_PRODUCT / VT_NEG_INNER_PRODUCT
+  int metric;               // VT_COSINE / VT_INNER_PRODUCT / VT_NEG_INNER_PRODUCT; VT_L2 / VT_L2_SQUARED (a column with xx)
   float t1, t2;
   double qn;                // >= ||q||
   double eta;               // >= ||q - t1 Q1 - t2 Q2||
-  double kerr;              // K1's summation error per unit of ||q|| ||x_r||
+  double kerr;              // K1's summation error per unit of ||q|| ||x_r||; 0 for the L2 family, whose
+                            // interval of the real dot carries K1's rounding as a relative term of the distance instead
   uint32_t k;               // entries per block list (k' of DESIGN 4.10)
-  uint64_t *part_keys;      // [blocks][k]: orderable(key(hi_r)) << 32 | id rank
-  Payload *part_pay;        // [blocks][k]: row, key(lo_r) as a float
+  uint64_t *part_keys;      // [blocks][k]: orderable(key(hi_r)) << 32 | id rank (L2 family: orderable(kmin_r))
+  Payload *part_pay;        // [blocks][k]: row, key(lo_r) as a float (L2 family: kmax_r)
+  double qq_lo, qq_hi;      // L2 family: ||q||^2 lies in [qq_lo, qq_hi]
 };
 size_t sketch_scan_lds_bytes(uint32_t d, uint32_t k);  // 0: not supported
 hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStream_t s);
@@ -842,9 +852,10 @@ hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStrea
 // One block over the lists of launch_sketch_scan: Kt = the k-th smallest key(lo) retained; every retained row whose
 // key(hi) <= Kt is a candidate; certified iff they number at most `cap` and no list consists of candidates alone (a
 // full list whose largest key(hi) is <= Kt).  K1q's tail.  info = {outcome, candidates, Kt bits, 0} (host-mapped), outcome
-//   1: certified, and the block rescored the candidates itself with K1's arithmetic (X, q, order, metric; *status
-//      raised like K1's) and wrote the k best, sorted, with the status word into *out like launch_select -- taken when
-//      they are few enough for its LDS (at most 256);
+//   1: certified, and the block rescored the candidates itself with K1's arithmetic (X, q, order, metric -- the dot
+//      family's products or the L2 family's squared differences and root; *status raised like K1's) and wrote the k
+//      best, sorted, with the status word into *out like launch_select -- taken when they are few enough for its LDS
+//      (at most 256);
 //   2: certified, rows[0..*count) hold the candidates for a gathered K1;
 //   0: not certified (*count = 0).
 struct SketchTailArgs {

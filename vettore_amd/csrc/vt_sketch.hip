@@ -1,4 +1,4 @@
-// vt_sketch.hip -- K1q: a lone cosine / dot search nominated from an int8 sketch of the rows (gfx950), and the tail behind
+// vt_sketch.hip -- K1q: a lone cosine / dot / L2 search nominated from an int8 sketch of the rows (gfx950), and the tail behind
 // its pass -- which K1s and K1f share --; the builders of K1s's 6-bit sketch in two planes follow below (its pass:
 // vt_sketch6.hip; K1f, the 5-bit sketch: vt_sketch5.hip).
 //
@@ -11,6 +11,10 @@
 //     every block keeps its k' smallest (key(hi_r), id rank) keys (WaveTopK, K1's list layout) with key(lo_r) beside them.
 // sketch_tail_kernel then proves that the retained rows with key(hi) <= Kt hold the exact top k and rescores those few
 // with K1's exact arithmetic itself; a longer candidate list goes through the gathered K1.
+// The L2 family (L2, squared L2) takes the same pass over a column that keeps xx_r >= ||x_r||^2 in the metadata run's free
+// dword: ||q - x_r||^2 = ||q||^2 + ||x_r||^2 - 2 q.x_r, so [a_r - e_r, a_r + e_r] (without K1's summation term) gives an
+// interval of the real squared distance, K1's f32 value lies within a relative kappa of that, and the two words kept per
+// row are kmin_r and kmax_r themselves -- the rank of both metrics is the raw value.
 #include "vt_sketch.cuh"
 
 #include <algorithm>
@@ -19,7 +23,9 @@ namespace vt {
 
 namespace {
 
-// One wave per row: quantise, write the row's chunks and its {s, rho, nu} in the tiled layout.
+// One wave per row: quantise, write the row's chunks and its {s, rho, nu} in the tiled layout.  WITH_XX (the L2 family's
+// column): sum x^2 in f64 beside the residual, and xx_r -- f32, rounded up, of that sum times 1 + 2^-30 -- in the fourth dword.
+template <bool WITH_XX>
 __device__ __forceinline__ void sketch_row(const float *__restrict__ X, size_t stride, uint32_t row, bool have_row, uint32_t d,
                                            uint32_t nch, unsigned char *__restrict__ img, unsigned long long *max_norm, int lane) {
   const float *src = X + (size_t)row * stride;
@@ -32,6 +38,7 @@ __device__ __forceinline__ void sketch_row(const float *__restrict__ X, size_t s
   const bool quantise = have_row && m > 0.0f && finite_f32(inv) && s > 0.0f;
   if (!quantise) s = 0.0f;
   double res = 0.0;   // sum of (x - s X)^2, f64
+  double sq = 0.0;    // sum of x^2, f64 (WITH_XX)
   uint32_t xx = 0;    // sum of X^2, exact
   for (uint32_t c = lane; c < nch; c += kWave) {
     uint32_t w[4];
@@ -49,6 +56,7 @@ __device__ __forceinline__ void sketch_row(const float *__restrict__ X, size_t s
         }
         const double r = (double)x - (double)s * (double)q;  // (exact: s q has at most 31 significant bits)
         res += r * r;
+        if constexpr (WITH_XX) sq += (double)x * (double)x;
         xx += (uint32_t)(q * q);
         word |= ((uint32_t)q & 0xffu) << (8 * b);
       }
@@ -57,28 +65,33 @@ __device__ __forceinline__ void sketch_row(const float *__restrict__ X, size_t s
     *reinterpret_cast<u32x4 *>(img + sketch_offset(row, c, nch)) = u32x4{w[0], w[1], w[2], w[3]};
   }
   res = wave_sum_d(res);
+  if constexpr (WITH_XX) sq = wave_sum_d(sq);
   xx = wave_sum_u(xx);
   if (lane == 0) {
     // (each f64 sum above carries at most d relative roundings of 2^-53: the 2^-30 margin covers any d this path takes)
     const double rho = sqrt(res) * (1.0 + 0x1p-30);
     const double nu = (double)s * sqrt((double)xx) * (1.0 + 0x1p-30);
     const float rho_f = f32_up(rho), nu_f = f32_up(nu);
+    uint32_t xx_w = 0u;
+    if constexpr (WITH_XX) xx_w = __float_as_uint(f32_up(sq * (1.0 + 0x1p-30)));
     *reinterpret_cast<u32x4 *>(img + sketch_offset(row, nch, nch)) =
-        u32x4{__float_as_uint(s), __float_as_uint(rho_f), __float_as_uint(nu_f), 0u};
+        u32x4{__float_as_uint(s), __float_as_uint(rho_f), __float_as_uint(nu_f), xx_w};
     const double bound = ((double)rho_f + (double)nu_f) * kSlack;
     unsigned long long bits = (unsigned long long)__double_as_longlong(bound);
     atomicMax(max_norm, bits);  // (non-negative f64: the bit patterns order like the values)
   }
 }
 
+template <bool WITH_XX>
 __global__ __launch_bounds__(256) void sketch_build_kernel(const float *__restrict__ X, size_t stride, uint32_t n_src,
                                                            uint32_t rows_img, uint32_t d, uint32_t nch, unsigned char *img,
                                                            unsigned long long *max_norm) {
   const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   if (w >= rows_img) return;
-  sketch_row(X, stride, w, w < n_src, d, nch, img, max_norm, threadIdx.x & 63);
+  sketch_row<WITH_XX>(X, stride, w, w < n_src, d, nch, img, max_norm, threadIdx.x & 63);
 }
 
+template <bool WITH_XX>
 __global__ __launch_bounds__(256) void sketch_rows_kernel(const float *__restrict__ X, size_t stride, const uint32_t *__restrict__ list,
                                                           uint32_t count, uint32_t rows_img, uint32_t d, uint32_t nch,
                                                           unsigned char *img, unsigned long long *max_norm) {
@@ -86,7 +99,7 @@ __global__ __launch_bounds__(256) void sketch_rows_kernel(const float *__restric
   if (w >= count) return;
   const uint32_t row = list[w];
   if (row >= rows_img) return;
-  sketch_row(X, stride, row, true, d, nch, img, max_norm, threadIdx.x & 63);
+  sketch_row<WITH_XX>(X, stride, row, true, d, nch, img, max_norm, threadIdx.x & 63);
 }
 
 // ---- the pass ---------------------------------------------------------------------------------
@@ -94,7 +107,9 @@ __global__ __launch_bounds__(256) void sketch_rows_kernel(const float *__restric
 // flight in a register ring that runs on across tiles.  The query's two levels sit in LDS: chunk c's 16 bytes are
 // wave-uniform, so a chunk costs one broadcast ds_read_b128 per level and eight v_dot4c_i32_i8.  The tile's last load is
 // the rows' metadata: the lane then holds everything its row's interval needs, no other memory access.
-template <int CAP>
+// L2: the L2 family's instantiation -- the same loop; the epilogue turns the dot's interval into the two words that hold
+// K1's squared distance (or its root), DESIGN 4.10.  The dot family's instantiation is the code it was without it.
+template <int CAP, bool L2>
 __global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch_scan_kernel(const SketchScanArgs a) {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const uint32_t ld8 = a.nch * 16;
@@ -177,14 +192,32 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void sketch_scan_kernel(cons
         const double rho = (double)__uint_as_float(meta.y), nu = (double)__uint_as_float(meta.z);
         const double av = s * (t1 * (double)f1 + t2 * (double)f2);
         const double e = (qn * rho + eta * nu + kerr * qn * (nu + rho) + 0x1p-40 * nu * (qn + eta)) * kSlack + tiny;
-        const float hi = f32_up(av + e), lo = f32_down(av - e);
         float khi_rank, klo_rank;  // key(lo) >= key(hi): the rank functions fall as the dot rises
-        if (a.metric == M_COS) {
-          klo_rank = 1.0f - hi;
-          khi_rank = 1.0f - lo;
+        if constexpr (L2) {
+          // (kerr = 0: |q.x_r - av| <= e bounds the REAL dot.)  The real ||q - x_r||^2 = qq + xx_r - 2 q.x_r lies in
+          // [v_lo, v_hi]; K1's f32 sum of rounded squared differences -- no term negative, nothing cancels -- within
+          // kappa = (d + 16) 2^-23 of it, relatively, and `tiny`.  xx_r is the fourth dword: at most 2^-22 above ||x_r||^2.
+          const double xxu = (double)__uint_as_float(meta.w), xxl = xxu * (1.0 - 0x1p-22);
+          const double kappa = ((double)a.d + 16.0) * 0x1p-23;
+          const double delta = 0x1p-40 * (a.qq_hi + xxu + 2.0 * e);
+          const double v_lo = fmax(0.0, a.qq_lo + xxl - 2.0 * (av + e) - delta);
+          const double v_hi = a.qq_hi + xxu - 2.0 * (av - e) + delta;
+          klo_rank = f32_down(v_lo * (1.0 - kappa) - tiny);
+          klo_rank = klo_rank > 0.0f ? klo_rank : 0.0f;  // (+0.0: K1's sum of squares is never below it)
+          khi_rank = f32_up(v_hi * (1.0 + kappa) + tiny);
+          if (a.metric == M_L2) {  // K1's own root: correctly rounded, hence monotone
+            klo_rank = __builtin_sqrtf(klo_rank);
+            khi_rank = __builtin_sqrtf(khi_rank);
+          }
         } else {
-          klo_rank = -hi;
-          khi_rank = -lo;
+          const float hi = f32_up(av + e), lo = f32_down(av - e);
+          if (a.metric == M_COS) {
+            klo_rank = 1.0f - hi;
+            khi_rank = 1.0f - lo;
+          } else {
+            klo_rank = -hi;
+            khi_rank = -lo;
+          }
         }
         const uint32_t rank = valid ? (a.id_rank ? a.id_rank[row] : row) : 0u;
         const uint64_t key = ((uint64_t)orderable(klo_rank) << 32) | rank;
@@ -281,6 +314,8 @@ __device__ __forceinline__ void radix_pick_bin(const uint32_t *hist, uint32_t *p
   }
 }
 
+// L2: the L2 family's instantiation rescores with K1's squared differences and, for VT_L2, K1's root.
+template <bool L2>
 __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchTailArgs a) {
   extern __shared__ __align__(16) uint32_t dyn[];  // the key(lo) words; once Kt is known: per-list counts, chunk sums
   __shared__ uint32_t hist[256];
@@ -444,6 +479,7 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
 
   // K1 on the candidates: wave w takes candidates w, w + 16, ...; lane l the floats [256 s + 4 l, + 4) of segment s
   float *S = reinterpret_cast<float *>(dyn + lists4);  // [cnt][ss]
+  constexpr int OP = L2 ? OP_L2 : OP_DOT;
   const int odd = lane & 1;
   const uint32_t cfull = a.d / 8, tail = a.d % 8, tail_base = a.ss - 12;
   for (uint32_t c = (uint32_t)w; c < cnt; c += kTailThreads / kWave) {
@@ -461,8 +497,8 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const uint32_t col = s0 + u * 256 + (uint32_t)lane * 4;
-        const f32x4 pr = elem4<OP_DOT>(OP_DOT, qv[u], xv[u]);
-        const float sum = chunk_sum<OP_DOT, -1>(OP_DOT, a.order, pr.x, pr.y, pr.z, pr.w, odd);
+        const f32x4 pr = elem4<OP>(OP, qv[u], xv[u]);
+        const float sum = chunk_sum<OP, -1>(OP, a.order, pr.x, pr.y, pr.z, pr.w, odd);
         const uint32_t ch = col >> 3;
         if (col < a.ld) {
           if (ch < cfull) {
@@ -493,7 +529,8 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
     for (; c < cfull; ++c) acc = acc + Sr[c];
     for (uint32_t j = 0; j < tail; ++j) acc = acc + Sr[tail_base + j];
     // distances.rs:42-68 compute(): value, finiteness, f64 recovery -- as scan_topk_kernel has them
-    raw = a.metric == M_NIP ? -acc : acc;
+    if constexpr (L2) raw = a.metric == M_L2 && finite_f32(acc) ? __builtin_sqrtf(acc) : acc;
+    else raw = a.metric == M_NIP ? -acc : acc;
     bool valid = true;
     if (!finite_f32(raw)) {
       const float rec = recover_overflow(a.metric, a.q, a.X + (size_t)row * a.stride, a.d);
@@ -504,9 +541,11 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
         valid = false;
       }
     }
-    float rank = raw;
-    if (a.metric == M_COS) rank = 1.0f - raw;
-    else if (a.metric == M_IP) rank = -raw;
+    float rank = raw;  // (the L2 family ranks by the raw value)
+    if constexpr (!L2) {
+      if (a.metric == M_COS) rank = 1.0f - raw;
+      else if (a.metric == M_IP) rank = -raw;
+    }
     if (valid) key = ((uint64_t)orderable(rank) << 32) | (a.id_rank ? a.id_rank[row] : row);
   }
   if (tid < kTailFuseMax) c_key[tid] = key;
@@ -964,22 +1003,41 @@ __global__ __launch_bounds__(256) void sketch6_rows_kernel(const float *__restri
 
 }  // namespace
 
-hipError_t launch_sketch_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+template <bool WITH_XX>
+static hipError_t sketch_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
                                unsigned long long *max_norm, hipStream_t s) {
   if (d == 0 || d > kSketchMaxDim || rows_img % kSketchTileRows) return hipErrorInvalidValue;
   if (rows_img == 0) return hipSuccess;
-  hipLaunchKernelGGL(sketch_build_kernel, dim3((rows_img + 3) / 4), dim3(256), 0, s, X, stride, n_src, rows_img, d,
+  hipLaunchKernelGGL(sketch_build_kernel<WITH_XX>, dim3((rows_img + 3) / 4), dim3(256), 0, s, X, stride, n_src, rows_img, d,
                      sketch_ld8(d) / 16, static_cast<unsigned char *>(img), max_norm);
   return hipGetLastError();
 }
 
-hipError_t launch_sketch_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+template <bool WITH_XX>
+static hipError_t sketch_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
                               void *img, unsigned long long *max_norm, hipStream_t s) {
   if (d == 0 || d > kSketchMaxDim) return hipErrorInvalidValue;
   if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(sketch_rows_kernel, dim3((count + 3) / 4), dim3(256), 0, s, X, stride, list, count, rows_img, d,
+  hipLaunchKernelGGL(sketch_rows_kernel<WITH_XX>, dim3((count + 3) / 4), dim3(256), 0, s, X, stride, list, count, rows_img, d,
                      sketch_ld8(d) / 16, static_cast<unsigned char *>(img), max_norm);
   return hipGetLastError();
+}
+
+hipError_t launch_sketch_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                               unsigned long long *max_norm, hipStream_t s) {
+  return sketch_build<false>(X, stride, n_src, rows_img, d, img, max_norm, s);
+}
+hipError_t launch_sketch_build_xx(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
+                                  unsigned long long *max_norm, hipStream_t s) {
+  return sketch_build<true>(X, stride, n_src, rows_img, d, img, max_norm, s);
+}
+hipError_t launch_sketch_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                              void *img, unsigned long long *max_norm, hipStream_t s) {
+  return sketch_rows<false>(X, stride, list, count, rows_img, d, img, max_norm, s);
+}
+hipError_t launch_sketch_rows_xx(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
+                                 void *img, unsigned long long *max_norm, hipStream_t s) {
+  return sketch_rows<true>(X, stride, list, count, rows_img, d, img, max_norm, s);
 }
 
 size_t sketch_scan_lds_bytes(uint32_t d, uint32_t k) {
@@ -992,16 +1050,16 @@ size_t sketch_scan_lds_bytes(uint32_t d, uint32_t k) {
 hipError_t launch_sketch_scan(const SketchScanArgs &a, uint32_t blocks, hipStream_t s) {
   const size_t lds = sketch_scan_lds_bytes(a.d, a.k);
   if (!lds || a.nch != sketch_ld8(a.d) / 16 || blocks == 0 || !a.part_keys || !a.part_pay) return hipErrorInvalidValue;
-  if (a.k <= (uint32_t)kSmallK) {
-    hipError_t e = allow_lds(sketch_scan_kernel<kCapSmall>, lds);
+  const bool l2 = a.metric == M_L2 || a.metric == M_L2SQ;
+  if (!l2 && a.metric != M_COS && a.metric != M_IP && a.metric != M_NIP) return hipErrorInvalidValue;
+  auto launch = [&](auto kernel) -> hipError_t {
+    hipError_t e = allow_lds(kernel, lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sketch_scan_kernel<kCapSmall>, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
-  } else {
-    hipError_t e = allow_lds(sketch_scan_kernel<kCapLarge>, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sketch_scan_kernel<kCapLarge>, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
-  }
-  return hipGetLastError();
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
+    return hipGetLastError();
+  };
+  if (a.k <= (uint32_t)kSmallK) return l2 ? launch(sketch_scan_kernel<kCapSmall, true>) : launch(sketch_scan_kernel<kCapSmall, false>);
+  return l2 ? launch(sketch_scan_kernel<kCapLarge, true>) : launch(sketch_scan_kernel<kCapLarge, false>);
 }
 
 size_t sketch_tail_lds_bytes(uint32_t lists, uint32_t kp, uint32_t d) {
@@ -1020,9 +1078,12 @@ hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s) {
   a.ld = padded_dim(a.d);
   a.ss = a.ld / 8 + 12;  // (K1's panel row: 4 * odd dwords, the eight tail products behind the sums)
   a.lds_words = (uint32_t)(lds / 4);
-  hipError_t e = allow_lds(sketch_tail_kernel, lds);
+  const bool l2 = a.metric == M_L2 || a.metric == M_L2SQ;
+  if (!l2 && a.metric != M_COS && a.metric != M_IP && a.metric != M_NIP) return hipErrorInvalidValue;
+  auto kernel = l2 ? sketch_tail_kernel<true> : sketch_tail_kernel<false>;
+  hipError_t e = allow_lds(kernel, lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(sketch_tail_kernel, dim3(1), dim3(kTailThreads), lds, s, a);
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(kTailThreads), lds, s, a);
   return hipGetLastError();
 }
 
