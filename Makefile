@@ -24,11 +24,11 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch6 vt_sketch5 vt_sketch4 vt_sketch4_rescore vt_hnsw vt_mmr vt_prepare
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch_batch vt_sketch6 vt_sketch5 vt_sketch4 vt_sketch4_rescore vt_hnsw vt_mmr vt_prepare
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -53,7 +53,9 @@ NOSCRATCH_vt_maxsim_batch := maxsim_batch_kernel
 NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_encode_slab_kernel muvera_sketch_kernel muvera_table_kernel
 # K1q, K1s, K1f and K1n (the int8, 6-bit, 5-bit and 4-bit sketch passes): the register ring must stay in registers; K1q's
 # tail and the threshold, refine and collect kernels behind the other three likewise carry no scratch segment
-NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_thresh_kernel sketch_refine_kernel sketch_collect_kernel
+NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_tail_group_kernel sketch_thresh_kernel sketch_refine_kernel sketch_collect_kernel
+# K1qm (a group of 2..8 queries in one pass over the int8 sketch): 2 G sums per lane beside the ring, all in registers
+NOSCRATCH_vt_sketch_batch := sketch_scan_multi_kernel
 NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
 NOSCRATCH_vt_sketch5      := sketch5_scan_kernel
 NOSCRATCH_vt_sketch4      := sketch4_scan_kernel
@@ -91,7 +93,8 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
 
 # (what the sketch units share)
-$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/vt_sketch4.o: $(CSRC)/vt_sketch.cuh
+$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/vt_sketch4.o: $(CSRC)/vt_sketch.cuh
+$(LIBDIR)/vt_sketch_batch.o: $(CSRC)/host/vt_sketchbatch.h
 
 # (the pass K9r and K9rb share; K11 and K12 take its finish_raw)
 $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_maxsim_pair.cuh
@@ -172,6 +175,15 @@ $(LIBDIR)/sketch_l2_probe.o: tests/sketch_l2_probe.cpp $(CSRC)/vt_device.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch_l2_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/sketch_l2_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# K1qm's kernels behind a probe (tests/sketch_batch_probe.cpp; tests/test_gpu_sketch_batch_kernels.py loads it): the group
+# pass and the group tail beside the lone pass and the lone tail, on a test's arrays.  Test infrastructure, as above.
+$(LIBDIR)/sketch_batch_probe.o: tests/sketch_batch_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch_batch_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/sketch_batch_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

@@ -763,6 +763,15 @@ typedef struct vt_profile {
   uint64_t sketch4_builds;           /* whole builds of the 4-bit sketch */
   uint64_t sketch4_patched_rows;     /* rows re-quantised in place after mutations */
   uint64_t sketch4_finished;         /* searches whose result the filtered K1 behind the pass wrote itself (no select, one wait) */
+  /* K1qm: batches and meeting callers of 2..8 queries nominated from one pass over the int8 sketch (the lone counters
+   * above are not touched by these passes) */
+  uint64_t sketch_batch_launches;    /* group passes over the int8 sketch */
+  uint64_t sketch_batch_queries;     /* queries that entered a group pass */
+  double sketch_batch_ms;
+  uint64_t sketch_batch_bytes;       /* what the group passes read: whole tiles and their metadata, once per group */
+  uint64_t sketch_batch_candidates;  /* candidates the groups' tail blocks counted, summed over queries */
+  uint64_t sketch_batch_fallbacks;   /* queries a group handed on unanswered (not certified, or a candidate list too long for the tail's block) */
+  uint64_t sketch_batch_tail_rescored; /* queries finished by their tail block */
 } vt_profile;
 int vt_flat_set_profiling(vt_flat *index, int enabled);
 int vt_flat_get_profile(vt_flat *index, vt_profile *out, int reset);

@@ -576,7 +576,38 @@ bool allocation_failed(int st, const std::string &why) {
   return st == VT_ERR_NOMEM || (st == VT_ERR_DEVICE && (why.find("hipMalloc") != std::string::npos || why.find("hipHostMalloc") != std::string::npos));
 }
 
-// Rank column strictly current, norms current when batch_uses_mfma (shard_prepare).
+// K1qm's stage of a batch (sketch_batch_wanted said yes, the int8 column is current): the queries the lone path's overflow
+// gates would turn away stay out -- K1's own scan decides those --, the others are planned into groups of near-equal
+// size (host/vt_sketchbatch.h) and every group is one sketch_group_search.  Whatever is not `done` afterwards is the
+// caller's to serve.  (The groups of one call run one after the other on `c`: alternating with the spare context, as
+// funnel_groups does, has not been measured.)
+int sketch_batch_stage(Shard *ix, Ctx &c, const float *queries, size_t nq, size_t limit, vt_hits **out, std::vector<char> &done) {
+  const uint32_t d = (uint32_t)ix->dim;
+  const bool l2 = sketch_l2_metric(ix->metric);
+  std::vector<size_t> fit;
+  for (size_t i = 0; i < nq; ++i) {
+    float m1 = 0.0f;
+    double qq = 0.0;
+    sketch_query_norms(queries + i * d, d, &m1, &qq);
+    if (vt_host::sketch_batch_query_fits(l2, std::sqrt(qq) * (1.0 + 0x1p-30), ix->sketch_max_norm)) fit.push_back(i);
+  }
+  const uint32_t gmax = vt_host::sketch_batch_max_group(d, sketch_list_k(limit));
+  size_t first = 0;
+  for (uint32_t size : vt_host::sketch_batch_plan(fit.size(), gmax)) {
+    const std::vector<size_t> which(fit.begin() + first, fit.begin() + first + size);
+    VT_TRY(sketch_group_search(ix, c, queries, which, limit, out, done));
+    first += size;
+  }
+  return VT_OK;
+}
+
+// Rank column strictly current; norms current when batch_uses_mfma, or the int8 sketch when sketch_batch_wanted
+// (shard_prepare; batch_need says which).
+unsigned batch_need(const Shard *ix, size_t nq, size_t limit) {
+  if (sketch_batch_wanted(ix, nq, limit)) return NEED_SKETCH8;  // (not the norms: the groups read neither them nor the shadow)
+  return batch_uses_mfma(ix, nq, limit) ? NEED_NORMS : 0u;
+}
+
 int batch_ready(Shard *ix, Ctx &c, const float *queries, size_t nq, size_t d, size_t limit, vt_hits **out) {
   // every query is validated like flat_search would (flat.rs:97-101), in order
   if (limit == 0) {
@@ -589,7 +620,15 @@ int batch_ready(Shard *ix, Ctx &c, const float *queries, size_t nq, size_t d, si
     return VT_OK;
   }
   std::vector<char> done(nq, 0);
-  const bool use_mfma = batch_uses_mfma(ix, nq, limit);
+  // K1qm first: small batches and meeting callers share passes over the int8 sketch.  The queries its groups leave
+  // (declined, not certified, a long candidate list) go on below as the queries a stage leaves over always have -- not
+  // through the matrix cores, whose norms and shadow nobody was asked to bring up to date for this call.
+  const bool sketch_groups = sketch_batch_wanted(ix, nq, limit);
+  if (sketch_groups && ix->sketch.current(sketch_elems(ix))) {
+    VT_TRY(sketch_batch_stage(ix, c, queries, nq, limit, out, done));
+    if (std::find(done.begin(), done.end(), (char)0) == done.end()) return VT_OK;
+  }
+  const bool use_mfma = !sketch_groups && batch_uses_mfma(ix, nq, limit);
   const bool bf16 = batch_nominates_bf16(ix);
   if (use_mfma) {
     std::vector<float> tau2(nq, std::numeric_limits<float>::quiet_NaN());

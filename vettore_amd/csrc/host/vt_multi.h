@@ -44,8 +44,9 @@ int on_all_shards(vt_flat *h, F fn) {
 // A read on a one-shard handle: under the shared lock on a leased context when the derived
 // columns it needs are current; otherwise (or when a lazy search hit a tie only the true id
 // order can cut) under the exclusive lock, which first brings them up to date.
-template <class F>
-int read_single(vt_flat *h, unsigned need, size_t limit, F &&fn) {
+// `more_need(ix)`: what the body may turn out to want besides, asked under the exclusive lock before its last run.
+template <class F, class M>
+int read_single(vt_flat *h, unsigned need, size_t limit, F &&fn, M &&more_need) {
   Shard *ix = h->shards[0].get();
   bool escalated = false;
   {
@@ -71,11 +72,16 @@ int read_single(vt_flat *h, unsigned need, size_t limit, F &&fn) {
     // ago (a writer may have pushed the corpus past a threshold between the caller's look at it
     // and this run, so that the body now wants norms it did not ask for) is brought up to date
     // here, all of it, and the body runs once more.  kEscalate never leaves this function.
-    VT_TRY(shard_prepare(ix, need | NEED_STRICT_RANKS | NEED_NORMS, limit));
+    VT_TRY(shard_prepare(ix, need | NEED_STRICT_RANKS | NEED_NORMS | more_need(ix), limit));
     st = fn(ix, ix->ctx);
     if (st == kEscalate) return fail(VT_ERR_DEVICE, "internal: a search found its derived columns stale under the exclusive lock");
   }
   return st;
+}
+
+template <class F>
+int read_single(vt_flat *h, unsigned need, size_t limit, F &&fn) {
+  return read_single(h, need, limit, fn, [](Shard *) { return 0u; });
 }
 
 // flat.rs:88-93 on one shard.
@@ -420,8 +426,12 @@ int batch_multi(vt_flat *h, const float *queries, size_t nq, size_t d, size_t li
   for (size_t s = 0; s < S; ++s) all[s] = s;
   auto shard_job = [&](size_t s) -> int {
     Shard *ix = h->shards[s].get();
-    const unsigned need = NEED_STRICT_RANKS | NEED_NZBITS | (batch_uses_mfma(ix, nq, limit) ? NEED_NORMS : 0u);
-    if (shard_stale(ix, need, limit)) VT_TRY(shard_prepare(ix, need, limit));
+    // (twice: what the batch needs may change once the ranks are strictly current -- K1qm's groups then want the int8
+    // sketch -- or once that column has been refused for want of room: the batch then runs as it did before there were groups)
+    for (int round = 0; round < 2; ++round) {
+      const unsigned need = NEED_STRICT_RANKS | NEED_NZBITS | batch_need(ix, nq, limit);
+      if (shard_stale(ix, need, limit)) VT_TRY(shard_prepare(ix, need, limit));
+    }
     // (this worker's lists go into the merge and nowhere else: they name their rows, the ids -- 2 560 string
     // copies per 256 queries and shard -- are copied once, for the winners.  The request is this job's, on this thread.)
     const int st = guarded([&]() -> int {
@@ -901,17 +911,19 @@ int batch_direct(vt_flat *h, const float *queries, size_t nq, size_t d, size_t l
     unsigned need = NEED_STRICT_RANKS | NEED_NZBITS;
     {
       std::shared_lock<std::shared_mutex> rl(h->rw);
-      if (batch_uses_mfma(h->shards[0].get(), nq, limit)) need |= NEED_NORMS;
+      need |= batch_need(h->shards[0].get(), nq, limit);  // (the norms and the shadow, or the int8 sketch for K1qm's groups)
     }
     st = read_single(h, need, limit, [&](Shard *ix, Ctx &c) -> int {
       for (size_t i = 0; i < nq; ++i) {  // (a second run after an escalation starts clean)
         delete out[i];
         out[i] = nullptr;
       }
-      if (ix->n && batch_uses_mfma(ix, nq, limit) && shard_stale(ix, NEED_NORMS, limit)) return kEscalate;
+      // (batch_need now: the corpus may have crossed a cut since the look above, or the int8 column was refused -- then
+      // the batch runs as it did before there were groups, norms and all)
+      if (ix->n && shard_stale(ix, batch_need(ix, nq, limit), limit)) return kEscalate;
       const int rs = batch_ready(ix, c, queries, nq, d, limit, out);
       return rs == VT_OK && after ? after(ix, c) : rs;
-    });
+    }, [&](Shard *ix) { return batch_need(ix, nq, limit); });  // (the int8 sketch, when K1qm's groups turn out to want it)
   }
   if (st != VT_OK)
     for (size_t i = 0; i < nq; ++i) {

@@ -6,7 +6,7 @@
 namespace {
 
 // ---- what a reader needs up to date before it may run under the shared lock ----------
-enum : unsigned { NEED_RANKS = 1, NEED_STRICT_RANKS = 2, NEED_BITS = 4, NEED_NORMS = 8, NEED_NZBITS = 16, NEED_SKETCH = 32 };
+enum : unsigned { NEED_RANKS = 1, NEED_STRICT_RANKS = 2, NEED_BITS = 4, NEED_NORMS = 8, NEED_NZBITS = 16, NEED_SKETCH = 32, NEED_SKETCH8 = 64 };
 // Internal: only the true id order can decide (a tie at the boundary of a lazy search).
 constexpr int kEscalate = -101;
 
@@ -79,6 +79,27 @@ bool sketch_wanted(const Shard *ix, size_t limit) {
   return vt::env::on(vt::env::FORCE_SKETCH) || vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= cut;
 }
 size_t sketch_elems(const Shard *ix) { return vt::sketch_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
+
+// K1qm (vt_sketch_batch.hip): a batch -- or callers that met -- of 2..kSketchBatchMaxQueries queries with limits up
+// to 32 shares passes over the int8 sketch, eight queries a pass, where a lone search of the handle would read it and
+// the f32 rows reach the batch cut (host/vt_sketchbatch.h holds the gate, the cuts and the planner as plain C++).
+// force_sketch = 2 lifts the cut and the query bound (tests); sketch = 2 keeps batches off the sketch.  NEED_SKETCH8 asks
+// for the int8 column alone and means nothing where sketch_wanted says no.
+bool sketch_batch_wanted(const Shard *ix, size_t nq, size_t limit) {
+  if (!sketch_wanted(ix, limit)) return false;
+  vt_host::SketchBatchShape s;
+  s.dot_metric = sketch_dot_metric(ix->metric);
+  s.l2_metric = sketch_l2_metric(ix->metric);
+  s.strictly_ranked = ix->ranks_clean;
+  s.single_nominate = ix->single_nominate;
+  s.refused = ix->sketch.refused;
+  s.dim = (uint32_t)ix->dim;
+  s.row_bytes = (double)ix->n * ix->ld * 4.0;
+  s.sketch = vt::env::get(vt::env::SKETCH);
+  s.force = vt::env::get(vt::env::FORCE_SKETCH);
+  s.column_lacks_xx = ix->sketch.valid && !ix->sketch_xx;
+  return vt_host::sketch_batch_gate(s, nq, limit);
+}
 
 // K1s (vt_sketch6.hip; its tail and builders: vt_sketch.hip): where K1q applies, limits up to kSketch6MaxLimit over f32 rows of at least
 // kSketch6MinBytes read the 6-bit sketch instead -- 0.755 of the int8 sketch's bytes -- with block lists of kSketch6ListK
@@ -212,7 +233,7 @@ ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   if ((need & NEED_NZBITS) && pattern_search_applies(ix, limit)) w.nz_bits = bwords;
   if (need & NEED_NORMS) w.norms = rows;
   if ((need & NEED_NORMS) && shadow_wanted(ix)) w.shadow = shadow_elems(ix);
-  if ((need & NEED_SKETCH) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
+  if ((need & (NEED_SKETCH | NEED_SKETCH8)) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
   if ((need & NEED_SKETCH) && sketch6_wanted(ix, limit)) w.sketch6 = sketch6_elems(ix);
   if ((need & NEED_SKETCH) && sketch5_wanted(ix, limit)) w.sketch5 = sketch5_elems(ix);
   if ((need & NEED_SKETCH) && sketch4_wanted(ix, limit)) w.sketch4 = sketch4_elems(ix);
@@ -431,6 +452,138 @@ int sketch_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   std::vector<vt::Entry> entries(c.hRes.p->e, c.hRes.p->e + c.hRes.p->count);
   VT_TRY(make_hits(ix, entries, out));
   *done = true;
+  return VT_OK;
+}
+
+// ||q||^2 in f64 and max |q_i|, as sketch_search forms them
+void sketch_query_norms(const float *query, uint32_t d, float *m1_out, double *qq_out) {
+  float m1 = 0.0f;
+  double qq = 0.0;
+  for (uint32_t i = 0; i < d; ++i) {
+    m1 = std::max(m1, std::fabs(query[i]));
+    qq += (double)query[i] * (double)query[i];
+  }
+  *m1_out = m1;
+  *qq_out = qq;
+}
+
+// K1qm, one host wait: the queries `which` (2..8 rows of `queries`, none of which sketch_batch_query_fits
+// turned away) in ONE pass over the int8 sketch, then one launch of K1q's tail with a block per query -- blit, pass, tail,
+// wait, as a lone K1q search.  Each query's levels, bounds and lists are the ones sketch_search would form for it, so a
+// query whose block certified and rescored (outcome 1) gets flat_search's hits and done[which[g]] = 1.  A query whose
+// candidate list is too long for the block (outcome 2), or not certified (0), or whose rescoring raised K1's overflow
+// flag, stays unanswered for what batch_ready does with left-over queries, and counts as a fallback: no second chain here.
+int sketch_group_search(Shard *ix, Ctx &c, const float *queries, const std::vector<size_t> &which, size_t limit, vt_hits **out,
+                        std::vector<char> &done) {
+  const uint32_t ng = (uint32_t)which.size();
+  const uint32_t d = (uint32_t)ix->dim, ld = ix->ld, ld8 = vt::sketch_ld8(d), nch = ld8 / 16;
+  const uint32_t kp = sketch_list_k(limit), k = (uint32_t)limit;
+  const uint32_t group = vt::sketch_scan_multi_group(ng);
+  const size_t lds = vt::sketch_scan_multi_lds_bytes(d, kp, group);
+  if (ng < 2 || ng > (uint32_t)vt::kSketchMultiMax || !lds) return fail(VT_ERR_DEVICE, "internal: a sketch group the pass does not take");
+  const bool l2 = sketch_l2_metric(ix->metric);
+  const double up = 1.0 + 0x1p-30;
+  // one upload: the ng f32 queries (the tail's), then `group` images of two levels (the pass's; the places past ng zero)
+  const size_t img_floats = 2 * (size_t)ld8 / 4;
+  const size_t total = (size_t)ng * ld + (size_t)group * img_floats;
+  VT_TRY(c.dBQ.ensure(total));
+  VT_TRY(c.hBQ.ensure(total));
+  VT_TRY(c.hQ.ensure((size_t)ld + img_floats));
+  if (c.hSkResid.size() < d) c.hSkResid.resize(d);
+  vt::SketchScanMultiArgs a{};
+  for (uint32_t g = 0; g < ng; ++g) {
+    const float *query = queries + which[g] * d;
+    float m1 = 0.0f, t1 = 0.0f, t2 = 0.0f;
+    double qq = 0.0, ee = 0.0;
+    sketch_query_norms(query, d, &m1, &qq);
+    sketch_query_image(c, query, d, ld, ld8, m1, &t1, &t2, &ee);  // (into c.hQ: the query padded to ld, its two levels behind)
+    std::memcpy(c.hBQ.p + (size_t)g * ld, c.hQ.p, (size_t)ld * sizeof(float));
+    std::memcpy(c.hBQ.p + (size_t)ng * ld + (size_t)g * img_floats, c.hQ.p + ld, img_floats * sizeof(float));
+    a.t1[g] = t1;
+    a.t2[g] = t2;
+    a.qn[g] = std::sqrt(qq) * up;
+    a.eta[g] = std::sqrt(ee) * up;
+    a.kerr[g] = l2 ? 0.0 : 8.0 * d * 0x1p-24;  // (as sketch_search)
+    a.qq_lo[g] = qq / up;
+    a.qq_hi[g] = qq * up;
+  }
+  if (group > ng) std::memset(c.hBQ.p + (size_t)ng * ld + (size_t)ng * img_floats, 0, (size_t)(group - ng) * img_floats * sizeof(float));
+  c.qbits_kind = 0;  // (c.hQ no longer holds the query last uploaded)
+  VT_HIP(hipMemcpyAsync(c.dBQ.p, c.hBQ.p, total * sizeof(float), hipMemcpyHostToDevice, c.stream));
+
+  // (two to four blocks a CU, as many as its LDS holds of them: K1q's grid where the group is small)
+  const uint32_t per_cu = (uint32_t)std::min<size_t>(4, (160 * 1024) / (lds + vt_host::kSketchBatchLdsStatic));
+  const uint32_t blocks = (uint32_t)c.num_cus * std::max(1u, per_cu);
+  VT_TRY(c.dSkKeys.ensure((size_t)ng * blocks * kp));
+  VT_TRY(c.dSkPay.ensure((size_t)ng * blocks * kp));
+  VT_TRY(c.dSkRows.ensure((size_t)vt::kSketchMultiMax * kSketchCandCap));
+  VT_TRY(c.dSkCount.ensure(vt::kSketchMultiMax));
+  VT_TRY(c.hSkInfo.ensure(4 * vt::kSketchMultiMax));
+  VT_TRY(c.hSkgRes.ensure(vt::kSketchMultiMax));
+  if (c.dSkgStatus.count < (size_t)vt::kSketchMultiMax) {
+    VT_TRY(c.dSkgStatus.ensure(vt::kSketchMultiMax));
+    VT_HIP(hipMemsetAsync(c.dSkgStatus.p, 0, vt::kSketchMultiMax * sizeof(int), c.stream));
+  }
+  uint32_t *info = c.hSkInfo.mapped();
+  vt::ResultBlock *res = c.hSkgRes.mapped();
+  if (!info || !res) return fail(VT_ERR_DEVICE, "hipHostGetDevicePointer (sketch group status)");
+  a.img = ix->sketch.buf.p;
+  a.id_rank = ix->dRank.p;
+  a.qimg = reinterpret_cast<const int8_t *>(c.dBQ.p + (size_t)ng * ld);
+  a.n = ix->n;
+  a.d = d;
+  a.nch = nch;
+  a.ng = ng;
+  a.metric = ix->metric;
+  a.k = kp;
+  a.part_keys = c.dSkKeys.p;
+  a.part_pay = c.dSkPay.p;
+  VT_TRY(c.mark_begin());
+  VT_HIP(vt::launch_sketch_scan_multi(a, blocks, c.stream));
+  VT_TRY(c.mark_end());
+  vt::SketchTailArgs ta{};  // (query 0's: block g takes its own slice)
+  ta.keys = c.dSkKeys.p;
+  ta.pay = c.dSkPay.p;
+  ta.lists = blocks;
+  ta.kp = kp;
+  ta.k = k;
+  ta.cap = kSketchCandCap;
+  ta.rows = c.dSkRows.p;
+  ta.count = c.dSkCount.p;
+  ta.info = info;
+  ta.X = ix->dX;
+  ta.stride = ld;
+  ta.q = c.dBQ.p;
+  ta.id_rank = ix->dRank.p;
+  ta.d = d;
+  ta.metric = ix->metric;
+  ta.order = ix->order;
+  ta.status = c.dSkgStatus.p;
+  ta.out = res;
+  VT_HIP(vt::launch_sketch_tail_group(ta, ng, ld, c.stream));
+  VT_HIP(hipStreamSynchronize(c.stream));
+  if (c.profiling) {
+    float ms = 0.f;
+    VT_TRY(c.span_ms(&ms));
+    c.prof.sketch_batch_launches += 1;
+    c.prof.sketch_batch_queries += ng;
+    c.prof.sketch_batch_ms += ms;
+    c.prof.sketch_batch_bytes += (uint64_t)vt::sketch_bytes(ix->n, d);
+    VT_TRY(c.book_scan(1, ix->n, (uint64_t)vt::sketch_bytes(ix->n, d)));  // (a pass over the rows' sketch: a scan, as K1q's counts)
+  }
+  for (uint32_t g = 0; g < ng; ++g) {
+    const uint32_t *gi = c.hSkInfo.p + 4 * g;
+    const vt::ResultBlock &rb = c.hSkgRes.p[g];
+    if (c.profiling) c.prof.sketch_batch_candidates += gi[1];
+    if (gi[0] != 1u || rb.status != 0) {
+      if (c.profiling) c.prof.sketch_batch_fallbacks += 1;
+      continue;
+    }
+    if (c.profiling) c.prof.sketch_batch_tail_rescored += 1;
+    std::vector<vt::Entry> entries(rb.e, rb.e + std::min<uint32_t>(rb.count, k));
+    VT_TRY(make_hits(ix, entries, &out[which[g]]));
+    done[which[g]] = 1;
+  }
   return VT_OK;
 }
 

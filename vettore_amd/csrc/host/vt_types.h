@@ -55,6 +55,11 @@ struct Ctx {
   DevBuf<uint32_t> dSkRows, dSkCount;
   PinnedBuf<uint32_t> hSkInfo;
   std::vector<double> hSkResid;
+  // K1qm (vt_search.h, sketch_group_search) takes the five above at a group's size ([G][blocks][k'] lists, [G][cap] rows,
+  // [G] counts, [G][4] info) and, per query of the group, a result block the tail writes through the host mapping and a
+  // status word (zero between calls: the tail takes what it raised back)
+  PinnedBuf<vt::ResultBlock> hSkgRes;
+  DevBuf<int> dSkgStatus;
   DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
   DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
   DevBuf<uint32_t> dSkParts;  // K1s / K1f: the threshold kernel's k smallest words per block, then its live counts

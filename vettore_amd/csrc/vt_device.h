@@ -877,6 +877,33 @@ struct SketchTailArgs {
 };
 hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s);
 
+// ---- K1qm (vt_sketch_batch.hip): 2..8 such searches in one pass over the int8 sketch -----------------------------------
+// Query g of the group has its own two levels, bounds and lists; the two words kept for (query g, row r) are bit for bit
+// launch_sketch_scan's for that query alone.  The pass is compiled for groups of 2, 4 and 8 (sketch_scan_multi_group(ng):
+// the one a group of ng runs as); qimg holds that many images, the ones past ng zero.  k <= kSmallK.
+constexpr int kSketchMultiMax = 8;
+struct SketchScanMultiArgs {
+  const void *img;
+  const uint32_t *id_rank;
+  const int8_t *qimg;       // [sketch_scan_multi_group(ng)][2][ld8]
+  uint32_t n, d, nch, ng;   // nch = ld8 / 16; 2 <= ng <= kSketchMultiMax
+  int metric;               // as SketchScanArgs
+  uint32_t k;               // entries per block list (k')
+  uint64_t *part_keys;      // [ng][blocks][k], as launch_sketch_scan writes a query's
+  Payload *part_pay;        // [ng][blocks][k]
+  float t1[kSketchMultiMax], t2[kSketchMultiMax];  // per query, as SketchScanArgs has them
+  double qn[kSketchMultiMax], eta[kSketchMultiMax], kerr[kSketchMultiMax];
+  double qq_lo[kSketchMultiMax], qq_hi[kSketchMultiMax];
+};
+uint32_t sketch_scan_multi_group(uint32_t ng);
+// (two blocks must fit a CU: 0 when `group` images and wave buffers take more than half its LDS, or k > kSmallK)
+size_t sketch_scan_multi_lds_bytes(uint32_t d, uint32_t k, uint32_t group);
+hipError_t launch_sketch_scan_multi(const SketchScanMultiArgs &a, uint32_t blocks, hipStream_t s);
+// launch_sketch_tail for every query of a group in one launch, a block per query: `a` is query 0's; block g takes the
+// slice g of keys / pay ([ng][lists][kp]) and of rows ([ng][cap]), count + g, info + 4 g, q + g * q_stride, out + g and
+// status + g.  Each block's outcome is what launch_sketch_tail gives on that slice.
+hipError_t launch_sketch_tail_group(SketchTailArgs a, uint32_t ng, size_t q_stride, hipStream_t s);
+
 // The same certification behind K1s's and K1f's passes, spread over the card in two launches (vt_sketch.hip): Kt, the
 // candidates, their count and the full-list check are the ones launch_sketch_tail would give; nothing is rescored (the
 // caller queues the gathered K1 and its select behind).  launch_sketch_thresh: every block's k smallest key(lo) words

@@ -46,7 +46,7 @@ enum Parse {
   X(REDUCE_ORDER, "reduce_order", P_ORDER, 3, "lane order of `wide::f32x8::reduce_add` for indexes created afterwards: `pair`, `avx`, `seq`, `sse2` (default; DESIGN 3.3); per handle: `vt_flat_set_reduce_order`") \
   X(BATCH_NOMINATE, "batch_nominate", P_NOMINATE, 2, "`f32`: batches nominate on the FP32 matrix cores (K2) instead of the bf16 ones (K2b / K2s, the default); per handle: `vt_flat_set_batch_nominate`") \
   X(BATCH_SHADOW, "batch_shadow", P_SHADOW, 1, "`0` / `off`: never build the bf16 shadow of the rows (K2b from the f32 rows instead of K2s); per handle: `vt_flat_set_batch_shadow`") \
-  X(SKETCH, "sketch", P_FLAG, 1, "`0`: lone cosine / dot searches never read the int8 sketch of the rows (K1q, DESIGN 4.10): every one is a K1 scan of the f32 rows") \
+  X(SKETCH, "sketch", P_FLAG, 1, "`0`: lone cosine / dot searches never read the int8 sketch of the rows (K1q, DESIGN 4.10): every one is a K1 scan of the f32 rows, and batches never share a pass over it (K1qm); `2`: lone searches read the sketches, batches and meeting callers never do (the A/B switch of K1qm within one build)") \
   X(SKETCH6, "sketch6", P_FLAG, 1, "`0`: large lone cosine / dot searches never read the 6-bit sketch (K1s, DESIGN 4.10) nor the 5-bit one (K1f) nor the 4-bit one (K1n): the int8 sketch serves them; `2`: never the 5-bit and 4-bit ones: the 6-bit sketch serves them; `3`: never the 4-bit one: the 5-bit sketch serves them") \
   X(SINGLE_NOMINATE, "single_nominate", P_FLAG, 0, "`1`: lone searches go through the shadow like a batch of one (opt-in); per handle: `vt_flat_set_single_nominate`") \
   X(BF16_MIN_RANK, "bf16_min_rank", P_INT, 6, "K2b / K2s: smallest sample rank the threshold is taken from (default 6)") \
@@ -71,7 +71,7 @@ enum Parse {
   X(FORCE_BATCH_MFMA, "force_batch_mfma", P_NONE, 0, "tests: the shared matrix-core pass whatever the cost model says (small corpora)") \
   X(FORCE_SWEEP_GROUPS, "force_sweep_groups", P_NONE, 0, "tests and soaks: K1p sweeps on corpora of a few MB") \
   X(FORCE_MULTI_SCAN, "force_multi_scan", P_NONE, 0, "tests: K1m on corpora of a few thousand rows") \
-  X(FORCE_SKETCH, "force_sketch", P_NONE, 0, "tests: lone cosine / dot searches read the int8 sketch on corpora of a few MB") \
+  X(FORCE_SKETCH, "force_sketch", P_NONE, 0, "tests: lone cosine / dot searches read the int8 sketch on corpora of a few MB; `2`: and batches and meeting callers of two or more queries share passes over it (K1qm), whatever their number") \
   X(FORCE_SKETCH6, "force_sketch6", P_NONE, 0, "tests: lone cosine / dot searches with limits up to 32 read the 6-bit sketch on corpora of a few MB; `2`: and those with limits up to 10 the 5-bit sketch first; `3`: and the 4-bit sketch before that") \
   X(FORCE_THRESHOLD_SELECT, "force_threshold_select", P_NONE, 0, "tests: the key-column threshold path for limits 257..4 096 on small corpora") \
   X(BF16_RANK, "bf16_rank", P_NONE, 0, "tests: K2b / K2s take their threshold from exactly this sample rank (`= limit` leaves no margin: every query takes the second pass)") \

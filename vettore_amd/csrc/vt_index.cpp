@@ -36,6 +36,7 @@
 #include "host/vt_idtable.h"
 #include "host/vt_sketch6.h"
 #include "host/vt_sketch5.h"
+#include "host/vt_sketchbatch.h"
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
@@ -1384,6 +1385,13 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.sketch4_builds += p.sketch4_builds;
       t.sketch4_patched_rows += p.sketch4_patched_rows;
       t.sketch4_finished += p.sketch4_finished;
+      t.sketch_batch_launches += p.sketch_batch_launches;
+      t.sketch_batch_queries += p.sketch_batch_queries;
+      t.sketch_batch_ms += p.sketch_batch_ms;
+      t.sketch_batch_bytes += p.sketch_batch_bytes;
+      t.sketch_batch_candidates += p.sketch_batch_candidates;
+      t.sketch_batch_fallbacks += p.sketch_batch_fallbacks;
+      t.sketch_batch_tail_rescored += p.sketch_batch_tail_rescored;
       if (reset) c.prof = vt_profile{};
     });
   if (reset) h->xprof = vt_profile{};

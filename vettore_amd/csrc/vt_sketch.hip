@@ -315,8 +315,10 @@ __device__ __forceinline__ void radix_pick_bin(const uint32_t *hist, uint32_t *p
 }
 
 // L2: the L2 family's instantiation rescores with K1's squared differences and, for VT_L2, K1's root.
+// (The block's whole work as a function: sketch_tail_kernel runs it on its arguments, sketch_tail_group_kernel -- K1qm's
+// tail, a block per query of a group -- on block g's slice of them.)
 template <bool L2>
-__global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchTailArgs a) {
+__device__ __forceinline__ void sketch_tail_body(const SketchTailArgs a) {
   extern __shared__ __align__(16) uint32_t dyn[];  // the key(lo) words; once Kt is known: per-list counts, chunk sums
   __shared__ uint32_t hist[256];
   __shared__ uint32_t s_prefix, s_remaining, s_total, s_count, s_fail, s_live, s_nsv, s_kt;
@@ -575,6 +577,27 @@ __global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchT
     a.info[2] = kt;
     a.info[3] = 0u;
   }
+}
+
+template <bool L2>
+__global__ __launch_bounds__(kTailThreads) void sketch_tail_kernel(const SketchTailArgs a) {
+  sketch_tail_body<L2>(a);
+}
+
+// K1qm's tail: block g is launch_sketch_tail's one block on query g's lists, rows, count, info, query, result and status.
+template <bool L2>
+__global__ __launch_bounds__(kTailThreads) void sketch_tail_group_kernel(const SketchTailArgs a0, size_t q_stride) {
+  const uint32_t g = blockIdx.x;
+  SketchTailArgs a = a0;
+  a.keys += (size_t)g * a0.lists * a0.kp;
+  a.pay += (size_t)g * a0.lists * a0.kp;
+  a.rows += (size_t)g * a0.cap;
+  a.count += g;
+  a.info += 4 * g;
+  a.q += (size_t)g * q_stride;
+  a.status += g;
+  a.out += g;
+  sketch_tail_body<L2>(a);
 }
 
 // ---- the tail of K1s and K1f, spread over the card: two kernels, Kt across the boundary between them ------------------
@@ -1084,6 +1107,25 @@ hipError_t launch_sketch_tail(SketchTailArgs a, hipStream_t s) {
   hipError_t e = allow_lds(kernel, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kernel, dim3(1), dim3(kTailThreads), lds, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sketch_tail_group(SketchTailArgs a, uint32_t ng, size_t q_stride, hipStream_t s) {
+  if (a.lists == 0 || a.kp == 0 || a.k == 0 || a.k > a.kp || a.k > (uint32_t)kMaxFusedK || !a.rows || !a.count || !a.info || !a.out ||
+      !a.status || a.d == 0 || ng == 0 || ng > (uint32_t)kSketchMultiMax || a.cap == 0)
+    return hipErrorInvalidValue;
+  const size_t lds = sketch_tail_lds_bytes(a.lists, a.kp, a.d);
+  if (lds > kMaxLds - 8 * 1024) return hipErrorInvalidValue;
+  a.ld = padded_dim(a.d);
+  a.ss = a.ld / 8 + 12;  // (as launch_sketch_tail)
+  a.lds_words = (uint32_t)(lds / 4);
+  if (q_stride < a.ld) return hipErrorInvalidValue;
+  const bool l2 = a.metric == M_L2 || a.metric == M_L2SQ;
+  if (!l2 && a.metric != M_COS && a.metric != M_IP && a.metric != M_NIP) return hipErrorInvalidValue;
+  auto kernel = l2 ? sketch_tail_group_kernel<true> : sketch_tail_group_kernel<false>;
+  hipError_t e = allow_lds(kernel, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(ng), dim3(kTailThreads), lds, s, a, q_stride);
   return hipGetLastError();
 }
 
