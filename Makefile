@@ -24,7 +24,7 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch_batch vt_sketch6 vt_sketch5 vt_sketch4 vt_sketch4_rescore vt_hnsw vt_mmr vt_prepare
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch_batch vt_sketch_nibble vt_sketch4_rescore vt_hnsw vt_mmr vt_prepare
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
@@ -56,10 +56,9 @@ NOSCRATCH_vt_muvera       := muvera_encode_kernel muvera_encode_slab_kernel muve
 NOSCRATCH_vt_sketch       := sketch_scan_kernel sketch_tail_kernel sketch_tail_group_kernel sketch_thresh_kernel sketch_refine_kernel sketch_collect_kernel
 # K1qm (a group of 2..8 queries in one pass over the int8 sketch): 2 G sums per lane beside the ring, all in registers
 NOSCRATCH_vt_sketch_batch := sketch_scan_multi_kernel
-NOSCRATCH_vt_sketch6      := sketch6_scan_kernel
-NOSCRATCH_vt_sketch5      := sketch5_scan_kernel
-NOSCRATCH_vt_sketch4      := sketch4_scan_kernel
-# K1s's pass branches three ways per run on wave-uniform cursors.  By default the CFG structurizer lays the three arms out in
+NOSCRATCH_vt_sketch_nibble := sketch6_scan_kernel sketch5_scan_kernel sketch4_scan_kernel
+# The nibble passes (K1s, K1f, K1n: one skeleton, vt_sketch_nibble.cuh) branch three ways per run on wave-uniform cursors --
+# H-run, L-run, metadata; K1n two ways.  By default the CFG structurizer lays the three arms out in
 # a row behind flags, as it must for divergent branches, and every sum then lives across all arms and is copied in each
 # (about 400 v_mov_b32 per tile at d = 768, profiles/sketch6_loop/isa_counts.txt); told to leave wave-uniform regions as
 # written, the arms hold their dots alone.  For that unit only: no other kernel is built this way.
@@ -67,11 +66,9 @@ NOSCRATCH_vt_sketch4      := sketch4_scan_kernel
 # tile's run blocks) are this toolchain's.  A compiler without it fails the build (unknown argument); one that changes what
 # it does still builds a correct kernel (every test holds either way) but may bring the copies back: after a ROCm update
 # count again as profiles/sketch6_loop/isa_counts.txt says, and compare the pass's time.
-EXTRA_vt_sketch6          := -mllvm -structurizecfg-skip-uniform-regions=true
-# (K1f's pass, the 5-bit sketch: the same loop with another L plane)
-EXTRA_vt_sketch5          := $(EXTRA_vt_sketch6)
-# (K1n's pass, the 4-bit sketch: the same loop with two arms, data and metadata)
-EXTRA_vt_sketch4          := $(EXTRA_vt_sketch6)
+# (The three widths' builders are in the unit too.  K1s's were built without the option before they moved here and come out
+# instruction for instruction as they did: profiles/sketch_nibble/isa_counts.txt.)
+EXTRA_vt_sketch_nibble    := -mllvm -structurizecfg-skip-uniform-regions=true
 # K1n's last link (candidates rescored from the pass's lists): a round of loaded rows indexed statically, the recovery by
 # value as in K1 -- no scratch segment, no spill
 NOSCRATCH_vt_sketch4_rescore := sketch4_rescore_kernel
@@ -93,7 +90,8 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 	$(if $(NOSPILL_$*),$(CHECK_SCRATCH) $(LIBDIR)/$*.resources $(NOSPILL_$*))
 
 # (what the sketch units share)
-$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/vt_sketch4.o: $(CSRC)/vt_sketch.cuh
+$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_sketch.cuh
+$(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_sketch_nibble.cuh
 $(LIBDIR)/vt_sketch_batch.o: $(CSRC)/host/vt_sketchbatch.h
 
 # (the pass K9r and K9rb share; K11 and K12 take its finish_raw)
@@ -130,14 +128,14 @@ $(LIBDIR)/libvt_callers.so: tools/callers_native.cpp include/vettore_flat.h $(LI
 $(LIBDIR)/libvt_callers_hooks.so: tools/callers_native.cpp include/vettore_flat.h $(LIBDIR)/libvettore_hip_hooks.so
 	g++ -O2 -std=c++17 -fPIC -shared tools/callers_native.cpp -Iinclude -L$(LIBDIR) -lvettore_hip_hooks -lpthread -Wl,-rpath,'$$ORIGIN' -o $@
 
-# The sketch kernels on their own behind a probe (tests/sketch_probe.cpp: builders, passes and the spread certification
+# The sketch kernels on their own behind a probe (tests/sketch_probe.cpp: the four builders and passes and the spread certification
 # launched one at a time on a test's arrays; tests/test_gpu_sketch_kernels.py loads it with ctypes): test infrastructure.
-# The three sketch units and the probe, nothing else of the library, and no export map; the package never loads it.
+# vt_sketch.o, vt_sketch_nibble.o and the probe, nothing else of the library, and no export map; the package never loads it.
 $(LIBDIR)/sketch_probe.o: tests/sketch_probe.cpp $(CSRC)/vt_device.h $(CSRC)/host/vt_sketch5.h $(CSRC)/host/vt_sketch6.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
-$(LIBDIR)/libvt_sketch_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch6.o $(LIBDIR)/vt_sketch5.o $(LIBDIR)/sketch_probe.o
+$(LIBDIR)/libvt_sketch_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_nibble.o $(LIBDIR)/sketch_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 # K1n's kernels behind a probe of their own (tests/sketch4_probe.cpp; tests/test_gpu_sketch4_kernels.py loads it): the
@@ -146,7 +144,7 @@ $(LIBDIR)/sketch4_probe.o: tests/sketch4_probe.cpp $(CSRC)/vt_device.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
-$(LIBDIR)/libvt_sketch4_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch4.o $(LIBDIR)/sketch4_probe.o
+$(LIBDIR)/libvt_sketch4_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_nibble.o $(LIBDIR)/sketch4_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 # The kernel that finishes K1n's chain behind a probe (tests/sketch4_finish_probe.cpp; tests/test_gpu_sketch4_finish_kernels.py

@@ -1,5 +1,5 @@
 // sketch4_probe.cpp -- test infrastructure (tests/test_gpu_sketch4_kernels.py), as sketch_probe.cpp is for the other three
-// sketches: K1n's builders and pass (vt_sketch4.hip) and the chain behind it with the exact threshold (vt_sketch.hip:
+// sketches: K1n's builders and pass (vt_sketch_nibble.hip) and the chain behind it with the exact threshold (vt_sketch.hip:
 // sketch_thresh_kernel filing slots, sketch_refine_kernel, sketch_collect_kernel taking the published word) launched one
 // at a time on the caller's own arrays.  Built into libvt_sketch4_probe.so from those two units and this file alone; the
 // product library never sees it.

@@ -1,4 +1,4 @@
-"""The numpy model of K1n's 4-bit sketch (vt_sketch4.hip): the column, the interval and the exact-threshold
+"""The numpy model of K1n's 4-bit sketch (vt_sketch_nibble.hip): the column, the interval and the exact-threshold
 rule behind the pass.  The query's levels are the 6-bit sketch's (sketch6_ref.query_levels), unchanged."""
 import numpy as np
 

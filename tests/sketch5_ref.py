@@ -1,4 +1,4 @@
-"""numpy restatement of the 5-bit sketch (K1f: vettore_amd/csrc/vt_sketch5.hip, host/vt_sketch5.h): the row
+"""numpy restatement of the 5-bit sketch (K1f: vettore_amd/csrc/vt_sketch_nibble.hip, host/vt_sketch5.h): the row
 quantiser, the tile layout with its one-bit L plane, and the interval every row's K1 dot must lie in -- levels 1-3 of the
 query (sketch6_ref.query_levels, the 6-bit sketch's own) meet the H plane, levels 1-2 the L plane, and level 3's share
 there, Q3.L with 0 <= L_i <= 1, is replaced by its centre c3 and half-width w3.

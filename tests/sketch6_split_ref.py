@@ -1,4 +1,4 @@
-"""numpy restatement of the 6-bit pass with its last query level kept off the L plane (K1s: vettore_amd/csrc/vt_sketch6.hip,
+"""numpy restatement of the 6-bit pass with its last query level kept off the L plane (K1s: vettore_amd/csrc/vt_sketch_nibble.hip,
 host/vt_sketch6.h sketch6_level_sums), beside sketch6_ref.py: levels 1-3 meet the H plane, levels 1-2 the L
 plane, and level 3's share there, Q3.L with 0 <= L_i <= 3, is replaced by its centre c3 and half-width w3.
 Test infrastructure for tests/test_sketch6_split_model.py and tests/test_gpu_sketch6_split.py; nothing of the library is loaded."""

@@ -1,7 +1,7 @@
-// sketch_probe.cpp -- test infrastructure (tests/test_gpu_sketch_kernels.py): the sketch builders, the three sketch passes
-// and the spread certification (vt_sketch.hip, vt_sketch6.hip, vt_sketch5.hip) launched one at a time on the caller's own
+// sketch_probe.cpp -- test infrastructure (tests/test_gpu_sketch_kernels.py): the sketch builders, the four sketch passes
+// and the spread certification (vt_sketch.hip, vt_sketch_nibble.hip) launched one at a time on the caller's own
 // arrays, so that a test can read back what no search returns: a sketch image, a row's interval words, Kt and the candidate
-// set.  Built into libvt_sketch_probe.so from the three sketch units and this file alone; the product library never sees it.
+// set.  Built into libvt_sketch_probe.so from those two units and this file alone; the product library never sees it.
 //
 // Every entry point takes and returns host arrays, owns its device buffers for the length of the call (hipMalloc, blocking
 // copies, one stream, a synchronise before the copies back) and returns the hipError_t as an int.  The launchers are called
@@ -49,9 +49,13 @@ struct Dev {  // the call's device buffers and its stream, released on every way
 };
 
 size_t image_bytes(int width, uint32_t rows, uint32_t d) {
-  return width == 8 ? vt::sketch_bytes(rows, d) : width == 6 ? vt::sketch6_bytes(rows, d) : vt::sketch5_bytes(rows, d);
+  return width == 8   ? vt::sketch_bytes(rows, d)
+         : width == 6 ? vt::sketch6_bytes(rows, d)
+         : width == 5 ? vt::sketch5_bytes(rows, d)
+                      : vt::sketch4_bytes(rows, d);
 }
-bool known(int width) { return width == 8 || width == 6 || width == 5; }
+bool known(int width) { return width == 8 || width == 6 || width == 5 || width == 4; }
+uint32_t block_lists(int width) { return width == 4 ? vt::kSketch4BlockLists : 1; }  // lists a block of the pass leaves
 
 }  // namespace
 
@@ -59,6 +63,7 @@ extern "C" {
 
 size_t vtp_image_bytes(int width, uint32_t rows, uint32_t d) { return known(width) ? image_bytes(width, rows, d) : 0; }
 uint32_t vtp_thresh_blocks(uint32_t lists, uint32_t kp) { return vt::sketch_thresh_blocks(lists, kp); }
+uint32_t vtp_block_lists(int width) { return known(width) ? block_lists(width) : 0; }
 
 // launch_sketch*_build over X[x_floats] (rows `stride` floats apart) into an image of rows_img rows pre-filled with 0xA5;
 // *max_norm is the f64's bits, in and out.
@@ -72,7 +77,10 @@ int vtp_build(int width, const float *X, size_t x_floats, size_t stride, uint32_
   unsigned char *dI = dv.get<unsigned char>(img_bytes, 0xA5);
   unsigned long long *dM = dv.get<unsigned long long>(8, 0, max_norm, 8);
   if (dv.err != hipSuccess) return dv.err;
-  auto launch = width == 8 ? vt::launch_sketch_build : width == 6 ? vt::launch_sketch6_build : vt::launch_sketch5_build;
+  auto launch = width == 8   ? vt::launch_sketch_build
+                : width == 6 ? vt::launch_sketch6_build
+                : width == 5 ? vt::launch_sketch5_build
+                             : vt::launch_sketch4_build;
   dv.err = launch(dX, stride, n_src, rows_img, d, dI, dM, dv.stream);
   if (dv.sync()) dv.back(img, dI, img_bytes) && dv.back(max_norm, dM, 8);
   return dv.err;
@@ -92,7 +100,10 @@ int vtp_rows(int width, const float *X, size_t x_floats, size_t stride, const ui
   unsigned char *dI = dv.get<unsigned char>(img_bytes, 0xA5, img, img_bytes);
   unsigned long long *dM = dv.get<unsigned long long>(8, 0, max_norm, 8);
   if (dv.err != hipSuccess) return dv.err;
-  auto launch = width == 8 ? vt::launch_sketch_rows : width == 6 ? vt::launch_sketch6_rows : vt::launch_sketch5_rows;
+  auto launch = width == 8   ? vt::launch_sketch_rows
+                : width == 6 ? vt::launch_sketch6_rows
+                : width == 5 ? vt::launch_sketch5_rows
+                             : vt::launch_sketch4_rows;
   dv.err = launch(dX, stride, dL, count, rows_img, d, dI, dM, dv.stream);
   if (dv.sync()) dv.back(img, dI, img_bytes) && dv.back(max_norm, dM, 8);
   return dv.err;
@@ -100,7 +111,8 @@ int vtp_rows(int width, const float *X, size_t x_floats, size_t stride, const ui
 
 // launch_sketch*_scan with `blocks` blocks and lists of k over an image of n rows.  qimg: the query's levels as the pass
 // reads them (width 8: [2][ld8] int8; else [3][ld8 / 8] dwords of nibbles), t: their scales (2 or 3).  keys, pay
-// ({row, raw bits}) and, for widths 6 and 5, lo_words and hi_words come back as [blocks][k], pre-filled with 0xA5.
+// ({row, raw bits}) and, for the nibble widths, lo_words and hi_words come back as [blocks * vtp_block_lists(width)][k],
+// pre-filled with 0xA5.  (Width 4 reads neither c3 nor w3.)
 int vtp_scan(int width, const unsigned char *img, size_t img_bytes, uint32_t n, uint32_t d, int metric, const uint32_t *id_rank,
              const unsigned char *qimg, size_t qimg_bytes, const float *t, double qn, double eta, double kerr, double c3, double w3,
              uint32_t k, uint32_t blocks, unsigned long long *keys, uint32_t *pay, uint32_t *lo_words, uint32_t *hi_words) {
@@ -109,7 +121,7 @@ int vtp_scan(int width, const unsigned char *img, size_t img_bytes, uint32_t n, 
   if (img_bytes != image_bytes(width, n, d) || qimg_bytes != (width == 8 ? 2 * (size_t)ld8 : 3 * (size_t)ld8 / 2))
     return hipErrorInvalidValue;
   if (width != 8 && (!lo_words || !hi_words)) return hipErrorInvalidValue;
-  const size_t slots = (size_t)blocks * k;
+  const size_t slots = (size_t)blocks * block_lists(width) * k;
   Dev dv;
   unsigned char *dI = dv.get<unsigned char>(img_bytes, 0, img, img_bytes);
   unsigned char *dQ = dv.get<unsigned char>(qimg_bytes, 0, qimg, qimg_bytes);
@@ -156,7 +168,8 @@ int vtp_scan(int width, const unsigned char *img, size_t img_bytes, uint32_t n, 
     a.part_pay = dP;
     a.lo_words = dLo;
     a.hi_words = dHi;
-    dv.err = (width == 6 ? vt::launch_sketch6_scan : vt::launch_sketch5_scan)(a, blocks, dv.stream);
+    auto launch = width == 6 ? vt::launch_sketch6_scan : width == 5 ? vt::launch_sketch5_scan : vt::launch_sketch4_scan;
+    dv.err = launch(a, blocks, dv.stream);
   }
   if (dv.sync() && dv.back(keys, dK, slots * 8) && dv.back(pay, dP, slots * 8) && width != 8)
     dv.back(lo_words, dLo, slots * 4) && dv.back(hi_words, dHi, slots * 4);

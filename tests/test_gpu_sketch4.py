@@ -1,5 +1,5 @@
 """GPU parity tests for K1n: lone cosine / dot searches with limits up to 10 nominated from the 4-bit sketch of the rows
-(sketch4_scan_kernel, vettore_amd/csrc/vt_sketch4.hip) with the threshold taken from the exact keys of k
+(sketch4_scan_kernel, vettore_amd/csrc/vt_sketch_nibble.hip) with the threshold taken from the exact keys of k
 rows (sketch_refine_kernel, vt_sketch.hip), and the 5-bit sketch (K1f), the 6-bit sketch (K1s), the int8 sketch (K1q) and
 the f32 rows behind it, in that order.
 

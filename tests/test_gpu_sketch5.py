@@ -1,5 +1,5 @@
 """GPU parity tests for K1f: lone cosine / dot searches with limits up to 10 nominated from the 5-bit sketch of the rows
-(sketch5_scan_kernel, vettore_amd/csrc/vt_sketch5.hip), with the 6-bit sketch (K1s), the int8 sketch (K1q)
+(sketch5_scan_kernel, vettore_amd/csrc/vt_sketch_nibble.hip), with the 6-bit sketch (K1s), the int8 sketch (K1q)
 and the f32 rows behind it, in that order.
 
 Like the other sketches it is an accelerator and must never show in a result: every hit equals the oracle's restatement of

@@ -1,5 +1,5 @@
 """GPU parity tests for the 6-bit pass with its third query level kept off the L plane, its operands read through the scalar
-cache and its loop of wave-uniform branches (sketch6_scan_kernel, vettore_amd/csrc/vt_sketch6.hip), and for the tail that
+cache and its loop of wave-uniform branches (sketch6_scan_kernel, vettore_amd/csrc/vt_sketch_nibble.hip), and for the tail that
 reads the pass's word arrays (sketch_tail_kernel, vt_sketch.hip): DESIGN.md 4.10.
 
 Every hit equals the oracle's bit for bit and no search falls back: rows built so that the dropped term sits at an end of

@@ -2,8 +2,8 @@
 
 The model tests (test_sketch8_model.py, test_sketch6_split_model.py, test_sketch5_model.py) show on the CPU that the
 model's interval holds the oracle's dot; test_gpu_sketch*.py show that a search's hits are the oracle's.  Here the kernels
-themselves are launched through tests/sketch_probe.cpp (libvt_sketch_probe.so: the three sketch units and nothing else of
-the library) and what no search returns is read back:
+themselves are launched through tests/sketch_probe.cpp (libvt_sketch_probe.so: vt_sketch.hip, vt_sketch_nibble.hip and
+nothing else of the library) and what no search returns is read back:
 
   A  the builders' images, byte for byte against pack_tiles, and rho / nu against the exact norms;
   B  the passes' lists and word arrays: every row's two words equal the model's (sketch*_ref.pass_words) bit for bit and hold
@@ -12,7 +12,10 @@ the library) and what no search returns is read back:
      the count, the full-list refusal, and the state two calls share.
 
 Geometry of B.  The 5-bit pass numbers its waves across the blocks first, so with blocks = tiles block b owns tile b alone
-and a list of 64 holds all its rows.  The int8 pass numbers them block by block: with blocks = tiles / 4 and lists of 256
+and a list of 64 holds all its rows.  The 4-bit pass numbers them likewise (wave = wave-in-block * blocks + block) and
+leaves two lists a block, waves 0-1 and waves 2-3: tile t goes to wave w = t mod 4 blocks, which is wave-in-block
+w div blocks of block w mod blocks; with blocks = tiles every tile has the first list of its block to itself and the second
+lists stay empty.  The int8 pass numbers them block by block: with blocks = tiles / 4 and lists of 256
 block b owns tiles 4 b .. 4 b + 3.  The 6-bit pass numbers them block by block too but takes lists of at most 64, so no
 launch over several tiles returns every row: it is launched once per tile, on that tile's slice of the image, and meets
 several tiles per wave in the ring tests.
@@ -24,6 +27,7 @@ import os
 import numpy as np
 import pytest
 
+import sketch4_ref as ref4
 import sketch5_ref as ref5
 import sketch6_ref as ref6
 import sketch6_split_ref as split6
@@ -33,8 +37,10 @@ from test_sketch5_model import corpora, unit
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WIDTHS = (8, 6, 5)
-HALF = {8: 127, 6: 31, 5: 15}
+WIDTHS = (8, 6, 5, 4)
+NIBBLE_WIDTHS = (6, 5, 4)
+HALF = {8: 127, 6: 31, 5: 15, 4: 7}
+MODEL = {8: ref8, 6: ref6, 5: ref5, 4: ref4}
 COS, IP, NIP = ref6.M_COS, ref6.M_IP, ref6.M_NIP
 EMPTY_KEY = np.uint64(0xFFFFFFFFFFFFFFFF)
 EMPTY = np.uint32(0xFFFFFFFF)
@@ -54,6 +60,9 @@ class Probe:
         L.vtp_image_bytes.argtypes = [C.c_int, C.c_uint32, C.c_uint32]
         L.vtp_thresh_blocks.restype = C.c_uint32
         L.vtp_thresh_blocks.argtypes = [C.c_uint32, C.c_uint32]
+        L.vtp_block_lists.restype = C.c_uint32
+        L.vtp_block_lists.argtypes = [C.c_int]
+        assert [L.vtp_block_lists(w) for w in WIDTHS] == [1, 1, 1, 2]
         L.vtp_build.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t, u64p]
         L.vtp_rows.argtypes = [C.c_int, f32p, C.c_size_t, C.c_size_t, u32p, C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t, u64p]
         L.vtp_scan.argtypes = [C.c_int, u8p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, u32p, u8p, C.c_size_t, f32p,
@@ -94,9 +103,10 @@ class Probe:
         img = np.ascontiguousarray(img, np.uint8).reshape(-1)
         qimg = np.ascontiguousarray(qimg).view(np.uint8).reshape(-1)
         t = np.ascontiguousarray(t, np.float32)
-        keys = np.zeros((blocks, k), np.uint64)
-        pay = np.zeros((blocks, k, 2), np.uint32)
-        lo, hi = np.zeros((blocks, k), np.uint32), np.zeros((blocks, k), np.uint32)
+        lists = blocks * self.lib.vtp_block_lists(width)
+        keys = np.zeros((lists, k), np.uint64)
+        pay = np.zeros((lists, k, 2), np.uint32)
+        lo, hi = np.zeros((lists, k), np.uint32), np.zeros((lists, k), np.uint32)
         rank = None if id_rank is None else np.ascontiguousarray(id_rank, np.uint32)
         rc = self.lib.vtp_scan(width, self._p(img, C.c_ubyte), img.size, n, d, metric,
                                None if rank is None else self._p(rank, C.c_uint32), self._p(qimg, C.c_ubyte), qimg.size,
@@ -128,17 +138,17 @@ def probe():
     return Probe()
 
 
-# ---- one interface over the three models ---------------------------------------------------------------------------------
+# ---- one interface over the four models ----------------------------------------------------------------------------------
 def quantise(width, x):
-    return {8: ref8, 6: ref6, 5: ref5}[width].quantise_rows(x)
+    return MODEL[width].quantise_rows(x)
 
 
 def pack(width, X, s, rho, nu):
-    return {8: ref8, 6: ref6, 5: ref5}[width].pack_tiles(X, s, rho, nu).view(np.uint8).reshape(-1)
+    return MODEL[width].pack_tiles(X, s, rho, nu).view(np.uint8).reshape(-1)
 
 
 def runs_of(width, d):
-    return {8: ref8.chunks_of(d) + 1, 6: ref6.runs_of(d), 5: ref5.runs_of(d)}[width]
+    return ref8.chunks_of(d) + 1 if width == 8 else MODEL[width].runs_of(d)
 
 
 def unpack(width, img, n, d):
@@ -146,7 +156,7 @@ def unpack(width, img, n, d):
     if width == 8:
         return ref8.unpack_tiles(img.reshape(tiles, -1, 64, 16), n, d)
     shaped = img.view(np.uint32).reshape(tiles, -1, 64, 4)
-    return (ref6 if width == 6 else ref5).unpack_tiles(shaped, n, d)
+    return MODEL[width].unpack_tiles(shaped, n, d)
 
 
 def query_levels(width, q):
@@ -166,7 +176,7 @@ def query_image(width, Q, d):
 
 
 def level_bound(width, Q, t):
-    if width == 8:
+    if width in (8, 4):  # (no level kept off a plane)
         return 0.0, 0.0
     return (split6 if width == 6 else ref5).level_bound(Q[2], t[2])
 
@@ -174,7 +184,7 @@ def level_bound(width, Q, t):
 def pass_words(width, metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3):
     if width == 8:
         return ref8.pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr)
-    return (split6 if width == 6 else ref5).pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3)
+    return {6: split6, 5: ref5, 4: ref4}[width].pass_words(metric, X, s, rho, nu, Q, t, qn, eta, kerr, c3, w3)
 
 
 def padded_dim(d):
@@ -277,7 +287,8 @@ def builder_corpus(d, half, n):
 @pytest.mark.parametrize("d", [1, 7, 128, 129, 200, 256, 320, 768, 8320])
 @pytest.mark.parametrize("width", WIDTHS)
 def test_builders_write_the_models_image(probe, width, d):
-    """d = 8320: nch = 520, nl = 130 and 65 are all over 64, so a lane takes a second turn of the per-row loop at every width."""
+    """d = 8320: nch = 520, nl = 130 and 65 and the 4-bit sketch's nh = 260 are all over 64, so a lane takes a second turn of
+    the per-row loop at every width (a fifth at four bits)."""
     full = builder_corpus(d, HALF[width], 130)
     shapes = [(1, 64, 0), (63, 64, 64), (64, 64, 0), (65, 128, 0), (130, 192, 64), (65, 192, 0)]  # (the last: an empty tile beyond)
     if d == 8320:
@@ -337,10 +348,13 @@ def test_builders_patch_rows_in_place(probe, width, d):
 
 
 # ---- B. the passes ---------------------------------------------------------------------------------------------------------
-def owner_block(width, tile, blocks):
-    """The block whose list a tile's rows go to: waves = 4 blocks, tile t goes to wave t mod waves; the 5-bit pass numbers
-    its waves across the blocks first (wave = wave-in-block * blocks + block), the other two block by block."""
+def owner_list(width, tile, blocks):
+    """The list a tile's rows go to: waves = 4 blocks, tile t goes to wave t mod waves; the 5-bit and 4-bit passes number
+    their waves across the blocks first (wave = wave-in-block * blocks + block), the other two block by block; the 4-bit
+    pass leaves two lists a block, one per pair of waves."""
     w = tile % (4 * blocks)
+    if width == 4:
+        return 2 * (w % blocks) + (w // blocks) // 2
     return w % blocks if width == 5 else w // 4
 
 
@@ -383,16 +397,16 @@ def model_words(width, metric, img, n, d, qy):
 
 
 def run_scan(probe, width, img, n, d, metric, id_rank, qy, k, blocks):
-    """One launch; the lists checked slot by slot against the model: block b's list is exactly the k smallest
+    """One launch; the lists checked slot by slot against the model: list b is exactly the k smallest
     (key(hi) word, id rank) keys of the rows it owns, with both model words, and every other slot is empty.
     Returns {row: (first word, second word)} as the device has them."""
     first, second, _ = model_words(width, metric, img, n, d, qy)
     rank = np.arange(n, dtype=np.uint64) if id_rank is None else id_rank.astype(np.uint64)
     key = (first.astype(np.uint64) << np.uint64(32)) | rank
     keys, pay, lo, hi = probe.scan(width, img, n, d, metric, id_rank, qy.image, qy.t, qy.qn, qy.eta, qy.kerr, qy.c3, qy.w3, k, blocks)
-    owner = np.array([owner_block(width, r // 64, blocks) for r in range(n)])
+    owner = np.array([owner_list(width, r // 64, blocks) for r in range(n)])
     seen = {}
-    for b in range(blocks):
+    for b in range(len(keys)):
         mine = np.nonzero(owner == b)[0]
         want = mine[np.argsort(key[mine], kind="stable")][:k]
         live = keys[b] != EMPTY_KEY
@@ -416,8 +430,8 @@ def run_scan(probe, width, img, n, d, metric, id_rank, qy, k, blocks):
 def read_every_row(probe, width, img, n, d, metric, id_rank, qy):
     """Geometry G1 (the module's docstring): every row's two words as the device has them."""
     tiles = (n + 63) // 64
-    if width == 5:
-        seen = run_scan(probe, 5, img, n, d, metric, id_rank, qy, 64, tiles)
+    if width in (5, 4):
+        seen = run_scan(probe, width, img, n, d, metric, id_rank, qy, 64, tiles)
     elif width == 8:
         seen = run_scan(probe, 8, img, n, d, metric, id_rank, qy, 256, (tiles + 3) // 4)
     else:
@@ -492,10 +506,11 @@ def pass_corpus(width, d, metric, q):
     return x, huge, slice(lean_at, lean_at + 32)
 
 
-PASS_DIMS = {8: (7, 128, 129, 200, 256, 320, 768), 6: (129, 200, 256, 320, 768), 5: (129, 200, 256, 320, 768)}
+PASS_DIMS = {8: (7, 128, 129, 200, 256, 320, 768), 6: (129, 200, 256, 320, 768), 5: (129, 200, 256, 320, 768),
+             4: (129, 200, 256, 320, 768)}
 PASS_CASES = [(w, d) for w in WIDTHS for d in PASS_DIMS[w]]
 # the share of e_r the leaning rows must use on the model (it prints 0.82-0.88 for the int8 sketch, 0.83-0.87 for the two
-# nibble sketches)
+# 6- and 5-bit sketches, 0.85-0.89 for the 4-bit one)
 LEAN_FLOOR = 0.8
 
 
@@ -524,7 +539,7 @@ def test_passes_give_every_row_the_models_interval(probe, oracle_mod, width, d):
         # the leaning rows keep their teeth: on the model, |dot - a| reaches most of e
         qy = plans[0][0]
         first, second, _ = model_words(width, metric, img, n, d, qy)
-        model = {8: ref8, 6: split6, 5: ref5}[width]
+        model = {8: ref8, 6: split6, 5: ref5, 4: ref4}[width]
         a, e = model.intervals(X, s, rho, nu, q)
         dots = np.array([oracle_mod.compute(IP, q, row) for row in x[lean]], np.float64)
         used = (np.abs(dots - a[lean]) / e[lean]).max()
@@ -549,25 +564,31 @@ def test_passes_on_the_images_the_builders_wrote(probe, oracle_mod, width):
                      "device-built, width %d metric %d" % (width, metric), exempt=[huge])
 
 
+def ring_mid(width):
+    """A row of a second-turn tile: tile 5 (wave 1); at four bits tile 6, wave 2's, so that the block's second list meets one."""
+    return 64 * (6 if width == 4 else 5) + 9
+
+
 def ring_corpus(width, d):
     n = 64 * 9 + 5
     rng = np.random.default_rng(8800 + d + width)
     x = unit(rng.uniform(-1, 1, (n, d)).astype(np.float32))
     e = edge_rows(d, HALF[width], seed=1)
     x[np.arange(len(e)) * 67 % n] = e
-    x[[3, 64 * 5 + 9, n - 2]] = unit(rng.uniform(-1, 1, (3, d)).astype(np.float32))
+    x[[3, ring_mid(width), n - 2]] = unit(rng.uniform(-1, 1, (3, d)).astype(np.float32))
     return x
 
 
-RING_CASES = [(8, 7), (8, 129), (8, 320), (6, 129), (6, 320), (5, 129), (5, 320)]
+RING_CASES = [(8, 7), (8, 129), (8, 320), (6, 129), (6, 320), (5, 129), (5, 320), (4, 129), (4, 200), (4, 256), (4, 320), (4, 768)]
 
 
 @pytest.mark.parametrize("width,d", RING_CASES)
 def test_passes_walk_from_tile_to_tile(probe, width, d):
     """G2: one block, ten tiles (the four waves own 3, 3, 2, 2 of them, the last tile partial), lists of 64: every wave walks
     from a tile into the next through its load ring, its parked sums and its metadata run.  Runs per tile: int8 9, 17 and 25,
-    6-bit 13 and 19, 5-bit 11 and -- a multiple of the ring of 8 -- 16 at d = 320.  The list must be exactly the model's 64
-    smallest keys with the model's words (run_scan).  The queries put a retained row in a tile of each turn: a row of the
+    6-bit 13 and 19, 5-bit 11 and -- a multiple of the ring of 8 -- 16 at d = 320, 4-bit 9, 9, 9, 13 and 25.  The list must be
+    exactly the model's 64 smallest keys with the model's words (run_scan); the 4-bit pass leaves two, of waves 0-1's rows and
+    of waves 2-3's.  The queries put a retained row in a tile of each turn: a row of the
     first tile, of a second-turn tile, of the last, partial tile, and minus a query.  Then three blocks over the same image:
     each owns more than 64 rows and returns its own 64 smallest."""
     assert runs_of(width, d) % 8 != 0 or (width, d) == (5, 320)
@@ -576,16 +597,28 @@ def test_passes_walk_from_tile_to_tile(probe, width, d):
     img = pack(width, *quantise(width, x))
     rng = np.random.default_rng(d + width)
     perm = rng.permutation(n).astype(np.uint32)
-    for i, q in enumerate((x[3], x[64 * 5 + 9], x[n - 2], -x[3], unit(rng.uniform(-1, 1, (1, d)).astype(np.float32))[0])):
+    lists, mid = probe.lib.vtp_block_lists(width), ring_mid(width)
+    for i, q in enumerate((x[3], x[mid], x[n - 2], -x[3], unit(rng.uniform(-1, 1, (1, d)).astype(np.float32))[0])):
         qy = Query(width, q, arbitrary=rng if i == 4 else None)
         for metric, id_rank in ((COS, None), (IP, perm)) if i < 3 else ((NIP, perm),):
             seen = run_scan(probe, width, img, n, d, metric, id_rank, qy, 64, 1)
-            assert len(seen) == 64
+            assert len(seen) == lists * 64
             if i < 3:  # (the query's own row, in the first, a second-turn and the last tile, is among the retained)
-                assert (3, 64 * 5 + 9, n - 2)[i] in seen, (i, metric)
-    qy = Query(width, x[64 * 5 + 9])
+                assert (3, mid, n - 2)[i] in seen, (i, metric)
+    qy = Query(width, x[mid])
     seen = run_scan(probe, width, img, n, d, COS, perm, qy, 64, 3)
-    assert len(seen) == 3 * 64
+    assert len(seen) == 3 * lists * 64
+
+
+@pytest.mark.parametrize("width", NIBBLE_WIDTHS)
+def test_passes_refuse_a_tile_shorter_than_the_ring(probe, width):
+    """ld8 = 128: a tile of at most 7 runs, so two tiles could end in one group of the ring's loads -- the launcher refuses it
+    before anything is launched (the search goes to the int8 sketch)."""
+    d = 128
+    assert runs_of(width, d) <= 8
+    x = unit(np.random.default_rng(width).uniform(-1, 1, (64, d)).astype(np.float32))
+    probe.scan(width, pack(width, *quantise(width, x)), 64, d, COS, None, Query(width, x[0]).image, np.ones(3, np.float32),
+               1.0, 0.0, 0.0, 0.0, 0.0, 64, 1, expect=HIP_INVALID_VALUE)
 
 
 def test_the_hosts_query_levels_are_the_models(probe):

@@ -128,9 +128,7 @@ int shard_delete(Shard *ix, const char *id, size_t id_len, bool *began) {
     ix->max_id.clear();
     ix->max_rank = 0;
     ix->sketch.release();  // (an emptied index gives the sketch's room back)
-    ix->sketch6.release();
-    ix->sketch5.release();
-    ix->sketch4.release();
+    for (auto *col : ix->nibble_sketches()) col->release();
   }
   return VT_OK;
 }

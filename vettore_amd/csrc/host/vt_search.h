@@ -101,7 +101,7 @@ bool sketch_batch_wanted(const Shard *ix, size_t nq, size_t limit) {
   return vt_host::sketch_batch_gate(s, nq, limit);
 }
 
-// K1s (vt_sketch6.hip; its tail and builders: vt_sketch.hip): where K1q applies, limits up to kSketch6MaxLimit over f32 rows of at least
+// K1s (vt_sketch_nibble.hip; its tail: vt_sketch.hip): where K1q applies, limits up to kSketch6MaxLimit over f32 rows of at least
 // kSketch6MinBytes read the 6-bit sketch instead -- 0.755 of the int8 sketch's bytes -- with block lists of kSketch6ListK
 // entries; its wider intervals leave hundreds of candidates, which always go through the gathered K1.  The int8 pass is
 // its fallback: a pass that does not certify is followed by K1q, and after kSketch6MissLimit such passes in a row the
@@ -125,9 +125,8 @@ bool sketch6_wanted(const Shard *ix, size_t limit) {
   if (vt::sketch6_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
   return vt::env::on(vt::env::FORCE_SKETCH6) || (double)ix->n * ix->ld * 4.0 >= kSketch6MinBytes;
 }
-size_t sketch6_elems(const Shard *ix) { return vt::sketch6_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
-// K1f (vt_sketch5.hip; its tail: vt_sketch.hip): where K1s applies, limits up to kSketch5MaxLimit over f32 rows
+// K1f (vt_sketch_nibble.hip; its tail: vt_sketch.hip): where K1s applies, limits up to kSketch5MaxLimit over f32 rows
 // of at least kSketch5MinBytes read the 5-bit sketch first -- 0.838 of the 6-bit sketch's bytes.  Its intervals are twice as
 // wide and leave thousands of candidates (about 19 000 of 10 M uniform unit rows at d = 768), so its candidate list has a
 // row for every retained slot of the block lists and the gathered K1 behind it runs on kSketch5RescoreBlocks blocks (8-row
@@ -150,9 +149,8 @@ bool sketch5_wanted(const Shard *ix, size_t limit) {
   if (vt::sketch5_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
   return vt::env::get(vt::env::FORCE_SKETCH6) >= 2 || (double)ix->n * ix->ld * 4.0 >= kSketch5MinBytes;
 }
-size_t sketch5_elems(const Shard *ix) { return vt::sketch5_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
-// K1n (vt_sketch4.hip; its tail: vt_sketch.hip): where K1f applies, limits up to kSketch4MaxLimit over f32 rows
+// K1n (vt_sketch_nibble.hip; its tail: vt_sketch.hip): where K1f applies, limits up to kSketch4MaxLimit over f32 rows
 // of at least kSketch4MinBytes read the 4-bit sketch first -- 0.806 of the 5-bit sketch's bytes.  Its intervals are twice
 // K1f's again: under the sketch's own threshold Kt a quarter of the corpus would be a candidate.  The threshold is therefore
 // taken from the exact keys of the k rows with the smallest key(lo) (launch_sketch_refine, between the threshold and the
@@ -175,11 +173,10 @@ bool sketch4_wanted(const Shard *ix, size_t limit) {
   if (vt::sketch4_scan_lds_bytes((uint32_t)ix->dim, kSketch6ListK) == 0) return false;
   return vt::env::get(vt::env::FORCE_SKETCH6) >= 3 || (double)ix->n * ix->ld * 4.0 >= kSketch4MinBytes;
 }
-size_t sketch4_elems(const Shard *ix) { return vt::sketch4_bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 
 // What tells the sketch columns apart, by bits per element (8: K1q, 6: K1s, 5: K1f, 4: K1n): the column and what is kept
-// beside it, its builders and pass, its counters, and the shape of the chain behind the pass.  index_ensure_sketch and
-// sketch6_search go by this one table.
+// beside it, its builders and pass, its counters, the shape of the chain behind the pass, and when a search takes it.
+// index_ensure_sketch, nibble_search and every walk over the nibble tiers (kNibbleTiers) go by this one table.
 struct SketchKind {
   DerivedColumn<unsigned char> Shard::*col;
   double Shard::*max_norm;
@@ -195,35 +192,44 @@ struct SketchKind {
   uint32_t block_lists, cand_cap, rescore_blocks;  // lists a block of the pass leaves; the candidate list; the gathered K1's grid
   DevBuf<uint32_t> Ctx::*cand_rows;
   bool exact_threshold;  // Kt' from launch_sketch_refine
+  bool (*wanted)(const Shard *, size_t limit);
+  uint32_t miss_limit;  // passes in a row that did not certify before the shard stops taking the tier (K1q: none counted)
+  size_t elems(const Shard *ix) const { return bytes((uint32_t)std::max<size_t>(ix->cap, ix->n), (uint32_t)ix->dim); }
 };
+// The nibble tiers by bits per element, in the order a lone search tries them: the narrowest first, each the fallback of
+// the one before it (and each wanted only where the next is: sketch4_wanted / sketch5_wanted above).
+constexpr int kNibbleTiers[] = {4, 5, 6};
+constexpr size_t kNibbleTierCount = sizeof(kNibbleTiers) / sizeof(kNibbleTiers[0]);
 const SketchKind &sketch_kind(int bits) {
   static const SketchKind k8{&Shard::sketch, &Shard::sketch_max_norm, nullptr, vt::sketch_bytes, vt::launch_sketch_build, vt::launch_sketch_rows,
                              nullptr, &vt_profile::sketch_launches, &vt_profile::sketch_ms, &vt_profile::sketch_bytes,
                              &vt_profile::sketch_candidates, &vt_profile::sketch_fallbacks, &vt_profile::sketch_builds,
                              &vt_profile::sketch_patched_rows, vt::env::TEST_REFUSE_SKETCH, 1, kSketchCandCap, kSketchRescoreBlocks,
-                             &Ctx::dSkRows, false};
+                             &Ctx::dSkRows, false, sketch_wanted, 0};
   static const SketchKind k6{&Shard::sketch6, &Shard::sketch6_max_norm, &Shard::sketch6_misses, vt::sketch6_bytes, vt::launch_sketch6_build,
                              vt::launch_sketch6_rows, vt::launch_sketch6_scan, &vt_profile::sketch6_launches, &vt_profile::sketch6_ms,
                              &vt_profile::sketch6_bytes, &vt_profile::sketch6_candidates, &vt_profile::sketch6_fallbacks,
                              &vt_profile::sketch6_builds, &vt_profile::sketch6_patched_rows, vt::env::TEST_REFUSE_SKETCH6, 1,
-                             kSketch6CandCap, kSketch6RescoreBlocks, &Ctx::dSk6Rows, false};
+                             kSketch6CandCap, kSketch6RescoreBlocks, &Ctx::dSk6Rows, false, sketch6_wanted, kSketch6MissLimit};
   static const SketchKind k5{&Shard::sketch5, &Shard::sketch5_max_norm, &Shard::sketch5_misses, vt::sketch5_bytes, vt::launch_sketch5_build,
                              vt::launch_sketch5_rows, vt::launch_sketch5_scan, &vt_profile::sketch5_launches, &vt_profile::sketch5_ms,
                              &vt_profile::sketch5_bytes, &vt_profile::sketch5_candidates, &vt_profile::sketch5_fallbacks,
                              &vt_profile::sketch5_builds, &vt_profile::sketch5_patched_rows, vt::env::TEST_REFUSE_SKETCH5, 1,
-                             kSketch5CandCap, kSketch5RescoreBlocks, &Ctx::dSk5Rows, false};
+                             kSketch5CandCap, kSketch5RescoreBlocks, &Ctx::dSk5Rows, false, sketch5_wanted, kSketch5MissLimit};
   static const SketchKind k4{&Shard::sketch4, &Shard::sketch4_max_norm, &Shard::sketch4_misses, vt::sketch4_bytes, vt::launch_sketch4_build,
                              vt::launch_sketch4_rows, vt::launch_sketch4_scan, &vt_profile::sketch4_launches, &vt_profile::sketch4_ms,
                              &vt_profile::sketch4_bytes, &vt_profile::sketch4_candidates, &vt_profile::sketch4_fallbacks,
                              &vt_profile::sketch4_builds, &vt_profile::sketch4_patched_rows, vt::env::TEST_REFUSE_SKETCH4,
-                             vt::kSketch4BlockLists, kSketch4CandCap, kSketch4RescoreBlocks, &Ctx::dSk4Rows, true};
+                             vt::kSketch4BlockLists, kSketch4CandCap, kSketch4RescoreBlocks, &Ctx::dSk4Rows, true, sketch4_wanted,
+                             kSketch4MissLimit};
   return bits == 4 ? k4 : bits == 5 ? k5 : bits == 6 ? k6 : k8;
 }
 
 // The derived columns a reader with `need` / `limit` wants current, as the elements each must hold (0: not wanted).
 // shard_stale and shard_prepare both go by this one answer.  (A shard with rows.)
 struct ColumnsWanted {
-  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0, sketch6 = 0, sketch5 = 0, sketch4 = 0;
+  size_t bits = 0, nz_bits = 0, norms = 0, shadow = 0, sketch = 0;
+  size_t nibble[kNibbleTierCount] = {};  // by kNibbleTiers
 };
 ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   ColumnsWanted w;
@@ -234,9 +240,10 @@ ColumnsWanted columns_wanted(const Shard *ix, unsigned need, size_t limit) {
   if (need & NEED_NORMS) w.norms = rows;
   if ((need & NEED_NORMS) && shadow_wanted(ix)) w.shadow = shadow_elems(ix);
   if ((need & (NEED_SKETCH | NEED_SKETCH8)) && sketch_wanted(ix, limit)) w.sketch = sketch_elems(ix);
-  if ((need & NEED_SKETCH) && sketch6_wanted(ix, limit)) w.sketch6 = sketch6_elems(ix);
-  if ((need & NEED_SKETCH) && sketch5_wanted(ix, limit)) w.sketch5 = sketch5_elems(ix);
-  if ((need & NEED_SKETCH) && sketch4_wanted(ix, limit)) w.sketch4 = sketch4_elems(ix);
+  for (size_t t = 0; t < kNibbleTierCount; ++t) {
+    const SketchKind &kind = sketch_kind(kNibbleTiers[t]);
+    if ((need & NEED_SKETCH) && kind.wanted(ix, limit)) w.nibble[t] = kind.elems(ix);
+  }
   return w;
 }
 
@@ -248,10 +255,11 @@ bool shard_stale(const Shard *ix, unsigned need, size_t limit) {
     if (!ix->rank_dirty.empty() || ix->rank_dirty_all || ix->dRank.count < rows) return true;
   }
   const ColumnsWanted w = columns_wanted(ix, need, limit);
+  for (size_t t = 0; t < kNibbleTierCount; ++t)
+    if (w.nibble[t] && !(ix->*sketch_kind(kNibbleTiers[t]).col).current(w.nibble[t])) return true;
   return (w.bits && !ix->bits.current(w.bits)) || (w.nz_bits && !ix->nz_bits.current(w.nz_bits)) ||
          (w.norms && !ix->norms.current(w.norms)) || (w.shadow && !ix->shadow.current(w.shadow)) ||
-         (w.sketch && !ix->sketch.current(w.sketch)) || (w.sketch6 && !ix->sketch6.current(w.sketch6)) ||
-         (w.sketch5 && !ix->sketch5.current(w.sketch5)) || (w.sketch4 && !ix->sketch4.current(w.sketch4));
+         (w.sketch && !ix->sketch.current(w.sketch));
 }
 
 int index_ensure_bits(Shard *ix, bool nonzero, size_t bwords);
@@ -272,9 +280,8 @@ int shard_prepare(Shard *ix, unsigned need, size_t limit) {
   if (w.norms) VT_TRY(index_ensure_norms(ix, w.norms));
   if (w.shadow) VT_TRY(index_ensure_shadow(ix, w.shadow));
   if (w.sketch) VT_TRY(index_ensure_sketch(ix, w.sketch));
-  if (w.sketch6) VT_TRY(index_ensure_sketch(ix, w.sketch6, 6));
-  if (w.sketch5) VT_TRY(index_ensure_sketch(ix, w.sketch5, 5));
-  if (w.sketch4) VT_TRY(index_ensure_sketch(ix, w.sketch4, 4));
+  for (size_t t = kNibbleTierCount; t-- > 0;)  // (the widest first: where the card runs out of room, the narrowest goes without)
+    if (w.nibble[t]) VT_TRY(index_ensure_sketch(ix, w.nibble[t], kNibbleTiers[t]));
   return VT_OK;
 }
 
@@ -598,7 +605,7 @@ int sketch_group_search(Shard *ix, Ctx &c, const float *queries, const std::vect
 // rescores them, keeps the rows under that threshold and writes the sorted result itself, no select behind it.  (Rows too
 // long for its block: the collect with that threshold and the gathered K1 in filter mode, launch_scan_filter, as before.)
 // A search whose survivors overflow its short list queues the collect, the lists and the select behind a second wait.
-int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, int bits = 6) {
+int nibble_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, int bits) {
   const SketchKind &kind = sketch_kind(bits);
   const bool five = bits == 5;
   *done = false;
@@ -794,16 +801,6 @@ int sketch6_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *do
   return VT_OK;
 }
 
-// K1f: blit, the 5-bit pass, the threshold and collect kernels, the gathered K1 and its select behind one host wait.
-int sketch5_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
-  return sketch6_search(ix, c, query, limit, done, out, 5);
-}
-
-// K1n: blit, the 4-bit pass, the threshold and refine kernels and the rescoring kernel that finishes behind one host wait.
-int sketch4_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out) {
-  return sketch6_search(ix, c, query, limit, done, out, 4);
-}
-
 // flat.rs:96-124 on a shard whose rank column shard_prepare has brought up to date --
 // strictly (ranks_clean) or lazily (newcomers share kUnranked).  Read-only on the shard.
 // `lone`: a search on its own (flat_search), which takes K1q when the sketch is current; the single searches a batch
@@ -812,22 +809,13 @@ int search_ready(Shard *ix, Ctx &c, const float *query, size_t n, size_t limit, 
   if (limit == 0) return empty_hits(out);
   VT_TRY(validate_vector(query, n, ix->dim));
   if (ix->n == 0) return empty_hits(out);
-  if (lone && sketch4_wanted(ix, limit) && ix->sketch4.current(sketch4_elems(ix)) &&
-      ix->sketch4_misses.load(std::memory_order_relaxed) < kSketch4MissLimit) {
+  for (int bits : kNibbleTiers) {  // (K1n, then K1f, then K1s: a tier that is not taken or does not certify leaves it to the next)
+    const SketchKind &kind = sketch_kind(bits);
+    if (!lone || !kind.wanted(ix, limit) || !(ix->*kind.col).current(kind.elems(ix)) ||
+        (ix->*kind.misses).load(std::memory_order_relaxed) >= kind.miss_limit)
+      continue;
     bool done = false;
-    VT_TRY(sketch4_search(ix, c, query, limit, &done, out));
-    if (done) return VT_OK;
-  }
-  if (lone && sketch5_wanted(ix, limit) && ix->sketch5.current(sketch5_elems(ix)) &&
-      ix->sketch5_misses.load(std::memory_order_relaxed) < kSketch5MissLimit) {
-    bool done = false;
-    VT_TRY(sketch5_search(ix, c, query, limit, &done, out));
-    if (done) return VT_OK;
-  }
-  if (lone && sketch6_wanted(ix, limit) && ix->sketch6.current(sketch6_elems(ix)) &&
-      ix->sketch6_misses.load(std::memory_order_relaxed) < kSketch6MissLimit) {
-    bool done = false;
-    VT_TRY(sketch6_search(ix, c, query, limit, &done, out));
+    VT_TRY(nibble_search(ix, c, query, limit, &done, out, bits));
     if (done) return VT_OK;
   }
   if (lone && sketch_wanted(ix, limit) && ix->sketch.current(sketch_elems(ix))) {

@@ -1,4 +1,4 @@
-// vt_sketch5.h -- the host side of the 5-bit sketch (K1f: vt_sketch5.hip the builders and the pass): the sums
+// vt_sketch5.h -- the host side of the 5-bit sketch (K1f: vt_sketch_nibble.hip the builders and the pass): the sums
 // that bound the query level kept off its one-bit L plane, and a restatement of the row quantiser.  The query's
 // signed-nibble levels are the 6-bit sketch's (vt_sketch6.h, sketch6_query_levels), used as they are.  Stand-alone on
 // purpose (no HIP, no header of the library but vt_sketch6.h): vt_search.h uses it, and tests/sketch5_check.cpp builds it
@@ -23,7 +23,7 @@ inline void sketch5_level_bound(const uint32_t *level, uint32_t lw, float t, dou
   *w = half * (double)l1;
 }
 
-// The row quantiser as sketch5_row (vt_sketch5.hip) has it: s = max|x| / 15 in f32, X = round(x * (15 / max|x|)) clamped
+// The row quantiser as nibble_row (vt_sketch_nibble.cuh) has it: s = max|x| / 15 in f32, X = round(x * (15 / max|x|)) clamped
 // to [-15, 15]; X = 2 H + L with H = X >> 1 in [-8, 7] and L = X & 1.  rho >= ||x - s X|| and nu >= s ||X||, from f64
 // sums with a 2^-30 margin, rounded up to f32.  (The device sums in another order: its bounds may differ in the last bits.)
 inline void sketch5_quantise_row(const float *x, uint32_t d, int8_t *X, float *s_out, float *rho_out, float *nu_out) {

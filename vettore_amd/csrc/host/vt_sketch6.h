@@ -1,4 +1,4 @@
-// vt_sketch6.h -- the host side of the 6-bit sketch (K1s: vt_sketch6.hip the pass, vt_sketch.hip the builders):
+// vt_sketch6.h -- the host side of the 6-bit sketch (K1s: vt_sketch_nibble.hip the builders and the pass):
 // the query's signed-nibble levels, the sums that bound the level kept off the L plane, and a restatement of the row
 // quantiser.  Stand-alone on purpose (no HIP, no other header of the library): vt_search.h uses it, and
 // tests/sketch6_query_check.cpp and tests/sketch6_split_check.cpp build it with plain g++ under AddressSanitizer and UBSan.
@@ -64,7 +64,7 @@ inline void sketch6_level_sums(const uint32_t *level, uint32_t lw, int64_t *pos,
   *l1 = p - n;
 }
 
-// The row quantiser as sketch6_row (vt_sketch.hip) has it: s = max|x| / 31 in f32, X = round(x * (31 / max|x|)) clamped
+// The row quantiser as nibble_row (vt_sketch_nibble.cuh) has it: s = max|x| / 31 in f32, X = round(x * (31 / max|x|)) clamped
 // to [-31, 31]; X = 4 H + L with H = X >> 2 in [-8, 7] and L = X & 3.  rho >= ||x - s X|| and nu >= s ||X||, from f64
 // sums with a 2^-30 margin, rounded up to f32.  (The device sums in another order: its bounds may differ in the last bits.)
 inline void sketch6_quantise_row(const float *x, uint32_t d, int8_t *X, float *s_out, float *rho_out, float *nu_out) {

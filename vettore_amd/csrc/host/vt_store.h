@@ -13,19 +13,10 @@ int index_reserve_once(Shard *ix, uint32_t want_rows);
 // 5-bit sketch before that one, which serves in its place; and the 4-bit sketch first of all.
 int index_reserve(Shard *ix, uint32_t want_rows) {
   int st = index_reserve_once(ix, want_rows);
-  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch4.buf.p) {
+  for (auto *col : ix->nibble_sketches()) {
+    if (st == VT_OK || st == VT_ERR_UNSUPPORTED || !col->buf.p) continue;
     (void)hipStreamSynchronize(ix->ctx.stream);
-    ix->sketch4.refuse();
-    st = index_reserve_once(ix, want_rows);
-  }
-  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch5.buf.p) {
-    (void)hipStreamSynchronize(ix->ctx.stream);
-    ix->sketch5.refuse();
-    st = index_reserve_once(ix, want_rows);
-  }
-  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch6.buf.p) {
-    (void)hipStreamSynchronize(ix->ctx.stream);
-    ix->sketch6.refuse();
+    col->refuse();
     st = index_reserve_once(ix, want_rows);
   }
   if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->shadow.buf.p) {

@@ -60,12 +60,12 @@ struct Ctx {
   // status word (zero between calls: the tail takes what it raised back)
   PinnedBuf<vt::ResultBlock> hSkgRes;
   DevBuf<int> dSkgStatus;
-  DevBuf<uint32_t> dSk6Rows;  // K1s (sketch6_search): its longer candidate list
+  DevBuf<uint32_t> dSk6Rows;  // K1s (nibble_search, 6 bits): its longer candidate list
   DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
   DevBuf<uint32_t> dSkParts;  // K1s / K1f: the threshold kernel's k smallest words per block, then its live counts
   DevBuf<uint32_t> dSkSync;   // the collect kernel's claim, fail and ticket words (16 bytes, zeroed by the threshold kernel)
-  DevBuf<uint32_t> dSk5Rows;  // K1f (sketch5_search): its candidate list, a row for every retained slot
-  DevBuf<uint32_t> dSk4Rows;  // K1n (sketch4_search): likewise, over twice the lists
+  DevBuf<uint32_t> dSk5Rows;  // K1f (nibble_search, 5 bits): its candidate list, a row for every retained slot
+  DevBuf<uint32_t> dSk4Rows;  // K1n (nibble_search, 4 bits): likewise, over twice the lists
   // K12 (vt_mmr.h, mmr_run): a call's problems, per-candidate arrays and block partials; what goes up and what comes back
   // travel through the two pinned blocks (grow, never shrink: no allocation per call)
   DevBuf<vt::MmrProblem> dMmrProb;
@@ -347,7 +347,7 @@ struct Shard {
   double sketch_max_norm = 0.0;
   bool sketch_xx = false;
   // K1s: the rows in six bits, two planes (vt_device.h, Sketch6ScanArgs) -- 0.755 of the int8 sketch's bytes, read by the
-  // largest lone searches (vt_search.h, sketch6_search) with the int8 sketch as its fallback.  Kept on the int8 sketch's
+  // largest lone searches (vt_search.h, nibble_search) with the int8 sketch as its fallback.  Kept on the int8 sketch's
   // terms; the first column to go when the slab needs room.  sketch6_misses: consecutive passes the bound could not
   // certify (readers under the shared lock count; a rebuild of the column starts over) -- at kSketch6MissLimit the shard
   // stops taking the path.
@@ -355,17 +355,19 @@ struct Shard {
   double sketch6_max_norm = 0.0;
   std::atomic<uint32_t> sketch6_misses{0};
   // K1f: the rows in five bits, two planes (vt_device.h, above launch_sketch5_scan) -- 0.838 of the 6-bit sketch's bytes,
-  // read first by the largest lone searches (vt_search.h, sketch5_search) with the 6-bit and int8 sketches behind it.  Kept
+  // read first by the largest lone searches (vt_search.h, nibble_search) with the 6-bit and int8 sketches behind it.  Kept
   // on the 6-bit sketch's terms, misses included (kSketch5MissLimit); the first column to go when the slab needs room.
   DerivedColumn<unsigned char> sketch5;
   double sketch5_max_norm = 0.0;
   std::atomic<uint32_t> sketch5_misses{0};
   // K1n: the rows in four bits, one plane with its own scale (vt_device.h, above launch_sketch4_scan) -- 0.806 of the 5-bit
-  // sketch's bytes, read first by the largest lone searches (vt_search.h, sketch4_search) with the other three behind it.
+  // sketch's bytes, read first by the largest lone searches (vt_search.h, nibble_search) with the other three behind it.
   // Kept on the 5-bit sketch's terms, misses included (kSketch4MissLimit); the first column to go when the slab needs room.
   DerivedColumn<unsigned char> sketch4;
   double sketch4_max_norm = 0.0;
   std::atomic<uint32_t> sketch4_misses{0};
+  // (the three nibble columns, narrowest first: the order the slab takes their room back in)
+  std::array<DerivedColumn<unsigned char> *, 3> nibble_sketches() { return {&sketch4, &sketch5, &sketch6}; }
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
   // ids
@@ -427,9 +429,7 @@ struct Shard {
       norms.touch(rows[i]);
       shadow.touch(rows[i]);
       sketch.touch(rows[i]);
-      sketch6.touch(rows[i]);
-      sketch5.touch(rows[i]);
-      sketch4.touch(rows[i]);
+      for (auto *col : nibble_sketches()) col->touch(rows[i]);
     }
   }
   void forget_derived() {
@@ -438,9 +438,7 @@ struct Shard {
     norms.forget();
     shadow.forget();
     sketch.forget();
-    sketch6.forget();
-    sketch5.forget();
-    sketch4.forget();
+    for (auto *col : nibble_sketches()) col->forget();
   }
   // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
   // shadow gives its room back.
@@ -452,12 +450,10 @@ struct Shard {
     shadow.buf.release();
     sketch.reset();
     sketch.buf.release();
-    sketch6.reset();
-    sketch6.buf.release();
-    sketch5.reset();
-    sketch5.buf.release();
-    sketch4.reset();
-    sketch4.buf.release();
+    for (auto *col : nibble_sketches()) {
+      col->reset();
+      col->buf.release();
+    }
   }
 };
 

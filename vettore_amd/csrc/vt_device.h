@@ -1000,7 +1000,7 @@ struct Sketch6ScanArgs {
 size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_sketch6_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
 
-// ---- K1f (vt_sketch5.hip): the same search over a 5-bit sketch in two planes -- 0.838 of K1s's bytes -----------------
+// ---- K1f (vt_sketch_nibble.hip): the same search over a 5-bit sketch in two planes -- 0.838 of K1s's bytes -----------------
 // Row r is kept as X_r = round(x_r / s_r) in [-15, 15] with s_r = max_i |x_ri| / 15, split as X = 2 H + L: H = X >> 1
 // (arithmetic, [-8, 7]) a signed nibble, L = X & 1 one bit; rho_r and nu_r as K1q has them.  Layout, per tile of 64 rows,
 // in 1-KiB runs of 16 bytes per row: ld8 / 32 runs of H in K1s's H layout, then ld8 / 128 runs of L -- in dword j of run
@@ -1022,7 +1022,7 @@ hipError_t launch_sketch5_rows(const float *X, size_t stride, const uint32_t *li
 size_t sketch5_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_sketch5_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
 
-// ---- K1n (vt_sketch4.hip): the same search over a 4-bit sketch in one plane -- 0.806 of K1f's bytes -------------------
+// ---- K1n (vt_sketch_nibble.hip): the same search over a 4-bit sketch in one plane -- 0.806 of K1f's bytes -------------------
 // Row r is kept as X_r = round(x_r / s_r) in [-7, 7] with s_r = max_i |x_ri| / 7, one signed nibble per element; rho_r and
 // nu_r as K1q has them.  Layout, per tile of 64 rows, in 1-KiB runs of 16 bytes per row: ld8 / 32 runs in K1s's H layout
 // (nibble i of dword j of run c is element 32 c + 8 j + i), then one run of {s, rho, nu, 0}: ld8 / 32 + 1 KiB per tile.

@@ -9,6 +9,7 @@
 #include "vt_env.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cfloat>
 #include <chrono>

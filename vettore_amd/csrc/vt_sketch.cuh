@@ -1,5 +1,7 @@
-// vt_sketch.cuh -- what the sketch units share (vt_sketch.hip: K1q, the tail, the builders of the int8 and 6-bit sketches;
-// vt_sketch6.hip: K1s's pass; vt_sketch5.hip: K1f's builders and pass): wave reductions, the outward f64 -> f32 roundings of the bounds and their slack.
+// vt_sketch.cuh -- what the sketch units share (vt_sketch.hip: K1q, the int8 sketch's builders, the tail and the kernels
+// behind the nibble passes; vt_sketch_batch.hip: K1qm; vt_sketch_nibble.hip, through vt_sketch_nibble.cuh: the builders and
+// passes of K1s, K1f and K1n): the 16-byte vector type, wave reductions, the outward f64 -> f32 roundings of the bounds and
+// their slack.
 #pragma once
 #include "vt_scan.cuh"
 

@@ -1,6 +1,6 @@
 // vt_sketch.hip -- K1q: a lone cosine / dot / L2 search nominated from an int8 sketch of the rows (gfx950), and the tail behind
-// its pass -- which K1s and K1f share --; the builders of K1s's 6-bit sketch in two planes follow below (its pass:
-// vt_sketch6.hip; K1f, the 5-bit sketch: vt_sketch5.hip).
+// its pass -- which K1s and K1f share -- with the threshold, refine and collect kernels behind the nibble sketches' passes
+// (K1s, K1f, K1n: vt_sketch_nibble.hip, builders and passes).
 //
 // The sketch (layout and bounds: vt_device.h, SketchScanArgs) holds a quarter of the f32 rows' bytes.  K1q streams it
 // once and gives every row an interval [lo_r, hi_r] that provably holds what K1 would compute for it:
@@ -948,82 +948,6 @@ __global__ __launch_bounds__(kSpreadThreads) void sketch_collect_kernel(const Sk
   }
 }
 
-// ---- K1s: the 6-bit sketch in two planes (layout: vt_device.h, Sketch6ScanArgs) ---------------------------------------
-// One wave per row, a lane per 64 elements: quantise to [-31, 31], write the two H-runs and the L-run of those elements.
-__device__ __forceinline__ void sketch6_row(const float *__restrict__ X, size_t stride, uint32_t row, bool have_row, uint32_t d,
-                                            uint32_t ld8, unsigned char *__restrict__ img, unsigned long long *max_norm, int lane) {
-  const float *src = X + (size_t)row * stride;
-  float m = 0.0f;
-  if (have_row)
-    for (uint32_t i = lane; i < d; i += kWave) m = fmaxf(m, fabsf(src[i]));
-  m = wave_max_f(m);
-  float s = m / 31.0f;
-  float inv = 31.0f / m;
-  const bool quantise = have_row && m > 0.0f && finite_f32(inv) && s > 0.0f;
-  if (!quantise) s = 0.0f;
-  const uint32_t nh = ld8 / 32, nl = ld8 / 64, runs = nh + nl + 1;
-  double res = 0.0;   // sum of (x - s X)^2, f64
-  uint32_t xx = 0;    // sum of X^2, exact
-  for (uint32_t c = lane; c < nl; c += kWave) {
-    uint32_t lw[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      uint32_t hw[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t word = 0;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          const uint32_t i = c * 64 + h * 32 + j * 8 + b;
-          const float x = have_row && i < d ? src[i] : 0.0f;
-          int q = 0;
-          if (quantise) {
-            q = (int)rintf(x * inv);
-            q = q > 31 ? 31 : (q < -31 ? -31 : q);
-          }
-          const double r = (double)x - (double)s * (double)q;  // (exact: s q has at most 29 significant bits)
-          res += r * r;
-          xx += (uint32_t)(q * q);
-          word |= ((uint32_t)(q >> 2) & 0xfu) << (4 * b);
-          lw[j] |= ((uint32_t)q & 3u) << (4 * b + 2 * h);
-        }
-        hw[j] = word;
-      }
-      *reinterpret_cast<u32x4 *>(img + sketch6_offset(row, 2 * c + h, runs)) = u32x4{hw[0], hw[1], hw[2], hw[3]};
-    }
-    *reinterpret_cast<u32x4 *>(img + sketch6_offset(row, nh + c, runs)) = u32x4{lw[0], lw[1], lw[2], lw[3]};
-  }
-  res = wave_sum_d(res);
-  xx = wave_sum_u(xx);
-  if (lane == 0) {
-    const double rho = sqrt(res) * (1.0 + 0x1p-30);
-    const double nu = (double)s * sqrt((double)xx) * (1.0 + 0x1p-30);
-    const float rho_f = f32_up(rho), nu_f = f32_up(nu);
-    *reinterpret_cast<u32x4 *>(img + sketch6_offset(row, nh + nl, runs)) =
-        u32x4{__float_as_uint(s), __float_as_uint(rho_f), __float_as_uint(nu_f), 0u};
-    const double bound = ((double)rho_f + (double)nu_f) * kSlack;
-    atomicMax(max_norm, (unsigned long long)__double_as_longlong(bound));
-  }
-}
-
-__global__ __launch_bounds__(256) void sketch6_build_kernel(const float *__restrict__ X, size_t stride, uint32_t n_src,
-                                                            uint32_t rows_img, uint32_t d, uint32_t ld8, unsigned char *img,
-                                                            unsigned long long *max_norm) {
-  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (w >= rows_img) return;
-  sketch6_row(X, stride, w, w < n_src, d, ld8, img, max_norm, threadIdx.x & 63);
-}
-
-__global__ __launch_bounds__(256) void sketch6_rows_kernel(const float *__restrict__ X, size_t stride, const uint32_t *__restrict__ list,
-                                                           uint32_t count, uint32_t rows_img, uint32_t d, uint32_t ld8,
-                                                           unsigned char *img, unsigned long long *max_norm) {
-  const uint32_t w = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (w >= count) return;
-  const uint32_t row = list[w];
-  if (row >= rows_img) return;
-  sketch6_row(X, stride, row, true, d, ld8, img, max_norm, threadIdx.x & 63);
-}
-
 }  // namespace
 
 template <bool WITH_XX>
@@ -1173,24 +1097,6 @@ hipError_t launch_sketch_refine(SketchRefineArgs a, hipStream_t s) {
   hipError_t e = allow_lds(sketch_refine_kernel, lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(sketch_refine_kernel, dim3(1), dim3(kTailThreads), lds, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_sketch6_build(const float *X, size_t stride, uint32_t n_src, uint32_t rows_img, uint32_t d, void *img,
-                                unsigned long long *max_norm, hipStream_t s) {
-  if (d == 0 || d > kSketchMaxDim || rows_img % kSketchTileRows) return hipErrorInvalidValue;
-  if (rows_img == 0) return hipSuccess;
-  hipLaunchKernelGGL(sketch6_build_kernel, dim3((rows_img + 3) / 4), dim3(256), 0, s, X, stride, n_src, rows_img, d,
-                     sketch_ld8(d), static_cast<unsigned char *>(img), max_norm);
-  return hipGetLastError();
-}
-
-hipError_t launch_sketch6_rows(const float *X, size_t stride, const uint32_t *list, uint32_t count, uint32_t rows_img, uint32_t d,
-                               void *img, unsigned long long *max_norm, hipStream_t s) {
-  if (d == 0 || d > kSketchMaxDim) return hipErrorInvalidValue;
-  if (count == 0) return hipSuccess;
-  hipLaunchKernelGGL(sketch6_rows_kernel, dim3((count + 3) / 4), dim3(256), 0, s, X, stride, list, count, rows_img, d,
-                     sketch_ld8(d), static_cast<unsigned char *>(img), max_norm);
   return hipGetLastError();
 }
 
