@@ -1,7 +1,8 @@
 // The host side of the 6-bit sketch (vettore_amd/csrc/host/vt_sketch6.h) is plain C++: built here with g++ under
 // AddressSanitizer and UBSan.  The query's nibble levels must be signed nibbles |Q_j| <= 7 with zero padding, and
 // q - sum_j t_j Q_j, recomputed here in f64, must be the eta the bound is given; the row quantiser must satisfy
-// X = 4 H + L with its rho and nu above the sums recomputed here.
+// X = 4 H + L with its rho and nu above the sums recomputed here.  The bound of the level kept off the L plane (c3, w3)
+// must be 1.5 t (P + N) and 1.5 t ||Q||_1 of sums formed here from the integers the level was packed from.
 #include "../vettore_amd/csrc/host/vt_sketch6.h"
 
 #include <cfloat>
@@ -74,9 +75,35 @@ static void check_row(const std::vector<float> &x, const char *name) {
   CHECK(std::isfinite(rho) && std::isfinite(nu) && s >= 0.0f, "%s: s %g", name, (double)s);
 }
 
+// One level of d signed nibbles (`zero`: all of them 0; else mixed signs), packed here as sketch6_query_levels packs them.
+static void check_level_bound(uint32_t d, bool zero, float t, std::mt19937 &rng) {
+  const uint32_t lw = sketch6_level_words(d);
+  std::vector<uint32_t> level(lw, 0u);  // exact-size: a read past its end is AddressSanitizer's to report
+  std::uniform_int_distribution<int> pick(-7, 7);
+  long long pos = 0, neg = 0, l1 = 0;
+  for (uint32_t i = 0; i < d; ++i) {
+    const int v = zero ? 0 : (i == 0 ? 7 : i == 1 ? -7 : pick(rng));  // (both signs are there whatever the draw)
+    level[i >> 3] |= ((uint32_t)v & 0xfu) << (4 * (i & 7));
+    if (v > 0) pos += v;
+    if (v < 0) neg += v;
+    l1 += v < 0 ? -v : v;
+  }
+  double c = -1.0, w = -1.0;
+  sketch6_level_bound(level.data(), lw, t, &c, &w);
+  // (integers below 2^13 times a 24-bit scale times 1.5: every product is exact in f64, so the sums must agree to the bit)
+  const double want_c = 1.5 * (double)t * (double)(pos + neg), want_w = 1.5 * (double)t * (double)l1;
+  CHECK(c == want_c && w == want_w, "level bound d=%u zero=%d: c %.17g (want %.17g), w %.17g (want %.17g)", d, (int)zero, c, want_c, w, want_w);
+  CHECK(w >= std::fabs(c), "level bound d=%u: |c| %.17g above w %.17g", d, c, w);
+  if (zero) CHECK(c == 0.0 && w == 0.0, "level bound d=%u of a zero level: c %.17g w %.17g", d, c, w);
+}
+
 int main() {
   std::mt19937 rng(20260722);
   std::uniform_real_distribution<float> u(-1.0f, 1.0f);
+  for (uint32_t d : {129u, 256u}) {  // off and on the 128 grid
+    check_level_bound(d, false, 0.0123f, rng);
+    check_level_bound(d, true, 0.0123f, rng);
+  }
   for (uint32_t d : {1u, 7u, 8u, 31u, 33u, 129u, 192u, 257u, 768u, 1001u}) {
     std::vector<float> q(d);
     for (auto &v : q) v = u(rng);

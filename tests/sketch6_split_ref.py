@@ -41,7 +41,7 @@ def intervals(X, s, rho, nu, q):
 
 
 def level_bound(Q3, t3):
-    """c3, w3 as host/vt_search.h forms them for the 6-bit pass: 1.5 t3 (P3 + N3) and 1.5 t3 ||Q3||_1."""
+    """c3, w3 as host/vt_sketch6.h (sketch6_level_bound) forms them for the 6-bit pass: 1.5 t3 (P3 + N3) and 1.5 t3 ||Q3||_1."""
     pos, neg, l1 = level_sums(Q3)
     t15 = 1.5 * np.float64(np.float32(t3))
     return t15 * float(pos + neg), t15 * float(l1)

@@ -1,5 +1,5 @@
 """numpy restatement of the int8 sketch's L2 family (K1q over an L2 / squared-L2 handle: vettore_amd/csrc/vt_sketch.hip
-sketch_row<true>, the L2 epilogue of sketch_scan_kernel, sketch_tail_kernel's certification; host/vt_search.h sketch_search;
+sketch_row<true>, the L2 epilogue of sketch_scan_kernel, sketch_tail_kernel's certification; host/vt_sketchsearch.h sketch_search;
 DESIGN.md 4.10, DESIGN_APPENDIX A.5b): the column with xx_r in the metadata run's fourth dword, the two words every row gets,
 the tail's certificate over the block lists, and the corpora the CPU model test and the GPU tests share.
 Everything the dot family has already is sketch8_ref's / sketch6_ref's.
@@ -14,7 +14,7 @@ M_L2, M_L2SQ = 0, 1
 TILE_ROWS = ref8.TILE_ROWS
 EMPTY = np.uint32(0xFFFFFFFF)
 KAPPA_BITS = -23   # kappa = (d + 16) 2^-23
-CAND_CAP = 4096    # host/vt_search.h kSketchCandCap
+CAND_CAP = 4096    # host/vt_sketchtiers.h, the int8 tier's cand_cap
 FUSE_MAX = 256     # vt_sketch.hip kTailFuseMax
 
 
@@ -175,7 +175,7 @@ def tail_outcome(cert, lists, kp, d):
 
 
 def list_k(limit):
-    """host/vt_search.h sketch_list_k."""
+    """host/vt_sketchtiers.h sketch_list_k."""
     return max(2 * limit, limit + 16)
 
 

@@ -1,5 +1,5 @@
 """numpy restatement of the int8 sketch (K1q: vettore_amd/csrc/vt_sketch.hip sketch_row / sketch_scan_kernel, vt_device.h
-sketch_offset, host/vt_search.h sketch_query_image): the row quantiser, the chunked tile layout, the query's
+sketch_offset, host/vt_sketchsearch.h sketch_query_image): the row quantiser, the chunked tile layout, the query's
 two int8 levels and the interval every row's K1 dot must lie in.
 Test infrastructure for tests/test_sketch8_model.py and tests/test_gpu_sketch_kernels.py; nothing of the library is loaded."""
 import numpy as np

@@ -42,7 +42,7 @@ def spiky_case(metric):
     return x, ids, qs
 
 
-# ---- the host side restated (host/vt_sketchbatch.h, host/vt_search.h) --------------------------------------------------
+# ---- the host side restated (host/vt_sketchbatch.h, host/vt_sketchsearch.h) --------------------------------------------------
 def list_k(limit):
     return max(2 * limit, limit + 16)
 

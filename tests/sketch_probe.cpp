@@ -5,7 +5,7 @@
 //
 // Every entry point takes and returns host arrays, owns its device buffers for the length of the call (hipMalloc, blocking
 // copies, one stream, a synchronise before the copies back) and returns the hipError_t as an int.  The launchers are called
-// as host/vt_search.h calls them; what that file computes on the way (the query's levels, the norms) is an input here.
+// as host/vt_sketchsearch.h calls them; what that file computes on the way (the query's levels, the norms) is an input here.
 // Every size a kernel will index with is checked against the caller's buffer lengths first: hipErrorInvalidValue, nothing
 // launched.
 #include "vt_device.h"

@@ -10,14 +10,15 @@ the 5-bit and 6-bit paths alone, = 1 the 6-bit one; VT_SKETCH6=3 switches the 4-
 import numpy as np
 import pytest
 
+import support
 from test_gpu_parity import GpuIndex, bits, nifs, unwrap  # noqa: F401  (nifs: fixture)
 from test_gpu_sketch import COS, IP, check, make_corpus, queries
 from test_gpu_sketch6 import loaded
 
 pytestmark = pytest.mark.gpu
 
-CAND_CAP = 131072  # kSketch4CandCap
-MISS_LIMIT = 4     # kSketch4MissLimit
+CAND_CAP = 131072  # the 4-bit tier's cand_cap (host/vt_sketchtiers.h)
+MISS_LIMIT = 4     # ... and its miss_limit
 
 
 def tile_bytes(d):
@@ -156,6 +157,19 @@ def test_switched_off_the_5bit_sketch_serves(nifs, oracle_mod, vt_debug):
     check(nifs, oracle_mod, g.ref, IP, x, ids, qs, 10)
     prof = nifs.flat_get_profile(g.ref)
     assert prof["sketch4_launches"] == 0 and prof["sketch4_builds"] == 0 and prof["sketch5_launches"] == len(qs), prof
+
+
+def test_no_room_for_the_4bit_sketch_means_the_5bit_one(nifs, oracle_mod, request, vt_debug):
+    """(test_refuse_sketch4, libvettore_hip_hooks.so only: the test re-runs itself there.)"""
+    if support.rerun_with_hooks_library(request):
+        return
+    vt_debug.set("test_refuse_sketch4", 1)
+    vt_debug.set("force_sketch6", 3)
+    x, ids = make_corpus(8000, 192, 12, True, oracle_mod)
+    g = loaded(nifs, COS, x, ids)
+    check(nifs, oracle_mod, g.ref, COS, x, ids, queries(np.random.default_rng(2), x, 4, COS, oracle_mod), 10)
+    prof = nifs.flat_get_profile(g.ref)
+    assert prof["sketch4_launches"] == 0 and prof["sketch4_builds"] == 0 and prof["sketch5_launches"] == 4, prof
 
 
 def test_force_sketch6_at_2_never_selects_the_4bit_path(nifs, oracle_mod, vt_debug):

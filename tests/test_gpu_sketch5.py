@@ -18,9 +18,9 @@ from test_gpu_sketch6 import loaded
 
 pytestmark = pytest.mark.gpu
 
-MAX_LIMIT = 10    # kSketch5MaxLimit
-CAND_CAP = 65536  # kSketch5CandCap
-MISS_LIMIT = 4    # kSketch5MissLimit
+MAX_LIMIT = 10    # the 5-bit tier's max_limit (host/vt_sketchtiers.h)
+CAND_CAP = 65536  # ... its cand_cap
+MISS_LIMIT = 4    # ... and its miss_limit
 
 
 def tile_bytes(d):

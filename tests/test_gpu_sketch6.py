@@ -16,8 +16,8 @@ from test_gpu_sketch import COS, IP, NIP, check, make_corpus, queries
 
 pytestmark = pytest.mark.gpu
 
-CAND_CAP = 32768  # kSketch6CandCap
-MISS_LIMIT = 4    # kSketch6MissLimit
+CAND_CAP = 32768  # the 6-bit tier's cand_cap (host/vt_sketchtiers.h)
+MISS_LIMIT = 4    # ... and its miss_limit
 
 
 def tile_bytes(d):

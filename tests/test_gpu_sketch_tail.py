@@ -15,7 +15,7 @@ from test_gpu_sketch import COS, IP, NIP, check, make_corpus, queries
 pytestmark = pytest.mark.gpu
 
 FUSE_MAX = 256  # kTailFuseMax: candidates the tail's block rescored itself at most
-CAND_CAP = 4096  # kSketchCandCap
+CAND_CAP = 4096  # the int8 tier's cand_cap (host/vt_sketchtiers.h)
 
 
 def with_copies(x, row, every):

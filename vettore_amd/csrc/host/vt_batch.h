@@ -585,17 +585,16 @@ int sketch_batch_stage(Shard *ix, Ctx &c, const float *queries, size_t nq, size_
   const uint32_t d = (uint32_t)ix->dim;
   const bool l2 = sketch_l2_metric(ix->metric);
   std::vector<size_t> fit;
+  std::vector<SketchQuery> sq(nq);
   for (size_t i = 0; i < nq; ++i) {
-    float m1 = 0.0f;
-    double qq = 0.0;
-    sketch_query_norms(queries + i * d, d, &m1, &qq);
-    if (vt_host::sketch_batch_query_fits(l2, std::sqrt(qq) * (1.0 + 0x1p-30), ix->sketch_max_norm)) fit.push_back(i);
+    sq[i] = sketch_query(queries + i * d, d);
+    if (vt_host::sketch_batch_query_fits(l2, sq[i].qn, ix->sketches[vt_host::kTier8].max_norm)) fit.push_back(i);
   }
   const uint32_t gmax = vt_host::sketch_batch_max_group(d, sketch_list_k(limit));
   size_t first = 0;
   for (uint32_t size : vt_host::sketch_batch_plan(fit.size(), gmax)) {
     const std::vector<size_t> which(fit.begin() + first, fit.begin() + first + size);
-    VT_TRY(sketch_group_search(ix, c, queries, which, limit, out, done));
+    VT_TRY(sketch_group_search(ix, c, queries, sq, which, limit, out, done));
     first += size;
   }
   return VT_OK;
@@ -624,7 +623,7 @@ int batch_ready(Shard *ix, Ctx &c, const float *queries, size_t nq, size_t d, si
   // (declined, not certified, a long candidate list) go on below as the queries a stage leaves over always have -- not
   // through the matrix cores, whose norms and shadow nobody was asked to bring up to date for this call.
   const bool sketch_groups = sketch_batch_wanted(ix, nq, limit);
-  if (sketch_groups && ix->sketch.current(sketch_elems(ix))) {
+  if (sketch_groups && ix->sketches[vt_host::kTier8].col.current(sketch_kind(vt_host::kTier8).elems(ix))) {
     VT_TRY(sketch_batch_stage(ix, c, queries, nq, limit, out, done));
     if (std::find(done.begin(), done.end(), (char)0) == done.end()) return VT_OK;
   }

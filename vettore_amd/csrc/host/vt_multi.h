@@ -127,8 +127,7 @@ int shard_delete(Shard *ix, const char *id, size_t id_len, bool *began) {
     ix->ranks_clean = true;
     ix->max_id.clear();
     ix->max_rank = 0;
-    ix->sketch.release();  // (an emptied index gives the sketch's room back)
-    for (auto *col : ix->nibble_sketches()) col->release();
+    for (SketchTier &t : ix->sketches) t.col.release();  // (an emptied index gives the sketches' room back)
   }
   return VT_OK;
 }
@@ -805,7 +804,7 @@ int search_direct(vt_flat *h, const float *query, size_t n, size_t limit, vt_hit
   }
   // (vt_flat_set_single_nominate: the first lone search then also brings the norms and the bf16 shadow up to date)
   const Shard *s0 = h->shards[0].get();
-  // (and the int8 sketch where sketch_wanted says a lone search reads it: the first such search builds it)
+  // (and the int8 sketch where sketch_tiers_wanted says a lone search reads it: the first such search builds it)
   const unsigned need = NEED_RANKS | NEED_NZBITS | NEED_SKETCH |
                         (s0->single_nominate && limit <= (size_t)vt::kMaxFusedK ? NEED_NORMS | NEED_STRICT_RANKS : 0u);
   return read_single(h, need, limit, [&](Shard *ix, Ctx &c) -> int {

@@ -1,7 +1,7 @@
 // vt_sketch5.h -- the host side of the 5-bit sketch (K1f: vt_sketch_nibble.hip the builders and the pass): the sums
 // that bound the query level kept off its one-bit L plane, and a restatement of the row quantiser.  The query's
 // signed-nibble levels are the 6-bit sketch's (vt_sketch6.h, sketch6_query_levels), used as they are.  Stand-alone on
-// purpose (no HIP, no header of the library but vt_sketch6.h): vt_search.h uses it, and tests/sketch5_check.cpp builds it
+// purpose (no HIP, no header of the library but vt_sketch6.h): vt_sketchsearch.h uses it, and tests/sketch5_check.cpp builds it
 // with plain g++ under AddressSanitizer and UBSan.
 #pragma once
 

@@ -1,7 +1,8 @@
 // vt_sketch6.h -- the host side of the 6-bit sketch (K1s: vt_sketch_nibble.hip the builders and the pass):
-// the query's signed-nibble levels, the sums that bound the level kept off the L plane, and a restatement of the row
-// quantiser.  Stand-alone on purpose (no HIP, no other header of the library): vt_search.h uses it, and
-// tests/sketch6_query_check.cpp and tests/sketch6_split_check.cpp build it with plain g++ under AddressSanitizer and UBSan.
+// the query's signed-nibble levels, the sums that bound the level kept off the L plane and the bound itself, and a
+// restatement of the row quantiser.  Stand-alone on purpose (no HIP, no other header of the library): vt_sketchsearch.h uses
+// it, and tests/sketch6_query_check.cpp and tests/sketch6_split_check.cpp build it with plain g++ under AddressSanitizer
+// and UBSan.
 #pragma once
 
 #include <algorithm>
@@ -62,6 +63,16 @@ inline void sketch6_level_sums(const uint32_t *level, uint32_t lw, int64_t *pos,
   *pos = p;
   *neg = n;
   *l1 = p - n;
+}
+
+// The bound itself, for the pass: the last level stays off the L plane, and its share there is *c -+ *w per unit of s_r with
+// *c = 1.5 t (*pos + *neg) and *w = 1.5 t ||Q||_1 (the middle of [3 *neg, 3 *pos] and half its width; exact: 25 bits times 19).
+inline void sketch6_level_bound(const uint32_t *level, uint32_t lw, float t, double *c, double *w) {
+  int64_t pos = 0, neg = 0, l1 = 0;
+  sketch6_level_sums(level, lw, &pos, &neg, &l1);
+  const double t3 = 1.5 * (double)t;
+  *c = t3 * (double)(pos + neg);
+  *w = t3 * (double)l1;
 }
 
 // The row quantiser as nibble_row (vt_sketch_nibble.cuh) has it: s = max|x| / 31 in f32, X = round(x * (31 / max|x|)) clamped

@@ -1,6 +1,6 @@
 // vt_sketchbatch.h -- the host side of K1qm (vt_sketch_batch.hip): which batches share passes over the int8
 // sketch, how their queries are split into groups, how large a group the pass's LDS takes, and which query must stay out.
-// Stand-alone on purpose (no HIP, no header of the library): vt_search.h and vt_batch.h use it, vt_sketch_batch.hip ties
+// Stand-alone on purpose (no HIP, no header of the library): vt_sketchsearch.h and vt_batch.h use it, vt_sketch_batch.hip ties
 // its constants to the device side's with static_asserts, and tests/sketch_batch_plan_check.cpp builds it with plain g++
 // under AddressSanitizer and UBSan.
 #pragma once
@@ -25,7 +25,7 @@ constexpr size_t kSketchBatchLdsLimit = 80 * 1024;
 constexpr size_t kSketchBatchLdsStatic = 1024;
 
 constexpr uint32_t sketch_batch_ld8(uint32_t d) { return (d + 127) / 128 * 128; }
-inline uint32_t sketch_batch_list_k(size_t limit) { return (uint32_t)std::max<size_t>(2 * limit, limit + 16); }
+constexpr uint32_t sketch_batch_list_k(size_t limit) { return (uint32_t)std::max<size_t>(2 * limit, limit + 16); }
 
 // The group sizes the pass is compiled for.  2, 4 and 8: the pass's cost is the stream's until the 2 G dots per dword
 // outweigh it, so a group of 3 loses little as a group of 4 and one of 5..7 little as one of 8, and every further size
@@ -91,7 +91,7 @@ constexpr size_t kSketchBatchMaxQueries = 4;
 constexpr size_t kSketchBatchWideQueries = 8;
 constexpr double kSketchBatchWideMaxBytes = 3.0 * 1024 * (1 << 20);
 
-// What the gate looks at, as plain values (vt_search.h fills it from the shard and the settings).
+// What the gate looks at, as plain values (vt_sketchsearch.h fills it from the shard and the settings).
 struct SketchBatchShape {
   bool dot_metric = false, l2_metric = false;  // the handle's metric family (neither: no sketch serves it)
   bool strictly_ranked = false;                // the rank column is strictly current

@@ -13,22 +13,15 @@ int index_reserve_once(Shard *ix, uint32_t want_rows);
 // 5-bit sketch before that one, which serves in its place; and the 4-bit sketch first of all.
 int index_reserve(Shard *ix, uint32_t want_rows) {
   int st = index_reserve_once(ix, want_rows);
-  for (auto *col : ix->nibble_sketches()) {
-    if (st == VT_OK || st == VT_ERR_UNSUPPORTED || !col->buf.p) continue;
+  auto retry_without = [&](auto &col) {
+    if (st == VT_OK || st == VT_ERR_UNSUPPORTED || !col.buf.p) return;
     (void)hipStreamSynchronize(ix->ctx.stream);
-    col->refuse();
+    col.refuse();
     st = index_reserve_once(ix, want_rows);
-  }
-  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->shadow.buf.p) {
-    (void)hipStreamSynchronize(ix->ctx.stream);
-    ix->shadow.refuse();
-    st = index_reserve_once(ix, want_rows);
-  }
-  if (st != VT_OK && st != VT_ERR_UNSUPPORTED && ix->sketch.buf.p) {  // (then the int8 sketch, a quarter of it)
-    (void)hipStreamSynchronize(ix->ctx.stream);
-    ix->sketch.refuse();
-    st = index_reserve_once(ix, want_rows);
-  }
+  };
+  for (int t = 0; t < vt_host::kNibbleTierCount; ++t) retry_without(ix->sketches[t].col);
+  retry_without(ix->shadow);
+  retry_without(ix->sketches[vt_host::kTier8].col);  // (then the int8 sketch, a quarter of the slab's size)
   return st;
 }
 

@@ -47,25 +47,23 @@ struct Ctx {
   DevBuf<vt::Entry> dBOut;
   DevBuf<unsigned long long> dBNorm;
   DevBuf<unsigned char> dBQimage;  // K2b: the batch's queries in bf16, fragment order
-  // K1q (vt_search.h, sketch_search): the pass's block lists, the certified candidate rows and their count,
+  // K1q (vt_sketchsearch.h, sketch_search): the pass's block lists, the certified candidate rows and their count,
   // {outcome, candidates, Kt, 0} written by the tail kernel through the host mapping, and the host's scratch for the
-  // query's first-level residual (grows, never shrinks: no allocation per search)
+  // query's first-level residual (grows, never shrinks: no allocation per search).  dSkRows: a candidate list per tier
+  // (vt_sketchtiers.h), each at its tier's cap -- K1f's and K1n's hold a row for every retained slot of the pass's lists.
   DevBuf<uint64_t> dSkKeys;
   DevBuf<vt::Payload> dSkPay;
-  DevBuf<uint32_t> dSkRows, dSkCount;
+  DevBuf<uint32_t> dSkRows[vt_host::kSketchTierCount], dSkCount;
   PinnedBuf<uint32_t> hSkInfo;
   std::vector<double> hSkResid;
-  // K1qm (vt_search.h, sketch_group_search) takes the five above at a group's size ([G][blocks][k'] lists, [G][cap] rows,
+  // K1qm (vt_sketchsearch.h, sketch_group_search) takes the five above at a group's size ([G][blocks][k'] lists, [G][cap] rows,
   // [G] counts, [G][4] info) and, per query of the group, a result block the tail writes through the host mapping and a
   // status word (zero between calls: the tail takes what it raised back)
   PinnedBuf<vt::ResultBlock> hSkgRes;
   DevBuf<int> dSkgStatus;
-  DevBuf<uint32_t> dSk6Rows;  // K1s (nibble_search, 6 bits): its longer candidate list
   DevBuf<uint32_t> dSkLoWords, dSkHiWords;  // K1s: the key(lo) / key(hi) word of every list slot, for the tail
   DevBuf<uint32_t> dSkParts;  // K1s / K1f: the threshold kernel's k smallest words per block, then its live counts
   DevBuf<uint32_t> dSkSync;   // the collect kernel's claim, fail and ticket words (16 bytes, zeroed by the threshold kernel)
-  DevBuf<uint32_t> dSk5Rows;  // K1f (nibble_search, 5 bits): its candidate list, a row for every retained slot
-  DevBuf<uint32_t> dSk4Rows;  // K1n (nibble_search, 4 bits): likewise, over twice the lists
   // K12 (vt_mmr.h, mmr_run): a call's problems, per-candidate arrays and block partials; what goes up and what comes back
   // travel through the two pinned blocks (grow, never shrink: no allocation per call)
   DevBuf<vt::MmrProblem> dMmrProb;
@@ -298,6 +296,13 @@ inline const MergeRequest *merge_request_of(const Shard *ix) {
   return t_merge_request && t_merge_request->shard == ix ? t_merge_request : nullptr;
 }
 
+// One sketch tier's state on a shard (Shard::sketches says how it is kept).
+struct SketchTier {
+  DerivedColumn<unsigned char> col;
+  double max_norm = 0.0;
+  std::atomic<uint32_t> misses{0};
+};
+
 // One shard = one GPU's share of the rows: the slab, its derived columns, the ids of
 // its rows.  A plain index has exactly one; vt_flat_new_sharded deals rows to several.
 struct Shard {
@@ -337,37 +342,23 @@ struct Shard {
   // the room back (index_reserve), it is refused and batches stream the f32 rows.
   DerivedColumn<uint16_t> shadow;
   int shadow_mode = default_shadow();  // VT_SHADOW_*
+  // The sketches of the rows, by tier (vt_sketchtiers.h: narrowest first), each with an upper bound of every row's norm (a
+  // value only while the column is valid; patches only raise it) and the consecutive passes its bound could not certify
+  // (readers under the shared lock count; a rebuild of the column starts over) -- at the tier's miss limit the shard stops
+  // taking it.  Optional, like the shadow: refused when the card has no room, given back when the slab needs it
+  // (index_reserve) and when the index is emptied.
   // K1q: the rows once more in int8 with a per-row scale and error bounds (vt_device.h, SketchScanArgs) -- a quarter of
-  // the bytes a lone cosine / dot / L2 search reads (vt_search.h, sketch_search).  Optional, like the shadow: refused when the
-  // card has no room, given back when the slab needs it (index_reserve) and when the index is emptied.
-  // sketch_max_norm: an upper bound of every row's norm (a value only while the column is valid; patches only raise it).
-  // sketch_xx: the column carries xx_r >= ||x_r||^2 in the metadata run's fourth dword -- an L2 / squared-L2 handle's,
-  // fixed when the column is built (a handle's metric never changes) and kept by every patch.
-  DerivedColumn<unsigned char> sketch;
-  double sketch_max_norm = 0.0;
-  bool sketch_xx = false;
+  // the bytes a lone cosine / dot / L2 search reads (vt_sketchsearch.h, sketch_search).
   // K1s: the rows in six bits, two planes (vt_device.h, Sketch6ScanArgs) -- 0.755 of the int8 sketch's bytes, read by the
-  // largest lone searches (vt_search.h, nibble_search) with the int8 sketch as its fallback.  Kept on the int8 sketch's
-  // terms; the first column to go when the slab needs room.  sketch6_misses: consecutive passes the bound could not
-  // certify (readers under the shared lock count; a rebuild of the column starts over) -- at kSketch6MissLimit the shard
-  // stops taking the path.
-  DerivedColumn<unsigned char> sketch6;
-  double sketch6_max_norm = 0.0;
-  std::atomic<uint32_t> sketch6_misses{0};
+  // largest lone searches (vt_sketchsearch.h, nibble_search) with the int8 sketch as its fallback.
   // K1f: the rows in five bits, two planes (vt_device.h, above launch_sketch5_scan) -- 0.838 of the 6-bit sketch's bytes,
-  // read first by the largest lone searches (vt_search.h, nibble_search) with the 6-bit and int8 sketches behind it.  Kept
-  // on the 6-bit sketch's terms, misses included (kSketch5MissLimit); the first column to go when the slab needs room.
-  DerivedColumn<unsigned char> sketch5;
-  double sketch5_max_norm = 0.0;
-  std::atomic<uint32_t> sketch5_misses{0};
+  // read first, with the 6-bit and int8 sketches behind it.
   // K1n: the rows in four bits, one plane with its own scale (vt_device.h, above launch_sketch4_scan) -- 0.806 of the 5-bit
-  // sketch's bytes, read first by the largest lone searches (vt_search.h, nibble_search) with the other three behind it.
-  // Kept on the 5-bit sketch's terms, misses included (kSketch4MissLimit); the first column to go when the slab needs room.
-  DerivedColumn<unsigned char> sketch4;
-  double sketch4_max_norm = 0.0;
-  std::atomic<uint32_t> sketch4_misses{0};
-  // (the three nibble columns, narrowest first: the order the slab takes their room back in)
-  std::array<DerivedColumn<unsigned char> *, 3> nibble_sketches() { return {&sketch4, &sketch5, &sketch6}; }
+  // sketch's bytes, read first of all, with the other three behind it.
+  SketchTier sketches[vt_host::kSketchTierCount];
+  // sketch_xx: the int8 column carries xx_r >= ||x_r||^2 in the metadata run's fourth dword -- an L2 / squared-L2 handle's,
+  // fixed when the column is built (a handle's metric never changes) and kept by every patch.
+  bool sketch_xx = false;
   // (atomic: search_direct looks at it before it takes the handle's lock, vt_flat_set_single_nominate writes it under the exclusive one)
   std::atomic<int> single_nominate{default_single_nominate()};  // vt_flat_set_single_nominate: lone searches through the shadow
   // ids
@@ -428,8 +419,7 @@ struct Shard {
       nz_bits.touch(rows[i]);
       norms.touch(rows[i]);
       shadow.touch(rows[i]);
-      sketch.touch(rows[i]);
-      for (auto *col : nibble_sketches()) col->touch(rows[i]);
+      for (SketchTier &t : sketches) t.col.touch(rows[i]);
     }
   }
   void forget_derived() {
@@ -437,8 +427,7 @@ struct Shard {
     nz_bits.forget();
     norms.forget();
     shadow.forget();
-    sketch.forget();
-    for (auto *col : nibble_sketches()) col->forget();
+    for (SketchTier &t : sketches) t.col.forget();
   }
   // A new dimension (first insert, or after the index was emptied): the derived data belongs to the old rows, and the
   // shadow gives its room back.
@@ -448,11 +437,9 @@ struct Shard {
     norms.reset();
     shadow.reset();
     shadow.buf.release();
-    sketch.reset();
-    sketch.buf.release();
-    for (auto *col : nibble_sketches()) {
-      col->reset();
-      col->buf.release();
+    for (SketchTier &t : sketches) {
+      t.col.reset();
+      t.col.buf.release();
     }
   }
 };

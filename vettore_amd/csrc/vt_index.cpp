@@ -38,6 +38,7 @@
 #include "host/vt_sketch6.h"
 #include "host/vt_sketch5.h"
 #include "host/vt_sketchbatch.h"
+#include "host/vt_sketchtiers.h"
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
@@ -49,6 +50,7 @@
 #include "host/vt_launch.h"
 #include "host/vt_select.h"
 #include "host/vt_store.h"
+#include "host/vt_sketchsearch.h"
 #include "host/vt_search.h"
 #include "host/vt_batch.h"
 #include "host/vt_quantized.h"
@@ -1355,36 +1357,18 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       t.shadow_build_ms += p.shadow_build_ms;
       t.shadow_patched_rows += p.shadow_patched_rows;
       t.sweep_queries += p.sweep_queries;
-      t.sketch_launches += p.sketch_launches;
-      t.sketch_ms += p.sketch_ms;
-      t.sketch_bytes += p.sketch_bytes;
-      t.sketch_candidates += p.sketch_candidates;
-      t.sketch_fallbacks += p.sketch_fallbacks;
-      t.sketch_builds += p.sketch_builds;
-      t.sketch_patched_rows += p.sketch_patched_rows;
+      for (int tier = 0; tier < vt_host::kSketchTierCount; ++tier) {  // (each tier's own counters: sketch_kind)
+        const SketchKind &k = sketch_kind(tier);
+        t.*k.launches += p.*k.launches;
+        t.*k.ms += p.*k.ms;
+        t.*k.bytes_read += p.*k.bytes_read;
+        t.*k.candidates += p.*k.candidates;
+        t.*k.fallbacks += p.*k.fallbacks;
+        t.*k.builds += p.*k.builds;
+        t.*k.patched_rows += p.*k.patched_rows;
+      }
       t.sketch_tail_rescored += p.sketch_tail_rescored;
-      t.sketch6_launches += p.sketch6_launches;
-      t.sketch6_ms += p.sketch6_ms;
-      t.sketch6_bytes += p.sketch6_bytes;
-      t.sketch6_candidates += p.sketch6_candidates;
-      t.sketch6_fallbacks += p.sketch6_fallbacks;
-      t.sketch6_builds += p.sketch6_builds;
-      t.sketch6_patched_rows += p.sketch6_patched_rows;
       t.sketch6_tail_words += p.sketch6_tail_words;
-      t.sketch5_launches += p.sketch5_launches;
-      t.sketch5_ms += p.sketch5_ms;
-      t.sketch5_bytes += p.sketch5_bytes;
-      t.sketch5_candidates += p.sketch5_candidates;
-      t.sketch5_fallbacks += p.sketch5_fallbacks;
-      t.sketch5_builds += p.sketch5_builds;
-      t.sketch5_patched_rows += p.sketch5_patched_rows;
-      t.sketch4_launches += p.sketch4_launches;
-      t.sketch4_ms += p.sketch4_ms;
-      t.sketch4_bytes += p.sketch4_bytes;
-      t.sketch4_candidates += p.sketch4_candidates;
-      t.sketch4_fallbacks += p.sketch4_fallbacks;
-      t.sketch4_builds += p.sketch4_builds;
-      t.sketch4_patched_rows += p.sketch4_patched_rows;
       t.sketch4_finished += p.sketch4_finished;
       t.sketch_batch_launches += p.sketch_batch_launches;
       t.sketch_batch_queries += p.sketch_batch_queries;
