@@ -28,7 +28,7 @@ DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_bat
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -182,6 +182,17 @@ $(LIBDIR)/sketch_batch_probe.o: tests/sketch_batch_probe.cpp $(CSRC)/vt_device.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch_batch_probe.so: $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/sketch_batch_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# The matrix-core nomination kernels behind a probe (tests/batch_probe.cpp; tests/test_gpu_batch_kernels.py loads it): K2, K2b
+# and K2s in pass and dense mode, the images, the row norms, the threshold kernels and the batched select on a test's arrays,
+# with the certificate's margin (host/vt_batchbound.h) exported beside them.  vt_batch.o, vt_batch_bf16.o, vt_batch_shadow.o
+# and the probe, nothing else of the library.  Test infrastructure, as above.
+$(LIBDIR)/batch_probe.o: tests/batch_probe.cpp $(CSRC)/vt_device.h $(CSRC)/vt_env.h $(CSRC)/host/vt_batchbound.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_batch_probe.so: $(LIBDIR)/vt_batch.o $(LIBDIR)/vt_batch_bf16.o $(LIBDIR)/vt_batch_shadow.o $(LIBDIR)/batch_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

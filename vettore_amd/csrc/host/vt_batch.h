@@ -274,7 +274,8 @@ int batch_group_finish(Shard *ix, Ctx &c, BatchGroupRun &run, vt_hits **out, std
   // 2^-126 per element times the other operand, sqrt(d) 2^-126 (|q| + X) over a row.  Rounding
   // to bf16 can overflow only near f32's largest values: such queries are never certified here
   // (the guard below), nor is any whose margin is not finite.
-  const double u = std::ldexp(1.0, -24), ub = std::ldexp(1.0, -8);
+  // (the margin itself: host/vt_batchbound.h -- the kernel tests take their tolerances from the same function)
+  const double u = std::ldexp(1.0, -24);
   const double xnorm = std::sqrt(ix->max_sqnorm);
   if (retry_tau) retry_tau->assign(nq, std::numeric_limits<float>::quiet_NaN());
   std::vector<size_t> accepted;
@@ -292,23 +293,16 @@ int batch_group_finish(Shard *ix, Ctx &c, BatchGroupRun &run, vt_hits **out, std
     const vt::Entry *e = c.hBOut.p + i * k;
     const double tau = (double)c.hBTau.p[i];
     const double raw_k = (double)e[k - 1].raw;
-    const bool magnitudes_ok = !bf16 || (qnorm[i] < 1e18 && xnorm < 1e18);
+    const bool magnitudes_ok = vt_host::batch_magnitudes_ok(bf16, qnorm[i], xnorm);
     bool accept = false;
     double tau2 = std::numeric_limits<double>::quiet_NaN();  // threshold that certifies given these k exact hits
+    const double eps = vt_host::batch_eps(l2_family, bf16, d, qnorm[i], xnorm);
     if (l2_family) {
-      double eps = 3.5 * (double)d * u * (qnorm[i] + xnorm) * (qnorm[i] + xnorm);
-      if (bf16)
-        eps = 2.0 * (2.0 * ub + ub * ub) * qnorm[i] * xnorm + 8.0 * (double)d * u * (qnorm[i] + xnorm) * (qnorm[i] + xnorm) +
-              std::ldexp(1.0, -120) * std::sqrt((double)d) * (qnorm[i] + xnorm);
       const double l2sq_k = (ix->metric == VT_L2 ? raw_k * raw_k : raw_k) * (1.0 + 16.0 * u);
       const double bound = qnorm[i] * qnorm[i] * (1.0 - 4.0 * u) - eps;
       accept = l2sq_k <= bound - tau;
       tau2 = bound - l2sq_k * (1.0 + 16.0 * u);
     } else {
-      double eps = 2.5 * (double)d * u * qnorm[i] * xnorm;
-      if (bf16)
-        eps = (2.0 * ub + ub * ub + 8.0 * (double)d * u) * qnorm[i] * xnorm +
-              std::ldexp(1.0, -120) * std::sqrt((double)d) * (qnorm[i] + xnorm);
       const double dot_k = ix->metric == VT_NEG_INNER_PRODUCT ? -raw_k : raw_k;
       const double slack = ix->metric == VT_COSINE ? 4.0 * u * std::max(1.0, std::fabs(1.0 - dot_k)) : 0.0;
       accept = tau + eps + slack <= dot_k;

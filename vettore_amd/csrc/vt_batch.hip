@@ -433,7 +433,10 @@ __global__ __launch_bounds__(kTauThreads) void sample_tau_kernel(const float *__
         s_bin = b;
         s_below = below;
       }
-      if (lane == kWave - 1 && incl < krem) {  // fewer than rank values: the smallest score
+      // Fewer than rank values: every digit takes this way, the prefix ends as ~0 and the answer below is a NaN -- no
+      // score reaches it, the query nominates nothing and is not certified.  (Not the smallest score, which the
+      // small-rank path above and sample_tau_groups_kernel give: the callers clamp a rank above 16 to the sample's size.)
+      if (lane == kWave - 1 && incl < krem) {
         s_bin = 255;
         s_below = 0;
       }

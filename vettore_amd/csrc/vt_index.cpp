@@ -39,6 +39,7 @@
 #include "host/vt_sketch5.h"
 #include "host/vt_sketchbatch.h"
 #include "host/vt_sketchtiers.h"
+#include "host/vt_batchbound.h"
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
