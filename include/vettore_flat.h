@@ -539,10 +539,16 @@ int vt_mv_memory(const vt_mv *store, size_t *vectors, size_t *row_capacity, size
  * with one launch, every answer equal to the lone call's: with query_status a query's own error lands in
  * query_status[i] with out[i] NULL and the call returns VT_OK; without it the first failing query's status is returned
  * and every out[i] is NULL (vt_mv_top_k_batch's convention).
- * One mutex per handle: every call excludes every other.  Rows of deleted nodes stay dead in the slab until the last
- * node goes (then slab and dimension go, and the next insert may bring another dimension; internal ids keep counting
- * and are never reused); an internal-id counter at 2^32 returns VT_ERR_NOMEM.  The slab holds at most 2^30 - 64 rows,
- * dead ones included: a traversal on a larger slab returns VT_ERR_UNSUPPORTED (vt_last_error says so). */
+ * One mutex per handle: every call excludes every other.  A delete, and an insert of an id that exists, leaves the old
+ * node's slab row and list words dead.  They come back on an insert, never on a delete: an insert that finds, behind its
+ * own erasure, more dead rows than live nodes and at least 64 of them first gathers the survivors into a fresh slab and
+ * renumbers every list entry on the device (compaction; the buffers may shrink), so the dead rows never exceed
+ * max(live, 63) by more than the erasures since the last insert.  Graph, internal ids and hits are untouched by it.  A
+ * card without room for the second set of buffers postpones it without an error; a mirror it finds apart from the graph
+ * is VT_ERR_DEVICE and poisons the handle.  When the last node goes, slab and dimension go (the next insert may bring
+ * another dimension; internal ids keep counting and are never reused); an internal-id counter at 2^32 returns
+ * VT_ERR_NOMEM.  The slab holds at most 2^30 - 64 rows, dead ones included: a traversal on a larger slab returns
+ * VT_ERR_UNSUPPORTED (vt_last_error says so). */
 typedef struct vt_hnsw vt_hnsw;
 int vt_hnsw_new(int metric_code, int device, size_t m, size_t m0, size_t ef_construction, size_t ef_search,
                 size_t max_level, vt_hnsw **out);
@@ -564,8 +570,10 @@ int vt_hnsw_neighbors(const vt_hnsw *index, uint64_t internal_id, uint32_t layer
 /* Totals since vt_hnsw_new -- traversal_launches: launches of the traversal kernel; traversals: searches and insert
  * descents asked of it; reruns: traversals that outgrew their scratch and ran again with full-size scratch. */
 int vt_hnsw_counters(const vt_hnsw *index, uint64_t *traversal_launches, uint64_t *traversals, uint64_t *reruns);
-/* rows: slab rows handed out; row_capacity: rows the slab holds; dead_rows: rows of deleted nodes; edges: entries of
- * all adjacency lists.  Any out pointer may be NULL. */
+/* rows: slab rows handed out since the last compaction (live and dead; the live count right behind one); row_capacity:
+ * rows the slab holds (1024 doubled until they fit; a compaction may shrink it); dead_rows: rows among `rows` whose node
+ * was deleted or replaced (0 again at a compaction); edges: entries of all adjacency lists.  rows - dead_rows is
+ * vt_hnsw_len.  Any out pointer may be NULL. */
 int vt_hnsw_memory(const vt_hnsw *index, size_t *rows, size_t *row_capacity, size_t *dead_rows, size_t *edges);
 
 /* ------------------------------------------- MMR reranking and diversified search

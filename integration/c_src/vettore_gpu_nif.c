@@ -939,6 +939,21 @@ static ERL_NIF_TERM hnsw_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
   return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
 }
 
+/* hnsw_memory(ref) -> {:ok, {rows, row_capacity, dead_rows, edges}} | {:error, binary}
+ * (no counterpart in the reference: vt_hnsw_memory's four numbers.  rows counts the slab rows handed out since the last
+ * compaction, dead_rows returns to 0 at one: include/vettore_flat.h) */
+static ERL_NIF_TERM hnsw_memory(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  size_t rows, cap, dead, edges;
+  (void)argc;
+  if (!r) return enif_make_badarg(env);
+  int st = vt_hnsw_memory(r->h, &rows, &cap, &dead, &edges);
+  if (st != VT_OK) return mk_error(env, st);
+  return enif_make_tuple2(env, mk_atom(env, "ok"),
+                          enif_make_tuple(env, 4, enif_make_uint64(env, (ErlNifUInt64)rows), enif_make_uint64(env, (ErlNifUInt64)cap),
+                                          enif_make_uint64(env, (ErlNifUInt64)dead), enif_make_uint64(env, (ErlNifUInt64)edges)));
+}
+
 /* ------------------------------------------------------- MMR reranking
  * Vettore.Distance.mmr_rerank/5 and Vettore.rerank/4 on the device.  The Elixir layer validates in the reference's
  * order and converts numbers with `/ 1` (flat_gpu.ex); what crosses here is floats, and what comes back is the chosen
@@ -1146,6 +1161,7 @@ static ErlNifFunc funcs[] = {
   {"hnsw_insert_many", 2, hnsw_insert_many, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_delete", 2, hnsw_delete, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_search", 3, hnsw_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_memory", 1, hnsw_memory, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"mmr_rerank", 5, mmr_rerank, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"flat_mmr_rerank", 4, flat_mmr_rerank, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"flat_mmr_search", 6, flat_mmr_search, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -197,6 +197,7 @@ defmodule Vettore.Index.FlatGpu do
   defdelegate hnsw_insert_many(ref, entries), to: Nifs
   defdelegate hnsw_delete(ref, id), to: Nifs
   defdelegate hnsw_search(ref, query, limit), to: Nifs
+  defdelegate hnsw_memory(ref), to: Nifs
 
   # ---- MMR reranking and diversified search on the resident rows (DESIGN 4.15)
   @doc """

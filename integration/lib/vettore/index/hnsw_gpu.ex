@@ -54,6 +54,18 @@ defmodule Vettore.Index.HnswGpu do
     end
   end
 
+  @doc """
+  What the index holds on the device: `{:ok, %{rows: _, row_capacity: _, dead_rows: _, edges: _}}`.  `rows` are the slab
+  rows handed out since the last compaction and `dead_rows` those of them whose node was deleted or replaced.  An insert
+  that finds more dead rows than live ones, and at least 64 of them, compacts first: `dead_rows` is 0 again, `rows` the
+  live count, and `row_capacity` may shrink.  A delete never compacts.
+  """
+  def memory(%Collection{index_state: ref}) do
+    with {:ok, {rows, row_capacity, dead_rows, edges}} <- Nifs.hnsw_memory(ref) do
+      {:ok, %{rows: rows, row_capacity: row_capacity, dead_rows: dead_rows, edges: edges}}
+    end
+  end
+
   defp to_result(collection, {id, raw}) do
     case Collection.get(collection, id) do
       {:ok, %Embedding{} = embedding} ->

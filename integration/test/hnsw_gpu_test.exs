@@ -40,6 +40,33 @@ defmodule Vettore.Index.HnswGpuTest do
     end
   end
 
+  test "an insert gives the rows of deleted nodes back once they outnumber the live ones" do
+    gpu = collection(HnswGpu, :cosine, m: 4, m0: 8, ef_construction: 24, ef_search: 12)
+    cpu = collection(HNSW, :cosine, m: 4, m0: 8, ef_construction: 24, ef_search: 12)
+    docs = vectors(200)
+
+    for {id, v} <- docs, c <- [gpu, cpu] do
+      :ok = Vettore.put(c, %Vettore.Embedding{id: id, vector: v, value: id})
+    end
+
+    for {id, _v} <- Enum.take(docs, 130), c <- [gpu, cpu] do
+      :ok = Vettore.delete(c, id)
+    end
+
+    # deletes never compact
+    assert {:ok, %{rows: 200, dead_rows: 130, row_capacity: 1024}} = HnswGpu.memory(gpu)
+
+    for c <- [gpu, cpu] do
+      :ok = Vettore.put(c, %Vettore.Embedding{id: "one-more", vector: for(_ <- 1..8, do: 0.25), value: "one-more"})
+    end
+
+    assert {:ok, %{rows: 71, dead_rows: 0, row_capacity: 1024}} = HnswGpu.memory(gpu)
+
+    for {_id, q} <- Enum.take(docs, 10), limit <- [1, 5, 70] do
+      assert Vettore.search(gpu, q, limit: limit) == Vettore.search(cpu, q, limit: limit), limit
+    end
+  end
+
   test "options and metrics are rejected as hnsw.ex rejects them" do
     for bad <- [[m: 0], [m0: 2_049], [m: 16, m0: 8], [ef_construction: 8], [ef_search: 0], [max_level: 65], [unknown: 1], [m: 8, m: 8], :m] do
       assert HnswGpu.new(:l2, bad) == {:error, :invalid_hnsw_options}

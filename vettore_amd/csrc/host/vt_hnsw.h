@@ -6,8 +6,10 @@
 //
 // The contract: after any inserts and deletes the graph -- levels, entry, every list -- is the reference's, and a search
 // returns the reference's ids in its order with the raw values' bits.  One mutex per handle, every call exclusive.
-// Rows are handed out in insertion order and never reused while a node lives (the rows of deleted nodes stay dead:
-// no compaction), so a row number orders like the internal id and the device names nodes by rows.  The slab doubles by
+// Rows are handed out in insertion order and never reused while a node lives, so a row number orders like the internal
+// id and the device names nodes by rows.  The row of a deleted node stays dead until an insert finds more dead rows
+// than live ones (host/vt_hnswplan.h: the rule, never on a delete): then the survivors are gathered in row order into
+// a fresh slab and mirror with every list entry renumbered (K11c), and the buffers may shrink.  The slab doubles by
 // allocate + copy; when the last node goes the slab and the dimension go too (`next` keeps counting).
 #pragma once
 
@@ -89,8 +91,7 @@ void hnsw_forget(vt_hnsw *h) {
 int hnsw_reserve(vt_hnsw *h, uint64_t rows, uint64_t upper) {
   hipStream_t s = h->ctx.stream;
   if (rows > h->capacity) {
-    uint64_t cap = h->capacity ? h->capacity : 1024;
-    while (cap < rows) cap *= 2;
+    const uint64_t cap = vt_host::hnsw_capacity_for(rows);
     DevBuf<float> nX;
     DevBuf<uint32_t> nAdj, nLevel, nUpoff;
     VT_TRY(hnsw_alloc(nX, (size_t)cap * h->stride));
@@ -112,8 +113,7 @@ int hnsw_reserve(vt_hnsw *h, uint64_t rows, uint64_t upper) {
     h->capacity = cap;
   }
   if (upper > h->dUpper.count || !h->dUpper.p) {
-    uint64_t cap = h->dUpper.p ? h->dUpper.count : 4096;
-    while (cap < upper) cap *= 2;
+    const uint64_t cap = vt_host::hnsw_upper_capacity_for(upper);
     DevBuf<uint32_t> nUp;
     VT_TRY(hnsw_alloc(nUp, (size_t)cap));
     if (h->upper_used) {
@@ -255,6 +255,101 @@ int hnsw_erase(vt_hnsw *h, const std::string &id, bool *mutated) {
   return hnsw_patch_mirror(h, none);
 }
 
+// hipMalloc into an empty buffer without a word in the call's error text; false: refused (the HIP error is cleared)
+template <typename T>
+bool hnsw_try_alloc(DevBuf<T> &b, size_t want) {
+  b.release();
+  want = std::max<size_t>(want, 1);
+  if (hipMalloc(reinterpret_cast<void **>(&b.p), want * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return false;
+  }
+  b.count = want;
+  return true;
+}
+
+// An insert into a graph with nodes, behind its erase: when the dead rows outnumber the live ones (vt_hnswplan.h) the
+// survivors move, in row order, into a fresh slab and mirror (K11c).  Everything is allocated before anything changes,
+// and a card without room for the second set of buffers means no compaction this time: no error, the handle as it
+// was.  A HIP error leaves the handle as it was too.  A guard of the kernel that fired means the mirror had parted from
+// the graph before: nothing is swapped, the handle is poisoned.
+int hnsw_compact_if_due(vt_hnsw *h) {
+  const uint64_t live = h->graph.len();
+  if (live == 0 || !vt_host::hnsw_compact_due(live, h->dead_rows)) return VT_OK;
+  std::vector<vt_host::HnswRowLevel> rl;
+  rl.reserve((size_t)live);
+  for (uint64_t r = 0; r < h->rows_used; ++r) {
+    const vt_host::HnswNode *n = h->graph.node(h->row_id[(size_t)r]);
+    if (n && n->row == r) rl.push_back(vt_host::HnswRowLevel{(uint32_t)r, n->level});
+  }
+  vt_host::HnswCompactPlan plan;
+  if (rl.size() != live || !vt_host::hnsw_compact_plan(rl, h->m, &plan)) return VT_OK;  // (what fits now fits with fewer rows)
+
+  DevBuf<float> nX;
+  DevBuf<uint32_t> nAdj, nLevel, nUpoff, nUpper, dRemap, dPlan, dStatus;
+  const size_t n = (size_t)plan.rows_used;
+  if (!hnsw_try_alloc(nX, (size_t)plan.capacity * h->stride) || !hnsw_try_alloc(nAdj, (size_t)plan.capacity * (h->m0 + 1)) ||
+      !hnsw_try_alloc(nLevel, (size_t)plan.capacity) || !hnsw_try_alloc(nUpoff, (size_t)plan.capacity) ||
+      !hnsw_try_alloc(nUpper, (size_t)plan.upper_capacity) || !hnsw_try_alloc(dRemap, (size_t)h->rows_used) ||
+      !hnsw_try_alloc(dPlan, 2 * n) || !hnsw_try_alloc(dStatus, vt::kHnswCompactGuards))
+    return VT_OK;
+
+  hipStream_t s = h->ctx.stream;
+  VT_HIP(hipMemcpyAsync(dPlan.p, plan.src.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  VT_HIP(hipMemcpyAsync(dPlan.p + n, plan.upoff.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  vt::HnswCompactArgs a{};
+  a.X = h->X.p;
+  a.adj0 = h->dAdj0.p;
+  a.level = h->dLevel.p;
+  a.upoff = h->dUpoff.p;
+  a.upper = h->dUpper.p;
+  a.old_rows = (uint32_t)h->rows_used;
+  a.old_upper = h->upper_used;
+  a.stride = h->stride;
+  a.m = (uint32_t)h->m;
+  a.m0 = (uint32_t)h->m0;
+  a.src = dPlan.p;
+  a.new_upoff = dPlan.p + n;
+  a.rows = (uint32_t)n;
+  a.new_upper = plan.upper_used;
+  a.remap = dRemap.p;
+  a.outX = nX.p;
+  a.out_adj0 = nAdj.p;
+  a.out_level = nLevel.p;
+  a.out_upoff = nUpoff.p;
+  a.out_upper = nUpper.p;
+  a.status = dStatus.p;
+  VT_HIP(vt::launch_hnsw_compact(a, s));
+  uint32_t fired[vt::kHnswCompactGuards] = {};
+  VT_HIP(hipMemcpyAsync(fired, dStatus.p, sizeof fired, hipMemcpyDeviceToHost, s));
+  VT_HIP(hipStreamSynchronize(s));
+  static const char *const kGuard[vt::kHnswCompactGuards] = {"a list names a row beyond the slab", "a list names a dead row",
+                                                            "a list is longer than its degree",
+                                                            "a level or list offset is not the graph's"};
+  for (uint32_t g = 0; g < vt::kHnswCompactGuards; ++g)
+    if (fired[g]) {
+      h->poisoned = true;
+      return fail(VT_ERR_DEVICE, std::string("hnsw index: compaction found the device mirror apart from the graph: ") + kGuard[g]);
+    }
+
+  mv_swap(h->X, nX);
+  mv_swap(h->dAdj0, nAdj);
+  mv_swap(h->dLevel, nLevel);
+  mv_swap(h->dUpoff, nUpoff);
+  mv_swap(h->dUpper, nUpper);
+  h->graph.close_rows();
+  std::vector<uint64_t> ids(n);
+  for (size_t i = 0; i < n; ++i) ids[i] = h->row_id[plan.src[i]];
+  h->row_id = std::move(ids);
+  h->row_upoff = std::move(plan.upoff);
+  h->rows_used = plan.rows_used;
+  h->dead_rows = 0;
+  h->upper_used = plan.upper_used;
+  h->capacity = plan.capacity;
+  return VT_OK;
+}
+
 }  // namespace
 
 
@@ -272,6 +367,7 @@ int hnsw_insert_one(vt_hnsw *h, const char *id, size_t id_len, const float *vec,
   VT_TRY(h->ctx.bind());
   const std::string ext(id_len ? id : "", id_len);
   VT_TRY(hnsw_erase(h, ext, mutated));  // an existing id goes first, whatever happens to the insert
+  VT_TRY(hnsw_compact_if_due(h));       // (an emptied graph went through hnsw_forget; a delete never compacts)
   if (!h->graph.ids_left()) return fail(VT_ERR_NOMEM, "hnsw index: the internal id counter reached 2^32");
   const uint64_t iid = h->graph.take_id();
   const uint32_t level = h->graph.level_for(ext.data(), ext.size());

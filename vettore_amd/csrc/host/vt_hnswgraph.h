@@ -15,9 +15,13 @@
 // is a sort by (kept distance, id) and a truncation, no distance is computed twice, and a prune cannot fail once the
 // traversal succeeded.
 //
-// Out of scope, on purpose: the slab rows of deleted nodes stay dead (a node's row is handed out once, rows only come
-// back when the last node goes and the slab with it) -- no compaction; and an internal-id counter that reaches 2^32
-// refuses further inserts (VT_ERR_NOMEM at the C ABI): the device addresses nodes with 32 bits.
+// Slab rows: a node's row is handed out by the caller and stays the node's until the caller compacts its slab
+// (host/vt_hnswplan.h says when): close_rows() then renumbers the live nodes 0 .. len() - 1 in the order of their old
+// rows, which is the order of the internal ids, and that is all it changes.  Rows also come back when the last node
+// goes and the slab with it.
+//
+// Out of scope, on purpose: an internal-id counter that reaches 2^32 refuses further inserts (VT_ERR_NOMEM at the
+// C ABI): the device addresses nodes with 32 bits.
 #pragma once
 
 #include <algorithm>
@@ -180,6 +184,22 @@ class HnswGraph {
       changed_.clear();  // (the mirror goes with the slab)
     }
     return true;
+  }
+
+  // The slab was compacted: every live node's (old row, level) in row order, and node.row = its place in that list.
+  // Levels, lists, entry, ids and the changed lists stay as they are.
+  std::vector<std::pair<uint32_t, uint32_t>> close_rows() {
+    std::vector<std::pair<uint32_t, HnswNode *>> by_row;
+    by_row.reserve(nodes_.size());
+    for (auto &kv : nodes_) by_row.emplace_back(kv.second.row, &kv.second);
+    std::sort(by_row.begin(), by_row.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+    std::vector<std::pair<uint32_t, uint32_t>> out;
+    out.reserve(by_row.size());
+    for (size_t i = 0; i < by_row.size(); ++i) {
+      out.emplace_back(by_row[i].first, by_row[i].second->level);
+      by_row[i].second->row = (uint32_t)i;
+    }
+    return out;
   }
 
   // The adjacency lists that changed since the last clear_changed(), as (internal id, layer): the device mirror is

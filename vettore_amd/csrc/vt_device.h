@@ -719,6 +719,38 @@ struct HnswPatch {
 };
 hipError_t launch_hnsw_patch(const HnswPatch *p, uint32_t n, uint32_t *adj0, uint32_t *upper, uint32_t *level, uint32_t *upoff,
                              hipStream_t s);
+// K11c: compaction of a slab and its mirror into fresh buffers (host/vt_hnswplan.h: the plan).  New row i is old row
+// src[i] (ascending): its slab row and level are copied, its upper-layer lists move to new_upoff[i], and every list
+// entry -- the mirror names nodes by rows -- goes through remap[old row] = new row.  Behind a list's count its entries,
+// behind them zeros up to the list's stride: the new buffers hold nothing uninitialised below rows / new_upper.
+// What the old buffers hold is not trusted: nothing outside them is read, and what should not be there is reported in
+// status[0 .. 4), one word per guard (0 or 1, plain stores), with kHnswNoRow or an empty list in its place.
+constexpr uint32_t kHnswNoRow = 0xFFFFFFFFu;   // remap[] of a dead row
+enum : uint32_t {
+  kHnswCompactBeyond = 0,  // a list entry >= old_rows (checked before remap[] is read)
+  kHnswCompactDead = 1,    // a list entry that names a dead row
+  kHnswCompactCount = 2,   // a list's count above m0 / m (clamped)
+  kHnswCompactShape = 3,   // src[], a level or an upper-layer offset of the old mirror that disagrees with the plan
+  kHnswCompactGuards = 4
+};
+struct HnswCompactArgs {
+  // the old slab and mirror: old_rows rows used, old_upper words of upper-layer lists used
+  const float *X;
+  const uint32_t *adj0, *level, *upoff, *upper;
+  uint32_t old_rows;
+  uint64_t old_upper;
+  uint32_t stride, m, m0;  // floats a row (a multiple of 4), entries per upper-layer list, per layer-0 list
+  // the plan: `rows` survivors, new_upper words of upper-layer lists behind them
+  const uint32_t *src, *new_upoff;
+  uint32_t rows;
+  uint64_t new_upper;
+  uint32_t *remap;         // [old_rows], filled here
+  // the new buffers: at least `rows` rows, new_upper words
+  float *outX;
+  uint32_t *out_adj0, *out_level, *out_upoff, *out_upper;
+  uint32_t *status;        // [kHnswCompactGuards], zeroed here
+};
+hipError_t launch_hnsw_compact(const HnswCompactArgs &a, hipStream_t s);
 
 // ---- K12 (vt_mmr.hip): MMR reranking (vettore_distance.ex:416-519), one step kernel queued once per round ------------
 // A call solves `nprob` problems over one row matrix.  Problem p owns entries [off, off + n) of the per-candidate arrays;

@@ -20,6 +20,9 @@
 // hash of 2 * cap rows for the visited set (fresh per search_layer).  A traversal that would visit more than `cap`
 // nodes, or whose ef exceeds it, ends with kHnswRetry and changes nothing the host uses: the host runs it again with
 // cap >= nodes + 64, which no traversal outgrows.
+//
+// K11c, further down: the compaction of the slab and the mirror into fresh buffers once dead rows outnumber live ones
+// (host/vt_hnswplan.h) -- a gather of rows and a renumbering of every list entry, nothing of the traversal's.
 #include "vt_maxsim_pair.cuh"  // finish_raw beside vt_scan.cuh's chain
 
 namespace vt {
@@ -412,6 +415,99 @@ __global__ void hnsw_patch_kernel(const HnswPatch *p, uint32_t n, uint32_t *adj0
   dst[r.dst] = r.val;
 }
 
+// ---- K11c: compaction (vt_device.h: HnswCompactArgs).  Four small kernels in stream order behind two memsets: the
+// remap table, the rows with level and offset, the layer-0 lists, the upper-layer lists.  A thread owns one 16-byte
+// unit of a row or one word of a list; consecutive threads take consecutive units / words, so the stores are dense
+// and the loads are dense within a row (1-12 KB) or a list.
+
+// where new row i's upper-layer lists end
+__device__ __forceinline__ uint64_t compact_upper_end(const HnswCompactArgs &a, uint32_t i) {
+  return i + 1 < a.rows ? (uint64_t)a.new_upoff[i + 1] : a.new_upper;
+}
+
+// true: old row s carries `words` words of upper-layer lists, as the plan says, and they lie inside the old array
+__device__ __forceinline__ bool compact_shape_ok(const HnswCompactArgs &a, uint32_t s, uint64_t words) {
+  if ((uint64_t)a.level[s] * (a.m + 1) != words) return false;
+  return words == 0 || (uint64_t)a.upoff[s] + words <= a.old_upper;
+}
+
+__global__ void hnsw_remap_kernel(const HnswCompactArgs a) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.rows) return;
+  const uint32_t s = a.src[i];
+  if (s >= a.old_rows) {
+    a.status[kHnswCompactShape] = 1;
+    return;
+  }
+  a.remap[s] = i;
+}
+
+__global__ void hnsw_compact_rows_kernel(const HnswCompactArgs a, uint32_t rs4) {
+  const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u >= (size_t)a.rows * rs4) return;
+  const uint32_t i = (uint32_t)(u / rs4), c = (uint32_t)(u % rs4);
+  const uint32_t s = a.src[i];
+  const bool there = s < a.old_rows;
+  f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (there) v = reinterpret_cast<const f32x4 *>(a.X)[(size_t)s * rs4 + c];
+  reinterpret_cast<f32x4 *>(a.outX)[u] = v;
+  if (c == 0) {
+    const uint64_t words = compact_upper_end(a, i) - a.new_upoff[i];
+    if (there && !compact_shape_ok(a, s, words)) a.status[kHnswCompactShape] = 1;
+    a.out_level[i] = (uint32_t)(words / (a.m + 1));  // (the plan's level: the mirror's, or the shape guard fired)
+    a.out_upoff[i] = a.new_upoff[i];
+  }
+}
+
+// word `pos` of a list's new image: the count (clamped to lim), the entries renumbered, zeros behind them
+__device__ __forceinline__ uint32_t compact_list_word(const HnswCompactArgs &a, const uint32_t *list, uint32_t lim, uint32_t pos) {
+  uint32_t cnt = list[0];
+  if (cnt > lim) {
+    a.status[kHnswCompactCount] = 1;
+    cnt = lim;
+  }
+  if (pos == 0) return cnt;
+  if (pos > cnt) return 0;
+  const uint32_t e = list[pos];
+  if (e >= a.old_rows) {  // before the table is read
+    a.status[kHnswCompactBeyond] = 1;
+    return kHnswNoRow;
+  }
+  const uint32_t r = a.remap[e];
+  if (r == kHnswNoRow) a.status[kHnswCompactDead] = 1;
+  return r;
+}
+
+__global__ void hnsw_compact_adj0_kernel(const HnswCompactArgs a) {
+  const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t ls = a.m0 + 1;
+  if (u >= (size_t)a.rows * ls) return;
+  const uint32_t i = (uint32_t)(u / ls), pos = (uint32_t)(u % ls);
+  const uint32_t s = a.src[i];
+  a.out_adj0[u] = s < a.old_rows ? compact_list_word(a, a.adj0 + (size_t)s * ls, a.m0, pos) : 0u;
+}
+
+__global__ void hnsw_compact_upper_kernel(const HnswCompactArgs a) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= a.new_upper) return;
+  // the row whose lists hold word w: the last one that starts at or before it (rows of level 0 hold no word)
+  uint32_t lo = 0, hi = a.rows;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if ((uint64_t)a.new_upoff[mid] <= w) lo = mid;
+    else hi = mid;
+  }
+  const uint32_t i = lo, s = a.src[i];
+  const uint64_t first = a.new_upoff[i], words = compact_upper_end(a, i) - first, off = w - first;
+  uint32_t out = 0;
+  if (s < a.old_rows && first <= w && off < words && compact_shape_ok(a, s, words)) {
+    const uint32_t ls = a.m + 1;
+    const uint32_t layer = (uint32_t)(off / ls), pos = (uint32_t)(off % ls);
+    out = compact_list_word(a, a.upper + (size_t)a.upoff[s] + (size_t)layer * ls, a.m, pos);
+  }
+  a.out_upper[w] = out;
+}
+
 template <int OP, int ORDER>
 hipError_t launch_t(const HnswTravArgs &a, uint32_t nslots, hipStream_t s) {
   const bool staged = a.tt != 0;
@@ -468,6 +564,25 @@ hipError_t launch_hnsw_patch(const HnswPatch *p, uint32_t n, uint32_t *adj0, uin
                              hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(dev::hnsw_patch_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, n, adj0, upper, level, upoff);
+  return hipGetLastError();
+}
+
+hipError_t launch_hnsw_compact(const HnswCompactArgs &a, hipStream_t s) {
+  if (a.stride == 0 || a.stride % 4 || a.old_rows == kHnswNoRow || a.rows > a.old_rows) return hipErrorInvalidValue;
+  constexpr size_t kBlock = 256, kMaxBlocks = 0x7fffffffu;
+  const uint32_t rs4 = a.stride / 4;
+  const size_t row_blocks = ((size_t)a.rows * rs4 + kBlock - 1) / kBlock;
+  const size_t adj_blocks = ((size_t)a.rows * (a.m0 + 1) + kBlock - 1) / kBlock;
+  const size_t up_blocks = (size_t)((a.new_upper + kBlock - 1) / kBlock);
+  if (row_blocks > kMaxBlocks || adj_blocks > kMaxBlocks || up_blocks > kMaxBlocks) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(a.status, 0, kHnswCompactGuards * sizeof(uint32_t), s);
+  if (e != hipSuccess) return e;
+  if (a.old_rows && (e = hipMemsetAsync(a.remap, 0xFF, (size_t)a.old_rows * sizeof(uint32_t), s)) != hipSuccess) return e;
+  if (a.rows == 0) return hipSuccess;
+  hipLaunchKernelGGL(dev::hnsw_remap_kernel, dim3((unsigned)((a.rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a);
+  hipLaunchKernelGGL(dev::hnsw_compact_rows_kernel, dim3((unsigned)row_blocks), dim3(kBlock), 0, s, a, rs4);
+  hipLaunchKernelGGL(dev::hnsw_compact_adj0_kernel, dim3((unsigned)adj_blocks), dim3(kBlock), 0, s, a);
+  if (up_blocks) hipLaunchKernelGGL(dev::hnsw_compact_upper_kernel, dim3((unsigned)up_blocks), dim3(kBlock), 0, s, a);
   return hipGetLastError();
 }
 

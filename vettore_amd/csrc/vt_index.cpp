@@ -43,6 +43,7 @@
 #include "host/vt_mvstore.h"
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
+#include "host/vt_hnswplan.h"
 #include "host/vt_mmrplan.h"
 #include "host/vt_fdeplan.h"
 #include "host/vt_concurrency.h"

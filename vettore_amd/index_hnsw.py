@@ -85,6 +85,13 @@ class HnswGpu:
         return _normalize_ok(nifs.hnsw_delete(collection.index_state, id_))
 
     @staticmethod
+    def memory(collection):
+        """What the index holds on the device: {"rows", "row_capacity", "dead_rows", "edges"} (vt_hnsw_memory).  `rows`
+        are the slab rows handed out since the last compaction; an insert that finds more dead rows than live ones, and
+        at least 64 of them, compacts first, and `dead_rows` is 0 again.  A delete never compacts."""
+        return nifs.hnsw_memory(collection.index_state)
+
+    @staticmethod
     def search(collection, query, opts=None):
         opts = {} if opts is None else opts
         if not isinstance(opts, dict) or any(k != "limit" for k in opts):
