@@ -94,8 +94,9 @@ $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/vt_sketch_nibble.o: 
 $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_sketch_nibble.cuh
 $(LIBDIR)/vt_sketch_batch.o: $(CSRC)/host/vt_sketchbatch.h
 
-# (the pass K9r and K9rb share; K11 and K12 take its finish_raw)
-$(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_maxsim_pair.cuh
+# (the one-lane pair arithmetic of K9, K9r, K9rb, K11 and K12; what the three MaxSim kernels share beside it)
+$(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_pair.cuh
+$(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o: $(CSRC)/vt_maxsim_pair.cuh
 
 HOSTHDR := $(wildcard $(CSRC)/host/*.h)
 $(LIBDIR)/vt_index.o: $(CSRC)/vt_index.cpp $(HOSTHDR) $(CSRC)/vt_device.h $(CSRC)/vt_env.h include/vettore_flat.h

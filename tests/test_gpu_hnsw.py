@@ -118,6 +118,51 @@ def test_graph_and_hits_are_the_restatements(nifs, ref_order, name, metric):
         assert len(nifs.hnsw_search(idx, [0.0, 1.0, 0.5], 1000)[1]) == 300
 
 
+_ORDER_CORPORA = {}
+
+
+def order_corpus(oracle_mod, name):
+    """(ids, vectors, queries, parameters, limit) for the lane-order test: "120x13" is staged in LDS and has one full
+    chunk and a scalar tail of five, "24x4100" lies past kHnswLdsDim and is walked in global memory.  The data must tell
+    the lane orders apart, or an index that ignored its order would pass: with these seeds the oracle's distances under
+    any two of the four orders differ in their bits for some (row, query) pair of either shape under L2 and under inner
+    product (worked out on the CPU when the test was written; orders 0 and 3: 120x13 -- 37 of 360 pairs under L2, 95 under
+    inner product; 24x4100 -- 5 and 56 of 72), and the assertion below keeps it so."""
+    if name not in _ORDER_CORPORA:
+        n, d, p, limit = {"120x13": (120, 13, params(4, 8, 30), 10), "24x4100": (24, 4100, params(4, 8, 20), 5)}[name]
+        rng = np.random.default_rng(sum(name.encode()))
+        vecs = rng.standard_normal((n, d)).astype(np.float32)
+        queries = rng.standard_normal((3, d)).astype(np.float32)
+        for metric in (L2, INNER_PRODUCT):
+            bits = []
+            for order in (0, 1, 2, 3):
+                oracle_mod.set_reduce_order(order)
+                bits.append(tuple(f32bits(oracle_mod.compute(metric, v, q)) for v in vecs for q in queries))
+            assert len(set(bits)) == 4, (name, metric)
+        _ORDER_CORPORA[name] = ([b"k%d" % ((i * 7919) % 100003) for i in range(n)], vecs, queries, p, limit)
+    return _ORDER_CORPORA[name]
+
+
+@pytest.mark.parametrize("metric", [L2, INNER_PRODUCT])
+@pytest.mark.parametrize("name,order", [("120x13", 0), ("120x13", 1), ("120x13", 2), ("120x13", 3), ("24x4100", 1)])
+def test_the_four_lane_orders(nifs, oracle_mod, vt_debug, name, order, metric):
+    """K11's chains in every lane order (an index takes the library's order when it is made): graph and hits are the
+    restatement's under the same order."""
+    try:
+        ids, vecs, queries, p, limit = order_corpus(oracle_mod, name)
+        vt_debug.set("reduce_order", order)
+        oracle_mod.set_reduce_order(order)
+        ref = HnswIndex(metric, **p)
+        ref.insert_many(list(zip(ids, vecs)))
+        idx = new_gpu(nifs, metric, p)
+        assert nifs.hnsw_insert_many(idx, list(zip(ids, vecs))) == ("ok", ())
+        assert_same_graph(nifs, idx, ref)
+        for q in [vecs[0]] + list(queries):
+            assert_same_search(nifs, idx, ref, q, limit)
+    finally:
+        oracle_mod.set_reduce_order(oracle_mod.DEFAULT_ORDER)
+
+
 @pytest.mark.parametrize("metric", [L2, INNER_PRODUCT])
 def test_ties_duplicates_and_signed_zeros(nifs, ref_order, metric):
     """An integer grid with many duplicate vectors: equal distances everywhere, so every (distance, id) tie-break and

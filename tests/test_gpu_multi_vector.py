@@ -74,6 +74,35 @@ def test_top_k_bitwise_against_the_reference(nifs, oracle_mod, vt_debug, metric,
         oracle_mod.set_reduce_order(oracle_mod.DEFAULT_ORDER)
 
 
+@pytest.mark.parametrize("order", [1, 2])
+def test_the_other_two_lane_orders(nifs, oracle_mod, vt_debug, order):
+    """Orders 1 and 2 through the stateless kernel: a lane with one chunk and a scalar tail (d = 9) or two chunks and one
+    (d = 17), documents of one vector, of a wave and of a wave and a vector more (a second lane round), one query vector
+    and nine (a second group of eight whose last seven slots are clamped).  The seed is one under which the data tells
+    either order from the default one: under inner product and under L2 some score's bits differ between the two
+    (found on the CPU, and asserted below)."""
+    try:
+        rng = np.random.default_rng(4460 + order)
+        for metric in (3, 0, 6):
+            told_apart = False
+            for d in (9, 17):
+                docs = [("one", vectors(rng, 1, d, metric)), ("wave", vectors(rng, 64, d, metric)),
+                        ("wave+1", vectors(rng, 65, d, metric))]
+                for nq in (1, 9):
+                    query = vectors(rng, nq, d, metric)
+                    oracle_mod.set_reduce_order(oracle_mod.DEFAULT_ORDER)
+                    default = maxsim_ref.top_k(docs, query, metric, len(docs))
+                    oracle_mod.set_reduce_order(order)
+                    want = maxsim_ref.top_k(docs, query, metric, len(docs))
+                    told_apart |= sorted((h[0], f32bits(h[1])) for h in want) != sorted((h[0], f32bits(h[1])) for h in default)
+                    vt_debug.set("reduce_order", order)
+                    got = nifs.multi_vector_top_k(docs, query, metric, len(docs))
+                    assert_same_hits(got, want, (metric, order, d, nq))
+            assert told_apart or metric == 6, (metric, order)  # (a maximum is the same in any order)
+    finally:
+        oracle_mod.set_reduce_order(oracle_mod.DEFAULT_ORDER)
+
+
 def test_error_precedence_follows_the_document_order(nifs):
     ip = 3
     ok = [[1.0, 0.5]]

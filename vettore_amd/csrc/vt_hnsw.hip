@@ -7,7 +7,7 @@
 // and the slab of rows.
 //
 // Distances: rank_distance(metric, stored row, query) (distances.rs:108-119) is one lane's own serial chain in the
-// reference's order -- K1's elem / comb / chunk_sum1 / scalar tail, K9's finish_raw with the recovery by value -- so a
+// reference's order -- vt_pair.cuh's f32 chain, stored row on the left, and its finish_raw with the recovery by value -- so a
 // hop's neighbours are scored side by side, one lane each: the unvisited neighbours of up to 64 list entries are
 // compacted into a pending list, their rows staged into the wave's LDS tile with coalesced 16-byte loads, `tt` rows at
 // a time (tt = 64 down to 2 by the row length), and lane r walks row r of the tile against the query, which sits in
@@ -23,7 +23,7 @@
 //
 // K11c, further down: the compaction of the slab and the mirror into fresh buffers once dead rows outnumber live ones
 // (host/vt_hnswplan.h) -- a gather of rows and a renumbering of every list entry, nothing of the traversal's.
-#include "vt_maxsim_pair.cuh"  // finish_raw beside vt_scan.cuh's chain
+#include "vt_pair.cuh"
 
 namespace vt {
 namespace dev {
@@ -144,7 +144,7 @@ __device__ __forceinline__ const uint32_t *list_of(const HnswDev &g, uint32_t ro
 // praw[j] = compute(metric, row pend[j], query) for j < m <= 64; false: a pair failed ("metric overflow")
 template <int OP, int ORDER, bool STAGED>
 __device__ __forceinline__ bool eval_pending(const Trav &t, uint32_t m) {
-  const uint32_t lane = t.lane, d = t.g.d, cfull = d / 8;
+  const uint32_t lane = t.lane, d = t.g.d;
   const uint32_t step = STAGED ? t.tt : (uint32_t)kWave;
   bool bad = false;
   wave_lds_fence();  // pend is written
@@ -162,25 +162,12 @@ __device__ __forceinline__ bool eval_pending(const Trav &t, uint32_t m) {
       wave_lds_fence();
     }
     if (lane < cnt) {
-      const float *xg = t.g.X + (size_t)t.pend[j0 + lane] * t.g.stride;
-      const float *x = STAGED ? t.tile + (size_t)lane * t.ld : xg;
-      const float *q = t.q;
-      float acc = 0.0f;
-      for (uint32_t c = 0; c < cfull; ++c) {
-        const f32x4 xa = *reinterpret_cast<const f32x4 *>(x + c * 8);
-        const f32x4 xb = *reinterpret_cast<const f32x4 *>(x + c * 8 + 4);
-        const f32x4 qa = *reinterpret_cast<const f32x4 *>(q + c * 8);
-        const f32x4 qb = *reinterpret_cast<const f32x4 *>(q + c * 8 + 4);
-        // left = stored row, right = query
-        const float l[8] = {elem<OP>(0, xa.x, qa.x), elem<OP>(0, xa.y, qa.y), elem<OP>(0, xa.z, qa.z),
-                            elem<OP>(0, xa.w, qa.w), elem<OP>(0, xb.x, qb.x), elem<OP>(0, xb.y, qb.y),
-                            elem<OP>(0, xb.z, qb.z), elem<OP>(0, xb.w, qb.w)};
-        acc = comb<OP>(0, acc, chunk_sum1<OP, ORDER>(l));
-      }
-      for (uint32_t e = cfull * 8; e < d; ++e) acc = comb<OP>(0, acc, elem<OP>(0, x[e], q[e]));  // the scalar tail
-      const float raw = finish_raw<OP>(t.metric, acc, xg, q, d);
-      t.praw[j0 + lane] = raw;
-      bad = bad || raw != raw;  // (a list may take several tile rounds: a failed pair of any of them fails the traversal)
+      const float *x = STAGED ? t.tile + (size_t)lane * t.ld : t.g.X + (size_t)t.pend[j0 + lane] * t.g.stride;
+      const float *const q[1] = {t.q};
+      float raw[1];
+      f32_raws<OP, ORDER, 1, true, false>(t.metric, q, x, d, raw);  // left = stored row, right = query
+      t.praw[j0 + lane] = raw[0];
+      bad = bad || raw[0] != raw[0];  // (a list may take several tile rounds: a failed pair of any of them fails the traversal)
     }
   }
   wave_lds_fence();  // praw is written
@@ -517,16 +504,6 @@ hipError_t launch_t(const HnswTravArgs &a, uint32_t nslots, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <int OP>
-hipError_t launch_ordered(const HnswTravArgs &a, uint32_t nslots, hipStream_t s) {
-  switch (a.order) {
-    case 0: return launch_t<OP, 0>(a, nslots, s);
-    case 1: return launch_t<OP, 1>(a, nslots, s);
-    case 2: return launch_t<OP, 2>(a, nslots, s);
-    default: return launch_t<OP, 3>(a, nslots, s);
-  }
-}
-
 }  // namespace
 
 }  // namespace dev
@@ -552,12 +529,9 @@ size_t hnsw_lds_bytes(uint32_t d, uint32_t tt, uint32_t ld) {
 hipError_t launch_hnsw_traverse(const HnswTravArgs &a, uint32_t nslots, hipStream_t s) {
   using namespace dev;
   if (nslots == 0) return hipSuccess;
-  switch (a.metric) {
-    case M_COS:
-    case M_IP: return launch_ordered<OP_DOT>(a, nslots, s);
-    case M_L2: return launch_ordered<OP_L2>(a, nslots, s);
-    default: return hipErrorInvalidValue;
-  }
+  if (a.metric != M_COS && a.metric != M_IP && a.metric != M_L2) return hipErrorInvalidValue;  // (the index's three metrics)
+  return dispatch_pair<1u << OP_DOT | 1u << OP_L2 | kPairCosAsDot>(
+      a.metric, a.order, [&](auto op, auto order) { return launch_t<op(), order()>(a, nslots, s); });
 }
 
 hipError_t launch_hnsw_patch(const HnswPatch *p, uint32_t n, uint32_t *adj0, uint32_t *upper, uint32_t *level, uint32_t *upoff,

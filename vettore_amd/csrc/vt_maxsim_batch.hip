@@ -27,12 +27,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_batch_kernel(con
   const uint32_t ndesc = grp.ndesc, qst = a.q_stride;
   const uint32_t slot0 = grp.desc0 * kQB, qn = ndesc * kQB;
   float *qs = lds;
-  {
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(a.Q + (size_t)slot0 * qst);
-    const uint32_t n4 = qn * qst / 4;
-    for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) reinterpret_cast<f32x4 *>(qs)[i] = src[i];
-  }
-  __syncthreads();
+  stage_query_panel(qs, a.Q + (size_t)slot0 * qst, qn * qst / 4);
   const uint32_t tt = 1u << ttl, groups = (uint32_t)kWave >> ttl;
   const uint32_t qg = lane >> ttl;
   MaxSimTileWalk w;
@@ -79,27 +74,12 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_batch_kernel(con
           for (int k = 0; k < kQB; ++k) {
             const float b = __shfl(best[k], (int)(h << ttl), kWave);
             const int f = __shfl(bad[k] ? 1 : 0, (int)(h << ttl), kWave);
-            if (st || (uint32_t)k >= nlive) continue;
-            if (f) {
-              st = kErrOverflow;
-              continue;
-            }
-            tot += b;
-            if (!finite_f32(tot)) st = kErrScoreOverflow;
+            if ((uint32_t)k < nlive) add_query_max(b, f != 0, tot, st);
           }
         }
         if (!(ds.info & kMaxSimBatchLast) || lane != 0) continue;
         const size_t at = (size_t)ds.set * a.key_stride + i;
-        if (st) {
-          a.keys[at] = kEmptyKey;
-          atomicMin(a.first_error + ds.set, ((unsigned long long)i << 8) | (unsigned)st);
-        } else {
-          a.keys[at] = ((uint64_t)~orderable(tot) << 32) | doc_rank[i];  // descending score, then id
-          Payload p;
-          p.row = i;
-          p.raw = tot;
-          a.pay[at] = p;
-        }
+        write_document(a.keys + at, a.pay + at, a.first_error + ds.set, i, doc_rank + i, tot, st);
       }
     }
   }
@@ -115,16 +95,6 @@ hipError_t launch_t(const MaxSimBatchArgs &a, const MaxSimResidentPlan &p, uint3
   return hipGetLastError();
 }
 
-template <int OP>
-hipError_t launch_ordered(const MaxSimBatchArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s) {
-  switch (a.order) {
-    case 0: return launch_t<OP, 0>(a, p, blocks, s);
-    case 1: return launch_t<OP, 1>(a, p, blocks, s);
-    case 2: return launch_t<OP, 2>(a, p, blocks, s);
-    default: return launch_t<OP, 3>(a, p, blocks, s);
-  }
-}
-
 }  // namespace
 
 }  // namespace dev
@@ -134,16 +104,9 @@ hipError_t launch_maxsim_batch(const MaxSimBatchArgs &a, const MaxSimResidentPla
   if (a.ngroups == 0 || a.ngroups > 65535 || blocks == 0 || a.max_ndesc == 0 || a.q_stride != p.q_stride ||
       maxsim_resident_lds_bytes(a.max_ndesc * kQB, a.q_stride, p) > kResidentLds)
     return hipErrorInvalidValue;
-  switch (a.metric) {
-    case M_COS: return launch_t<MS_COS, 0>(a, p, blocks, s);
-    case M_IP:
-    case M_NIP: return launch_ordered<OP_DOT>(a, p, blocks, s);
-    case M_L2:
-    case M_L2SQ: return launch_ordered<OP_L2>(a, p, blocks, s);
-    case M_L1: return launch_ordered<OP_L1>(a, p, blocks, s);
-    case M_LINF: return launch_ordered<OP_LINF>(a, p, blocks, s);
-    default: return hipErrorInvalidValue;  // (float Hamming / Jaccard: the single-set path)
-  }
+  // (no counts: float Hamming / Jaccard take the single-set path)
+  return dispatch_pair<kPairF32 | kPairCos>(a.metric, a.order,
+                                            [&](auto op, auto order) { return launch_t<op(), order()>(a, p, blocks, s); });
 }
 
 }  // namespace vt

@@ -1,56 +1,52 @@
-// vt_maxsim_pair.cuh -- what K9r (vt_maxsim_resident.hip) and K9rb (vt_maxsim_batch.hip) share: one wave's pass over one
-// document of a resident store for the eight query vectors of each of its lanes.  A lane is (row of the tile, group of
+// vt_maxsim_pair.cuh -- what is MaxSim's own around the pair arithmetic of vt_pair.cuh: the three steps K9 (vt_maxsim.hip),
+// K9r (vt_maxsim_resident.hip) and K9rb (vt_maxsim_batch.hip) share, and one wave's pass over one document of a resident
+// store for the eight query vectors of each of its lanes (K9r, K9rb).  In the pass a lane is (row of the tile, group of
 // eight query vectors); the document's rows come through the wave's LDS tile, `tt` at a time, and every (query vector,
-// document vector) pair is one lane's own chain in the reference's order (K9's arithmetic, vt_maxsim.hip).  The two
-// kernels differ only in where a lane's eight query vectors come from and in what they do with the maxima.
+// document vector) pair is one lane's own chain.  K9r and K9rb differ only in where a lane's eight query vectors come
+// from and in what they do with the maxima.
 #pragma once
-#include "vt_scan.cuh"
+#include "vt_pair.cuh"
 
 namespace vt {
 namespace dev {
 
 namespace {
 
-constexpr int kQB = 8;                       // query vectors per lane pass (as in K9)
 constexpr size_t kResidentLds = 128 * 1024;  // LDS of a block: the query panel and four tiles
-enum { MS_COS = 6, MS_COUNT = 7 };           // beside OP_DOT / OP_L2 / OP_L1 / OP_LINF
 
-// compute() (distances.rs:42-68) after the f32 chain, and similarity_value (distances.rs:122-128): K9's, word for word
-template <int OP>
-__device__ __forceinline__ float finish_raw(int metric, float acc, const float *q, const float *x, uint32_t d) {
-  float raw = acc;
-  if (metric == M_NIP) raw = -acc;
-  else if (metric == M_L2) raw = finite_f32(acc) ? __builtin_sqrtf(acc) : acc;
-  if (!finite_f32(raw)) raw = recover_overflow(metric, q, x, d);
-  return raw;
-}
-__device__ __forceinline__ float similarity(int metric, float raw) {
-  if (metric == M_COS || metric == M_IP) return raw;
-  if (metric == M_NIP) return -raw;
-  return 1.0f / (1.0f + raw);
+// The block's query panel into LDS: n4 16-byte units from Q, then the barrier (K9r, K9rb; K9 says why it keeps its own).
+__device__ __forceinline__ void stage_query_panel(float *qs, const float *Q, uint32_t n4) {
+  const f32x4 *src = reinterpret_cast<const f32x4 *>(Q);
+  for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) reinterpret_cast<f32x4 *>(qs)[i] = src[i];
+  __syncthreads();
 }
 
-// One pair, one lane, outside the f32 families (K12; K9 and the pass below run the same steps eight query vectors wide):
-// cosine() (distances.rs:160-177) over the two vectors' f64 norms -- fma(q, x, acc) == acc + q*x, a product of two f32 is
-// exact in f64; NaN: "metric overflow" --
-__device__ __forceinline__ float pair_cosine_raw(const float *q, const float *x, uint32_t d, double qn, double xn) {
-  double dot = 0.0;
-  for (uint32_t e = 0; e < d; ++e) dot = __builtin_fma((double)q[e], (double)x[e], dot);
-  if (qn == 0.0 || xn == 0.0) return 0.0f;
-  const double sim = dot / (qn * xn);
-  return isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
-}
-// and hamming() / jaccard() (distances.rs:319-347) over truthiness: integer counts, exact for any d
-__device__ __forceinline__ float pair_count_raw(int metric, const float *q, const float *x, uint32_t d) {
-  uint32_t ham = 0, inter = 0, uni = 0;
-  for (uint32_t e = 0; e < d; ++e) {
-    const bool ql = q[e] != 0.0f, xr = x[e] != 0.0f;
-    ham += ql != xr;
-    inter += ql && xr;
-    uni += ql || xr;
+// One step of the sum over query vectors -- sequential, in query order -- with the reference's error at the first query
+// vector that has one: `best` is the vector's maximum over the document, `bad` a failed pair among them (wave-uniform).
+__device__ __forceinline__ void add_query_max(float best, bool bad, float &tot, int &st) {
+  if (st) return;
+  if (bad) {
+    st = kErrOverflow;
+    return;
   }
-  if (metric == M_HAM) return (float)ham;
-  return uni == 0 ? 0.0f : 1.0f - (float)inter / (float)uni;
+  tot += best;
+  if (!finite_f32(tot)) st = kErrScoreOverflow;
+}
+
+// A finished document, by one lane: key and payload {row, score}, or kEmptyKey and (row << 8 | status) into *first_error
+// (atomicMin: the earliest document wins).
+__device__ __forceinline__ void write_document(uint64_t *key, Payload *pay, unsigned long long *first_error, uint32_t row,
+                                               const uint32_t *id_rank, float tot, int st) {
+  if (st) {
+    *key = kEmptyKey;
+    atomicMin(first_error, ((unsigned long long)row << 8) | (unsigned)st);
+  } else {
+    *key = ((uint64_t)~orderable(tot) << 32) | *id_rank;  // descending score, then id
+    Payload p;
+    p.row = row;
+    p.raw = tot;
+    *pay = p;
+  }
 }
 
 // A wave's view of the slab and of its LDS tile: wave-uniform but for the lane's own place in the staging walk.
@@ -76,7 +72,7 @@ __device__ __forceinline__ void maxsim_pass(const MaxSimTileWalk &w, uint32_t t0
   float *tile = w.tile;
   const uint32_t tok = lane & (tt - 1);
   const int metric = w.metric;
-  const uint32_t d = w.d, cfull = d / 8;
+  const uint32_t d = w.d;
   // the staging walk: 16-byte unit u of a tile is (row u / rs4, column u % rs4); a lane takes units lane, lane + 64, ...
   const uint32_t rs4 = (uint32_t)w.stride / 4, ld4 = ld / 4;
   const uint32_t row_first = lane / rs4, col_first = lane % rs4, row_step = kWave / rs4, col_step = kWave % rs4;
@@ -106,50 +102,14 @@ __device__ __forceinline__ void maxsim_pass(const MaxSimTileWalk &w, uint32_t t0
     const bool live = tok < cnt && qlive;  // (the others compute row 0 of the tile and drop it)
     const float *x = tile + (size_t)(tok < cnt ? tok : 0) * ld;
     float raw[kQB];
-    if (OP == MS_COS) {
-      // distances.rs:160-185 cosine(): fma(q, t, acc) == acc + q*t (a product of two f32 is exact in f64)
+    if constexpr (OP == PAIR_COS) {
       double dot[kQB];
-#pragma unroll
-      for (int k = 0; k < kQB; ++k) dot[k] = 0.0;
-      for (uint32_t e = 0; e < d; ++e) {
-        const double xv = (double)x[e];
-#pragma unroll
-        for (int k = 0; k < kQB; ++k) dot[k] = __builtin_fma((double)qk[k][e], xv, dot[k]);
-      }
+      cosine_dots(qk, x, d, dot);
       const double rn = w.tnorm[t0 + j0 + (tok < cnt ? tok : 0)];
 #pragma unroll
-      for (int k = 0; k < kQB; ++k) {
-        const double ln = qnorm[qi[k]];
-        raw[k] = 0.0f;
-        if (!(ln == 0.0 || rn == 0.0)) {
-          const double sim = dot[k] / (ln * rn);
-          raw[k] = isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
-        }
-      }
+      for (int k = 0; k < kQB; ++k) raw[k] = cosine_raw(dot[k], qnorm[qi[k]], rn);
     } else {
-      float acc[kQB];
-#pragma unroll
-      for (int k = 0; k < kQB; ++k) acc[k] = 0.0f;
-      for (uint32_t c = 0; c < cfull; ++c) {
-        const f32x4 xa = *reinterpret_cast<const f32x4 *>(x + c * 8);
-        const f32x4 xb = *reinterpret_cast<const f32x4 *>(x + c * 8 + 4);
-#pragma unroll
-        for (int k = 0; k < kQB; ++k) {
-          const f32x4 qa = *reinterpret_cast<const f32x4 *>(qk[k] + c * 8);
-          const f32x4 qb = *reinterpret_cast<const f32x4 *>(qk[k] + c * 8 + 4);
-          const float l[8] = {elem<OP>(0, qa.x, xa.x), elem<OP>(0, qa.y, xa.y), elem<OP>(0, qa.z, xa.z),
-                              elem<OP>(0, qa.w, xa.w), elem<OP>(0, qb.x, xb.x), elem<OP>(0, qb.y, xb.y),
-                              elem<OP>(0, qb.z, xb.z), elem<OP>(0, qb.w, xb.w)};
-          acc[k] = comb<OP>(0, acc[k], chunk_sum1<OP, ORDER>(l));
-        }
-      }
-      for (uint32_t e = cfull * 8; e < d; ++e) {  // the scalar tail, one element at a time (never the row's pad)
-        const float xe = x[e];
-#pragma unroll
-        for (int k = 0; k < kQB; ++k) acc[k] = comb<OP>(0, acc[k], elem<OP>(0, qk[k][e], xe));
-      }
-#pragma unroll
-      for (int k = 0; k < kQB; ++k) raw[k] = finish_raw<OP>(metric, acc[k], qk[k], x, d);
+      f32_raws<OP, ORDER, kQB, false, false>(metric, qk, x, d, raw);
     }
 #pragma unroll
     for (int k = 0; k < kQB; ++k) {

@@ -1,6 +1,6 @@
 // vt_maxsim_resident.hip -- K9r: MaxSim over documents that stay in device memory (vt_mv, host/vt_mvstore.h) (gfx950).
 //
-// K9's arithmetic (vt_maxsim.hip: one lane computes one (query vector, document vector) pair from start to finish, so
+// K9's arithmetic (vt_pair.cuh: one lane computes one (query vector, document vector) pair from start to finish, so
 // the reference's order needs no cross-lane exchange), fed differently.  K9 lets every lane walk its own document
 // vector out of global memory, `stride * 4` bytes from its neighbour's: one load instruction touches 64 cache lines.
 // Here a wave takes one document of the slot list at a time and brings its token rows into its own LDS tile with
@@ -27,12 +27,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(
   const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t qn = a.panel_qn, qst = a.q_stride;
   float *qs = lds;
-  {
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(a.Q + (size_t)a.panel_q0 * qst);
-    const uint32_t n4 = qn * qst / 4;
-    for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) reinterpret_cast<f32x4 *>(qs)[i] = src[i];
-  }
-  __syncthreads();
+  stage_query_panel(qs, a.Q + (size_t)a.panel_q0 * qst, qn * qst / 4);
   const uint32_t tt = 1u << ttl, groups = (uint32_t)kWave >> ttl;
   const uint32_t qg = lane >> ttl;
   MaxSimTileWalk w;
@@ -71,13 +66,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(
         for (int k = 0; k < kQB; ++k) {
           const float b = __shfl(best[k], (int)(h << ttl), kWave);
           const int f = __shfl(bad[k] ? 1 : 0, (int)(h << ttl), kWave);
-          if (st || g + h * kQB + k >= qn) continue;
-          if (f) {
-            st = kErrOverflow;
-            continue;
-          }
-          tot += b;
-          if (!finite_f32(tot)) st = kErrScoreOverflow;
+          if (g + h * kQB + k < qn) add_query_max(b, f != 0, tot, st);
         }
       }
     }
@@ -87,16 +76,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void maxsim_resident_kernel(
       a.status[i] = st;
       continue;
     }
-    if (st) {
-      a.keys[i] = kEmptyKey;
-      atomicMin(a.first_error, ((unsigned long long)(a.row0 + i) << 8) | (unsigned)st);
-    } else {
-      a.keys[i] = ((uint64_t)~orderable(tot) << 32) | a.id_rank[i];  // descending score, then id
-      Payload p;
-      p.row = a.row0 + i;
-      p.raw = tot;
-      a.pay[i] = p;
-    }
+    write_document(a.keys + i, a.pay + i, a.first_error, a.row0 + i, a.id_rank + i, tot, st);
   }
 }
 
@@ -120,16 +100,6 @@ hipError_t launch_t(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t b
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a, p.tile_log2, p.ld);
   return hipGetLastError();
-}
-
-template <int OP>
-hipError_t launch_ordered(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s) {
-  switch (a.order) {
-    case 0: return launch_t<OP, 0>(a, p, blocks, s);
-    case 1: return launch_t<OP, 1>(a, p, blocks, s);
-    case 2: return launch_t<OP, 2>(a, p, blocks, s);
-    default: return launch_t<OP, 3>(a, p, blocks, s);
-  }
 }
 
 }  // namespace
@@ -165,16 +135,9 @@ size_t maxsim_resident_lds_bytes(uint32_t panel_qn, uint32_t q_stride, const Max
 
 hipError_t launch_maxsim_resident(const MaxSimArgs &a, const MaxSimResidentPlan &p, uint32_t blocks, hipStream_t s) {
   using namespace dev;
-  switch (a.metric) {
-    case M_COS: return launch_t<MS_COS, 0>(a, p, blocks, s);
-    case M_IP:
-    case M_NIP: return launch_ordered<OP_DOT>(a, p, blocks, s);
-    case M_L2:
-    case M_L2SQ: return launch_ordered<OP_L2>(a, p, blocks, s);
-    case M_L1: return launch_ordered<OP_L1>(a, p, blocks, s);
-    case M_LINF: return launch_ordered<OP_LINF>(a, p, blocks, s);
-    default: return hipErrorInvalidValue;  // (float Hamming / Jaccard: K9 over the slab)
-  }
+  // (no counts: float Hamming / Jaccard are K9's over the slab)
+  return dispatch_pair<kPairF32 | kPairCos>(a.metric, a.order,
+                                            [&](auto op, auto order) { return launch_t<op(), order()>(a, p, blocks, s); });
 }
 
 hipError_t launch_mv_compact(const float *X, const double *norms, const uint32_t *src, uint32_t rows, uint32_t stride,

@@ -7,14 +7,11 @@
 // A pair is computed in the round in which the reference first computes it, so its "metric overflow" fails the call in
 // the same round; a round that never runs computes nothing.
 //
-// Arithmetic: one lane computes one (candidate, winner) pair from start to finish, candidate on the left --
-//   * eight metrics: K9's chain, one lane wide (elem / chunk_sum1 / comb of vt_scan.cuh in the selected lane order, the
-//     scalar tail, finish_raw with recover_overflow's f64 recovery);
-//   * Hamming and Jaccard: integer counts over truthiness, as K9 counts them;
-//   * cosine: the f64 dot over the two rows' f64 norms (distances.rs:160-177), each norm computed once, in launch 0;
-// then pair_similarity's f64 value and the f64 score.  The choice is a reduction under the key (largest score, smallest
+// Arithmetic: one lane computes one (candidate, winner) pair from start to finish, candidate on the left: vt_pair.cuh's
+// three families, one pair wide, cosine over the two rows' f64 norms, each computed once, in launch 0; then
+// pair_similarity's f64 value and the f64 score.  The choice is a reduction under the key (largest score, smallest
 // candidate): Enum.max_by keeps the first maximum, and the remaining candidates keep their list order.
-#include "vt_maxsim_pair.cuh"
+#include "vt_pair.cuh"
 
 namespace vt {
 namespace dev {
@@ -24,26 +21,22 @@ namespace {
 constexpr int kMmrThreads = 256;
 constexpr uint32_t kMmrHeadBytes = 80;  // the waves' reduction slots (4 x 16) and the round's {winner, failed}; a multiple of 16
 
-// compute(metric, q, x) (distances.rs:42-68; cosine: distances.rs:160-177 over the norms qn / xn).  NaN: "metric overflow".
+// compute(metric, q, x) (distances.rs:42-68; cosine over the norms qn / xn): vt_pair.cuh's, one pair wide.
+// NaN: "metric overflow".
 template <int OP, int ORDER>
 __device__ __forceinline__ float pair_raw(int metric, const float *q, const float *x, uint32_t d, double qn, double xn) {
-  if (OP == MS_COS) return pair_cosine_raw(q, x, d, qn, xn);   // (vt_maxsim_pair.cuh, beside finish_raw)
-  if (OP == MS_COUNT) return pair_count_raw(metric, q, x, d);
-  constexpr int FOP = OP < MS_COS ? OP : OP_DOT;  // (the f32 families only: the two above have returned)
-  float acc = 0.0f;
-  const uint32_t cfull = d / 8;
-  for (uint32_t c = 0; c < cfull; ++c) {
-    const f32x4 qa = *reinterpret_cast<const f32x4 *>(q + c * 8);
-    const f32x4 qb = *reinterpret_cast<const f32x4 *>(q + c * 8 + 4);
-    const f32x4 xa = *reinterpret_cast<const f32x4 *>(x + c * 8);
-    const f32x4 xb = *reinterpret_cast<const f32x4 *>(x + c * 8 + 4);
-    const float l[8] = {elem<FOP>(0, qa.x, xa.x), elem<FOP>(0, qa.y, xa.y), elem<FOP>(0, qa.z, xa.z),
-                        elem<FOP>(0, qa.w, xa.w), elem<FOP>(0, qb.x, xb.x), elem<FOP>(0, qb.y, xb.y),
-                        elem<FOP>(0, qb.z, xb.z), elem<FOP>(0, qb.w, xb.w)};
-    acc = comb<FOP>(0, acc, chunk_sum1<FOP, ORDER>(l));
+  const float *const qv[1] = {q};
+  float raw[1];
+  if constexpr (OP == PAIR_COS) {
+    double dot[1];
+    cosine_dots(qv, x, d, dot);
+    raw[0] = cosine_raw(dot[0], qn, xn);
+  } else if constexpr (OP == PAIR_COUNT) {
+    count_raws(metric, qv, x, d, raw);
+  } else {
+    f32_raws<OP, ORDER, 1, false, false>(metric, qv, x, d, raw);
   }
-  for (uint32_t e = cfull * 8; e < d; ++e) acc = comb<FOP>(0, acc, elem<FOP>(0, q[e], x[e]));  // the scalar tail
-  return finish_raw<FOP>(metric, acc, q, x, d);
+  return raw[0];
 }
 
 // pair_similarity (vettore_distance.ex:489-519): the f32 raw value as a double, then the metric's f64 step
@@ -131,7 +124,7 @@ __global__ __launch_bounds__(kMmrThreads) void mmr_step_kernel(const MmrArgs a, 
   double xn = 0.0;
   if (t >= 1) {
     const float *wrow = a.X + (size_t)a.rows[pr.off + winner] * a.stride;
-    if (OP == MS_COS) xn = a.norm[pr.off + winner];
+    if (OP == PAIR_COS) xn = a.norm[pr.off + winner];
     x = wrow;
     if (STAGED) {
       const uint32_t d4 = (a.d + 3) / 4;  // (a row's stride is a multiple of 4 floats: the pad is read, never used)
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(kMmrThreads) void mmr_step_kernel(const MmrArgs a, 
     double red = 0.0;  // maximum_redundancy with nothing chosen
     if (t == 0) {
       a.live[gi] = 1;
-      if (OP == MS_COS) {
+      if (OP == PAIR_COS) {
         double acc = 0.0;
         for (uint32_t e = 0; e < a.d; ++e) acc = __builtin_fma((double)q[e], (double)q[e], acc);
         a.norm[gi] = sqrt(acc);
@@ -163,7 +156,7 @@ __global__ __launch_bounds__(kMmrThreads) void mmr_step_kernel(const MmrArgs a, 
         continue;
       }
       if (!a.live[gi]) continue;
-      const float raw = pair_raw<OP, ORDER>(a.metric, q, x, a.d, OP == MS_COS ? a.norm[gi] : 0.0, xn);
+      const float raw = pair_raw<OP, ORDER>(a.metric, q, x, a.d, OP == PAIR_COS ? a.norm[gi] : 0.0, xn);
       if (raw != raw) {
         mine.failed = i < mine.failed ? i : mine.failed;
         continue;
@@ -201,16 +194,6 @@ hipError_t launch_t(const MmrArgs &a, uint32_t t, uint32_t blocks, uint32_t npro
   return hipGetLastError();
 }
 
-template <int OP>
-hipError_t launch_ordered(const MmrArgs &a, uint32_t t, uint32_t blocks, uint32_t nprob, hipStream_t s) {
-  switch (a.order) {
-    case 0: return launch_t<OP, 0>(a, t, blocks, nprob, s);
-    case 1: return launch_t<OP, 1>(a, t, blocks, nprob, s);
-    case 2: return launch_t<OP, 2>(a, t, blocks, nprob, s);
-    default: return launch_t<OP, 3>(a, t, blocks, nprob, s);
-  }
-}
-
 }  // namespace
 
 }  // namespace dev
@@ -225,17 +208,8 @@ hipError_t launch_mmr_step(const MmrArgs &a, uint32_t t, uint32_t blocks, uint32
   if (blocks == 0 || blocks > kMmrMaxBlocks || nprob > 65535u || a.block_rows == 0 || a.block_rows > kMmrBlockRows ||
       a.lds_dim > kMmrLdsDim || (a.stride & 3u) != 0)
     return hipErrorInvalidValue;
-  switch (a.metric) {
-    case M_COS: return launch_t<MS_COS, 0>(a, t, blocks, nprob, s);
-    case M_HAM:
-    case M_JAC: return launch_t<MS_COUNT, 0>(a, t, blocks, nprob, s);
-    case M_IP:
-    case M_NIP: return launch_ordered<OP_DOT>(a, t, blocks, nprob, s);
-    case M_L2:
-    case M_L2SQ: return launch_ordered<OP_L2>(a, t, blocks, nprob, s);
-    case M_L1: return launch_ordered<OP_L1>(a, t, blocks, nprob, s);
-    default: return launch_ordered<OP_LINF>(a, t, blocks, nprob, s);
-  }
+  return dispatch_pair<kPairF32 | kPairCos | kPairCount>(
+      a.metric, a.order, [&](auto op, auto order) { return launch_t<op(), order()>(a, t, blocks, nprob, s); });
 }
 
 }  // namespace vt
