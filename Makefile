@@ -28,7 +28,7 @@ DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_bat
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -97,6 +97,9 @@ $(LIBDIR)/vt_sketch_batch.o: $(CSRC)/host/vt_sketchbatch.h
 # (the one-lane pair arithmetic of K9, K9r, K9rb, K11 and K12; what the three MaxSim kernels share beside it)
 $(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_pair.cuh
 $(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o: $(CSRC)/vt_maxsim_pair.cuh
+
+# (the row-panel walk of K6b, K6bm and K1p and the group epilogue of the latter two)
+$(LIBDIR)/vt_cosine.o $(LIBDIR)/vt_prefix_multi.o: $(CSRC)/vt_panel.cuh
 
 HOSTHDR := $(wildcard $(CSRC)/host/*.h)
 $(LIBDIR)/vt_index.o: $(CSRC)/vt_index.cpp $(HOSTHDR) $(CSRC)/vt_device.h $(CSRC)/vt_env.h include/vettore_flat.h
@@ -204,6 +207,16 @@ $(LIBDIR)/hnsw_compact_probe.o: tests/hnsw_compact_probe.cpp $(CSRC)/vt_device.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_hnsw_compact_probe.so: $(LIBDIR)/vt_hnsw.o $(LIBDIR)/hnsw_compact_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# The row-panel kernels behind a probe (tests/panel_probe.cpp; tests/test_gpu_panel_kernels.py loads it): K1p, K6bm and K6b
+# launched one at a time on a test's arrays -- sample cells, tile maxima, lists, counts and the status word read back.
+# vt_cosine.o, vt_prefix_multi.o and the probe, nothing else of the library.  Test infrastructure, as above.
+$(LIBDIR)/panel_probe.o: tests/panel_probe.cpp $(CSRC)/vt_device.h $(CSRC)/vt_env.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_panel_probe.so: $(LIBDIR)/vt_cosine.o $(LIBDIR)/vt_prefix_multi.o $(LIBDIR)/panel_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

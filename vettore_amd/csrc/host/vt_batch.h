@@ -751,8 +751,8 @@ int batch_ready(Shard *ix, Ctx &c, const float *queries, size_t nq, size_t d, si
   if (!by_pattern && left.size() >= 2 && sweep_group_applies(ix, limit)) {
     const size_t stage = (size_t)ix->dim;
     std::vector<std::vector<size_t>> sweeps;
-    for (size_t g0 = 0; g0 + 2 <= left.size(); g0 += vt::kPrefixMultiMax)
-      sweeps.emplace_back(left.begin() + g0, left.begin() + std::min(left.size(), g0 + vt::kPrefixMultiMax));
+    for (size_t g0 = 0; g0 + 2 <= left.size(); g0 += vt::kGroupSweepMax)
+      sweeps.emplace_back(left.begin() + g0, left.begin() + std::min(left.size(), g0 + vt::kGroupSweepMax));
     // (a group with an overflow somewhere comes back undone: its queries go on below, each reporting its own; the
     // groups alternate between two contexts, funnel_groups)
     VT_TRY(funnel_groups(ix, c, queries, sweeps, &stage, 1, limit, limit, out, done, true));

@@ -72,7 +72,7 @@ int funnel_ready(Shard *ix, Ctx &c, const float *query, size_t n, const size_t *
 
 
 // ---- several funnel searches per sweep of the prefixes (cosine collections) ------------------
-// collection.ex:245-260 for up to kCosineMultiMax queries at once, the way quantized searches share
+// collection.ex:245-260 for up to kGroupSweepMax queries at once, the way quantized searches share
 // a sweep of the sign bits: stage 1 -- the f64 cosine over the first stages[0] coordinates of
 // EVERY row, 0.8 ms of a 0.88-ms funnel search at N = 10 M -- reads the prefixes once for the whole
 // group (cosine_scan_multi_kernel).  The scores are exact, so a threshold needs no margin: tau_q =
@@ -137,15 +137,14 @@ int funnel_group_queue(Shard *ix, Ctx &c, FunnelGroupRun &run, const float *quer
   // one upload: full queries [nq][ld] (f32), their prefixes as f64 [8][ldq] (what stage 1 reads, through
   // the scalar cache; ld and ldq are multiples of 64, so the block stays 32-byte aligned), list lengths
   const bool cosine = ix->metric == VT_COSINE;
-  static_assert(vt::kPrefixMultiMax == vt::kCosineMultiMax, "one group size");
   // (K1p reads all eight query rows whatever nq is: the buffer always holds eight)
-  const size_t q_floats = (size_t)vt::kCosineMultiMax * ld, p_floats = (size_t)vt::kCosineMultiMax * ldq * 2;
-  const size_t up_floats = q_floats + p_floats + 2 * vt::kCosineMultiMax;  // (+ [8] candidates per list, [8] keys per K1 stage list)
+  const size_t q_floats = (size_t)vt::kGroupSweepMax * ld, p_floats = (size_t)vt::kGroupSweepMax * ldq * 2;
+  const size_t up_floats = q_floats + p_floats + 2 * vt::kGroupSweepMax;  // (+ [8] candidates per list, [8] keys per K1 stage list)
   VT_TRY(c.dBQ.ensure(up_floats));
   VT_TRY(c.hBQ.ensure(up_floats));
-  VT_TRY(c.dBSample.ensure((size_t)vt::kCosineMultiMax * sample_rows));
-  VT_TRY(c.dBTau.ensure(vt::kCosineMultiMax));
-  VT_TRY(c.dBCount.ensure(vt::kCosineMultiMax));
+  VT_TRY(c.dBSample.ensure((size_t)vt::kGroupSweepMax * sample_rows));
+  VT_TRY(c.dBTau.ensure(vt::kGroupSweepMax));
+  VT_TRY(c.dBCount.ensure(vt::kGroupSweepMax));
   VT_TRY(c.ensure_part_lists((size_t)nq * kListCap));
   VT_TRY(c.dStageB.ensure(nq));
   constexpr uint32_t kStageBlocks = 4;  // K1 batch mode: blocks per query over its <= 256 candidates (8-row tiles)
@@ -168,13 +167,13 @@ int funnel_group_queue(Shard *ix, Ctx &c, FunnelGroupRun &run, const float *quer
   float *hTau = reinterpret_cast<float *>(c.hBig.p + ent_bytes + 96);             // [8]: the thresholds themselves
   uint64_t *hLastKey = reinterpret_cast<uint64_t *>(c.hBig.p + ent_bytes + 128);  // [8]: key of each list's k1-th (last kept) row
   std::memset(c.hBQ.p, 0, up_floats * sizeof(float));
-  vt::CosineScanMultiArgs a{};
+  vt::GroupSweepArgs a{};
   uint32_t *hcounts = reinterpret_cast<uint32_t *>(c.hBQ.p + q_floats + p_floats);
   for (uint32_t i = 0; i < nq; ++i) {
     const float *q = queries + which[i] * d;
     std::memcpy(c.hBQ.p + (size_t)i * ld, q, (size_t)d * sizeof(float));
     hcounts[i] = k1;
-    hcounts[vt::kCosineMultiMax + i] = kStageBlocks * k1;
+    hcounts[vt::kGroupSweepMax + i] = kStageBlocks * k1;
     if (!cosine) continue;
     double *qd = reinterpret_cast<double *>(c.hBQ.p + q_floats) + (size_t)i * ldq;
     double qq = 0.0;  // f64_dot(q, q) over the prefix (distances.rs:179-185)
@@ -186,56 +185,47 @@ int funnel_group_queue(Shard *ix, Ctx &c, FunnelGroupRun &run, const float *quer
   }
   VT_HIP(hipMemcpyAsync(c.dBQ.p, c.hBQ.p, up_floats * sizeof(float), hipMemcpyHostToDevice, c.stream));
   const uint32_t *dcounts = reinterpret_cast<const uint32_t *>(c.dBQ.p + q_floats + p_floats);
-  const uint32_t *dlens = dcounts + vt::kCosineMultiMax;
-  VT_HIP(hipMemsetAsync(c.dBCount.p, 0, vt::kCosineMultiMax * sizeof(uint32_t), c.stream));
+  const uint32_t *dlens = dcounts + vt::kGroupSweepMax;
+  VT_HIP(hipMemsetAsync(c.dBCount.p, 0, vt::kGroupSweepMax * sizeof(uint32_t), c.stream));
   a.X = ix->dX;
   a.stride = ix->ld;
+  a.Q = c.dBQ.p;
+  a.q_stride = ld;
   a.Qd = reinterpret_cast<const double *>(c.dBQ.p + q_floats);
   a.id_rank = ix->dRank.p;
   a.n = n;
   a.d = d1;
   a.nq = nq;
+  a.metric = ix->metric;
+  a.order = ix->order;
   a.status = c.dStatus.p;
-  vt::PrefixMultiArgs pa{};
-  pa.X = ix->dX;
-  pa.stride = ix->ld;
-  pa.Q = c.dBQ.p;
-  pa.q_stride = ld;
-  pa.id_rank = ix->dRank.p;
-  pa.n = n;
-  pa.d = d1;
-  pa.nq = nq;
-  pa.metric = ix->metric;
-  pa.order = ix->order;
-  pa.status = c.dStatus.p;
-  const size_t lds = cosine ? vt::cosine_scan_multi_lds_bytes() : vt::prefix_multi_lds_bytes();
+  const size_t lds = vt::group_sweep_lds_bytes();
+  const int per_cu = vt::group_sweep_blocks_per_cu(ix->metric);
   // pass 0: the sample's scores -> one threshold per query
-  a.sample = pa.sample = c.dBSample.p;
-  a.sample_stride = pa.sample_stride = sstride;
-  a.sample_rows = pa.sample_rows = by_maxima ? stiles : sample_rows;
-  a.sample_maxima = pa.sample_maxima = by_maxima ? 1u : 0u;
-  if (cosine) VT_HIP(vt::launch_cosine_scan_multi(a, c.grid_for(stiles, lds), c.stream));
-  else VT_HIP(vt::launch_prefix_multi(pa, c.grid_for(stiles, lds, vt::prefix_multi_blocks_per_cu()), c.stream));
-  if (by_maxima) VT_HIP(vt::launch_sample_tau_groups(c.dBSample.p, stiles, vt::kCosineMultiMax, nq, rank, c.dBTau.p, c.stream));
-  else VT_HIP(vt::launch_sample_tau(c.dBSample.p, sample_rows, vt::kCosineMultiMax, nq, rank, c.dBTau.p, c.stream));
+  a.sample = c.dBSample.p;
+  a.sample_stride = sstride;
+  a.sample_rows = by_maxima ? stiles : sample_rows;
+  a.sample_maxima = by_maxima ? 1u : 0u;
+  VT_HIP(vt::launch_group_sweep(a, c.grid_for(stiles, lds, per_cu), c.stream));
+  if (by_maxima) VT_HIP(vt::launch_sample_tau_groups(c.dBSample.p, stiles, vt::kGroupSweepMax, nq, rank, c.dBTau.p, c.stream));
+  else VT_HIP(vt::launch_sample_tau(c.dBSample.p, sample_rows, vt::kGroupSweepMax, nq, rank, c.dBTau.p, c.stream));
   // pass 1: every row's prefix once; (query, row) pairs at or above the thresholds into the lists
-  a.sample = pa.sample = nullptr;
-  a.sample_maxima = pa.sample_maxima = 0;
-  a.tau = pa.tau = c.dBTau.p;
-  a.cand_keys = pa.cand_keys = c.dPartKeys.p;
-  a.cand_pay = pa.cand_pay = c.dPartPay.p;
-  a.cand_count = pa.cand_count = c.dBCount.p;
-  a.cand_cap = pa.cand_cap = kListCap;
+  a.sample = nullptr;
+  a.sample_maxima = 0;
+  a.tau = c.dBTau.p;
+  a.cand_keys = c.dPartKeys.p;
+  a.cand_pay = c.dPartPay.p;
+  a.cand_count = c.dBCount.p;
+  a.cand_cap = kListCap;
   VT_TRY(c.mark_begin());
-  if (cosine) VT_HIP(vt::launch_cosine_scan_multi(a, c.grid_for(ntiles, lds), c.stream));
-  else VT_HIP(vt::launch_prefix_multi(pa, c.grid_for(ntiles, lds, vt::prefix_multi_blocks_per_cu()), c.stream));
+  VT_HIP(vt::launch_group_sweep(a, c.grid_for(ntiles, lds, per_cu), c.stream));
   VT_TRY(c.mark_end());
-  VT_HIP(hipMemcpyAsync(hListCount, c.dBCount.p, vt::kCosineMultiMax * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+  VT_HIP(hipMemcpyAsync(hListCount, c.dBCount.p, vt::kGroupSweepMax * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
   VT_HIP(vt::launch_select_lists(c.dPartKeys.p, c.dPartPay.p, nq, kListCap, c.dBCount.p, k1, c.dStageB.p,
                                  (uint32_t)sizeof(ResultBlock), c.stream, /*sixteen blocks per list=*/true));
   // what the acceptance test below looks at: the thresholds and the key of every list's last kept row
   // (copied out here: later stages reuse the blocks)
-  VT_HIP(hipMemcpyAsync(hTau, c.dBTau.p, vt::kCosineMultiMax * sizeof(float), hipMemcpyDeviceToHost, c.stream));
+  VT_HIP(hipMemcpyAsync(hTau, c.dBTau.p, vt::kGroupSweepMax * sizeof(float), hipMemcpyDeviceToHost, c.stream));
   VT_HIP(hipMemcpy2DAsync(hLastKey, sizeof(uint64_t), &c.dStageB.p->e[k1 - 1].key, sizeof(ResultBlock), sizeof(uint64_t), nq,
                           hipMemcpyDeviceToHost, c.stream));
   // later stages re-score the same candidates on a longer prefix (collection.ex:674-691), then
@@ -419,9 +409,9 @@ int funnel_batch_ready(Shard *ix, Ctx &c, const float *queries, size_t nq, size_
   std::vector<char> done(nq, 0);
   if (nq >= 2 && funnel_group_applies(ix, stages, nstages, candidates, limit)) {
     std::vector<std::vector<size_t>> groups;
-    for (size_t g0 = 0; g0 < nq; g0 += vt::kCosineMultiMax) {
+    for (size_t g0 = 0; g0 < nq; g0 += vt::kGroupSweepMax) {
       std::vector<size_t> which;
-      for (size_t i = g0; i < std::min<size_t>(nq, g0 + vt::kCosineMultiMax); ++i) which.push_back(i);
+      for (size_t i = g0; i < std::min<size_t>(nq, g0 + vt::kGroupSweepMax); ++i) which.push_back(i);
       if (which.size() < 2) break;
       groups.push_back(std::move(which));
     }

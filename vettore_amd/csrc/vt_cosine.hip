@@ -1,7 +1,7 @@
 // vt_cosine.hip -- the exact f64 cosine of vector_top_k (gfx950): K6 rerank of a candidate list, K6b scan of a
 // prefix of every row with fused top-k, K6b for eight queries a sweep; and K7 normalisation.  Each kernel is
 // followed by its LDS formula and its launcher.
-#include "vt_scan.cuh"
+#include "vt_panel.cuh"
 
 namespace vt {
 
@@ -124,18 +124,11 @@ __global__ __launch_bounds__(64) void cosine_rerank_kernel(const CosineRerankArg
   }
   const double qq = __shfl(acc, 0, kWave), xx = __shfl(acc, 1, kWave), qx = __shfl(acc, 2, kWave);
   if (lane != 0) return;
-  const double ln = sqrt(qq), rn = sqrt(xx);
-  float raw = 0.0f;
-  bool ok = true;
-  if (!(ln == 0.0 || rn == 0.0)) {
-    double sim = qx / (ln * rn);
-    if (!isfinite(sim)) {
-      ok = false;
-      atomicMax(a.status, kErrOverflow);
-    } else {
-      sim = sim < -1.0 ? -1.0 : (sim > 1.0 ? 1.0 : sim);
-      raw = (float)sim;
-    }
+  float raw = cosine_raw(qx, sqrt(qq), sqrt(xx));  // distances.rs:160-177
+  const bool ok = raw == raw;
+  if (!ok) {
+    atomicMax(a.status, kErrOverflow);
+    raw = 0.0f;
   }
   const uint32_t rk = a.id_rank ? a.id_rank[src] : src;
   a.out_keys[i] = ok ? (((uint64_t)orderable(1.0f - raw) << 32) | rk) : kEmptyKey;
@@ -163,109 +156,72 @@ namespace {
 
 // K6b: exact f64 cosine of a prefix of every row + fused top-k.  The reference
 // folds |x|^2 and q.x sequentially in f64, element by element, so the K1 trick
-// applies one level down: a wave owns 64 rows and walks them in panels of 64
-// floats; a panel is read with coalesced 16-B loads (4 rows x 256 B per wave
-// instruction), parked in a wave-private LDS panel S[64][68] (stride 4*odd), and
-// lane r then runs row r's two f64 chains over it -- 64 chains in parallel.
-// (r05: PANEL = 32 -- 8 wave loads of 8 rows x 128 B per panel, half the prefetch registers -- is what K1p, K6bm and this
-// kernel run on, DESIGN_APPENDIX A.15; r06: the 64-float builds of r04 have left the library)
-constexpr int kCsRows = 64, kCsPanelFloats = 32;
-
+// applies one level down: a wave owns 64 rows and walks them in panels of 32
+// floats (PanelWalk, vt_panel.cuh), and lane r runs row r's two f64 chains over
+// the parked panel -- 64 chains in parallel.
 template <int CAP, int PANEL>
 __global__ __launch_bounds__(kWavesPerBlock *kWave) void cosine_scan_kernel(const CosineScanArgs a) {
-  constexpr int kCsPanel = PANEL, kCsStride = PANEL + 4;
-  constexpr int kLanesPerRow = PANEL / 4, kRowsPerLoad = 64 / kLanesPerRow, kLoads = kCsRows / kRowsPerLoad;
   extern __shared__ __align__(16) float cs_lds[];
   const int lane = threadIdx.x & (kWave - 1);
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t ldq = padded_dim(a.d);
   float *qs = cs_lds;
-  float *S = cs_lds + ldq + wib * (kCsRows * kCsStride);
-  unsigned char *tkbuf = reinterpret_cast<unsigned char *>(cs_lds + ldq + kWavesPerBlock * (kCsRows * kCsStride)) +
-                         wib * WaveTopK<CAP>::lds_bytes();
+  unsigned char *tkbuf = reinterpret_cast<unsigned char *>(cs_lds + ldq + panel_lds_floats()) + wib * WaveTopK<CAP>::lds_bytes();
   for (uint32_t i = threadIdx.x; i < ldq; i += blockDim.x) qs[i] = a.q[i];
   __syncthreads();
 
-  const uint32_t total_waves = gridDim.x * kWavesPerBlock;
-  const uint32_t wave_global = blockIdx.x * kWavesPerBlock + wib;
-  const uint32_t ntiles = (a.n + kCsRows - 1) / kCsRows;
-  const uint32_t npanel = (a.d + kCsPanel - 1) / kCsPanel;
   const double ln = sqrt(a.qq);
 
   WaveTopK<CAP> tk;
   tk.init(tkbuf, a.k);
-  // The panel after the one being summed is already on its way: its 16 loads are
-  // issued as soon as the current panel has been parked in LDS, so a wave keeps
-  // 16 KiB in flight through its f64 chain phase (without this the kernel sat at
-  // 4.3 TB/s of prefix bytes; a plain strided read of the same bytes does 6.5).
-  f32x4 v[kLoads];
-  const int lrow = lane / kLanesPerRow, lcol = (lane % kLanesPerRow) * 4;  // this lane's row within a load, its column
-  auto issue = [&](uint32_t t, uint32_t p) {
-#pragma unroll
-    for (int s = 0; s < kLoads; ++s) {
-      uint32_t r = t * kCsRows + kRowsPerLoad * s + lrow;
-      r = r < a.n ? r : a.n - 1;
-      v[s] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(a.X + (size_t)r * a.stride + p * kCsPanel + lcol));
-    }
-  };
-  if (wave_global < ntiles) issue(wave_global, 0);
-  for (uint32_t t = wave_global; t < ntiles; t += total_waves) {
-    const uint32_t grow = t * kCsRows + lane;
-    const bool valid_row = grow < a.n;
-    const uint32_t my_rank = (valid_row && a.id_rank) ? a.id_rank[grow] : grow;
-    double xx = 0.0, qx = 0.0;
-    for (uint32_t p = 0; p < npanel; ++p) {
-#pragma unroll
-      for (int s = 0; s < kLoads; ++s) *reinterpret_cast<f32x4 *>(S + (kRowsPerLoad * s + lrow) * kCsStride + lcol) = v[s];
-      wave_lds_fence();
-      if (p + 1 < npanel) issue(t, p + 1);
-      else if (t + total_waves < ntiles) issue(t + total_waves, 0);
-      const uint32_t cnt = a.d - p * kCsPanel < (uint32_t)kCsPanel ? a.d - p * kCsPanel : (uint32_t)kCsPanel;
-      const float *Sr = S + lane * kCsStride;
-      const float *qp = qs + p * kCsPanel;
-      // fma(x, y, acc) == acc + x*y here: the product of two f32 is exact in f64
-      uint32_t j = 0;
-      for (; j + 4 <= cnt; j += 4) {
-        const f32x4 xv = *reinterpret_cast<const f32x4 *>(Sr + j);
-        const f32x4 qv = *reinterpret_cast<const f32x4 *>(qp + j);
-        xx = __builtin_fma((double)xv.x, (double)xv.x, xx);
-        qx = __builtin_fma((double)qv.x, (double)xv.x, qx);
-        xx = __builtin_fma((double)xv.y, (double)xv.y, xx);
-        qx = __builtin_fma((double)qv.y, (double)xv.y, qx);
-        xx = __builtin_fma((double)xv.z, (double)xv.z, xx);
-        qx = __builtin_fma((double)qv.z, (double)xv.z, qx);
-        xx = __builtin_fma((double)xv.w, (double)xv.w, xx);
-        qx = __builtin_fma((double)qv.w, (double)xv.w, qx);
-      }
-      for (; j < cnt; ++j) {
-        const double xd = (double)Sr[j];
-        xx = __builtin_fma(xd, xd, xx);
-        qx = __builtin_fma((double)qp[j], xd, qx);
-      }
-      wave_lds_fence();
-    }
-    // distances.rs:160-177
-    const double rn = sqrt(xx);
-    float raw = 0.0f;
-    bool valid = valid_row;
-    if (!(ln == 0.0 || rn == 0.0)) {
-      double sim = qx / (ln * rn);
-      if (!isfinite(sim)) {
-        if (valid) atomicMax(a.status, kErrOverflow);
-        valid = false;
-      } else {
-        sim = sim < -1.0 ? -1.0 : (sim > 1.0 ? 1.0 : sim);
-        raw = (float)sim;
-      }
-    }
-    const uint64_t key = ((uint64_t)orderable(1.0f - raw) << 32) | my_rank;
-    if (a.has_lo) valid = valid && key > a.lo_key;
-    if (a.key_out) {
-      if (valid_row) a.key_out[grow] = valid ? key : kEmptyKey;
-    } else {
-      tk.offer(valid, key, grow, raw, lane);
-    }
-  }
+  uint32_t my_rank;
+  double xx, qx;
+  walk_panels<PANEL>(
+      a, 1u, cs_lds + ldq, lane, wib,
+      [&](uint32_t, uint32_t grow) {
+        my_rank = (grow < a.n && a.id_rank) ? a.id_rank[grow] : grow;
+        xx = 0.0, qx = 0.0;
+      },
+      [&](uint32_t p, const float *Sr) {
+        const uint32_t cnt = a.d - p * PANEL < (uint32_t)PANEL ? a.d - p * PANEL : (uint32_t)PANEL;
+        const float *qp = qs + p * PANEL;
+        // fma(x, y, acc) == acc + x*y here: the product of two f32 is exact in f64
+        uint32_t j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+          const f32x4 xv = *reinterpret_cast<const f32x4 *>(Sr + j);
+          const f32x4 qv = *reinterpret_cast<const f32x4 *>(qp + j);
+          xx = __builtin_fma((double)xv.x, (double)xv.x, xx);
+          qx = __builtin_fma((double)qv.x, (double)xv.x, qx);
+          xx = __builtin_fma((double)xv.y, (double)xv.y, xx);
+          qx = __builtin_fma((double)qv.y, (double)xv.y, qx);
+          xx = __builtin_fma((double)xv.z, (double)xv.z, xx);
+          qx = __builtin_fma((double)qv.z, (double)xv.z, qx);
+          xx = __builtin_fma((double)xv.w, (double)xv.w, xx);
+          qx = __builtin_fma((double)qv.w, (double)xv.w, qx);
+        }
+        for (; j < cnt; ++j) {
+          const double xd = (double)Sr[j];
+          xx = __builtin_fma(xd, xd, xx);
+          qx = __builtin_fma((double)qp[j], xd, qx);
+        }
+      },
+      [&](uint32_t, uint32_t grow) {
+        const bool valid_row = grow < a.n;
+        float raw = cosine_raw(qx, ln, sqrt(xx));  // distances.rs:160-177
+        bool valid = valid_row;
+        if (raw != raw) {
+          if (valid) atomicMax(a.status, kErrOverflow);
+          valid = false;
+          raw = 0.0f;
+        }
+        const uint64_t key = ((uint64_t)orderable(1.0f - raw) << 32) | my_rank;
+        if (a.has_lo) valid = valid && key > a.lo_key;
+        if (a.key_out) {
+          if (valid_row) a.key_out[grow] = valid ? key : kEmptyKey;
+        } else {
+          tk.offer(valid, key, grow, raw, lane);
+        }
+      });
   if (a.key_out) return;
   __shared__ uint32_t s_counts[kWavesPerBlock];
   tk.merge_block(wib, kWavesPerBlock, s_counts, lane);
@@ -276,8 +232,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void cosine_scan_kernel(cons
 
 size_t cosine_scan_lds_bytes(uint32_t d, uint32_t k) {
   const size_t buf = k <= (uint32_t)kSmallK ? WaveTopK<kCapSmall>::lds_bytes() : WaveTopK<kCapLarge>::lds_bytes();
-  const size_t bytes = ((size_t)padded_dim(d) + (size_t)kWavesPerBlock * kCsRows * (kCsPanelFloats + 4)) * sizeof(float) +
-                       kWavesPerBlock * buf;
+  const size_t bytes = ((size_t)padded_dim(d) + panel_lds_floats()) * sizeof(float) + kWavesPerBlock * buf;
   return bytes <= kMaxLds ? bytes : 0;
 }
 
@@ -290,173 +245,102 @@ hipError_t launch_cosine_scan(const CosineScanArgs &a, uint32_t blocks, hipStrea
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
     return hipGetLastError();
   };
-  if (a.k <= (uint32_t)kSmallK) return go(cosine_scan_kernel<kCapSmall, kCsPanelFloats>);
-  return go(cosine_scan_kernel<kCapLarge, kCsPanelFloats>);
+  if (a.k <= (uint32_t)kSmallK) return go(cosine_scan_kernel<kCapSmall, kPanelFloats>);
+  return go(cosine_scan_kernel<kCapLarge, kPanelFloats>);
 }
 
-// K6b, several queries per sweep (CosineScanMultiArgs in vt_device.h).  The row walk is
-// cosine_scan_kernel's: a wave parks a 64-row x 64-float panel in LDS, the next panel's 16 loads
-// already on their way, then lane r walks row r -- one x.x chain and nq q.x chains, each the
-// single kernel's sequence of f64 FMAs.  The queries are wave-uniform: they come as f64 through
+// K6b, several queries per sweep (GroupSweepArgs in vt_device.h).  The row walk is
+// cosine_scan_kernel's (PanelWalk, vt_panel.cuh): lane r walks row r of the parked panel -- one x.x chain and nq q.x
+// chains, each the single kernel's sequence of f64 FMAs.  The queries are wave-uniform: they come as f64 through
 // the scalar cache (constant address space => s_load) and enter the FMAs as SGPR operands -- read
 // from LDS as f32 like the single kernel's one query, eight queries cost 8 LDS reads and 32
 // conversions per 4 row elements and lane beside the 36 FMAs, and the pass was LDS / VALU bound
 // at 3.5 TB/s of prefix bytes.
-// PANEL (r05): K1p's finding carried over -- the same walk on 64 x 32-float panels (8 wave loads of 8 rows x 128 B, half
-// the prefetch registers) at the same two blocks per CU; VT_CS_PANEL=64 is the r04 form (A/B, DESIGN_APPENDIX A.15).
 template <int PANEL>
-__global__ __launch_bounds__(kWavesPerBlock *kWave) void cosine_scan_multi_kernel(const CosineScanMultiArgs a) {
-  constexpr int kCsPanel = PANEL, kCsStride = PANEL + 4;  // (shadow the single kernel's 64 / 68)
-  constexpr int kLanesPerRow = PANEL / 4, kRowsPerLoad = 64 / kLanesPerRow, kLoads = kCsRows / kRowsPerLoad;
+__global__ __launch_bounds__(kWavesPerBlock *kWave) void cosine_scan_multi_kernel(const GroupSweepArgs a) {
   extern __shared__ __align__(16) float csm_lds[];
   const int lane = threadIdx.x & (kWave - 1);
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t ldq = padded_dim(a.d);
   typedef const __attribute__((address_space(4))) double *cd_p;
   cd_p qd = (cd_p)(uintptr_t)a.Qd;
-  float *S = csm_lds + wib * (kCsRows * kCsStride);
   const bool dense = a.sample != nullptr;
-  const uint32_t total_waves = gridDim.x * kWavesPerBlock;
-  const uint32_t wave_global = blockIdx.x * kWavesPerBlock + wib;
-  const uint32_t ntiles_all = (a.n + kCsRows - 1) / kCsRows;
-  const uint32_t step = dense ? a.sample_stride : 1u;           // dense: every step-th tile
-  const uint32_t ntiles = (ntiles_all + step - 1) / step;        // tiles this launch walks
-  const uint32_t npanel = (a.d + kCsPanel - 1) / kCsPanel;
-  // the thresholds, once, through the scalar cache (read per tile as vector loads each brought a wait for the NEXT
-  // tile's sixteen panel loads into the epilogue: K1p's note, vt_prefix_multi.hip)
-  typedef const __attribute__((address_space(4))) float *cf_p;
-  float tauv[kCosineMultiMax];
+  const uint32_t step = dense ? a.sample_stride : 1u;  // dense: every step-th tile
+  float tauv[kGroupSweepMax];
+  group_thresholds(a, dense, tauv);
+  double xx, qx[kGroupSweepMax];
+  walk_panels<PANEL>(
+      a, step, csm_lds, lane, wib,
+      [&](uint32_t, uint32_t) {
+        xx = 0.0;
 #pragma unroll
-  for (uint32_t q = 0; q < kCosineMultiMax; ++q) tauv[q] = INFINITY;
-  if (!dense) {
-    cf_p tp = (cf_p)(uintptr_t)a.tau;
+        for (uint32_t q = 0; q < kGroupSweepMax; ++q) qx[q] = 0.0;
+      },
+      [&](uint32_t p, const float *Sr) {
+        const uint32_t cnt = a.d - p * PANEL < (uint32_t)PANEL ? a.d - p * PANEL : (uint32_t)PANEL;
+        cd_p qp = qd + p * PANEL;
+        // fma(x, y, acc) == acc + x*y here: the product of two f32 is exact in f64
+        uint32_t j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+          const f32x4 xv = *reinterpret_cast<const f32x4 *>(Sr + j);
+          const double x0 = (double)xv.x, x1 = (double)xv.y, x2 = (double)xv.z, x3 = (double)xv.w;
+          xx = __builtin_fma(x0, x0, xx);
+          xx = __builtin_fma(x1, x1, xx);
+          xx = __builtin_fma(x2, x2, xx);
+          xx = __builtin_fma(x3, x3, xx);
+          // (all eight slots, unused ones zero: a branch between the queries puts a wait behind every
+          // scalar load; straight-line, the eight loads go out together)
+          double w[kGroupSweepMax][4];
 #pragma unroll
-    for (uint32_t q = 0; q < kCosineMultiMax; ++q)
-      if (q < a.nq) tauv[q] = tp[q];
-  }
-  f32x4 v[kLoads];
-  const int lrow = lane / kLanesPerRow, lcol = (lane % kLanesPerRow) * 4;  // this lane's row within a load, its column
-  auto issue = [&](uint32_t ti, uint32_t p) {
-    const uint32_t t = ti * step;
+          for (uint32_t q = 0; q < kGroupSweepMax; ++q) {
+            cd_p wp = qp + q * ldq + j;
+            w[q][0] = wp[0];
+            w[q][1] = wp[1];
+            w[q][2] = wp[2];
+            w[q][3] = wp[3];
+          }
 #pragma unroll
-    for (int s = 0; s < kLoads; ++s) {
-      uint32_t r = t * kCsRows + kRowsPerLoad * s + lrow;
-      r = r < a.n ? r : a.n - 1;
-      v[s] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(a.X + (size_t)r * a.stride + p * kCsPanel + lcol));
-    }
-  };
-  if (wave_global < ntiles) issue(wave_global, 0);
-  for (uint32_t ti = wave_global; ti < ntiles; ti += total_waves) {
-    const uint32_t grow = ti * step * kCsRows + lane;
-    const bool valid_row = grow < a.n;
-    double xx = 0.0, qx[kCosineMultiMax];
-#pragma unroll
-    for (uint32_t q = 0; q < kCosineMultiMax; ++q) qx[q] = 0.0;
-    for (uint32_t p = 0; p < npanel; ++p) {
-#pragma unroll
-      for (int s = 0; s < kLoads; ++s) *reinterpret_cast<f32x4 *>(S + (kRowsPerLoad * s + lrow) * kCsStride + lcol) = v[s];
-      wave_lds_fence();
-      if (p + 1 < npanel) issue(ti, p + 1);
-      else if (ti + total_waves < ntiles) issue(ti + total_waves, 0);
-      const uint32_t cnt = a.d - p * kCsPanel < (uint32_t)kCsPanel ? a.d - p * kCsPanel : (uint32_t)kCsPanel;
-      const float *Sr = S + lane * kCsStride;
-      cd_p qp = qd + p * kCsPanel;
-      // fma(x, y, acc) == acc + x*y here: the product of two f32 is exact in f64
-      uint32_t j = 0;
-      for (; j + 4 <= cnt; j += 4) {
-        const f32x4 xv = *reinterpret_cast<const f32x4 *>(Sr + j);
-        const double x0 = (double)xv.x, x1 = (double)xv.y, x2 = (double)xv.z, x3 = (double)xv.w;
-        xx = __builtin_fma(x0, x0, xx);
-        xx = __builtin_fma(x1, x1, xx);
-        xx = __builtin_fma(x2, x2, xx);
-        xx = __builtin_fma(x3, x3, xx);
-        // (all eight slots, unused ones zero: a branch between the queries puts a wait behind every
-        // scalar load; straight-line, the eight loads go out together)
-        double w[kCosineMultiMax][4];
-#pragma unroll
-        for (uint32_t q = 0; q < kCosineMultiMax; ++q) {
-          cd_p wp = qp + q * ldq + j;
-          w[q][0] = wp[0];
-          w[q][1] = wp[1];
-          w[q][2] = wp[2];
-          w[q][3] = wp[3];
+          for (uint32_t q = 0; q < kGroupSweepMax; ++q) {
+            qx[q] = __builtin_fma(w[q][0], x0, qx[q]);
+            qx[q] = __builtin_fma(w[q][1], x1, qx[q]);
+            qx[q] = __builtin_fma(w[q][2], x2, qx[q]);
+            qx[q] = __builtin_fma(w[q][3], x3, qx[q]);
+          }
         }
+        for (; j < cnt; ++j) {
+          const double xd = (double)Sr[j];
+          xx = __builtin_fma(xd, xd, xx);
 #pragma unroll
-        for (uint32_t q = 0; q < kCosineMultiMax; ++q) {
-          qx[q] = __builtin_fma(w[q][0], x0, qx[q]);
-          qx[q] = __builtin_fma(w[q][1], x1, qx[q]);
-          qx[q] = __builtin_fma(w[q][2], x2, qx[q]);
-          qx[q] = __builtin_fma(w[q][3], x3, qx[q]);
+          for (uint32_t q = 0; q < kGroupSweepMax; ++q) qx[q] = __builtin_fma(qp[q * ldq + j], xd, qx[q]);
         }
-      }
-      for (; j < cnt; ++j) {
-        const double xd = (double)Sr[j];
-        xx = __builtin_fma(xd, xd, xx);
+      },
+      [&](uint32_t ti, uint32_t grow) {
+        // distances.rs:160-177, once per query
+        const bool valid_row = grow < a.n;
+        const double rn = sqrt(xx);
 #pragma unroll
-        for (uint32_t q = 0; q < kCosineMultiMax; ++q) qx[q] = __builtin_fma(qp[q * ldq + j], xd, qx[q]);
-      }
-      wave_lds_fence();
-    }
-    // distances.rs:160-177, once per query
-    const double rn = sqrt(xx);
-#pragma unroll
-    for (uint32_t q = 0; q < kCosineMultiMax; ++q) {
-      if (q >= a.nq) break;
-      const double ln = sqrt(a.qq[q]);
-      float raw = 0.0f;
-      bool valid = valid_row;
-      if (!(ln == 0.0 || rn == 0.0)) {
-        double sim = qx[q] / (ln * rn);
-        if (!isfinite(sim)) {
-          if (valid && !dense) atomicMax(a.status, kErrOverflow);
-          valid = false;
-        } else {
-          sim = sim < -1.0 ? -1.0 : (sim > 1.0 ? 1.0 : sim);
-          raw = (float)sim;
+        for (uint32_t q = 0; q < kGroupSweepMax; ++q) {
+          if (q >= a.nq) break;
+          float raw = cosine_raw(qx[q], sqrt(a.qq[q]), rn);
+          bool valid = valid_row;
+          if (raw != raw) {
+            if (valid && !dense) atomicMax(a.status, kErrOverflow);
+            valid = false;
+            raw = 0.0f;
+          }
+          group_file(a, dense, q, tauv[q], valid, raw, 1.0f - raw, raw, grow, ti, lane);
         }
-      }
-      if (dense) {
-        if (a.sample_maxima) {  // the tile's best score, one value per query and tile
-          float m = valid ? raw : -INFINITY;
-#pragma unroll
-          for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, kWave));
-          if (lane == 0 && ti < a.sample_rows) a.sample[(size_t)q * a.sample_rows + ti] = m;
-          continue;
-        }
-        const uint32_t i = ti * kCsRows + lane;  // position in the sample
-        if (i < a.sample_rows) a.sample[(size_t)q * a.sample_rows + i] = valid ? raw : -INFINITY;
-        continue;
-      }
-      const bool hit = valid && raw >= tauv[q];
-      const uint64_t m = __ballot(hit);
-      if (m) {
-        uint32_t base = 0;
-        if (lane == (int)__builtin_ctzll(m)) base = atomicAdd(&a.cand_count[q], (uint32_t)__popcll(m));
-        base = (uint32_t)__shfl((int)base, (int)__builtin_ctzll(m), kWave);
-        const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
-        if (hit && pos < a.cand_cap) {
-          const uint32_t my_rank = a.id_rank ? a.id_rank[grow] : grow;  // (only in the rare lanes that list a row)
-          a.cand_keys[(size_t)q * a.cand_cap + pos] = ((uint64_t)orderable(1.0f - raw) << 32) | my_rank;
-          Payload pv;
-          pv.row = grow;
-          pv.raw = raw;
-          a.cand_pay[(size_t)q * a.cand_cap + pos] = pv;
-        }
-      }
-    }
-  }
+      });
 }
 
-size_t cosine_scan_multi_lds_bytes() { return (size_t)kWavesPerBlock * kCsRows * (kCsPanelFloats + 4) * sizeof(float); }
-
-hipError_t launch_cosine_scan_multi(const CosineScanMultiArgs &a, uint32_t blocks, hipStream_t s) {
-  const size_t lds = cosine_scan_multi_lds_bytes();
-  if (!a.Qd || ((uintptr_t)a.Qd & 31) || a.nq == 0 || a.nq > kCosineMultiMax || a.n == 0 || a.d == 0) return hipErrorInvalidValue;
+hipError_t launch_cosine_scan_multi(const GroupSweepArgs &a, uint32_t blocks, hipStream_t s) {
+  const size_t lds = group_sweep_lds_bytes();
+  if (!a.Qd || ((uintptr_t)a.Qd & 31) || a.nq == 0 || a.nq > kGroupSweepMax || a.n == 0 || a.d == 0) return hipErrorInvalidValue;
   if (a.sample ? (a.sample_stride == 0 || a.sample_rows == 0) : (!a.tau || !a.cand_keys || !a.cand_pay || !a.cand_count))
     return hipErrorInvalidValue;
-  hipError_t e = allow_lds(cosine_scan_multi_kernel<kCsPanelFloats>, lds);
+  hipError_t e = allow_lds(cosine_scan_multi_kernel<kPanelFloats>, lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cosine_scan_multi_kernel<kCsPanelFloats>, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
+  hipLaunchKernelGGL(cosine_scan_multi_kernel<kPanelFloats>, dim3(blocks), dim3(kWavesPerBlock * kWave), lds, s, a);
   return hipGetLastError();
 }
 

@@ -463,28 +463,34 @@ struct CosineScanArgs {
 size_t cosine_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_cosine_scan(const CosineScanArgs &a, uint32_t blocks, hipStream_t s);
 
-// K6b for up to kCosineMultiMax queries in ONE sweep of the rows' prefixes (funnel_search's stage 1,
-// collection.ex:245-260 -> search.rs:56-60, for several callers at once): every lane owns a row and
-// carries x.x once and q.x per query as sequential f64 chains -- the values are the single kernel's,
-// bit for bit.  No per-wave top-k buffers (eight of them would not fit beside the row panels):
-//   dense mode (`sample` set): the scores of every `sample_stride`-th tile of 64 rows go to
-//     sample[q * sample_rows + i] -- launch_sample_tau turns them into one threshold per query;
-//   sweep mode: every (query, row) with raw >= tau[q] is appended to the query's list as
-//     (key, {row, raw}) -- key as in the single kernel -- cand_count[q] counting ALL of them;
-//     the host checks k <= count <= cap (else that query takes the single path) and
-//     launch_select_lists cuts each list to its k best.
-constexpr uint32_t kCosineMultiMax = 8;
-struct CosineScanMultiArgs {
+// A group's sweep: stage 1 of funnel_search (collection.ex:245-260 -> search.rs:56-60) for up to kGroupSweepMax callers in
+// ONE sweep of the rows' first d coordinates.  Every lane owns a row, read through a 64 x 32-float LDS panel
+// (vt_panel.cuh); the queries are wave-uniform and come through the scalar cache.  Two kernels serve it:
+//   K6bm (cosine collections): x.x once and q.x per query as sequential f64 chains (distances.rs:160-177) -- the values
+//     are K6b's, bit for bit.  Reads Qd and qq.  No per-wave top-k buffers (eight would not fit beside the row panels).
+//   K1p (the dot / L2 / L1 / Linf families): the index's own metric in K1's arithmetic -- eight separately rounded
+//     products per chunk, the horizontal add in the lane order `order`, acc += chunk sum, the scalar tail
+//     (distances.rs:197-262).  Reads Q, q_stride, metric and order.
+// Both score "larger is better" -- raw for cosine, -rank_value for the others -- and run in two modes:
+//   dense (`sample` set): the scores of every `sample_stride`-th tile of 64 rows go to sample[q * sample_rows + i]
+//     (launch_sample_tau turns them into one threshold per query); with `sample_maxima` only the BEST score of every
+//     sampled tile: sample[q * sample_rows + tile], sample_rows = the launch's tiles (launch_sample_tau_groups);
+//   sweep: every (query, row) with score >= tau[q] is appended to the query's list as (key, {row, raw}) -- key as in the
+//     single kernel -- cand_count[q] counting ALL of them; the host checks k <= count <= cap (else that query takes
+//     the single path) and launch_select_lists cuts each list to its k best.
+constexpr uint32_t kGroupSweepMax = 8;
+struct GroupSweepArgs {
   const float *X;
   size_t stride;
-  const double *Qd;          // [kCosineMultiMax][padded_dim(d)] device: the queries' prefixes as f64 (exact), unused rows zero
-  double qq[kCosineMultiMax];  // f64_dot(q, q) over the first d coordinates (sequential, host)
+  const float *Q;            // K1p: [kGroupSweepMax][q_stride] f32 queries (device; unused rows readable), q_stride % 8 == 0
+  uint32_t q_stride;
+  const double *Qd;          // K6bm: [kGroupSweepMax][padded_dim(d)] device: the queries' prefixes as f64 (exact), unused rows zero
+  double qq[kGroupSweepMax];  // K6bm: f64_dot(q, q) over the first d coordinates (sequential, host)
   const uint32_t *id_rank;
   uint32_t n, d, nq;
+  int metric, order;         // K1p runs the dot / L2 / L1 / Linf families, K6bm cosine; not the pattern metrics
   float *sample;             // dense mode when set
   uint32_t sample_stride, sample_rows;
-  // (r05) dense mode files only the BEST score of every sampled 64-row tile: sample[q * sample_rows + tile], with
-  // sample_rows = the launch's tiles; the threshold then comes from launch_sample_tau_groups (the K2s sample's scheme)
   uint32_t sample_maxima;
   const float *tau;          // [nq] sweep mode
   uint64_t *cand_keys;       // [nq][cand_cap]
@@ -493,41 +499,17 @@ struct CosineScanMultiArgs {
   uint32_t cand_cap;
   int *status;
 };
-size_t cosine_scan_multi_lds_bytes();
-hipError_t launch_cosine_scan_multi(const CosineScanMultiArgs &a, uint32_t blocks, hipStream_t s);
-
-// K1p: the index's own metric (K1's arithmetic: eight separately rounded products per chunk, the horizontal add in
-// the lane order `order`, acc += chunk sum, the scalar tail -- distances.rs:197-262) over the first d coordinates of
-// EVERY row for up to kPrefixMultiMax queries in ONE sweep of the prefixes: stage 1 of funnel_search on an L2 / dot /
-// L1 / Linf collection (collection.ex:245-260 -> search.rs:56-60) for several callers at once.  Lane r walks row r
-// through a 64 x 64-float LDS panel like K6b; the queries come through the scalar cache.  Modes as K6b's:
-//   dense (`sample` set): -rank_value of every sample_stride-th tile's rows to sample[q * sample_rows + i]
-//     (larger = better: launch_sample_tau's order);
-//   sweep: every (query, row) with -rank_value >= tau[q] is appended to the query's list as (key, {row, raw}),
-//     key as in K1; cand_count[q] counts all of them.
-constexpr uint32_t kPrefixMultiMax = 8;
-struct PrefixMultiArgs {
-  const float *X;
-  size_t stride;
-  const float *Q;            // [kPrefixMultiMax][q_stride] f32 queries (device; unused rows readable), q_stride % 8 == 0
-  uint32_t q_stride;
-  const uint32_t *id_rank;
-  uint32_t n, d, nq;
-  int metric, order;         // metrics of the dot / L2 / L1 / Linf families (not cosine, not the pattern metrics)
-  float *sample;
-  uint32_t sample_stride, sample_rows;
-  uint32_t sample_maxima;    // as in CosineScanMultiArgs
-  const float *tau;
-  uint64_t *cand_keys;       // [nq][cand_cap]
-  Payload *cand_pay;
-  uint32_t *cand_count;      // [nq], zeroed by the caller
-  uint32_t cand_cap;
-  int *status;
-};
 bool prefix_multi_supports(int metric);
-size_t prefix_multi_lds_bytes();
-int prefix_multi_blocks_per_cu();  // resident blocks per CU the launch is sized for (2)
-hipError_t launch_prefix_multi(const PrefixMultiArgs &a, uint32_t blocks, hipStream_t s);
+hipError_t launch_cosine_scan_multi(const GroupSweepArgs &a, uint32_t blocks, hipStream_t s);
+hipError_t launch_prefix_multi(const GroupSweepArgs &a, uint32_t blocks, hipStream_t s);
+size_t group_sweep_lds_bytes();
+// resident blocks per CU the launch is sized for: K1p's 2 (three or four blocks of the narrow panel fit a CU, and are
+// slower: DESIGN_APPENDIX A.15); 0 -- the context's default -- where K6bm runs
+inline int group_sweep_blocks_per_cu(int metric) { return prefix_multi_supports(metric) ? 2 : 0; }
+// the kernel that serves a.metric
+inline hipError_t launch_group_sweep(const GroupSweepArgs &a, uint32_t blocks, hipStream_t s) {
+  return prefix_multi_supports(a.metric) ? launch_prefix_multi(a, blocks, s) : launch_cosine_scan_multi(a, blocks, s);
+}
 
 // Diagnostic (vt_device_read_peak): one pass of the bare LDS-DMA read stream over the whole 384-KiB tiles of
 // `buf` (read_peak_bytes(bytes) of it), `blocks` blocks of 512 threads -- one per CU; launch_peak_fill puts

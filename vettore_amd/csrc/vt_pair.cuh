@@ -98,12 +98,7 @@ __device__ __forceinline__ void cosine_dots(const float *const (&v)[K], const fl
     for (int k = 0; k < K; ++k) dot[k] = __builtin_fma((double)v[k][e], xv, dot[k]);
   }
 }
-// ... and the raw value from the dot and the two vectors' f64 norms: a zero norm gives 0.0
-__device__ __forceinline__ float cosine_raw(double dot, double ln, double rn) {
-  if (ln == 0.0 || rn == 0.0) return 0.0f;
-  const double sim = dot / (ln * rn);
-  return isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
-}
+// ... and the raw value from the dot and the two vectors' f64 norms: cosine_raw (vt_scan.cuh)
 
 // raw[k] = hamming() / jaccard() (distances.rs:319-347) of (v[k], row) over truthiness
 template <int K>

@@ -179,6 +179,14 @@ __device__ __forceinline__ float chunk_sum1(const float (&l)[8]) {
 __device__ __forceinline__ float f64_as_f32_or_nan(double v) {  // distances.rs:92-98 f64_to_f32
   return isfinite(v) && v >= -(double)FLT_MAX && v <= (double)FLT_MAX ? (float)v : __builtin_nanf("");
 }
+// cosine()'s finish (distances.rs:160-177): the raw value from the f64 dot and the two vectors' f64 norms -- a zero norm
+// gives 0.0, a similarity that is not finite NaN ("metric overflow": what the caller does then is its own).  K6, K6b, K6bm
+// and the one-lane pair chains (vt_pair.cuh) finish with it.
+__device__ __forceinline__ float cosine_raw(double dot, double ln, double rn) {
+  if (ln == 0.0 || rn == 0.0) return 0.0f;
+  const double sim = dot / (ln * rn);
+  return isfinite(sim) ? (float)fmin(fmax(sim, -1.0), 1.0) : __builtin_nanf("");
+}
 __device__ __noinline__ static float recover_overflow(int metric, const float *q, const float *x, uint32_t d) {
   double acc = 0.0;
   switch (metric) {
