@@ -28,7 +28,7 @@ DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_bat
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch4_best_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -92,6 +92,8 @@ $(LIBDIR)/%.o: $(CSRC)/%.hip $(DEVHDR)
 # (what the sketch units share)
 $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_batch.o $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_sketch.cuh
 $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_sketch_nibble.cuh
+# (one row's exact key by one wave: the refine kernel and the 4-bit pass's best rows)
+$(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_rowscore.cuh
 $(LIBDIR)/vt_sketch_batch.o: $(CSRC)/host/vt_sketchbatch.h
 
 # (the one-lane pair arithmetic of K9, K9r, K9rb, K11 and K12; what the three MaxSim kernels share beside it)
@@ -167,6 +169,15 @@ $(LIBDIR)/sketch4_rescore_probe.o: tests/sketch4_rescore_probe.cpp $(CSRC)/vt_de
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_sketch4_rescore_probe.so: $(LIBDIR)/vt_sketch4_rescore.o $(LIBDIR)/sketch4_rescore_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# K1n's threshold from its lists' best rows behind a probe (tests/sketch4_best_probe.cpp; tests/test_gpu_sketch4_best_kernels.py
+# loads it): the 4-bit pass asked for the best words, and the rescoring kernel handed such words.  Test infrastructure, as above.
+$(LIBDIR)/sketch4_best_probe.o: tests/sketch4_best_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_sketch4_best_probe.so: $(LIBDIR)/vt_sketch_nibble.o $(LIBDIR)/vt_sketch4_rescore.o $(LIBDIR)/sketch4_best_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 # The int8 sketch's L2 family behind a probe (tests/sketch_l2_probe.cpp; tests/test_gpu_sketch_l2_kernels.py loads it): the

@@ -770,7 +770,8 @@ typedef struct vt_profile {
   uint64_t sketch4_fallbacks;        /* passes the bound could not certify (the 5-bit sketch and what lies behind it then served) */
   uint64_t sketch4_builds;           /* whole builds of the 4-bit sketch */
   uint64_t sketch4_patched_rows;     /* rows re-quantised in place after mutations */
-  uint64_t sketch4_finished;         /* searches whose result the filtered K1 behind the pass wrote itself (no select, one wait) */
+  uint64_t sketch4_best;             /* searches whose exact threshold came from each list's best rows, inside the pass (no launch between pass and rescore) */
+  uint64_t sketch4_finished;        /* searches whose result the filtered K1 behind the pass wrote itself (no select, one wait) */
   /* K1qm: batches and meeting callers of 2..8 queries nominated from one pass over the int8 sketch (the lone counters
    * above are not touched by these passes) */
   uint64_t sketch_batch_launches;    /* group passes over the int8 sketch */

@@ -74,7 +74,7 @@ class Profile(C.Structure):
         ("sketch5_patched_rows", C.c_uint64),
         ("sketch4_launches", C.c_uint64), ("sketch4_ms", C.c_double), ("sketch4_bytes", C.c_uint64),
         ("sketch4_candidates", C.c_uint64), ("sketch4_fallbacks", C.c_uint64), ("sketch4_builds", C.c_uint64),
-        ("sketch4_patched_rows", C.c_uint64), ("sketch4_finished", C.c_uint64),
+        ("sketch4_patched_rows", C.c_uint64), ("sketch4_best", C.c_uint64), ("sketch4_finished", C.c_uint64),
         ("sketch_batch_launches", C.c_uint64), ("sketch_batch_queries", C.c_uint64), ("sketch_batch_ms", C.c_double),
         ("sketch_batch_bytes", C.c_uint64), ("sketch_batch_candidates", C.c_uint64),
         ("sketch_batch_fallbacks", C.c_uint64), ("sketch_batch_tail_rescored", C.c_uint64),

@@ -454,11 +454,8 @@ int nibble_query_upload(Ctx &c, const SketchKind &kind, const float *query, cons
   return VT_OK;
 }
 
-// The certification spread over the card: the threshold kernel over the pass's lists and, where the tier takes its
-// threshold from exact keys (K1n), launch_sketch_refine behind it.  *ta: what the collect kernel takes, kt_word set where
-// the refine ran.
-int nibble_threshold(Shard *ix, Ctx &c, int tier, uint32_t lists, uint32_t k, uint32_t *info, vt::SketchSpreadArgs *ta_out) {
-  const vt_host::SketchTierRow &row = vt_host::kSketchTiers[tier];
+// What the threshold and collect kernels take over the `lists` lists a nibble pass left on `c`.
+vt::SketchSpreadArgs nibble_spread_args(Ctx &c, int tier, uint32_t lists, uint32_t k, uint32_t *info) {
   const uint32_t kp = vt_host::kSketchNibbleListK, thresh_blocks = vt::sketch_thresh_blocks(lists, kp);
   vt::SketchSpreadArgs ta{};
   ta.lo_words = c.dSkLoWords.p;
@@ -467,13 +464,23 @@ int nibble_threshold(Shard *ix, Ctx &c, int tier, uint32_t lists, uint32_t k, ui
   ta.lists = lists;
   ta.kp = kp;
   ta.k = k;
-  ta.cap = row.cand_cap;
+  ta.cap = vt_host::kSketchTiers[tier].cand_cap;
   ta.parts = c.dSkParts.p;
   ta.live = c.dSkParts.p + (size_t)thresh_blocks * k;
   ta.sync = c.dSkSync.p;
   ta.rows = c.dSkRows[tier].p;
   ta.count = c.dSkCount.p;
   ta.info = info;
+  return ta;
+}
+
+// The certification spread over the card: the threshold kernel over the pass's lists and, where the tier takes its
+// threshold from exact keys (K1n), launch_sketch_refine behind it.  *ta: what the collect kernel takes, kt_word set where
+// the refine ran.
+int nibble_threshold(Shard *ix, Ctx &c, int tier, uint32_t lists, uint32_t k, uint32_t *info, vt::SketchSpreadArgs *ta_out) {
+  const vt_host::SketchTierRow &row = vt_host::kSketchTiers[tier];
+  vt::SketchSpreadArgs ta = nibble_spread_args(c, tier, lists, k, info);
+  const uint32_t thresh_blocks = vt::sketch_thresh_blocks(lists, ta.kp);
   if (row.exact_threshold) ta.slots = ta.live + thresh_blocks;
   VT_HIP(vt::launch_sketch_thresh(ta, c.stream));
   if (row.exact_threshold) {
@@ -484,7 +491,7 @@ int nibble_threshold(Shard *ix, Ctx &c, int tier, uint32_t lists, uint32_t k, ui
     ra.thresh_blocks = thresh_blocks;
     ra.k = k;
     ra.pay = c.dSkPay.p;
-    ra.slots_total = lists * kp;
+    ra.slots_total = lists * ta.kp;
     ra.X = ix->dX;
     ra.stride = ix->ld;
     ra.q = c.qsrc;
@@ -499,16 +506,35 @@ int nibble_threshold(Shard *ix, Ctx &c, int tier, uint32_t lists, uint32_t k, ui
   return VT_OK;
 }
 
+// Whether launch_sketch4_rescore takes the shard's rows: K1n's candidates are then rescored straight from the pass's lists.
+bool nibble_from_lists(const Shard *ix, uint32_t k, uint32_t kp) {
+  return sketch_dot_metric(ix->metric) && k <= (uint32_t)vt::kSmallK && vt::sketch4_rescore_lds_bytes((uint32_t)ix->dim, kp) != 0;
+}
+
+// Whether K1n takes its exact threshold from each list's best rows, rescored inside the pass: blit, pass,
+// rescore, wait -- no threshold and no refine launch.  The tier says so, the rescoring kernel takes the rows and the words
+// (two a list, a select of k <= kSketch4BestMaxK over at most kSketch4BestMaxWords in every block's head), the rows' chunk
+// sums fit the pass's wave buffers, a list's slots number at most the storing wave's 64 lanes, and every wave of the pass
+// owns a tile, so that the lists have rows to rescore.  Smaller corpora keep the chain they had, launch for launch.
+bool nibble_best_rows(const Shard *ix, int tier, uint32_t k, uint32_t kp, uint32_t blocks, uint32_t lists) {
+  const uint32_t ntiles = (ix->n + vt::kSketchTileRows - 1) / vt::kSketchTileRows;
+  return vt_host::kSketchTiers[tier].best_rows && nibble_from_lists(ix, k, kp) && k <= vt::kSketch4BestMaxK &&
+         (size_t)lists * vt::kSketch4BestRows <= vt::kSketch4BestMaxWords && kp <= 64u &&
+         vt::padded_dim((uint32_t)ix->dim) / 8 + 12 <= vt::kSketch4BestRowFloats && ntiles >= blocks * (uint32_t)vt::kWavesPerBlock;
+}
+
 // K1n's finish behind the exact threshold, and its one host wait: the rows whose rank word is <= Kt' are kept -- the k hits
 // and what ties the k-th -- and the last block sorts them into the result block: no lists, no select (the survivors lie
 // where the lists would).  Wherever its launcher takes the shape the candidates are rescored straight from the pass's lists
 // by one kernel (launch_sketch4_rescore) that certifies as the collect does and finishes as the filtered K1 does, no
 // candidate array (*from_lists); otherwise the collect with that threshold and the gathered K1 in filter mode.
+// best_words (nibble_best_rows said yes, the pass left them: best_count words): the rescoring kernel takes its threshold from
+// them in its head and publishes it in *ta.kt_word, which no launch has written -- nothing ran between the pass and it.
 int nibble_finish_exact(Shard *ix, Ctx &c, int tier, const vt::SketchSpreadArgs &ta, uint32_t *chain_words, uint32_t blocks,
-                        bool *from_lists, bool *delivered) {
+                        const uint32_t *best_words, uint32_t best_count, bool *from_lists, bool *delivered) {
   const vt_host::SketchTierRow &row = vt_host::kSketchTiers[tier];
-  const uint32_t d = (uint32_t)ix->dim;
-  *from_lists = sketch_dot_metric(ix->metric) && ta.k <= (uint32_t)vt::kSmallK && ta.kt_word && vt::sketch4_rescore_lds_bytes(d, ta.kp) != 0;
+  *from_lists = ta.kt_word && nibble_from_lists(ix, ta.k, ta.kp);
+  if (best_words && !*from_lists) return fail(VT_ERR_DEVICE, "internal: best rows without the rescoring kernel");
   if (!*from_lists) VT_HIP(vt::launch_sketch_collect(ta, c.stream));
   vt::ScanArgs fa = gathered_args(ix, c, ta.rows, row.cand_cap, ta.k);
   fa.hi_word = ta.kt_word;
@@ -527,6 +553,12 @@ int nibble_finish_exact(Shard *ix, Ctx &c, int tier, const vt::SketchSpreadArgs 
     ra.pay = ta.pay;
     ra.kp = ta.kp;
     ra.cap = row.cand_cap;
+    if (best_words) {
+      ra.s.hi_word = nullptr;
+      ra.best_words = best_words;
+      ra.best_count = best_count;
+      ra.kt_out = const_cast<uint32_t *>(ta.kt_word);
+    }
     VT_HIP(vt::launch_sketch4_rescore(ra, blocks, c.stream));
   } else {
     VT_HIP(vt::launch_scan_filter(fa, row.rescore_blocks, c.stream));
@@ -540,7 +572,9 @@ int nibble_finish_exact(Shard *ix, Ctx &c, int tier, const vt::SketchSpreadArgs 
 // kernel, the collect kernel), the gathered K1 over the candidate rows they left (the count read on the device: none when
 // the pass did not certify) and K1's select, all queued before the wait.  K1n ends behind its exact threshold instead
 // (nibble_finish_exact); a search of its whose survivors overflow the short list queues the collect, the lists and the
-// select behind a second wait.
+// select behind a second wait.  Where nibble_best_rows says so K1n's chain is blit, pass, rescore, wait: the pass leaves
+// the exact keys of each list's two best rows and the rescoring kernel takes its threshold from them (sketch4_best counts
+// these searches).
 // *done as sketch_search has it; a pass that does not certify counts towards the shard's miss limit.
 int nibble_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *done, vt_hits **out, int tier) {
   const SketchKind &kind = sketch_kind(tier);
@@ -560,7 +594,10 @@ int nibble_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   VT_TRY(c.dSkLoWords.ensure((size_t)lists * kp));
   VT_TRY(c.dSkHiWords.ensure((size_t)lists * kp));
   // (parts[thresh_blocks][k] | live[thresh_blocks] | K1n: slots[thresh_blocks][k] | the exact threshold's word)
-  VT_TRY(c.dSkParts.ensure((size_t)vt::sketch_thresh_blocks(lists, kp) * (2 * k + 1) + 1));
+  // (K1n from its lists' best rows: best_words[lists][2] | the threshold's word, in the same room)
+  const bool best = nibble_best_rows(ix, tier, k, kp, blocks, lists);
+  const size_t best_count = (size_t)lists * vt::kSketch4BestRows;
+  VT_TRY(c.dSkParts.ensure(std::max((size_t)vt::sketch_thresh_blocks(lists, kp) * (2 * k + 1) + 1, best_count + 1)));
   VT_TRY(c.dSkSync.ensure(4));
   VT_TRY(c.ensure_part_lists(std::max<size_t>((size_t)row.rescore_blocks * k, vt::kScanFilterCap)));  // (K1n: the survivors lie there)
   a.img = st.col.buf.p;
@@ -574,23 +611,39 @@ int nibble_search(Shard *ix, Ctx &c, const float *query, size_t limit, bool *don
   a.part_pay = c.dSkPay.p;
   a.lo_words = c.dSkLoWords.p;
   a.hi_words = c.dSkHiWords.p;
+  if (best) {
+    a.best_words = c.dSkParts.p;
+    a.X = ix->dX;
+    a.stride = ix->ld;
+    a.q = c.qsrc;  // (the blit in front of the pass carries it)
+    a.order = ix->order;
+  }
   VT_TRY(c.mark_begin());
   VT_HIP(kind.scan(a, blocks, c.stream));
   VT_TRY(c.mark_end());
   vt::SketchSpreadArgs ta{};
-  VT_TRY(nibble_threshold(ix, c, tier, lists, k, info, &ta));
+  if (best) {
+    ta = nibble_spread_args(c, tier, lists, k, info);
+    ta.kt_word = c.dSkParts.p + best_count;  // (the rescoring kernel's block 0 writes it)
+  } else {
+    VT_TRY(nibble_threshold(ix, c, tier, lists, k, info, &ta));
+  }
   bool from_lists = false, delivered = false;
-  if (row.exact_threshold) VT_TRY(nibble_finish_exact(ix, c, tier, ta, chain_words, blocks, &from_lists, &delivered));
+  if (row.exact_threshold)
+    VT_TRY(nibble_finish_exact(ix, c, tier, ta, chain_words, blocks, best ? c.dSkParts.p : nullptr, (uint32_t)best_count, &from_lists, &delivered));
   else VT_HIP(vt::launch_sketch_collect(ta, c.stream));
   if (!delivered && (!row.exact_threshold || c.hSkInfo.p[0] == 2u)) {
     // (K1n, certified but not delivered -- more survivors than the short list holds: thousands of rows tie the k-th key,
     // or the refine kept the sketch's own Kt: the lists and their select over the candidates, behind a second wait.  The
-    // rescoring kernel left no candidate array: the collect, over the lists still on the device, goes first.  Not a
-    // fallback.)
+    // rescoring kernel left no candidate array: the collect, over the lists still on the device, goes first -- with the
+    // word that kernel published where the best rows gave it, and its three shared words zeroed here, where no threshold
+    // kernel ran to zero them.  Not a fallback.)
+    if (best) VT_HIP(hipMemsetAsync(c.dSkSync.p, 0, 4 * sizeof(uint32_t), c.stream));
     if (from_lists) VT_HIP(vt::launch_sketch_collect(ta, c.stream));
     VT_TRY(rescore_gathered(ix, c, ta.rows, row.cand_cap, row.rescore_blocks, k));
   }
   const bool certified = (delivered || c.hSkInfo.p[0] == 2u) && c.hRes.p->status == 0;
+  if (best) c.prof.sketch4_best += 1;
   if (delivered && certified) c.prof.sketch4_finished += 1;
   if (c.profiling && kind.tail_words) c.prof.*kind.tail_words += c.hSkInfo.p[3] == 1u ? 1 : 0;
   return sketch_settle(ix, c, tier, certified, done, out);

@@ -32,6 +32,7 @@ struct SketchTierRow {
   uint32_t miss_limit;          // passes in a row that did not certify before the shard stops taking the tier (0: none counted)
   uint32_t block_lists;         // lists a block of the pass leaves
   bool exact_threshold;         // Kt' from launch_sketch_refine
+  bool best_rows;               // where the corpus gives every wave of the pass a tile: Kt'' from each list's best rows, inside the pass
   long off_at;                  // the value of its setting (`sketch` for the int8 tier, `sketch6` for the others) that switches it off
   long forced_from;             // force_sketch6 from this value on lifts min_bytes (1: any non-zero value; the int8 tier: or force_sketch)
 };
@@ -42,7 +43,10 @@ struct SketchTierRow {
 // taken from the exact keys of the k rows with the smallest key(lo) (launch_sketch_refine, between the threshold and the
 // collect kernels): the band is then one interval wide, not two, and leaves what K1f leaves behind Kt (tens of thousands
 // of 10 M uniform unit rows at d = 768), over a wider spread -- so the pass leaves two lists a block, the candidate list
-// has a row for every slot of those and the gathered K1 runs on its rescore_blocks blocks.  K1f is its fallback, on
+// has a row for every slot of those and the gathered K1 runs on its rescore_blocks blocks.  Where the corpus gives every wave
+// of the pass a tile (best_rows; vt_sketchsearch.h, nibble_best_rows) the exact keys come from each list's two best rows,
+// rescored by the wave that stores the list, and the threshold is their k-th smallest, found in the rescoring kernel's
+// head: no threshold and no refine launch.  K1f is its fallback, on
 // K1f's own terms; after miss_limit passes in a row that did not certify the shard stops taking K1n until the
 // column is built anew.  The settings are K1s's, one value further still (the product's list of settings stays as long
 // as it was): VT_SKETCH6=3 keeps K1s and K1f and switches K1n off -- the chain as it was without this column --;
@@ -93,12 +97,15 @@ struct SketchTierRow {
 // (force_sketch6 brings the int8 sketch with it: it is the 6-bit pass's fallback, and serves the limits that pass declines.)
 constexpr double kSketchMiB = 1 << 20;
 constexpr SketchTierRow kSketchTiers[kSketchTierCount] = {
-    //   min_bytes            min_bytes_l2        limit  k'  cand_cap  blocks misses lists exact  off forced
-    {4, 16.0 * 1024 * kSketchMiB, 0.0,                10, 64, 131072, 1024, 4, 2, true,  3, 3},
-    {5, 16.0 * 1024 * kSketchMiB, 0.0,                10, 64, 65536,  512,  4, 1, false, 2, 2},
-    {6, 16.0 * 1024 * kSketchMiB, 0.0,                32, 64, 32768,  256,  4, 1, false, 0, 1},
-    {8, 256.0 * kSketchMiB,       1024.0 * kSketchMiB, 128, 0, 4096,   32,   0, 1, false, 0, 1},
+    //   min_bytes            min_bytes_l2        limit  k'  cand_cap  blocks misses lists exact  best   off forced
+    {4, 16.0 * 1024 * kSketchMiB, 0.0,                10, 64, 131072, 1024, 4, 2, true,  true,  3, 3},
+    {5, 16.0 * 1024 * kSketchMiB, 0.0,                10, 64, 65536,  512,  4, 1, false, false, 2, 2},
+    {6, 16.0 * 1024 * kSketchMiB, 0.0,                32, 64, 32768,  256,  4, 1, false, false, 0, 1},
+    {8, 256.0 * kSketchMiB,       1024.0 * kSketchMiB, 128, 0, 4096,   32,   0, 1, false, false, 0, 1},
 };
+static_assert(!kSketchTiers[kTier5].best_rows && !kSketchTiers[kTier6].best_rows && !kSketchTiers[kTier8].best_rows &&
+                  (!kSketchTiers[kTier4].best_rows || kSketchTiers[kTier4].exact_threshold),
+              "only the 4-bit pass rescores its lists' best rows, and only in place of the refine");
 static_assert(sketch_list_k(kSketchTiers[kTier8].max_limit) <= kSketchListMax &&
                   sketch_list_k(kSketchTiers[kTier8].max_limit + 1) > kSketchListMax,
               "the int8 tier's limits are those whose list fits one wave buffer");

@@ -1009,7 +1009,20 @@ struct Sketch6ScanArgs {
   // [blocks][k] each, beside the lists: a slot's orderable key(lo) word and its orderable key(hi) word, 0xffffffff in both
   // for an empty slot -- what launch_sketch_thresh and launch_sketch_collect read in place of the lists themselves
   uint32_t *lo_words, *hi_words;
+  // K1n's threshold from each list's best rows (launch_sketch4_scan alone; null: the pass is what it is without these).
+  // The wave that stores a list rescores the list's two live slots of smallest key(lo) word (ties: the lower slot) with
+  // K1's arithmetic (vt_rowscore.cuh: X, stride, q padded to padded_dim(d) floats, the index's reduce order) and leaves
+  // their exact rank words in best_words[list][0..1]; 0xffffffff where the list has no such slot or the value is not
+  // finite.  Any k of these words bound the corpus's k-th key word from above (launch_sketch4_rescore takes the k-th
+  // smallest).  The rows' chunk sums lie in the wave buffers of the pair: padded_dim(d) / 8 + 12 <= kSketch4BestRowFloats.
+  uint32_t *best_words = nullptr;  // [blocks * kSketch4BlockLists][kSketch4BestRows]
+  const float *X = nullptr;
+  size_t stride = 0;
+  const float *q = nullptr;
+  int order = 0;
 };
+constexpr uint32_t kSketch4BestRows = 2;         // rows a list's storing wave rescores
+constexpr uint32_t kSketch4BestRowFloats = 512;  // a row's chunk sums and tail products at most: two wave buffers hold two rows
 // k <= kSmallK and ld8 >= 256 (a tile of ld8 = 128 is shorter than the load ring: K1q serves those); 0: not supported
 size_t sketch6_scan_lds_bytes(uint32_t d, uint32_t k);
 hipError_t launch_sketch6_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s);
@@ -1074,7 +1087,16 @@ struct Sketch4RescoreArgs {
   const Payload *pay;        // [blocks * kSketch4BlockLists][kp]
   uint32_t kp, cap;
   uint32_t ld, ss;           // set by the launcher
+  // The threshold from the pass's best rows (Sketch6ScanArgs::best_words; null: *s.hi_word as above).  Every block finds
+  // the same word before it judges a slot: Kt'' = the k-th smallest of the best_count words with multiplicity, 0xffffffff
+  // when fewer than k are live (every live slot is then a candidate).  It stands wherever *s.hi_word stood, info[2]
+  // included, and block 0 stores it to *kt_out.  best_count <= kSketch4BestMaxWords, k <= kSketch4BestMaxK.
+  const uint32_t *best_words = nullptr;
+  uint32_t best_count = 0;
+  uint32_t *kt_out = nullptr;
 };
+constexpr uint32_t kSketch4BestMaxWords = 4096;  // sixteen words a thread
+constexpr uint32_t kSketch4BestMaxK = 17;        // the words below the k-th thread minimum fit a word per thread: 16 (k - 1) <= 256
 size_t sketch4_rescore_lds_bytes(uint32_t d, uint32_t kp);
 hipError_t launch_sketch4_rescore(Sketch4RescoreArgs a, uint32_t blocks, hipStream_t s);
 

@@ -1371,6 +1371,7 @@ int vt_flat_get_profile(vt_flat *h, vt_profile *out, int reset) {
       }
       t.sketch_tail_rescored += p.sketch_tail_rescored;
       t.sketch6_tail_words += p.sketch6_tail_words;
+      t.sketch4_best += p.sketch4_best;
       t.sketch4_finished += p.sketch4_finished;
       t.sketch_batch_launches += p.sketch_batch_launches;
       t.sketch_batch_queries += p.sketch_batch_queries;

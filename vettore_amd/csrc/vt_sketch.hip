@@ -15,6 +15,7 @@
 // dword: ||q - x_r||^2 = ||q||^2 + ||x_r||^2 - 2 q.x_r, so [a_r - e_r, a_r + e_r] (without K1's summation term) gives an
 // interval of the real squared distance, K1's f32 value lies within a relative kappa of that, and the two words kept per
 // row are kmin_r and kmax_r themselves -- the rank of both metrics is the raw value.
+#include "vt_rowscore.cuh"
 #include "vt_sketch.cuh"
 
 #include <algorithm>
@@ -816,43 +817,17 @@ __global__ __launch_bounds__(kTailThreads) void sketch_refine_kernel(const Sketc
         qv[u] = in ? *reinterpret_cast<const f32x4 *>(a.q + col) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const uint32_t col = s0 + u * 256 + (uint32_t)lane * 4;
-        const f32x4 pr = elem4<OP_DOT>(OP_DOT, qv[u], xv[u]);
-        const float sum = chunk_sum<OP_DOT, -1>(OP_DOT, a.order, pr.x, pr.y, pr.z, pr.w, odd);
-        const uint32_t ch = col >> 3;
-        if (col < a.ld) {
-          if (ch < cfull) {
-            if (!odd) Srow[ch] = sum;
-          } else if (ch == cfull) {  // the tail chunk: the reference adds these products one by one
-            *reinterpret_cast<f32x4 *>(Srow + tail_base + odd * 4) = pr;
-          }
-        }
-      }
+      for (int u = 0; u < 4; ++u)
+        row_chunk<-1>(Srow, qv[u], xv[u], s0 + u * 256 + (uint32_t)lane * 4, a.ld, cfull, tail_base, a.order, odd);
     }
   }
   __syncthreads();
   if (tid < a.k && sel_row[tid] != 0xffffffffu) {
-    const float *Sr = S + (size_t)tid * a.ss;
-    float acc = 0.0f;
-    uint32_t c = 0;
-    for (; c + 4 <= cfull; c += 4) {
-      const f32x4 v = *reinterpret_cast<const f32x4 *>(Sr + c);
-      acc = acc + v.x;
-      acc = acc + v.y;
-      acc = acc + v.z;
-      acc = acc + v.w;
-    }
-    for (; c < cfull; ++c) acc = acc + Sr[c];
-    for (uint32_t j = 0; j < tail; ++j) acc = acc + Sr[tail_base + j];
-    // the value and its rank as scan_topk_kernel forms them; a value that is not finite goes through K1's f64 recovery
-    // there: here it only means that this call keeps the sketch's own threshold
-    const float raw = a.metric == M_NIP ? -acc : acc;
-    float rank = raw;
-    if (a.metric == M_COS) rank = 1.0f - raw;
-    else if (a.metric == M_IP) rank = -raw;
-    if (!finite_f32(raw) || !finite_f32(rank)) s_bad = 1;
-    else atomicMax(&s_max, orderable(rank));
+    // the value and its rank as scan_topk_kernel forms them (vt_rowscore.cuh); a value that is not finite goes through
+    // K1's f64 recovery there: here it only means that this call keeps the sketch's own threshold
+    uint32_t word;
+    if (!row_rank_word(a.metric, row_chain(S + (size_t)tid * a.ss, cfull, tail, tail_base), &word)) s_bad = 1;
+    else atomicMax(&s_max, word);
   }
   __syncthreads();
   if (tid == 0) *a.kt_out = s_bad ? kt : (s_max < kt ? s_max : kt);

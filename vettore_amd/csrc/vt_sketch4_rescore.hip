@@ -16,6 +16,10 @@
 //     word and key as scan_topk_kernel forms them.  Survivors, tickets and the finish are filter_claim / filter_finish of
 //     vt_scan.cuh; the block that draws the last ticket also writes what the collect's last block wrote: info[1] = the
 //     candidate total, info[2] = Kt', info[3] = 1, and info[0] = ok ? 2 : 0 unless it delivers.
+//   * The word itself: *hi_word, or -- handed the pass's best words (Sketch4RescoreArgs::best_words: the exact keys of each
+//     list's two best rows, left by the pass) -- their k-th smallest, Kt'', which every block finds for itself in its head
+//     from words that lie in L2 (best_select); block 0 publishes it for the chain behind a second wait.  No launch stands
+//     between the pass and this kernel then.
 // Nothing polls or waits for another block.
 #include "vt_scan.cuh"
 
@@ -32,6 +36,49 @@ constexpr uint32_t kFailBit = 2u;     // in fsync[1], beside the survivor list's
 __host__ __device__ inline uint32_t rescore_round_rows(uint32_t nseg) {
   const uint32_t r = (nseg <= kStaticSegs ? kRoundLoads : kLongLoads) / nseg;
   return r < kRoundRows ? r : kRoundRows;
+}
+
+constexpr uint32_t kBestPer = kSketch4BestMaxWords / (kWavesPerBlock * kWave);  // best words a thread holds
+
+// Kt'' (vt_device.h, Sketch4RescoreArgs::best_words): the k-th smallest of the block's 256 x kBestPer words with multiplicity,
+// v[] this thread's (0xffffffff: an empty word, or none).  Exact, by counting: U = the k-th smallest of the threads' minima
+// is the word of k distinct places, so Kt'' <= U, and a word below U lies with a thread whose minimum is below U -- fewer
+// than k threads, at most 16 (k - 1) <= 256 words (k <= kSketch4BestMaxK): they are filed a word per thread, and Kt'' is
+// their k-th smallest where they number k or more, U otherwise.  With fewer than k live words the k-th smallest is an empty
+// word: the open threshold.  Called by the whole block, every block alike: no block reads another's.
+__device__ __forceinline__ uint32_t best_select(const uint32_t (&v)[kBestPer], uint32_t k, uint32_t tid) {
+  __shared__ __align__(16) uint32_t s_w[kWavesPerBlock * kWave];
+  __shared__ uint32_t s_u, s_kt, s_below;
+  static_assert(16 * (kSketch4BestMaxK - 1) <= kWavesPerBlock * kWave && kBestPer == 16, "the words below U fit a word per thread");
+  uint32_t mine = 0xffffffffu;
+#pragma unroll
+  for (uint32_t u = 0; u < kBestPer; ++u) mine = v[u] < mine ? v[u] : mine;
+  s_w[tid] = mine;
+  if (tid == 0) s_below = 0;
+  __syncthreads();
+  auto place = [&](uint32_t x, uint32_t count, uint32_t *out) {  // *out = x where x is the k-th smallest of s_w[0..count)
+    uint32_t lt = 0, le = 0;
+    for (uint32_t j = 0; j < count; j += 4) {
+      const uint4 o = *reinterpret_cast<const uint4 *>(s_w + j);
+      lt += (o.x < x ? 1u : 0u) + (j + 1 < count && o.y < x ? 1u : 0u) + (j + 2 < count && o.z < x ? 1u : 0u) + (j + 3 < count && o.w < x ? 1u : 0u);
+      le += (o.x <= x ? 1u : 0u) + (j + 1 < count && o.y <= x ? 1u : 0u) + (j + 2 < count && o.z <= x ? 1u : 0u) + (j + 3 < count && o.w <= x ? 1u : 0u);
+    }
+    if (lt < k && k <= le) *out = x;  // (every thread that gets here writes the same word)
+  };
+  place(mine, kWavesPerBlock * kWave, &s_u);
+  __syncthreads();
+  const uint32_t ub = s_u;
+  if (mine < ub) {
+#pragma unroll
+    for (uint32_t u = 0; u < kBestPer; ++u)
+      if (v[u] < ub) s_w[atomicAdd(&s_below, 1u)] = v[u];
+  }
+  __syncthreads();
+  const uint32_t below = s_below;
+  if (below < k) return ub;
+  if (tid < below) place(s_w[tid], below, &s_kt);
+  __syncthreads();
+  return s_kt;
 }
 
 // NSEG: segments per row, 0: a.ld says (more than kStaticSegs)
@@ -56,7 +103,29 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, 4) void sketch4_rescore_kern
   const uint32_t slots = kSketch4BlockLists * a.kp, first = blockIdx.x * slots;
   const uint32_t h = tid < slots ? a.hi_words[first + tid] : 0xffffffffu;
   const uint32_t row = tid < slots ? a.pay[first + tid].row : 0u;  // (an empty slot's payload was never written: loaded, not used)
-  const uint32_t kt = *f.hi_word;
+  // (the threshold from the pass's best rows: their words ride in the same trip, sixteen a thread, four loads of 16 bytes
+  // where four words are there)
+  uint32_t bw[kBestPer];
+#pragma unroll
+  for (uint32_t u = 0; u < kBestPer; ++u) bw[u] = 0xffffffffu;
+  if (a.best_words) {
+#pragma unroll
+    for (uint32_t j = 0; j < kBestPer / 4; ++j) {
+      const uint32_t at = (j * blockDim.x + tid) * 4u;
+      if (at + 4u <= a.best_count) {
+        const uint4 w = *reinterpret_cast<const uint4 *>(a.best_words + at);
+        bw[4 * j] = w.x;
+        bw[4 * j + 1] = w.y;
+        bw[4 * j + 2] = w.z;
+        bw[4 * j + 3] = w.w;
+      } else {
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e)
+          if (at + e < a.best_count) bw[4 * j + e] = a.best_words[at + e];
+      }
+    }
+  }
+  uint32_t kt = a.best_words ? 0u : *f.hi_word;
   for (uint32_t i = tid; i < a.ld; i += blockDim.x) lds[i] = f.q[i];
   if (tid < kSketch4BlockLists) lcnt[tid] = 0;
   if (tid == 0) {
@@ -64,6 +133,10 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, 4) void sketch4_rescore_kern
     *filter_stored_flag() = 0;
   }
   __syncthreads();
+  if (a.best_words) {  // (the head: before any row is asked for)
+    kt = best_select(bw, f.k, tid);
+    if (blockIdx.x == 0 && tid == 0) *a.kt_out = kt;
+  }
 
   // the block's own lists: candidates' rows to LDS, each list's count
   {  // (whole waves: the claim votes)
@@ -264,8 +337,11 @@ hipError_t launch_sketch4_rescore(Sketch4RescoreArgs a, uint32_t blocks, hipStre
   const ScanArgs &f = a.s;
   const size_t lds = sketch4_rescore_lds_bytes(f.d, a.kp);
   if (!lds || blocks == 0 || f.k == 0 || f.k > (uint32_t)kSmallK || f.k > a.kp || metric_op(f.metric) != OP_DOT || f.has_lo ||
-      f.stride < padded_dim(f.d) || !f.X || !f.q || !a.hi_words || !a.pay || !f.hi_word || !f.surv_keys || !f.surv_pay ||
-      f.surv_cap == 0 || f.surv_cap > kScanFilterCap || !f.fsync || !f.out || !f.info || !f.status)
+      f.stride < padded_dim(f.d) || !f.X || !f.q || !a.hi_words || !a.pay || (!f.hi_word && !a.best_words) || !f.surv_keys ||
+      !f.surv_pay || f.surv_cap == 0 || f.surv_cap > kScanFilterCap || !f.fsync || !f.out || !f.info || !f.status)
+    return hipErrorInvalidValue;
+  if (a.best_words && (a.best_count == 0 || a.best_count > kSketch4BestMaxWords || f.k > kSketch4BestMaxK || !a.kt_out ||
+                       reinterpret_cast<uintptr_t>(a.best_words) % 16))
     return hipErrorInvalidValue;
   a.ld = padded_dim(f.d);
   a.ss = a.ld / 8 + 12;

@@ -2,6 +2,7 @@
 // holds a Plane policy per width, the kernels and the launchers; layout: vt_device.h, Sketch6ScanArgs; bounds: DESIGN 4.10):
 // the row builder and the pass, each written once, and the small helpers the pass is made of.
 #pragma once
+#include "vt_rowscore.cuh"
 #include "vt_sketch.cuh"
 
 namespace vt {
@@ -123,6 +124,65 @@ __device__ __forceinline__ int dot8x4(const u32x4 x, const u32x4 q, int acc) {
   return acc;
 }
 
+__device__ __forceinline__ uint32_t wave_min_u(uint32_t v) {
+#pragma unroll
+  for (int o = kWave / 2; o > 0; o >>= 1) {
+    const uint32_t t = (uint32_t)__shfl_xor((int)v, o, kWave);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+
+// K1n's threshold from each list's best rows (vt_device.h, Sketch6ScanArgs::best_words), by the wave that has
+// just stored list `list`: tk holds the list's n entries, slot i with lane i (k <= kWave).  The two live slots of smallest
+// key(lo) word, ties to the lower slot; the loads of both rows and of the query go out before any is waited for, three
+// segments of 256 floats at a time; vt_rowscore.cuh does the rest.  S: 2 ss floats of LDS the wave owns -- its own buffer
+// and that of the wave it absorbed, both done with: nothing of tk is read after the picks.
+template <int CAP>
+__device__ __forceinline__ void nibble_best_rows(const Sketch6ScanArgs &a, const WaveTopK<CAP> &tk, float *S, uint32_t list, int lane) {
+  constexpr uint32_t kSegs = 3;
+  const bool live = (uint32_t)lane < tk.n;
+  const uint64_t p = live ? tk.bp[lane] : 0ull;
+  const uint32_t w0 = live ? orderable(__uint_as_float((uint32_t)(p >> 32))) : 0xffffffffu;
+  const uint32_t m0 = wave_min_u(w0);
+  const int s0 = __ffsll((long long)__ballot(w0 == m0)) - 1;
+  const uint32_t w1 = lane == s0 ? 0xffffffffu : w0;
+  const uint32_t m1 = wave_min_u(w1);
+  const int s1 = __ffsll((long long)__ballot(w1 == m1 && lane != s0)) - 1;
+  const bool has0 = m0 != 0xffffffffu, has1 = m1 != 0xffffffffu;
+  // (a slot that is not there: row 0, loaded and not used)
+  const uint32_t r0 = has0 ? (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p, s0) : 0u;
+  const uint32_t r1 = has1 ? (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)p, s1) : 0u;
+  wave_lds_fence();  // (the picks are read: the buffers are free)
+  const uint32_t ld = padded_dim(a.d), ss = ld / 8 + 12, nseg = (ld + 255u) / 256u;
+  const uint32_t cfull = a.d / 8, tail = a.d % 8, tail_base = ss - 12;
+  const float *x0 = a.X + (size_t)r0 * a.stride, *x1 = a.X + (size_t)r1 * a.stride;
+  const uint32_t l4 = (uint32_t)lane * 4u;
+  const int odd = lane & 1;
+  for (uint32_t g = 0; g < nseg; g += kSegs) {
+    f32x4 v0[kSegs], v1[kSegs], qv[kSegs];
+#pragma unroll
+    for (uint32_t u = 0; u < kSegs; ++u) {  // (a lane past the row's end loads the row's last four floats: nothing is asked for conditionally)
+      const uint32_t col = (g + u) * 256u + l4, colc = col < ld ? col : ld - 4u;
+      v0[u] = *reinterpret_cast<const f32x4 *>(x0 + colc);
+      v1[u] = *reinterpret_cast<const f32x4 *>(x1 + colc);
+      qv[u] = *reinterpret_cast<const f32x4 *>(a.q + colc);
+    }
+#pragma unroll
+    for (uint32_t u = 0; u < kSegs; ++u) {
+      const uint32_t col = (g + u) * 256u + l4;
+      row_chunk<-1>(S, qv[u], v0[u], col, ld, cfull, tail_base, a.order, odd);
+      row_chunk<-1>(S + ss, qv[u], v1[u], col, ld, cfull, tail_base, a.order, odd);
+    }
+  }
+  wave_lds_fence();
+  if (lane < (int)kSketch4BestRows) {
+    uint32_t word;
+    const bool ok = row_rank_word(a.metric, row_chain(S + (uint32_t)lane * ss, cfull, tail, tail_base), &word);
+    a.best_words[(size_t)list * kSketch4BestRows + lane] = (lane ? has1 : has0) && ok ? word : 0xffffffffu;
+  }
+}
+
 // The pass: K1q's skeleton (a wave owns tiles wave, wave + waves, ...; a ring of kU one-KiB non-temporal loads that runs on
 // across tiles; the metadata as the tile's last load; WaveTopK lists of (key(hi), id rank) with key(lo) beside them).
 // What a run multiplies with is wave-uniform, so it never touches a vector register: the query's nibble levels are read
@@ -146,6 +206,8 @@ __device__ __forceinline__ int dot8x4(const u32x4 x, const u32x4 q, int acc) {
 //   l_run()           an L-run's dots
 //   sum()             how a finished tile's sums meet, in f64
 //   gather()          the block's waves into its kBlockLists lists: whether the calling wave holds one to store
+//   kBestRows         whether a storing wave may be asked for its list's best rows' exact keys (nibble_best_rows): a pair of
+//                     waves a list, so that the wave owns two buffers once the list is stored
 // Sums and Words are structs of named members, not arrays: as `int acc[3]` the sums cost the ring its order -- the eight loads
 // ahead of the loop are issued last first, the first slot then waits for all of them (vmcnt(0), no wait in the other
 // seven) and a group of eight runs behind its latest load (profiles/sketch_nibble/isa_counts.txt).
@@ -293,6 +355,10 @@ __device__ __forceinline__ void nibble_pass(const Sketch6ScanArgs &a) {
         wlo[i] = 0xffffffffu;
         whi[i] = 0xffffffffu;
       }
+    }
+    if constexpr (Plane::kBestRows) {
+      // (the storing wave's buffer and the one behind it, which it absorbed: no wave reads either again)
+      if (a.best_words) nibble_best_rows(a, tk, reinterpret_cast<float *>(tkbuf), blockIdx.x * Plane::kBlockLists + list, lane);
     }
   }
 }

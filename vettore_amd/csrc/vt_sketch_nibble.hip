@@ -34,6 +34,7 @@ struct TwoPlanes : NibbleWidth<BITS> {
     }
   };
   static constexpr uint32_t kBlockLists = 1;
+  static constexpr bool kBestRows = false;
   struct Words {
     u32x4 a, b, c, d;
   };
@@ -99,6 +100,8 @@ struct Plane5 : TwoPlanes<5> {
 // c3 / w3, no load issued and awaited inside a slot.  a_r = s_r sum_j t_j acc_j.  Each block leaves TWO lists (waves 0-1,
 // waves 2-3): the intervals are twice K1f's, and the candidates behind the exact threshold (vt_sketch.hip,
 // sketch_refine_kernel) number what K1f's do behind the sketch's own -- with a wider spread, hence twice the slots.
+// The pair's storing wave may be asked for the exact keys of the list's two best rows (kBestRows; nibble_best_rows): the
+// threshold then needs no launch of its own.
 struct Plane4 : NibbleWidth<4> {
   struct Sums {
     int h0 = 0, h1 = 0, h2 = 0;
@@ -115,7 +118,10 @@ struct Plane4 : NibbleWidth<4> {
   };
   static constexpr bool kBlockMajor = false;
   static constexpr uint32_t kBlockLists = kSketch4BlockLists;
+  static constexpr bool kBestRows = true;
   static_assert(kWavesPerBlock == 2 * (int)kSketch4BlockLists, "a list per pair of waves");
+  static_assert(kSketch4BestRows * kSketch4BestRowFloats * sizeof(float) <= 2 * WaveTopK<kCapSmall>::lds_bytes(),
+                "the best rows' chunk sums lie in the pair's two wave buffers");
   struct Words {
     u32x4 a, b, c;
   };
@@ -200,9 +206,14 @@ size_t nibble_scan_lds_bytes(uint32_t runs, uint32_t d, uint32_t k) {
   return kWavesPerBlock * WaveTopK<kCapSmall>::lds_bytes();  // (the list buffers: the query comes through the scalar cache)
 }
 
+// (best_rows: the width's pass takes Sketch6ScanArgs::best_words)
 template <class K>
-hipError_t nibble_launch_scan(K kernel, size_t lds, const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s) {
+hipError_t nibble_launch_scan(K kernel, size_t lds, bool best_rows, const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s) {
   if (!lds || a.ld8 != sketch_ld8(a.d) || blocks == 0 || !a.part_keys || !a.part_pay || !a.lo_words || !a.hi_words)
+    return hipErrorInvalidValue;
+  if (a.best_words && (!best_rows || !a.X || !a.q || a.stride < padded_dim(a.d) || a.k > (uint32_t)kWave ||
+                       padded_dim(a.d) / 8 + 12 > kSketch4BestRowFloats ||
+                       (a.metric != M_COS && a.metric != M_IP && a.metric != M_NIP)))
     return hipErrorInvalidValue;
   hipError_t e = allow_lds(kernel, lds);
   if (e != hipSuccess) return e;
@@ -224,7 +235,7 @@ hipError_t nibble_launch_scan(K kernel, size_t lds, const Sketch6ScanArgs &a, ui
   }                                                                                                                                \
   size_t sketch##N##_scan_lds_bytes(uint32_t d, uint32_t k) { return nibble_scan_lds_bytes(sketch##N##_runs(d), d, k); }           \
   hipError_t launch_sketch##N##_scan(const Sketch6ScanArgs &a, uint32_t blocks, hipStream_t s) {                                   \
-    return nibble_launch_scan(sketch##N##_scan_kernel, sketch##N##_scan_lds_bytes(a.d, a.k), a, blocks, s);                        \
+    return nibble_launch_scan(sketch##N##_scan_kernel, sketch##N##_scan_lds_bytes(a.d, a.k), N == 4, a, blocks, s);                \
   }
 VT_NIBBLE_LAUNCHERS(6)
 VT_NIBBLE_LAUNCHERS(5)
