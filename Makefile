@@ -28,7 +28,7 @@ DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_bat
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch4_best_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch4_best_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so $(LIBDIR)/libvt_select_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -228,6 +228,17 @@ $(LIBDIR)/panel_probe.o: tests/panel_probe.cpp $(CSRC)/vt_device.h $(CSRC)/vt_en
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_panel_probe.so: $(LIBDIR)/vt_cosine.o $(LIBDIR)/vt_prefix_multi.o $(LIBDIR)/panel_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# The selection kernels behind a probe (tests/select_probe.cpp; tests/test_gpu_select_kernels.py loads it): K3's one-block
+# radix select in its five launch forms, the spread select, the list sort, the cross-shard merge and the radix k-th passes
+# with their collect, launched one at a time on a test's arrays -- whole result blocks, lists, counts and the status word
+# read back.  vt_select.o and the probe, nothing else of the library.  Test infrastructure, as above.
+$(LIBDIR)/select_probe.o: tests/select_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_select_probe.so: $(LIBDIR)/vt_select.o $(LIBDIR)/select_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

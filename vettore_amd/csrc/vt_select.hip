@@ -218,6 +218,13 @@ __global__ __launch_bounds__(1024) void select_topk_kernel(const uint64_t *__res
       const uint64_t rem = sh > 0 ? (var & ((1ull << sh) - 1)) : 0ull;
       return rem ? 63 - __clzll((long long)rem) : -1;
     };
+    // Threshold when the walk ends in the bin `prefix`.  The whole bin is selected (its count is what remained): the bin's
+    // top.  Otherwise no varying bit is left below the digit and the bin holds more EQUAL keys than remain: their value is
+    // `prefix` itself (the constant low bits are in it), and the threshold must be that value -- under the bin's top the
+    // equals would pass "key < threshold" and race the strictly smaller keys for the k places.
+    auto bin_threshold = [](uint64_t pfx, int sh, bool whole) -> uint64_t {
+      return whole && sh ? (pfx | ((1ull << sh) - 1)) : pfx;
+    };
     // pass 2: first digit
     for_each_key(keys, m, tid, [&](uint64_t key, uint32_t) {
       if (live(key)) atomicAdd(&hist[(uint32_t)(key >> shift) & dmask], 1u);
@@ -230,7 +237,7 @@ __global__ __launch_bounds__(1024) void select_topk_kernel(const uint64_t *__res
     prefix |= (uint64_t)sb.bin << shift;
     mask |= (uint64_t)dmask << shift;
     if (sb.count == krem || next_hb(shift) < 0) {
-      T = prefix | (shift ? ((1ull << shift) - 1) : 0ull);  // the whole bin is selected
+      T = bin_threshold(prefix, shift, sb.count == krem);
     } else if (sb.count <= kSelCand) {
       // pass 3: winners below the bin, the bin itself into LDS
       const uint64_t bin_lo = prefix, bin_hi = prefix | ((1ull << shift) - 1);
@@ -272,7 +279,7 @@ __global__ __launch_bounds__(1024) void select_topk_kernel(const uint64_t *__res
         prefix |= (uint64_t)sb.bin << shift;
         mask |= (uint64_t)dmask << shift;
         if (sb.count == krem || next_hb(shift) < 0) {
-          Tc = prefix | (shift ? ((1ull << shift) - 1) : 0ull);
+          Tc = bin_threshold(prefix, shift, sb.count == krem);
           break;
         }
         hb = next_hb(shift);
@@ -314,7 +321,7 @@ __global__ __launch_bounds__(1024) void select_topk_kernel(const uint64_t *__res
         prefix |= (uint64_t)sb.bin << shift;
         mask |= (uint64_t)dmask << shift;
         if (sb.count == krem || next_hb(shift) < 0) {
-          T = prefix | (shift ? ((1ull << shift) - 1) : 0ull);
+          T = bin_threshold(prefix, shift, sb.count == krem);
           break;
         }
         hb = next_hb(shift);
