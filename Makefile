@@ -103,6 +103,9 @@ $(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o
 # (the row-panel walk of K6b, K6bm and K1p and the group epilogue of the latter two)
 $(LIBDIR)/vt_cosine.o $(LIBDIR)/vt_prefix_multi.o: $(CSRC)/vt_panel.cuh
 
+# (what the matrix-core nomination passes K2, K2b and K2s share: DMA piece, tile sequence and cursor, epilogue, launch)
+$(LIBDIR)/vt_batch.o $(LIBDIR)/vt_batch_bf16.o $(LIBDIR)/vt_batch_shadow.o: $(CSRC)/vt_nominate.cuh
+
 HOSTHDR := $(wildcard $(CSRC)/host/*.h)
 $(LIBDIR)/vt_index.o: $(CSRC)/vt_index.cpp $(HOSTHDR) $(CSRC)/vt_device.h $(CSRC)/vt_env.h include/vettore_flat.h
 	@mkdir -p $(LIBDIR)

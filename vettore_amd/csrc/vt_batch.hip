@@ -26,20 +26,13 @@
 // registers were measured 6-20 % slower: 32 B per row per instruction.)  k is
 // permuted inside a chunk (lane half h owns k = 16h..16h+15) -- harmless for a sum
 // that only nominates candidates.
-#include "vt_common.cuh"
+//
+// What K2 shares with K2b and K2s -- the DMA piece, the tile sequence and its cursor, the epilogue, the launch -- is in
+// vt_nominate.cuh; the timing experiments (VT_DBG: tools/batch_debug.sh, 2: no barrier, 4: no wait, 8: no append) too.
+#include "vt_nominate.cuh"
 
 #include <algorithm>
 #include <cstdlib>
-
-// Timing experiments on K2 (tools/batch_debug.sh) remove barriers and waits from the hot
-// loop: results are garbage with any bit set, and the host's acceptance test cannot tell.
-// They exist only in builds made with -DVT_BATCH_TIMING_EXPERIMENTS (make EXPERIMENTS=1);
-// the product library ignores VT_BATCH_DEBUG.
-#ifdef VT_BATCH_TIMING_EXPERIMENTS
-#define VT_DBG(a, bit) ((a).debug & (bit))
-#else
-#define VT_DBG(a, bit) false
-#endif
 
 namespace vt {
 
@@ -47,44 +40,8 @@ using namespace dev;
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kRowWaves = 4;  // waves per block, each owning RT * 32 rows of the block's tile
 constexpr int kQStride = 32;        // LDS floats per query row of a 32-k chunk (linear, swizzled slots)
-
-// One LDS-DMA piece: 64 lanes x 16 B from (wave-uniform base + 32-bit lane offset) to
-// LDS at lds_addr + lane * 16.  Written out so that the address is the SGPR-base form
-// (no 64-bit VALU add per piece) and the m0 write sits right in front of the load.
-// m0 is not listed as clobbered (the compiler reserves it); nothing else in these kernels
-// uses it: gfx9+ LDS instructions do not, and there is no register-indexed access.
-__device__ __forceinline__ void dma16(uint32_t lds_addr, const void *base, uint32_t lane_off) {
-  const uint64_t b = reinterpret_cast<uint64_t>(base);
-  const uint64_t sb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(sl), "v"(lane_off), "s"(sb));
-}
-
-// Cold path of the epilogue: some score of this lane's 16 (one query column, 16
-// rows) reaches the threshold.  Inlined into its (rare) branch: as an out-of-line call
-// it made the wave save and restore its live registers, 4 % of the pass.
-__device__ __forceinline__ void append_candidates(const BatchScoreArgs &a, f32x16 v, float tau, uint32_t qcol,
-                                               uint32_t row0, int h) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const uint32_t row = row0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-    const float s = v[i];
-    if (s >= tau && row < a.n_total) {
-      const uint32_t pos = atomicAdd(&a.cand_count[qcol], 1u);
-      if (pos < a.cand_cap) {
-        BatchCand cnd;
-        cnd.score = s;
-        cnd.row = row;
-        a.cand[(size_t)qcol * a.cand_cap + pos] = cnd;
-      }
-    }
-  }
-}
 
 // NT: 32-query tiles in the batch (a wave covers them all: 32 rows x NT*32
 // queries, NT*16 accumulator registers).
@@ -115,7 +72,7 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
   const uint32_t nchunk = a.ld / 32;
   const uint32_t ntiles = (a.n + kTileRowsB - 1) / kTileRowsB;
   if (blockIdx.x >= ntiles) return;
-  const uint32_t my_tiles = (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+  const uint32_t my_tiles = block_tiles(ntiles);
 
   // thresholds of the query columns this lane sees (column = 32*t + r)
   float tau[NT];
@@ -148,7 +105,7 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)qlds;
   auto dma_q = [&](int i, uint32_t c, int stage) {
     const uint32_t dst = lds0 + (uint32_t)(stage * (NQ * kQStride) + (wid * kDmaQ + i) * 8 * kQStride) * 4u;
-    dma16(dst, qbase + (size_t)c * 128, qoff[i]);
+    dma16<false, false>(dst, qbase + (size_t)c * 128, qoff[i]);
   };
   float *xlds = qlds + NS * (NQ * kQStride) + wid * (32 * kQStride);
   uint32_t xoff[kDmaX];      // of the tile the DMA cursor is in, relative to xbase
@@ -156,12 +113,9 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
   auto dma_x = [&](int i, uint32_t c, int stage) {
     const uint32_t dst = lds0 + (uint32_t)(NS * (NQ * kQStride) + wid * (32 * kQStride) +
                                            stage * (kRowWaves * 32 * kQStride) + i * 8 * kQStride) * 4u;
-    dma16(dst, xbase + (size_t)c * 128, xoff[i]);
+    dma16<false, false>(dst, xbase + (size_t)c * 128, xoff[i]);
   };
-  auto tile_row0 = [&](uint32_t k) {
-    const uint32_t tile = blockIdx.x + k * gridDim.x;
-    return (DENSE ? tile * a.sample_stride : tile) * kTileRowsB + wid * 32;  // DENSE: a strided sample of the tiles
-  };
+  auto tile_row0 = [&](uint32_t k) { return index_tile<DENSE>(a, k) * kTileRowsB + wid * 32; };
   auto set_xsrc = [&](uint32_t k) {
     const uint32_t row0 = tile_row0(k);
     const uint32_t block0 = row0 - wid * 32;  // first row of the block tile (< n_total for every tile visited)
@@ -180,20 +134,8 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
 #pragma unroll
     for (int i = 0; i < kDmaQ; ++i) dma_q(i, c, stage);
   };
-  // DMA cursor: tile dk (of this block's), chunk dc
-  uint32_t dk = 0, dc = 0;
-  // past the end of the sequence the cursor stays on the last chunk: the steady
-  // state keeps issuing (into a stage nobody reads any more) so that the loop body
-  // has no branches and the vmcnt arithmetic never changes
-  auto dma_advance = [&]() {
-    if (dc + 1 == nchunk && dk + 1 == my_tiles) return;
-    dc += 1;
-    if (dc == nchunk) {
-      dc = 0;
-      dk += 1;
-      set_xsrc(dk);
-    }
-  };
+  uint32_t dk = 0, dc = 0;  // DMA cursor: tile dk (of this block's), chunk dc
+  auto advance = [&]() { dma_advance(dk, dc, nchunk, my_tiles, set_xsrc); };
 
   f32x4 xa, qv[NT], xa_n, qv_n[NT];
   auto read_frags = [&](int stage, int j, f32x4 &xd, f32x4 *qd) {
@@ -209,9 +151,9 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
   // ring prologue: chunks 0 and 1 of the sequence, fragments of (chunk 0, step 0)
   set_xsrc(0);
   dma_chunk(0, 0);
-  dma_advance();
+  advance();
   dma_chunk(dc, 1);
-  dma_advance();
+  advance();
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kDmaPerChunk) : "memory");
   __builtin_amdgcn_s_barrier();
   read_frags(0, 0, xa, qv);
@@ -265,19 +207,19 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
 #pragma unroll
         for (int t = 0; t < NT; ++t) qv[t] = qv_n[t];
       }
-      dma_advance();
+      advance();
       stage = stage_n;
     }
 
-    // epilogue, one 32x32 tile at a time (C layout: column = lane & 31,
-    // row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5))
+    // epilogue, one 32x32 tile at a time (c32_row).  K2b's tile_epilogue is this but for the norm fetch; one function
+    // for both did not hold (profiles/nominate_header/resources.txt).
     const uint32_t grow0 = tile_row0(k);
     float xn[16];
     if (a.xnorm2) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const uint32_t row = grow0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-        xn[i] = a.xnorm2[row < a.n_total ? row : a.n_total - 1];
+        const uint32_t row = c32_row(grow0, i, h);
+        xn[i] = a.xnorm2[row < a.n_total ? row : a.n_total - 1];  // (clamped vector loads; K2b and K2s: scalar_norms)
       }
     }
 #pragma unroll
@@ -285,23 +227,23 @@ __global__ __launch_bounds__(kRowWaves *kWave) void mfma_scores_kernel(const Bat
       const uint32_t qcol = t * 32 + r;
       f32x16 v = acc[t];
       if (a.xnorm2) {
-        // L2 family: rank by s = 2 q.x - |x|^2 (larger s <=> smaller |q - x|^2)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) v[i] = 2.0f * v[i] - xn[i];
+        for (int i = 0; i < 16; ++i) v[i] = l2_rank(v[i], xn[i]);
       }
       if (DENSE) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const uint32_t off = (i & 3) + 8 * (i >> 2) + 4 * h;
+          const uint32_t off = c32_row(0, i, h);
           // dense sample matrix [query][sample row]
-          const uint32_t srow = (blockIdx.x + k * gridDim.x) * kTileRowsB + wid * 32 + off;
+          const uint32_t srow = sample_tile(k) * kTileRowsB + wid * 32 + off;
           a.sample[(size_t)qcol * a.sample_rows + srow] = grow0 + off < a.n_total ? v[i] : -INFINITY;
         }
       } else {
         float mx = v[0];
 #pragma unroll
         for (int i = 1; i < 16; ++i) mx = fmaxf(mx, v[i]);
-        if (mx >= tau[t] && !VT_DBG(a, 8u)) append_candidates(a, v, tau[t], qcol, grow0, h);
+        if (mx >= tau[t] && !VT_DBG(a, 8u))
+          append_candidates<false, 16>(a, v, tau[t], qcol, [=](int i) { return c32_row(grow0, i, h); });
       }
     }
   }
@@ -394,11 +336,7 @@ __global__ __launch_bounds__(kTauThreads) void sample_tau_kernel(const float *__
 #pragma unroll
       for (int w = 0; w < kTauThreads / kWave; ++w) answer = s_min[w] > answer ? s_min[w] : answer;
     }
-    if (threadIdx.x == 0) {
-      const uint32_t o = ~answer;
-      const uint32_t bits = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-      tau[blockIdx.x] = __uint_as_float(bits);
-    }
+    if (threadIdx.x == 0) tau[blockIdx.x] = from_orderable(~answer);
     return;
   }
   for (int shift = 24; shift >= 0; shift -= 8) {
@@ -447,24 +385,22 @@ __global__ __launch_bounds__(kTauThreads) void sample_tau_kernel(const float *__
     krem -= s_below;
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    // prefix is the key of the rank-th largest score
-    const uint32_t o = ~prefix;
-    const uint32_t bits = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-    tau[blockIdx.x] = __uint_as_float(bits);
-  }
+  if (threadIdx.x == 0) tau[blockIdx.x] = from_orderable(~prefix);  // prefix is the key of the rank-th largest score
 }
 
 // Per-row squared norms (f64 accumulation, stored as f32) and their maximum: the
-// L2-family score term and the row-norm bound of the error margin.
-__global__ __launch_bounds__(256) void row_sqnorm_kernel(const float *__restrict__ X, size_t stride, uint32_t n,
-                                                         uint32_t d, float *__restrict__ xnorm2,
-                                                         unsigned long long *out_bits) {
+// L2-family score term and the row-norm bound of the error margin.  LISTED: of the `n` rows
+// of `list` (norms of mutated rows patched in place), else of rows 0 .. n - 1.
+template <bool LISTED>
+__global__ __launch_bounds__(256) void row_sqnorm_kernel(const float *__restrict__ X, size_t stride,
+                                                         const uint32_t *__restrict__ list, uint32_t n, uint32_t d,
+                                                         float *__restrict__ xnorm2, unsigned long long *out_bits) {
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
   double best = 0.0;
-  for (uint32_t row = wave; row < n; row += nwaves) {
+  for (uint32_t i = wave; i < n; i += nwaves) {
+    const uint32_t row = LISTED ? list[i] : i;
     const float *x = X + (size_t)row * stride;
     double s = 0.0;
     for (uint32_t j = lane; j < d; j += kWave) s += (double)x[j] * (double)x[j];
@@ -474,27 +410,6 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const float *__restrict
     best = s > best ? s : best;
   }
   if (lane == 0) atomicMax(out_bits, (unsigned long long)__double_as_longlong(best));  // s >= 0: bits are monotone
-}
-
-// The same for a list of rows (norms of mutated rows patched in place).
-__global__ __launch_bounds__(256) void row_sqnorm_rows_kernel(const float *__restrict__ X, size_t stride,
-                                                              const uint32_t *__restrict__ list, uint32_t count, uint32_t d,
-                                                              float *__restrict__ xnorm2, unsigned long long *out_bits) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
-  double best = 0.0;
-  for (uint32_t i = wave; i < count; i += nwaves) {
-    const uint32_t row = list[i];
-    const float *x = X + (size_t)row * stride;
-    double s = 0.0;
-    for (uint32_t j = lane; j < d; j += kWave) s += (double)x[j] * (double)x[j];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, kWave);
-    if (lane == 0) xnorm2[row] = (float)s;
-    best = s > best ? s : best;
-  }
-  if (lane == 0) atomicMax(out_bits, (unsigned long long)__double_as_longlong(best));
 }
 
 // Batched K3: block b selects the k smallest of keys[b][0..m) (rank sort; m is small).
@@ -547,20 +462,8 @@ template <int NT>
 hipError_t launch_scores_nt(const BatchScoreArgs &a, bool dense, uint32_t blocks, hipStream_t s) {
   const size_t lds = (size_t)3 * (NT * 32 + kRowWaves * 32) * kQStride * sizeof(float);
   const dim3 block(kRowWaves * kWave);
-  if (dense) {
-    auto kern = mfma_scores_kernel<NT, true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(blocks), block, lds, s, a);
-  } else {
-    auto kern = mfma_scores_kernel<NT, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(blocks), block, lds, s, a);
-  }
-  return hipGetLastError();
+  return dense ? launch_with_lds(mfma_scores_kernel<NT, true>, dim3(blocks), block, lds, s, a)
+               : launch_with_lds(mfma_scores_kernel<NT, false>, dim3(blocks), block, lds, s, a);
 }
 
 }  // namespace
@@ -568,11 +471,9 @@ hipError_t launch_scores_nt(const BatchScoreArgs &a, bool dense, uint32_t blocks
 uint32_t batch_rows_per_block(uint32_t) { return kRowWaves * 32; }
 
 hipError_t launch_batch_scores(const BatchScoreArgs &a0, bool dense, uint32_t blocks, hipStream_t s) {
-  BatchScoreArgs a = a0;
+  BatchScoreArgs a = batch_args_for_launch(a0);
 #ifdef VT_BATCH_TIMING_EXPERIMENTS
-  a.debug = dense ? 0u : (uint32_t)env::get(env::BATCH_DEBUG);
-#else
-  a.debug = 0u;
+  a.debug = dense ? 0u : (uint32_t)env::get(env::BATCH_DEBUG);  // (K2's switches come from the settings table)
 #endif
   if (a.ld % 32 != 0 || a.nq_pad % 32 != 0 || a.nq_pad == 0 || a.nq_pad > 256) return hipErrorInvalidValue;
   switch (a.nq_pad / 32) {
@@ -628,7 +529,7 @@ __global__ __launch_bounds__(256) void sample_tau_groups_kernel(const float *__r
     }
     t = mn;
   }
-  if (lane == 0) tau[q] = __uint_as_float((t & 0x80000000u) ? (t & 0x7FFFFFFFu) : ~t);
+  if (lane == 0) tau[q] = from_orderable(t);
 }
 
 hipError_t launch_sample_tau_groups(const float *maxima, uint32_t groups, uint32_t nq, uint32_t nq_real, uint32_t rank, float *tau,
@@ -647,7 +548,7 @@ hipError_t launch_sample_tau(const float *sample, uint32_t sample_rows, uint32_t
 hipError_t launch_row_sqnorms(const float *X, size_t stride, uint32_t n, uint32_t d, float *xnorm2,
                               unsigned long long *out_bits, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3(2048), dim3(256), 0, s, X, stride, n, d, xnorm2, out_bits);
+  hipLaunchKernelGGL(row_sqnorm_kernel<false>, dim3(2048), dim3(256), 0, s, X, stride, nullptr, n, d, xnorm2, out_bits);
   return hipGetLastError();
 }
 
@@ -655,7 +556,7 @@ hipError_t launch_row_sqnorms_rows(const float *X, size_t stride, const uint32_t
                                    float *xnorm2, unsigned long long *out_bits, hipStream_t s) {
   if (count == 0) return hipSuccess;
   const uint32_t blocks = std::min<uint32_t>(2048, (count + 3) / 4);
-  hipLaunchKernelGGL(row_sqnorm_rows_kernel, dim3(blocks), dim3(256), 0, s, X, stride, list, count, d, xnorm2, out_bits);
+  hipLaunchKernelGGL(row_sqnorm_kernel<true>, dim3(blocks), dim3(256), 0, s, X, stride, list, count, d, xnorm2, out_bits);
   return hipGetLastError();
 }
 

@@ -29,30 +29,21 @@
 // LDS-DMA (128 KiB in flight per CU, hand-counted vmcnt like K1m: 3.19 ms against 3.08 -- depth
 // of the ring is not the limit); fragment reads issued one MFMA step ahead of their use,
 // across the barrier too (compute alone 2.06 ms against 2.07: not the fragment traffic either).
-#include "vt_common.cuh"
+//
+// The DMA piece, the packing, the tile sequence and its cursor, the filing of a candidate and the launch are
+// vt_nominate.cuh's.
+// Timing experiments (VT_DBG there; tools/k2b_probe.hip): 1: no fragment reads / MFMAs, 2: no barrier, 4: no query
+// DMA, 8: no candidate append, 16: no row DMA.
+#include "vt_nominate.cuh"
 
 #include <algorithm>
 #include <cstdlib>
-
-// Timing experiments (tools/k2b_probe.hip): only in builds made with -DVT_BATCH_TIMING_EXPERIMENTS;
-// results are garbage with any bit set.  1: no fragment reads / MFMAs, 2: no barrier, 4: no query
-// DMA, 8: no candidate append, 16: no row DMA.
-#ifdef VT_BATCH_TIMING_EXPERIMENTS
-#define VT_DBG(a, bit) ((a).debug & (bit))
-#else
-#define VT_DBG(a, bit) false
-#endif
 
 namespace vt {
 
 using namespace dev;
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kWavesB = 8;              // waves per block
 constexpr int kRowsB = kWavesB * 32;    // rows per block tile
@@ -69,30 +60,6 @@ constexpr uint32_t kXWaveBytes = 32 * 128;
 // KiB: every wave issues the same number of pieces, which is what the counted wait needs)
 constexpr int q_pieces(int qt) { return qt == 8 ? 2 : 1; }
 
-// One LDS-DMA piece: 64 lanes x 16 B from (wave-uniform base + 32-bit lane offset) to LDS at
-// lds_addr + lane * 16 (see vt_batch.hip: SGPR-base addressing, m0 written right in front).
-// NT: the rows are read once (nt), the query image is re-read by every block (default policy).
-template <bool NT>
-__device__ __forceinline__ void dma16(uint32_t lds_addr, const void *base, uint32_t lane_off) {
-  const uint64_t b = reinterpret_cast<uint64_t>(base);
-  const uint64_t sb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  if (NT) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" : : "s"(sl), "v"(lane_off), "s"(sb) : "memory");
-  else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(sl), "v"(lane_off), "s"(sb) : "memory");
-}
-
-__device__ __forceinline__ bf16x8 pack8(f32x4 lo, f32x4 hi) {
-  const bf16x2 p0 = __builtin_convertvector((f32x2){lo[0], lo[1]}, bf16x2);
-  const bf16x2 p1 = __builtin_convertvector((f32x2){lo[2], lo[3]}, bf16x2);
-  const bf16x2 p2 = __builtin_convertvector((f32x2){hi[0], hi[1]}, bf16x2);
-  const bf16x2 p3 = __builtin_convertvector((f32x2){hi[2], hi[3]}, bf16x2);
-  bf16x8 o;
-  o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1];
-  o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
-  return o;
-}
-
 // The queries as the B operand wants them: image[c][t][s][lane = 32h + r][e] =
 // bf16(Q[32t + r][32c + 16h + 8s + e]) -- a fragment read is 1 KiB of consecutive lanes.
 __global__ __launch_bounds__(256) void q_image_kernel(const float *__restrict__ Q, uint32_t ld, uint32_t nchunk, uint32_t qt,
@@ -105,49 +72,21 @@ __global__ __launch_bounds__(256) void q_image_kernel(const float *__restrict__ 
   image[i] = pack8(*reinterpret_cast<const f32x4 *>(src), *reinterpret_cast<const f32x4 *>(src + 4));
 }
 
-// Cold path of the epilogue (as in vt_batch.hip): a score of this lane's 16 reaches tau.
-__device__ __forceinline__ void append_candidates(const BatchScoreArgs &a, f32x16 v, float tau, uint32_t qcol,
-                                                  uint32_t row0, int h) {
-  // (the list addresses are loop-invariant; hoisted out of the tile loop they cost 16 registers
-  // this kernel does not have -- the compiler may not know where qcol comes from)
-  asm volatile("" : "+v"(qcol));
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const uint32_t row = row0 + (i & 3) + 8 * (i >> 2) + 4 * h;
-    const float s = v[i];
-    if (s >= tau && row < a.n_total) {
-      const uint32_t pos = atomicAdd(&a.cand_count[qcol], 1u);
-      if (pos < a.cand_cap) {
-        BatchCand cnd;
-        cnd.score = s;
-        cnd.row = row;
-        a.cand[(size_t)qcol * a.cand_cap + pos] = cnd;
-      }
-    }
-  }
-}
-
-// What a wave does with a finished 32-row x 256-query tile (C layout: column = lane & 31 =
-// query, row = (i & 3) + 8 * (i >> 2) + 4 * (lane >> 5)): pass 0 writes the dense sample
-// matrix, pass 1 appends the scores that reach the query's threshold.
+// What a wave does with a finished 32-row x 256-query tile (c32_row): pass 0 writes the dense sample
+// matrix, pass 1 appends the scores that reach the query's threshold.  grow0 / srow0: the wave's first
+// row in the index / in the sample.
 template <bool DENSE, int QT>
 __device__ __forceinline__ void tile_epilogue(const BatchScoreArgs &a, f32x16 (&acc)[QT], const float (&tau)[QT],
                                               uint32_t grow0, uint32_t srow0, int r, int h) {
-  // L2 family: the 32 row norms of this wave's tile.  The address is wave-uniform, so they come
-  // through the scalar cache (constant address space => s_load): a vector load here would sit in
-  // the same in-order queue as the row DMA, and the wait for it would drain the ring once per tile.
-  // (the norm column is as long as the slab's row capacity, a multiple of 32: a tile that starts
-  // below n_total ends inside it)
+  // L2 family: the 32 row norms of this wave's tile (scalar_norms)
   float xn[16];
   if (a.xnorm2) {
-    typedef const __attribute__((address_space(4))) float *cfloat_p;
     const uint32_t g0 = __builtin_amdgcn_readfirstlane(grow0);
     if (g0 < a.n_total) {
-      cfloat_p xc = (cfloat_p)(uintptr_t)(a.xnorm2 + g0);
+      scalar_f32_p xc = scalar_norms(a, g0);
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int off = (i & 3) + 8 * (i >> 2);
-        const float lo = xc[off], hi = xc[off + 4];
+        const float lo = xc[c32_row(0, i, 0)], hi = xc[c32_row(0, i, 1)];
         xn[i] = h ? hi : lo;
       }
     } else {
@@ -157,20 +96,17 @@ __device__ __forceinline__ void tile_epilogue(const BatchScoreArgs &a, f32x16 (&
   }
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
-    const uint32_t qcol = t * 32 + r;
+    uint32_t qcol = t * 32 + r;
     f32x16 v = acc[t];
     if (a.xnorm2) {
-      // L2 family: rank by s = 2 q.x - |x|^2 (larger s <=> smaller |q - x|^2)
 #pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = 2.0f * v[i] - xn[i];
+      for (int i = 0; i < 16; ++i) v[i] = l2_rank(v[i], xn[i]);
     }
     if (DENSE) {
-      uint32_t qc2 = qcol;
-      asm volatile("" : "+v"(qc2));  // (as in append_candidates: no hoisted address arithmetic)
-      const uint32_t qcol = qc2;
+      asm volatile("" : "+v"(qcol));  // (as in append_candidates: no hoisted address arithmetic)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const uint32_t off = (i & 3) + 8 * (i >> 2) + 4 * h;
+        const uint32_t off = c32_row(0, i, h);
         // dense sample matrix [query][sample row]
         a.sample[(size_t)qcol * a.sample_rows + srow0 + off] = grow0 + off < a.n_total ? v[i] : -INFINITY;
       }
@@ -178,7 +114,8 @@ __device__ __forceinline__ void tile_epilogue(const BatchScoreArgs &a, f32x16 (&
       float mx = v[0];
 #pragma unroll
       for (int i = 1; i < 16; ++i) mx = fmaxf(mx, v[i]);
-      if (mx >= tau[t] && !VT_DBG(a, 8u)) append_candidates(a, v, tau[t], qcol, grow0, h);
+      if (mx >= tau[t] && !VT_DBG(a, 8u))
+        append_candidates<true, 16>(a, v, tau[t], qcol, [=](int i) { return c32_row(grow0, i, h); });
     }
   }
 }
@@ -194,7 +131,7 @@ __global__ __launch_bounds__(kWavesB *kWave, 1) void bf16_scores_kernel(const Ba
   const uint32_t nchunk = a.ld / 32;
   const uint32_t ntiles = (a.n + kRowsB - 1) / kRowsB;
   if (blockIdx.x >= ntiles) return;
-  const uint32_t my_tiles = (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+  const uint32_t my_tiles = block_tiles(ntiles);
 
   float tau[QT];
 #pragma unroll
@@ -212,10 +149,7 @@ __global__ __launch_bounds__(kWavesB *kWave, 1) void bf16_scores_kernel(const Ba
   // rows: piece i = rows 8i .. 8i+7 of this wave's 32, lane L -> row L / 8, physical slot L % 8
   uint32_t xoff[4];
   const char *xbase = nullptr;  // first row of the DMA cursor's block tile (wave-uniform)
-  auto tile_row0 = [&](uint32_t k) {
-    const uint32_t tile = blockIdx.x + k * gridDim.x;
-    return (DENSE ? tile * a.sample_stride : tile) * kRowsB + wid * 32;
-  };
+  auto tile_row0 = [&](uint32_t k) { return index_tile<DENSE>(a, k) * kRowsB + wid * 32; };
   auto set_xsrc = [&](uint32_t k) {
     const uint32_t row0 = tile_row0(k);
     const uint32_t block0 = row0 - wid * 32;
@@ -239,24 +173,14 @@ __global__ __launch_bounds__(kWavesB *kWave, 1) void bf16_scores_kernel(const Ba
         dma16<false>(lds0 + stage * kQStageBytes + (qkib + i) * 1024, qimg + (size_t)c * kQStageBytes + i * 1024, qoff);
     }
   };
-  // DMA cursor; past the end of this block's sequence it stays on the last chunk, so the loop
-  // body has no branches and the vmcnt arithmetic never changes
-  uint32_t dk = 0, dc = 0;
-  auto dma_advance = [&]() {
-    if (dc + 1 == nchunk && dk + 1 == my_tiles) return;
-    dc += 1;
-    if (dc == nchunk) {
-      dc = 0;
-      dk += 1;
-      set_xsrc(dk);
-    }
-  };
+  uint32_t dk = 0, dc = 0;  // DMA cursor: tile dk (of this block's), chunk dc
+  auto advance = [&]() { dma_advance(dk, dc, nchunk, my_tiles, set_xsrc); };
 
   set_xsrc(0);
   dma_chunk(0, 0);
-  dma_advance();
+  advance();
   dma_chunk(dc, 1);
-  dma_advance();
+  advance();
 
   // fragment addresses of this lane inside a stage (the swizzle depends on r only)
   uint32_t xfrag[4];
@@ -281,7 +205,7 @@ __global__ __launch_bounds__(kWavesB *kWave, 1) void bf16_scores_kernel(const Ba
       if (!VT_DBG(a, 2u)) __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       dma_chunk(__builtin_amdgcn_readfirstlane(dc), stage_a);
-      dma_advance();
+      advance();
       if (VT_DBG(a, 1u)) {
         stage = stage == kStages - 1 ? 0 : stage + 1;
         continue;
@@ -312,10 +236,9 @@ __global__ __launch_bounds__(kWavesB *kWave, 1) void bf16_scores_kernel(const Ba
       stage = stage == kStages - 1 ? 0 : stage + 1;
     }
 
-    tile_epilogue<DENSE, QT>(a, acc, tau, tile_row0(k), (blockIdx.x + k * gridDim.x) * kRowsB + wid * 32, r, h);
+    tile_epilogue<DENSE, QT>(a, acc, tau, tile_row0(k), sample_tile(k) * kRowsB + wid * 32, r, h);
   }
 }
-
 
 }  // namespace
 
@@ -332,31 +255,20 @@ hipError_t launch_batch_q_image(const float *Q, uint32_t ld, uint32_t nq_pad, vo
   return hipGetLastError();
 }
 
-template <class K>
-hipError_t launch_one(K kern, size_t lds_bytes, const BatchScoreArgs &a, uint32_t blocks, hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWavesB * kWave), lds_bytes, s, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_batch_scores_bf16(const BatchScoreArgs &a0, bool dense, uint32_t blocks, hipStream_t s) {
-  BatchScoreArgs a = a0;
-#ifndef VT_BATCH_TIMING_EXPERIMENTS
-  a.debug = 0u;
-#endif
+  const BatchScoreArgs a = batch_args_for_launch(a0);
   if (a.ld % 32 != 0 || (a.nq_pad != 256 && a.nq_pad != 128 && a.nq_pad != 64) || a.Qimage == nullptr) return hipErrorInvalidValue;
   const int qt = (int)a.nq_pad / 32;
   const size_t lds_bytes = (size_t)kStages * (q_stage_bytes(qt) + kXStageBytes);
+  const dim3 grid(blocks), block(kWavesB * kWave);
   if (qt == 8)
-    return dense ? launch_one(bf16_scores_kernel<true, 8>, lds_bytes, a, blocks, s)
-                 : launch_one(bf16_scores_kernel<false, 8>, lds_bytes, a, blocks, s);
+    return dense ? launch_with_lds(bf16_scores_kernel<true, 8>, grid, block, lds_bytes, s, a)
+                 : launch_with_lds(bf16_scores_kernel<false, 8>, grid, block, lds_bytes, s, a);
   if (qt == 4)
-    return dense ? launch_one(bf16_scores_kernel<true, 4>, lds_bytes, a, blocks, s)
-                 : launch_one(bf16_scores_kernel<false, 4>, lds_bytes, a, blocks, s);
-  return dense ? launch_one(bf16_scores_kernel<true, 2>, lds_bytes, a, blocks, s)
-               : launch_one(bf16_scores_kernel<false, 2>, lds_bytes, a, blocks, s);
+    return dense ? launch_with_lds(bf16_scores_kernel<true, 4>, grid, block, lds_bytes, s, a)
+                 : launch_with_lds(bf16_scores_kernel<false, 4>, grid, block, lds_bytes, s, a);
+  return dense ? launch_with_lds(bf16_scores_kernel<true, 2>, grid, block, lds_bytes, s, a)
+               : launch_with_lds(bf16_scores_kernel<false, 2>, grid, block, lds_bytes, s, a);
 }
 
 }  // namespace vt

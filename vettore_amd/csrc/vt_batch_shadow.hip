@@ -27,7 +27,10 @@
 // The chunk sequence runs through all of the block's tiles; fragments of chunk m + 1 are read
 // under the MFMAs of chunk m (their registers rotate in place), so right behind the barrier both
 // waves of a SIMD have matrix work at hand.  One counted vmcnt + one raw s_barrier per chunk.
-#include "vt_common.cuh"
+//
+// The DMA piece, the packing, the tile sequence and its cursor, the filing of a candidate and the launch are
+// vt_nominate.cuh's.
+#include "vt_nominate.cuh"
 
 #include <algorithm>
 #include <cstdlib>
@@ -45,10 +48,6 @@ using namespace dev;
 
 namespace {
 
-typedef float f32x2s __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2s __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8s __attribute__((ext_vector_type(8)));
-
 constexpr int kWavesS = 8;               // waves per block: 4 row groups x 2 query halves
 constexpr int kRowsS = 256;              // rows per block tile
 constexpr int kRT = 4;                   // 16-row accumulator tiles per wave
@@ -56,23 +55,12 @@ constexpr uint32_t kAStage = 16 * 1024;  // a chunk of a block tile: 256 rows x 
 constexpr uint32_t b_stage(int qtw) { return (uint32_t)qtw * 2 * 1024; }  // 2 halves x QTW tiles x 1 KiB
 constexpr int b_pieces(int qtw) { return qtw == 8 ? 2 : 1; }              // per wave and chunk (QTW = 2: waves w and w + 4 copy the same KiB)
 
-__device__ __forceinline__ bf16x8s pack8s(f32x4 lo, f32x4 hi) {
-  const bf16x2s p0 = __builtin_convertvector((f32x2s){lo[0], lo[1]}, bf16x2s);
-  const bf16x2s p1 = __builtin_convertvector((f32x2s){lo[2], lo[3]}, bf16x2s);
-  const bf16x2s p2 = __builtin_convertvector((f32x2s){hi[0], hi[1]}, bf16x2s);
-  const bf16x2s p3 = __builtin_convertvector((f32x2s){hi[2], hi[3]}, bf16x2s);
-  bf16x8s o;
-  o[0] = p0[0]; o[1] = p0[1]; o[2] = p1[0]; o[3] = p1[1];
-  o[4] = p2[0]; o[5] = p2[1]; o[6] = p3[0]; o[7] = p3[1];
-  return o;
-}
-
 // ---- the image: built once, patched per mutated row ------------------------------------------
 // One wave per (16-row tile, 32-column chunk): lane 16 g + r reads 8 floats of row r (the four
 // lanes of a row 128 contiguous bytes), writes its 16 bytes of the fragment.  Rows >= rows_src do
 // not exist in the slab (the image is padded to whole block tiles): zeros.
 __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restrict__ X, size_t stride, uint32_t rows_src,
-                                                           uint32_t rows_img, uint32_t ld, bf16x8s *__restrict__ img) {
+                                                           uint32_t rows_img, uint32_t ld, bf16x8 *__restrict__ img) {
   const uint32_t nchunk = ld >> 5;
   const size_t units = (size_t)(rows_img >> 4) * nchunk;
   const int lane = threadIdx.x & 63;
@@ -87,7 +75,7 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float *__restri
       lo = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(src));
       hi = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(src + 4));
     }
-    img[u * 64 + lane] = pack8s(lo, hi);
+    img[u * 64 + lane] = pack8(lo, hi);
   }
 }
 
@@ -101,52 +89,23 @@ __global__ __launch_bounds__(256) void shadow_rows_kernel(const float *__restric
   const float *src = X + (size_t)row * stride;
   for (uint32_t p = lane; p < ld / 8; p += 64) {
     const f32x4 lo = *reinterpret_cast<const f32x4 *>(src + 8 * p), hi = *reinterpret_cast<const f32x4 *>(src + 8 * p + 4);
-    *reinterpret_cast<bf16x8s *>(img + shadow_index(row, 8 * p, ld)) = pack8s(lo, hi);
+    *reinterpret_cast<bf16x8 *>(img + shadow_index(row, 8 * p, ld)) = pack8(lo, hi);
   }
 }
 
 // The queries in the same fragment order, chunk-major: image[c][query / 16][g][query % 16][e] =
 // bf16(Q[query][32 c + 8 g + e]) -- a chunk's B operand is one run of nq_pad * 64 bytes.
 __global__ __launch_bounds__(256) void q_image16_kernel(const float *__restrict__ Q, uint32_t ld, uint32_t nchunk, uint32_t nqt,
-                                                        bf16x8s *__restrict__ image) {
+                                                        bf16x8 *__restrict__ image) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // one 16-B fragment slot each
   if (i >= nchunk * nqt * 64) return;
   const uint32_t lane = i & 63, qt = (i >> 6) % nqt, c = (i >> 6) / nqt;
   const uint32_t r = lane & 15, g = lane >> 4;
   const float *src = Q + (size_t)(16 * qt + r) * ld + 32 * c + 8 * g;
-  image[i] = pack8s(*reinterpret_cast<const f32x4 *>(src), *reinterpret_cast<const f32x4 *>(src + 4));
+  image[i] = pack8(*reinterpret_cast<const f32x4 *>(src), *reinterpret_cast<const f32x4 *>(src + 4));
 }
 
 // ---- the pass ---------------------------------------------------------------------------------
-template <bool NT>
-__device__ __forceinline__ void dma16s(uint32_t lds_addr, const void *base, uint32_t lane_off) {
-  const uint64_t b = reinterpret_cast<uint64_t>(base);
-  const uint64_t sb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
-                      (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)b);
-  const uint32_t sl = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  if (NT) asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 nt" : : "s"(sl), "v"(lane_off), "s"(sb) : "memory");
-  else asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(sl), "v"(lane_off), "s"(sb) : "memory");
-}
-
-// Cold path of the epilogue: one of this lane's 4 scores of a 16 x 16 tile reaches tau.
-__device__ __forceinline__ void append_candidates16(const BatchScoreArgs &a, f32x4 v, float tau, uint32_t qcol, uint32_t row0) {
-  asm volatile("" : "+v"(qcol));  // (no list address arithmetic hoisted out of the tile loop: it would cost registers all the time)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t row = row0 + i;
-    const float s = v[i];
-    if (s >= tau && row < a.n_total) {
-      const uint32_t pos = atomicAdd(&a.cand_count[qcol], 1u);
-      if (pos < a.cand_cap) {
-        BatchCand cnd;
-        cnd.score = s;
-        cnd.row = row;
-        a.cand[(size_t)qcol * a.cand_cap + pos] = cnd;
-      }
-    }
-  }
-}
-
 // A wave's finished 64-row x (16 QTW)-query tile (C layout of 16x16x32: column = lane & 15 = query,
 // row = 4 (lane >> 4) + register).  MODE 0 (the pass): scores that reach the query's threshold are appended.
 // MODE 1 (dense): the whole sample matrix is written (tools/k2s_probe compares it with K2b's).  MODE 2 (r05, what the
@@ -165,16 +124,12 @@ __device__ __forceinline__ void tile_epilogue16(const BatchScoreArgs &a, f32x4 (
   }
 #pragma unroll
   for (int i = 0; i < kRT; ++i) {
-    // L2 family: the 16 row norms of this sub-tile through the scalar cache (a vector load would sit in
-    // the DMA's in-order queue, and waiting for it would drain the ring once per tile); the norm
-    // column is as long as the slab's row capacity, a multiple of 32: a sub-tile that starts below
-    // n_total ends inside it.
+    // L2 family: the 16 row norms of this sub-tile (scalar_norms)
     float xn[4] = {0.f, 0.f, 0.f, 0.f};
     if (a.xnorm2) {
-      typedef const __attribute__((address_space(4))) float *cfloat_p;
       const uint32_t g0 = __builtin_amdgcn_readfirstlane(grow0 + 16 * i);
       if (g0 < a.n_total) {
-        cfloat_p xc = (cfloat_p)(uintptr_t)(a.xnorm2 + g0);
+        scalar_f32_p xc = scalar_norms(a, g0);
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const float s0 = xc[v], s1 = xc[4 + v], s2 = xc[8 + v], s3 = xc[12 + v];
@@ -182,27 +137,26 @@ __device__ __forceinline__ void tile_epilogue16(const BatchScoreArgs &a, f32x4 (
         }
       }
     }
-    const uint32_t row0 = grow0 + 16 * i + 4 * g;
+    const uint32_t row0 = c16_row(grow0 + 16 * i, g, 0);
 #pragma unroll
     for (int j = 0; j < QTW; ++j) {
       f32x4 v = acc[i][j];
       if (a.xnorm2) {
-        // L2 family: rank by s = 2 q.x - |x|^2 (larger s <=> smaller |q - x|^2)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = 2.0f * v[e] - xn[e];
+        for (int e = 0; e < 4; ++e) v[e] = l2_rank(v[e], xn[e]);
       }
       uint32_t qcol = qbase + 16 * j + c16;
       if (MODE == kModeDense) {
         asm volatile("" : "+v"(qcol));
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-          a.sample[(size_t)qcol * a.sample_rows + srow0 + 16 * i + 4 * g + e] = row0 + e < a.n_total ? v[e] : -INFINITY;
+          a.sample[(size_t)qcol * a.sample_rows + c16_row(srow0 + 16 * i, g, e)] = row0 + e < a.n_total ? v[e] : -INFINITY;
       } else if (MODE == kModeMaxima) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) gmax[j] = fmaxf(gmax[j], row0 + e < a.n_total ? v[e] : -INFINITY);
       } else {
         const float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-        if (mx >= tau[j] && !VT_SDBG(a, 8u)) append_candidates16(a, v, tau[j], qcol, row0);
+        if (mx >= tau[j] && !VT_SDBG(a, 8u)) append_candidates<true, 4>(a, v, tau[j], qcol, [=](int e) { return row0 + e; });
       }
     }
   }
@@ -231,7 +185,7 @@ __global__ __launch_bounds__(kWavesS *kWave, 1) void shadow_scores_kernel(const 
   const uint32_t nchunk = a.ld / 32;
   const uint32_t ntiles = (a.n + kRowsS - 1) / kRowsS;
   if (blockIdx.x >= ntiles) return;
-  const uint32_t my_tiles = (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
+  const uint32_t my_tiles = block_tiles(ntiles);
   const uint32_t qbase = (uint32_t)qh * QTW * 16;
 
   float tau[QTW];
@@ -256,53 +210,39 @@ __global__ __launch_bounds__(kWavesS *kWave, 1) void shadow_scores_kernel(const 
   const uint32_t aoff0 = (uint32_t)(2 * wid) * nchunk * 1024u + (uint32_t)lane * 16u, aoff1 = aoff0 + nchunk * 1024u;
   const uint32_t qkib = QTW == 8 ? (uint32_t)wid * 2 : QTW == 4 ? (uint32_t)wid : (uint32_t)wid & 3u;
   const uint32_t qoff = qkib * 1024 + (uint32_t)lane * 16u;
-  auto tile_index = [&](uint32_t k) {
-    const uint32_t tile = blockIdx.x + k * gridDim.x;
-    return DENSE ? tile * a.sample_stride : tile;
-  };
   const char *xbase = nullptr;  // the DMA cursor's block tile in the image (wave-uniform)
-  auto set_xsrc = [&](uint32_t k) { xbase = ximg + (size_t)tile_index(k) * 16 * nchunk * 1024; };
+  auto set_xsrc = [&](uint32_t k) { xbase = ximg + (size_t)index_tile<DENSE>(a, k) * 16 * nchunk * 1024; };
   auto dma_chunk = [&](uint32_t c, uint32_t stage) {
     const uint32_t sb = lds0 + stage * kStage;
     if (!VT_SDBG(a, 16u)) {
-      dma16s<true>(sb + (uint32_t)(2 * wid) * 1024, xbase + (size_t)c * 1024, aoff0);
-      dma16s<true>(sb + (uint32_t)(2 * wid + 1) * 1024, xbase + (size_t)c * 1024, aoff1);
+      dma16<true>(sb + (uint32_t)(2 * wid) * 1024, xbase + (size_t)c * 1024, aoff0);
+      dma16<true>(sb + (uint32_t)(2 * wid + 1) * 1024, xbase + (size_t)c * 1024, aoff1);
     }
     if (!VT_SDBG(a, 4u)) {
 #pragma unroll
       for (int i = 0; i < b_pieces(QTW); ++i)
-        dma16s<false>(sb + kAStage + (qkib + i) * 1024, qimg + (size_t)c * kBStage + i * 1024, qoff);
+        dma16<false>(sb + kAStage + (qkib + i) * 1024, qimg + (size_t)c * kBStage + i * 1024, qoff);
     }
   };
-  // DMA cursor; past the end of this block's sequence it stays on the last chunk, so the loop
-  // body has no branches and the vmcnt arithmetic never changes
-  uint32_t dk = 0, dc = 0;
-  auto dma_advance = [&]() {
-    if (dc + 1 == nchunk && dk + 1 == my_tiles) return;
-    dc += 1;
-    if (dc == nchunk) {
-      dc = 0;
-      dk += 1;
-      set_xsrc(dk);
-    }
-  };
+  uint32_t dk = 0, dc = 0;  // DMA cursor: tile dk (of this block's), chunk dc
+  auto advance = [&]() { dma_advance(dk, dc, nchunk, my_tiles, set_xsrc); };
 
   set_xsrc(0);
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     dma_chunk(dc, s);
-    dma_advance();
+    advance();
   }
 
   // this lane's fragment addresses inside a stage
   const uint32_t afrag = (uint32_t)(rg * kRT) * 1024 + (uint32_t)lane * 16;
   const uint32_t bfrag = kAStage + (uint32_t)(qh * QTW) * 1024 + (uint32_t)lane * 16;
-  bf16x8s af[kRT], bq[QTW];
+  bf16x8 af[kRT], bq[QTW];
   auto read_a = [&](uint32_t stage, int i) {
-    return *reinterpret_cast<const bf16x8s *>(lds + stage * kStage + afrag + i * 1024);
+    return *reinterpret_cast<const bf16x8 *>(lds + stage * kStage + afrag + i * 1024);
   };
   auto read_b = [&](uint32_t stage, int j) {
-    return *reinterpret_cast<const bf16x8s *>(lds + stage * kStage + bfrag + j * 1024);
+    return *reinterpret_cast<const bf16x8 *>(lds + stage * kStage + bfrag + j * 1024);
   };
 
   // chunk 0 has landed (the other S - 1 stay in flight) -- for every wave behind the barrier
@@ -332,7 +272,7 @@ __global__ __launch_bounds__(kWavesS *kWave, 1) void shadow_scores_kernel(const 
       if (!VT_SDBG(a, 2u)) __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       dma_chunk(__builtin_amdgcn_readfirstlane(dc), stage);
-      dma_advance();
+      advance();
       __builtin_amdgcn_sched_barrier(0);
       if (!VT_SDBG(a, 1u)) {
         // 4 MFMAs per query tile, then that tile's fragment of the NEXT chunk into the registers
@@ -343,7 +283,7 @@ __global__ __launch_bounds__(kWavesS *kWave, 1) void shadow_scores_kernel(const 
         // MFMA group 2.14; every wave's four in a slot of its own of the cluster, so that the CU's
         // address unit never sees two waves at once, 2.27 -- the memory system likes its requests in
         // bursts.)
-        bf16x8s an[kRT];
+        bf16x8 an[kRT];
         if (!VT_SDBG(a, 32u)) {
 #pragma unroll
           for (int i = 0; i < kRT; ++i) an[i] = read_a(stage_n, i);
@@ -374,37 +314,29 @@ __global__ __launch_bounds__(kWavesS *kWave, 1) void shadow_scores_kernel(const 
       stage = stage_n;
     }
 
-    const uint32_t tile = tile_index(k);
-    tile_epilogue16<MODE, QTW, DBG>(a, acc, tau, tile * kRowsS + rg * 64, (blockIdx.x + k * gridDim.x) * kRowsS + rg * 64,
-                                    (blockIdx.x + k * gridDim.x) * 4 + rg, qbase, lane);
+    tile_epilogue16<MODE, QTW, DBG>(a, acc, tau, index_tile<DENSE>(a, k) * kRowsS + rg * 64, sample_tile(k) * kRowsS + rg * 64,
+                                    sample_tile(k) * 4 + rg, qbase, lane);
   }
-}
-
-template <class K>
-hipError_t launch_one_s(K kern, size_t lds_bytes, const BatchScoreArgs &a, uint32_t blocks, hipStream_t s) {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(kWavesS * kWave), lds_bytes, s, a);
-  return hipGetLastError();
 }
 
 template <int QTW, int S>
 hipError_t launch_qs(const BatchScoreArgs &a, int mode, uint32_t blocks, hipStream_t s) {
   const bool dense = mode != kModePass;
   const size_t lds_bytes = (size_t)S * (kAStage + b_stage(QTW));
+  const dim3 grid(blocks), block(kWavesS * kWave);
 #ifdef VT_BATCH_TIMING_EXPERIMENTS
   if (a.debug && !dense && QTW == 8 && S == 5) {  // (the modes tools/k2s_probe.hip asks for: 256 columns, five stages)
     switch (a.debug) {
-#define VT_MODE(M) case M: return launch_one_s(shadow_scores_kernel<kModePass, 8, 5, M>, lds_bytes, a, blocks, s);
+#define VT_MODE(M) case M: return launch_with_lds(shadow_scores_kernel<kModePass, 8, 5, M>, grid, block, lds_bytes, s, a);
       VT_MODE(2u) VT_MODE(8u) VT_MODE(10u) VT_MODE(1u) VT_MODE(3u) VT_MODE(5u) VT_MODE(16u) VT_MODE(20u) VT_MODE(22u) VT_MODE(48u) VT_MODE(52u) VT_MODE(54u)
 #undef VT_MODE
       default: return hipErrorInvalidValue;
     }
   }
 #endif
-  if (mode == kModeMaxima) return launch_one_s(shadow_scores_kernel<kModeMaxima, QTW, S, 0u>, lds_bytes, a, blocks, s);
-  return dense ? launch_one_s(shadow_scores_kernel<kModeDense, QTW, S, 0u>, lds_bytes, a, blocks, s)
-               : launch_one_s(shadow_scores_kernel<kModePass, QTW, S, 0u>, lds_bytes, a, blocks, s);
+  if (mode == kModeMaxima) return launch_with_lds(shadow_scores_kernel<kModeMaxima, QTW, S, 0u>, grid, block, lds_bytes, s, a);
+  return dense ? launch_with_lds(shadow_scores_kernel<kModeDense, QTW, S, 0u>, grid, block, lds_bytes, s, a)
+               : launch_with_lds(shadow_scores_kernel<kModePass, QTW, S, 0u>, grid, block, lds_bytes, s, a);
 }
 
 // stages of the LDS ring: 5 x 32 KiB is all of a CU's LDS at 256 query columns
@@ -426,7 +358,7 @@ hipError_t launch_shadow_build(const float *X, size_t stride, uint32_t rows_src,
   const size_t units = (size_t)(rows_img / 16) * (ld / 32);
   const uint32_t blocks = (uint32_t)std::min<size_t>((units + 3) / 4, (size_t)256 * 32);
   hipLaunchKernelGGL(shadow_build_kernel, dim3(blocks), dim3(256), 0, s, X, stride, rows_src, rows_img, ld,
-                     reinterpret_cast<bf16x8s *>(img));
+                     reinterpret_cast<bf16x8 *>(img));
   return hipGetLastError();
 }
 
@@ -443,7 +375,7 @@ hipError_t launch_batch_q_image16(const float *Q, uint32_t ld, uint32_t nq_pad, 
   const uint32_t nchunk = ld / 32, nqt = nq_pad / 16;
   const uint32_t slots = nchunk * nqt * 64;
   hipLaunchKernelGGL(q_image16_kernel, dim3((slots + 255) / 256), dim3(256), 0, s, Q, ld, nchunk, nqt,
-                     reinterpret_cast<bf16x8s *>(image));
+                     reinterpret_cast<bf16x8 *>(image));
   return hipGetLastError();
 }
 
@@ -460,10 +392,7 @@ hipError_t launch_batch_sample_maxima_shadow(const BatchScoreArgs &a, uint32_t b
 uint32_t batch_shadow_sample_groups(uint32_t sample_tiles) { return sample_tiles * (kRowsS / 64); }
 
 static hipError_t launch_shadow_mode(const BatchScoreArgs &a0, int dense, uint32_t blocks, hipStream_t s) {
-  BatchScoreArgs a = a0;
-#ifndef VT_BATCH_TIMING_EXPERIMENTS
-  a.debug = 0u;
-#endif
+  const BatchScoreArgs a = batch_args_for_launch(a0);
   if (a.ld % 64 != 0 || (a.nq_pad != 256 && a.nq_pad != 128 && a.nq_pad != 64) || a.Qimage == nullptr || a.Xshadow == nullptr)
     return hipErrorInvalidValue;
   // (five stages are all of a CU's LDS at 256 columns; four leave 32 KB -- room for the small kernels of the groups

@@ -47,6 +47,9 @@ __device__ __forceinline__ uint32_t orderable(float f) {
   uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+__device__ __forceinline__ float from_orderable(uint32_t o) {  // its inverse
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
+}
 
 __device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
@@ -207,6 +210,24 @@ __device__ __forceinline__ bool f64_to_f32(double v, float *out) {
     return true;
   }
   return false;
+}
+
+// ---- host side: a launch with dynamic LDS ------------------------------------------------------
+constexpr size_t kMaxLds = 160 * 1024;
+
+template <typename K>
+inline hipError_t allow_lds(K kernel, size_t bytes) {
+  if (bytes <= 64 * 1024) return hipSuccess;
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)bytes);
+}
+
+template <typename K, typename... Args>
+inline hipError_t launch_with_lds(K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args &...args) {
+  hipError_t e = allow_lds(kernel, lds_bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, args...);
+  return hipGetLastError();
 }
 
 }  // namespace dev

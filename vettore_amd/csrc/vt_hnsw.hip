@@ -33,8 +33,7 @@ namespace {
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;
 
 __device__ __forceinline__ float key_dist(uint64_t key) {  // orderable()'s inverse
-  const uint32_t u = (uint32_t)(key >> 32);
-  return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+  return from_orderable((uint32_t)(key >> 32));
 }
 __device__ __forceinline__ uint64_t make_key(float dist, uint32_t row) { return ((uint64_t)orderable(dist) << 32) | row; }
 __device__ __forceinline__ float rank_of(int metric, float raw) {  // distances.rs:113-119 rank_value

@@ -636,22 +636,10 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave) void scan_topk_kernel(const 
   }
 }
 
-constexpr size_t kMaxLds = 160 * 1024;
-
-template <typename K>
-inline hipError_t allow_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)bytes);
-}
-
 template <int OP, int ORDER, int CAP, bool GENERAL, bool PADDED, bool QGLOBAL = false, bool FILTER = false>
 inline hipError_t launch_scan_t(const ScanDev &sd, uint32_t blocks, size_t lds, hipStream_t s, uint32_t nq = 1) {
-  auto kern = scan_topk_kernel<OP, ORDER, CAP, GENERAL, PADDED, QGLOBAL, FILTER>;
-  hipError_t e = allow_lds(kern, lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kern, dim3(blocks, nq), dim3(kWavesPerBlock * kWave), lds, s, sd);
-  return hipGetLastError();
+  return launch_with_lds(scan_topk_kernel<OP, ORDER, CAP, GENERAL, PADDED, QGLOBAL, FILTER>, dim3(blocks, nq),
+                         dim3(kWavesPerBlock * kWave), lds, s, sd);
 }
 
 // One translation unit per operation family instantiates its kernels.

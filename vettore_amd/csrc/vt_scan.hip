@@ -78,6 +78,8 @@ hipError_t launch_scan_batch(const ScanArgs &a, uint32_t blocks, uint32_t nq, hi
 // waves owns 384-KiB tiles of the buffer; wave w streams two 24-KiB runs of a tile KiB by KiB
 // (global_load_lds_dwordx4 nt: 64 lanes x 16 B per piece) into its 2 KiB of each of five LDS stages,
 // four chunks = 64 KiB per CU in flight behind a counted vmcnt.  Nothing is computed or written.
+// (The piece is vt_nominate.cuh's dma16<true> written out: through the function this kernel's instructions come out in
+// another order, and a yardstick's text does not change with a refactor of the things it measures.)
 // (r03's yardstick -- 16-byte loads to registers strided over the whole grid, on a zero-filled buffer
 // -- read SLOWER than the product's scan: a yardstick below the thing it measures is noise)
 constexpr uint32_t kPeakStages = 5, kPeakRun = 24 * 1024, kPeakTile = 16 * kPeakRun;
@@ -119,11 +121,7 @@ __global__ __launch_bounds__(256) void peak_fill_kernel(uint32_t *p, size_t n) {
 hipError_t launch_read_peak(const void *buf, size_t bytes, float *sink, uint32_t blocks, hipStream_t s) {
   (void)sink;
   const uint32_t ntiles = (uint32_t)(bytes / kPeakTile);  // (whole tiles only: read_peak_bytes() says how much that is)
-  const int lds_bytes = (int)(kPeakStages * 16384);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(read_peak_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(read_peak_kernel, dim3(blocks), dim3(512), lds_bytes, s, reinterpret_cast<const char *>(buf), ntiles);
-  return hipGetLastError();
+  return launch_with_lds(read_peak_kernel, dim3(blocks), dim3(512), kPeakStages * 16384, s, reinterpret_cast<const char *>(buf), ntiles);
 }
 size_t read_peak_bytes(size_t bytes) { return bytes / kPeakTile * kPeakTile; }
 hipError_t launch_peak_fill(void *buf, size_t bytes, hipStream_t s) {
