@@ -24,11 +24,11 @@ endif
 
 # (vt_scan_multi first: alone it compiles for as long as all the others together at -j4, so a clean build lasts as long
 # as that unit does once it starts at once; vt_hamming is the next longest at half of it)
-DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch_batch vt_sketch_nibble vt_sketch4_rescore vt_hnsw vt_mmr vt_prepare
+DEVSRC  := vt_scan_multi vt_select vt_hamming vt_ingest vt_cosine vt_scan vt_batch vt_batch_bf16 vt_batch_shadow vt_scan_dot vt_scan_l2 vt_scan_l1 vt_scan_misc vt_scan_general vt_scan_gather vt_scan_filter vt_prefix_multi vt_maxsim vt_maxsim_resident vt_maxsim_batch vt_muvera vt_sketch vt_sketch_batch vt_sketch_nibble vt_sketch4_rescore vt_hnsw vt_hnsw_stage vt_mmr vt_prepare
 DEVOBJ  := $(addprefix $(LIBDIR)/,$(addsuffix .o,$(DEVSRC)))
 DEVHDR  := $(CSRC)/vt_device.h $(CSRC)/vt_common.cuh $(CSRC)/vt_scan.cuh $(CSRC)/vt_env.h
 
-all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch4_best_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so $(LIBDIR)/libvt_select_probe.so oracle
+all: $(LIBDIR)/libvettore_hip.so $(LIBDIR)/libvettore_hip_hooks.so $(LIBDIR)/libvt_callers.so $(LIBDIR)/libvt_callers_hooks.so $(LIBDIR)/libvt_sketch_probe.so $(LIBDIR)/libvt_sketch4_probe.so $(LIBDIR)/libvt_sketch4_finish_probe.so $(LIBDIR)/libvt_sketch4_rescore_probe.so $(LIBDIR)/libvt_sketch4_best_probe.so $(LIBDIR)/libvt_sketch_l2_probe.so $(LIBDIR)/libvt_sketch_batch_probe.so $(LIBDIR)/libvt_batch_probe.so $(LIBDIR)/libvt_hnsw_compact_probe.so $(LIBDIR)/libvt_panel_probe.so $(LIBDIR)/libvt_select_probe.so $(LIBDIR)/libvt_hnsw_stage_probe.so oracle
 
 # What a device unit's build checks or adds, per unit:
 #   NOSCRATCH_<unit>  kernels that must neither spill nor carry a scratch segment
@@ -75,6 +75,9 @@ NOSCRATCH_vt_sketch4_rescore := sketch4_rescore_kernel
 # K11 (HNSW traversals): the distance chains are K9's with the recovery by value; heaps and visited set live in the
 # slot's global scratch, nothing is indexed dynamically in registers -- no scratch segment
 NOSCRATCH_vt_hnsw         := hnsw_traverse_kernel
+# K15 (the staged searches' scores over an HNSW slab): K11's chains, one lane a pair, the recovery by value; the sign-bit
+# sweep keeps its counts in scalar registers -- no scratch segment
+NOSCRATCH_vt_hnsw_stage   := hnsw_stage_bits_kernel hnsw_stage_score_kernel
 # K12 (MMR steps): one lane's chain per pair, K9's, with the recovery by value -- no scratch segment behind any of a call's launches
 NOSCRATCH_vt_mmr          := mmr_step_kernel
 # K14 (prepare rows): a lane's chain accumulators and a batch of loaded runs, all indexed statically -- no scratch segment
@@ -96,8 +99,8 @@ $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_sketch_nibble.cuh
 $(LIBDIR)/vt_sketch.o $(LIBDIR)/vt_sketch_nibble.o: $(CSRC)/vt_rowscore.cuh
 $(LIBDIR)/vt_sketch_batch.o: $(CSRC)/host/vt_sketchbatch.h
 
-# (the one-lane pair arithmetic of K9, K9r, K9rb, K11 and K12; what the three MaxSim kernels share beside it)
-$(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_pair.cuh
+# (the one-lane pair arithmetic of K9, K9r, K9rb, K11, K12 and K15p; what the three MaxSim kernels share beside it)
+$(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o $(LIBDIR)/vt_hnsw.o $(LIBDIR)/vt_hnsw_stage.o $(LIBDIR)/vt_mmr.o: $(CSRC)/vt_pair.cuh
 $(LIBDIR)/vt_maxsim.o $(LIBDIR)/vt_maxsim_resident.o $(LIBDIR)/vt_maxsim_batch.o: $(CSRC)/vt_maxsim_pair.cuh
 
 # (the row-panel walk of K6b, K6bm and K1p and the group epilogue of the latter two)
@@ -242,6 +245,16 @@ $(LIBDIR)/select_probe.o: tests/select_probe.cpp $(CSRC)/vt_device.h
 	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
 
 $(LIBDIR)/libvt_select_probe.so: $(LIBDIR)/vt_select.o $(LIBDIR)/select_probe.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
+
+# K15 behind a probe (tests/hnsw_stage_probe.cpp; tests/test_gpu_hnsw_stage_kernels.py loads it): the sign-bit sweep and
+# the prefix scores over a test's hand-made slab, every key and payload of the column read back.  vt_hnsw_stage.o and the
+# probe, nothing else of the library.  Test infrastructure, as above.
+$(LIBDIR)/hnsw_stage_probe.o: tests/hnsw_stage_probe.cpp $(CSRC)/vt_device.h
+	@mkdir -p $(LIBDIR)
+	$(HIPCC) $(HIPFLAGS) -I$(CSRC) -x hip -c $< -o $@
+
+$(LIBDIR)/libvt_hnsw_stage_probe.so: $(LIBDIR)/vt_hnsw_stage.o $(LIBDIR)/hnsw_stage_probe.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $^
 
 oracle:

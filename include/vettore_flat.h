@@ -560,6 +560,18 @@ int vt_hnsw_delete(vt_hnsw *index, const char *id, size_t id_len);
 int vt_hnsw_search(vt_hnsw *index, const float *query, size_t n, size_t limit, vt_hits **out);
 int vt_hnsw_search_batch(vt_hnsw *index, const float *queries, size_t nq, size_t d, size_t limit, vt_hits **out /* nq */,
                          int *query_status /* nq, may be NULL */);
+/* quantized_search, funnel_search and hybrid_search (collection.ex:232-348) on the index's rows: vt_flat_quantized_search,
+ * vt_flat_funnel_search and vt_flat_hybrid_search above also take an HNSW handle in the place of the flat one --
+ * VT_HNSW_STAGED(index) -- and the library tells the two kinds apart (it knows every live vt_hnsw).  The set of exported
+ * symbols is pinned (tests/test_fde_capi.py), so these searches have no entry points of their own.  The meanings, the
+ * validation order, the statuses and the rules for an empty answer are the flat handle's, with the number of live nodes
+ * for the row count -- over the same (id, vector) pairs the hits are the flat handle's, bit for bit: the slab holds the
+ * vectors as given, and the stages order by (rank.total_cmp, id bytes).  VT_GEN_SEARCH is the index's own traversal with
+ * limit = candidates (hnsw_candidates, collection.ex:594-600), its hits in result order.  The sign bits and prefixes are
+ * read from the f32 rows where they lie (csrc/vt_hnsw_stage.hip); the first such call after the set of nodes changed
+ * sorts the live ids once.  One mutex per handle, as for every other call; a poisoned handle answers
+ * VT_ERR_HNSW_POISONED.  No other vt_flat_ function takes an HNSW handle. */
+#define VT_HNSW_STAGED(index) ((vt_flat *)(index))
 size_t vt_hnsw_len(const vt_hnsw *index);
 long vt_hnsw_dimension(const vt_hnsw *index); /* -1: empty */
 /* Inspection (tests compare the graph with the reference's): a live id's internal id, level and whether it is the

@@ -421,13 +421,15 @@ static ERL_NIF_TERM flat_funnel_search_batch(ErlNifEnv *env, int argc, const ERL
 
 /* flat_hybrid_search(ref, [float], [{kind, candidates, [stage]}], limit)   collection.ex:325-345, :515-592
  * kind: 0 funnel, 1 quantized, 2 search; rerank: :exact */
-static ERL_NIF_TERM flat_hybrid_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
-  flat_res *r = get_flat(env, argv[0]);
+static hnsw_res *get_hnsw(ErlNifEnv *env, ERL_NIF_TERM t);
+/* (one body for both kinds of handle: hnsw_hybrid_search, further down, is the same call over the HNSW resource) */
+static ERL_NIF_TERM hybrid_search_on(ErlNifEnv *env, const ERL_NIF_TERM argv[], int on_hnsw) {
+  flat_res *r = on_hnsw ? NULL : get_flat(env, argv[0]);
+  hnsw_res *g = on_hnsw ? get_hnsw(env, argv[0]) : NULL;
   float *q;
   size_t n, limit;
   unsigned ngen;
-  (void)argc;
-  if (!r || !enif_get_list_length(env, argv[2], &ngen) || !get_size(env, argv[3], &limit) || !get_f32_list(env, argv[1], &q, &n))
+  if ((!r && !g) || !enif_get_list_length(env, argv[2], &ngen) || !get_size(env, argv[3], &limit) || !get_f32_list(env, argv[1], &q, &n))
     return enif_make_badarg(env);
   int *kinds = (int *)calloc(ngen + 1, sizeof(int));
   size_t *cands = (size_t *)calloc(ngen + 1, sizeof(size_t));
@@ -457,11 +459,16 @@ static ERL_NIF_TERM flat_hybrid_search(ErlNifEnv *env, int argc, const ERL_NIF_T
   } else {
     size_t dummy = 0;
     vt_hits *h;
-    int st = vt_flat_hybrid_search(r->h, q, n, kinds, cands, off, stages ? stages : &dummy, ngen, limit, &h);
+    int st = vt_flat_hybrid_search(g ? VT_HNSW_STAGED(g->h) : r->h, q, n, kinds, cands, off, stages ? stages : &dummy, ngen, limit, &h);
     res = st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
   }
   free(q); free(kinds); free(cands); free(off); free(stages);
   return res;
+}
+
+static ERL_NIF_TERM flat_hybrid_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return hybrid_search_on(env, argv, 0);
 }
 
 /* ------------------------------------------------------ stateless helpers */
@@ -939,6 +946,44 @@ static ERL_NIF_TERM hnsw_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM arg
   return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
 }
 
+/* hnsw_quantized_search(ref, [float], candidates, limit), hnsw_funnel_search(ref, [float], [stage], candidates, limit),
+ * hnsw_hybrid_search(ref, [float], [{kind, candidates, [stage]}], limit) -> {:ok, [{id, raw}]} | {:error, binary}
+ * (collection.ex:232-348 on the index's own rows: the flat NIFs' terms and answers; kind 2 is the index's traversal.
+ * The library's three staged entry points take either kind of handle: VT_HNSW_STAGED, include/vettore_flat.h) */
+static ERL_NIF_TERM hnsw_quantized_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  float *q;
+  size_t n, candidates, limit;
+  (void)argc;
+  if (!r || !get_f32_list(env, argv[1], &q, &n) || !get_size(env, argv[2], &candidates) || !get_size(env, argv[3], &limit))
+    return enif_make_badarg(env);
+  vt_hits *h;
+  int st = vt_flat_quantized_search(VT_HNSW_STAGED(r->h), q, n, candidates, limit, &h);
+  free(q);
+  return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
+}
+
+static ERL_NIF_TERM hnsw_funnel_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  hnsw_res *r = get_hnsw(env, argv[0]);
+  float *q;
+  size_t n, nst, candidates, limit, *stages;
+  (void)argc;
+  if (!r || !get_f32_list(env, argv[1], &q, &n)) return enif_make_badarg(env);
+  if (!get_size_list(env, argv[2], &stages, &nst) || !get_size(env, argv[3], &candidates) || !get_size(env, argv[4], &limit)) {
+    free(q);
+    return enif_make_badarg(env);
+  }
+  vt_hits *h;
+  int st = vt_flat_funnel_search(VT_HNSW_STAGED(r->h), q, n, stages, nst, candidates, limit, &h);
+  free(q); free(stages);
+  return st == VT_OK ? ok_hits(env, h) : mk_error(env, st);
+}
+
+static ERL_NIF_TERM hnsw_hybrid_search(ErlNifEnv *env, int argc, const ERL_NIF_TERM argv[]) {
+  (void)argc;
+  return hybrid_search_on(env, argv, 1);
+}
+
 /* hnsw_memory(ref) -> {:ok, {rows, row_capacity, dead_rows, edges}} | {:error, binary}
  * (no counterpart in the reference: vt_hnsw_memory's four numbers.  rows counts the slab rows handed out since the last
  * compaction, dead_rows returns to 0 at one: include/vettore_flat.h) */
@@ -1161,6 +1206,9 @@ static ErlNifFunc funcs[] = {
   {"hnsw_insert_many", 2, hnsw_insert_many, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_delete", 2, hnsw_delete, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_search", 3, hnsw_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_quantized_search", 4, hnsw_quantized_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_funnel_search", 5, hnsw_funnel_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
+  {"hnsw_hybrid_search", 4, hnsw_hybrid_search, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"hnsw_memory", 1, hnsw_memory, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"mmr_rerank", 5, mmr_rerank, ERL_NIF_DIRTY_JOB_IO_BOUND},
   {"flat_mmr_rerank", 4, flat_mmr_rerank, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -59,6 +59,9 @@ defmodule Vettore.Gpu.Nifs do
   def hnsw_insert_many(_ref, _entries), do: :erlang.nif_error(:nif_not_loaded)
   def hnsw_delete(_ref, _id), do: :erlang.nif_error(:nif_not_loaded)
   def hnsw_search(_ref, _query, _limit), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_quantized_search(_ref, _query, _candidates, _limit), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_funnel_search(_ref, _query, _stages, _candidates, _limit), do: :erlang.nif_error(:nif_not_loaded)
+  def hnsw_hybrid_search(_ref, _query, _generators, _limit), do: :erlang.nif_error(:nif_not_loaded)
   def hnsw_memory(_ref), do: :erlang.nif_error(:nif_not_loaded)
   def mmr_rerank(_metric_code, _rows, _scores, _alpha, _final_k), do: :erlang.nif_error(:nif_not_loaded)
   def flat_mmr_rerank(_ref, _initial, _alpha, _final_k), do: :erlang.nif_error(:nif_not_loaded)

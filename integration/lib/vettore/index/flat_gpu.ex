@@ -160,7 +160,7 @@ defmodule Vettore.Index.FlatGpu do
 
     with :ok <- validate_limit(limit),
          {:ok, prepared} <- Collection.prepare_query(collection, query),
-         {:ok, spec} <- generator_spec(generators, d, limit),
+         {:ok, spec} <- generator_spec(generators, d, limit, false),
          :ok <- if(rerank == :exact, do: :ok, else: {:error, {:invalid_rerank, rerank}}),
          {:ok, hits} <- Nifs.flat_hybrid_search(collection.index_state, prepared, spec, limit) do
       {:ok, Enum.flat_map(hits, &to_result(collection, &1))}
@@ -198,6 +198,30 @@ defmodule Vettore.Index.FlatGpu do
   defdelegate hnsw_delete(ref, id), to: Nifs
   defdelegate hnsw_search(ref, query, limit), to: Nifs
   defdelegate hnsw_memory(ref), to: Nifs
+  # the staged searches on an HNSW index's own rows (Vettore.Index.HnswGpu.quantized_search/3, funnel_search/3, hybrid_search/3)
+  defdelegate hnsw_quantized_search(ref, query, candidates, limit), to: Nifs
+  defdelegate hnsw_funnel_search(ref, query, stages, candidates, limit), to: Nifs
+  defdelegate hnsw_hybrid_search(ref, query, generators, limit), to: Nifs
+
+  # The option handling of the three staged searches, for Vettore.Index.HnswGpu: one statement of it.
+  @doc false
+  def staged_limit_and_candidates(opts) do
+    limit = Keyword.get(opts, :limit, 10)
+    candidates = Keyword.get(opts, :candidates, max_candidates(limit))
+    with :ok <- validate_limit(limit), :ok <- validate_candidates(candidates, limit), do: {:ok, limit, candidates}
+  end
+
+  @doc false
+  def staged_stages(d, opts) do
+    stages = funnel_stages(d, opts)
+    with :ok <- validate_stages(stages, d), do: {:ok, stages}
+  end
+
+  @doc false
+  def staged_limit(limit), do: validate_limit(limit)
+
+  @doc false
+  def staged_generators(generators, d, limit, hnsw?), do: generator_spec(generators, d, limit, hnsw?)
 
   # ---- MMR reranking and diversified search on the resident rows (DESIGN 4.15)
   @doc """
@@ -289,9 +313,10 @@ defmodule Vettore.Index.FlatGpu do
 
   # [{kind, candidates, stages}] as the NIF takes them (kind 0 funnel, 1 quantized, 2 search); errors as
   # run_hybrid_generator's (collection.ex:536-556, :1136-1142)
-  defp generator_spec(generators, d, limit) when is_list(generators) and generators != [] do
+  # hnsw?: the collection's index is an HNSW one, so the :hnsw generator exists (collection.ex:594-600): kind 2, as :search
+  defp generator_spec(generators, d, limit, hnsw?) when is_list(generators) and generators != [] do
     Enum.reduce_while(generators, {:ok, []}, fn generator, {:ok, acc} ->
-      case one_generator(generator, d, limit) do
+      case one_generator(generator, d, limit, hnsw?) do
         {:ok, entry} -> {:cont, {:ok, [entry | acc]}}
         error -> {:halt, error}
       end
@@ -302,11 +327,11 @@ defmodule Vettore.Index.FlatGpu do
     end
   end
 
-  defp generator_spec(_generators, _d, _limit), do: {:error, :invalid_generators}
+  defp generator_spec(_generators, _d, _limit, _hnsw?), do: {:error, :invalid_generators}
 
-  defp one_generator(name, d, limit) when is_atom(name), do: one_generator({name, []}, d, limit)
+  defp one_generator(name, d, limit, hnsw?) when is_atom(name), do: one_generator({name, []}, d, limit, hnsw?)
 
-  defp one_generator({name, opts}, d, limit) when is_atom(name) and is_list(opts) do
+  defp one_generator({name, opts}, d, limit, hnsw?) when is_atom(name) and is_list(opts) do
     allowed = if name == :funnel, do: [:candidates, :stages, :dimensions], else: [:candidates]
     candidates = Keyword.get(opts, :candidates, max_candidates(limit))
 
@@ -315,7 +340,7 @@ defmodule Vettore.Index.FlatGpu do
       not Keyword.keyword?(opts) -> {:error, :invalid_options}
       (dup = Enum.find(Keyword.keys(opts), &(length(Keyword.get_values(opts, &1)) > 1))) != nil -> {:error, {:duplicate_option, dup}}
       (extra = Keyword.keys(opts) -- allowed) != [] -> {:error, {:unsupported_option, hd(extra)}}
-      name == :hnsw -> {:error, :hnsw_index_required}
+      name == :hnsw and not hnsw? -> {:error, :hnsw_index_required}
       not (is_integer(candidates) and candidates > 0 and candidates <= @max_nif_usize) -> {:error, :invalid_candidates}
       name == :funnel ->
         stages = funnel_stages(d, opts)
@@ -325,7 +350,7 @@ defmodule Vettore.Index.FlatGpu do
     end
   end
 
-  defp one_generator(generator, _d, _limit), do: {:error, {:invalid_generator, generator}}
+  defp one_generator(generator, _d, _limit, _hnsw?), do: {:error, {:invalid_generator, generator}}
 
   # `index_options: [device: 0]` (default) or `[devices: [0, 1, 2, 3, 4, 5, 6, 7]]`: one resource whose
   # rows are spread over the GPUs of the node (collection.ex:100-103 hands the options over verbatim).

@@ -14,6 +14,7 @@ defmodule Vettore.Index.HnswGpu do
 
   alias Vettore.{Collection, Distance, Embedding, Result}
   alias Vettore.Gpu.Nifs
+  alias Vettore.Index.FlatGpu
 
   @default_options [m: 16, m0: 32, ef_construction: 100, ef_search: 64, max_level: 12]
   @option_keys Keyword.keys(@default_options)
@@ -50,6 +51,47 @@ defmodule Vettore.Index.HnswGpu do
          :ok <- validate_limit(limit),
          {:ok, query} <- Collection.prepare_query(collection, query),
          {:ok, hits} <- Nifs.hnsw_search(collection.index_state, query, limit) do
+      {:ok, Enum.flat_map(hits, &to_result(collection, &1))}
+    end
+  end
+
+  # ---- the collection's staged searches on the index's own rows ---------------------------------
+  # With the dispatch of INTEGRATION.md section 3 in collection.ex (`function_exported?(collection.index_mod, ...)`)
+  # `Vettore.quantized_search/3`, `funnel_search/3` and `hybrid_search/3` land here instead of the reference's ETS
+  # composition, with identical answers: the slab holds the vectors as given and the stages order by (rank, id).  The
+  # option handling is Vettore.Index.FlatGpu's; `:hnsw` and `:search` are both the index's own traversal, and
+  # hybrid_search defaults to `[:hnsw, :quantized]` (collection.ex:513).
+
+  @doc "collection.ex:276-295 on the index's rows."
+  def quantized_search(%Collection{} = collection, query, opts \\ []) do
+    with {:ok, limit, candidates} <- FlatGpu.staged_limit_and_candidates(opts),
+         {:ok, prepared} <- Collection.prepare_query(collection, query),
+         {:ok, hits} <- Nifs.hnsw_quantized_search(collection.index_state, prepared, candidates, limit) do
+      {:ok, Enum.flat_map(hits, &to_result(collection, &1))}
+    end
+  end
+
+  @doc "collection.ex:245-260 on the index's rows."
+  def funnel_search(%Collection{dimensions: d} = collection, query, opts \\ []) do
+    with {:ok, limit, candidates} <- FlatGpu.staged_limit_and_candidates(opts),
+         {:ok, stages} <- FlatGpu.staged_stages(d, opts),
+         {:ok, prepared} <- Collection.prepare_query(collection, query),
+         {:ok, hits} <- Nifs.hnsw_funnel_search(collection.index_state, prepared, stages, candidates, limit) do
+      {:ok, Enum.flat_map(hits, &to_result(collection, &1))}
+    end
+  end
+
+  @doc "collection.ex:325-345 with `rerank: :exact` on the index's rows; the default generators are `[:hnsw, :quantized]`."
+  def hybrid_search(%Collection{dimensions: d} = collection, query, opts \\ []) do
+    limit = Keyword.get(opts, :limit, 10)
+    generators = Keyword.get(opts, :generators, [:hnsw, :quantized])
+    rerank = Keyword.get(opts, :rerank, :exact)
+
+    with :ok <- FlatGpu.staged_limit(limit),
+         {:ok, prepared} <- Collection.prepare_query(collection, query),
+         {:ok, spec} <- FlatGpu.staged_generators(generators, d, limit, true),
+         :ok <- if(rerank == :exact, do: :ok, else: {:error, {:invalid_rerank, rerank}}),
+         {:ok, hits} <- Nifs.hnsw_hybrid_search(collection.index_state, prepared, spec, limit) do
       {:ok, Enum.flat_map(hits, &to_result(collection, &1))}
     end
   end

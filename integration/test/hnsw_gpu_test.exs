@@ -67,6 +67,30 @@ defmodule Vettore.Index.HnswGpuTest do
     end
   end
 
+  test "quantized, funnel and hybrid searches answer as the reference's composition over the same embeddings" do
+    # HnswGpu exports the three functions; the reference composes them from ETS whatever the index is (collection.ex:232-348)
+    for metric <- [:l2, :cosine, :inner_product] do
+      opts = [m: 4, m0: 8, ef_construction: 40, ef_search: 16]
+      gpu = collection(HnswGpu, metric, opts)
+      cpu = collection(HNSW, metric, opts)
+
+      for {id, v} <- vectors(300), c <- [gpu, cpu] do
+        :ok = Vettore.put(c, %Vettore.Embedding{id: id, vector: v, value: id})
+      end
+
+      for {_id, q} <- Enum.take(vectors(300), 5) do
+        assert HnswGpu.quantized_search(gpu, q, limit: 7, candidates: 40) == Vettore.quantized_search(cpu, q, limit: 7, candidates: 40)
+        assert HnswGpu.funnel_search(gpu, q, limit: 7, stages: [3, 6]) == Vettore.funnel_search(cpu, q, limit: 7, stages: [3, 6])
+        assert HnswGpu.hybrid_search(gpu, q, limit: 7) == Vettore.hybrid_search(cpu, q, limit: 7)
+        assert HnswGpu.hybrid_search(gpu, q, generators: [:hnsw, {:funnel, stages: [4]}]) ==
+                 Vettore.hybrid_search(cpu, q, generators: [:hnsw, {:funnel, stages: [4]}])
+      end
+
+      assert HnswGpu.funnel_search(gpu, for(_ <- 1..8, do: 0.5), stages: [9]) == {:error, :invalid_stages}
+      assert HnswGpu.quantized_search(gpu, for(_ <- 1..8, do: 0.5), limit: 0) == {:error, :invalid_limit}
+    end
+  end
+
   test "options and metrics are rejected as hnsw.ex rejects them" do
     for bad <- [[m: 0], [m0: 2_049], [m: 16, m0: 8], [ef_construction: 8], [ef_search: 0], [max_level: 65], [unknown: 1], [m: 8, m: 8], :m] do
       assert HnswGpu.new(:l2, bad) == {:error, :invalid_hnsw_options}

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import nifs
 from .index_flat import FlatGpu, Result, result_values, MAX_NIF_USIZE
-from .index_hnsw import HnswGpu
+from .index_hnsw import HnswGpu, HnswStagedGpu
 from .mv_store import ResidentMultiVector
 from . import muvera as muvera_mod
 
@@ -78,6 +78,16 @@ class Collection:
         for cb in ("new", "put", "put_many", "delete", "search"):
             if not hasattr(index_mod, cb):
                 return ("error", "invalid_index")
+        # `staged_searches: true` is the collection's own option too, for the HNSW index alone: the index module becomes
+        # HnswStagedGpu, which answers quantized_search / funnel_search / hybrid_search from the index's rows.  Without it
+        # an `index: "hnsw"` collection keeps answering {:error, :not_supported_by_index} (INTEGRATION.md 3.4 says why).
+        if isinstance(index_options, dict) and "staged_searches" in index_options:
+            index_options = dict(index_options)
+            staged = index_options.pop("staged_searches")
+            if not isinstance(staged, bool) or index_mod is not HnswGpu:
+                return ("error", "invalid_index_options")
+            if staged:
+                index_mod = HnswStagedGpu
         # `resident_multi_vector: true` is the collection's own option (not the index module's): every stored
         # embedding's vectors are mirrored into a device-resident store (mv_store.py) that the multi-vector searches read
         resident = False

@@ -37,6 +37,16 @@ struct vt_hnsw {
   PinnedBuf<uint32_t> hOut;
   // vt_hnsw_counters: launches of the traversal kernel, traversals asked for, traversals run again with full scratch
   uint64_t launches = 0, traversals = 0, reruns = 0;
+  // the staged searches (host/vt_hnswstage.h): `epoch` counts the changes of the row set -- an insert, a delete, a
+  // compaction, the last node's going --, rank_epoch is the one dIdRank was built at; the query (floats, then its sign bits
+  // in K15b's order), a stage's row list, and its key and payload columns
+  uint64_t epoch = 1, rank_epoch = 0;
+  DevBuf<uint32_t> dIdRank, dStageRows;
+  PinnedBuf<uint32_t> hStageWords;
+  DevBuf<float> dStageQ;
+  PinnedBuf<float> hStageQ;
+  DevBuf<uint64_t> dStageKeys;
+  DevBuf<vt::Payload> dStagePay;
 
   vt_hnsw(size_t m_, size_t m0_, size_t max_level) : graph(m_, m0_, max_level) {}
 };
@@ -85,6 +95,7 @@ void hnsw_forget(vt_hnsw *h) {
   h->capacity = h->rows_used = h->dead_rows = h->upper_used = 0;
   h->row_id.clear();
   h->row_upoff.clear();
+  ++h->epoch;
 }
 
 // room for `rows` rows and `upper` words of upper-layer lists: nothing changes when an allocation fails
@@ -247,6 +258,7 @@ int hnsw_erase(vt_hnsw *h, const std::string &id, bool *mutated) {
   h->graph.erase(id);
   *mutated = true;
   ++h->dead_rows;
+  ++h->epoch;
   if (h->graph.len() == 0) {
     hnsw_forget(h);
     return VT_OK;
@@ -347,6 +359,7 @@ int hnsw_compact_if_due(vt_hnsw *h) {
   h->dead_rows = 0;
   h->upper_used = plan.upper_used;
   h->capacity = plan.capacity;
+  ++h->epoch;
   return VT_OK;
 }
 
@@ -421,6 +434,7 @@ int hnsw_insert_one(vt_hnsw *h, const char *id, size_t id_len, const float *vec,
   p.push_back(vt::HnswPatch{row, (uint32_t)h->upper_used, 3});
   h->upper_used = upper_need;
   ++h->rows_used;
+  ++h->epoch;
   return hnsw_patch_mirror(h, p);
 }
 

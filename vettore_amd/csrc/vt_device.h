@@ -734,6 +734,47 @@ struct HnswCompactArgs {
 };
 hipError_t launch_hnsw_compact(const HnswCompactArgs &a, hipStream_t s);
 
+// ---- K15 (vt_hnsw_stage.hip): the staged searches' scores over an HNSW slab where it lies ------------------------------
+// Both kernels write keys[i] / pay[i] for every scanned position i, in the key-column convention at the top of this file:
+// kEmptyKey for a dead row (id_rank[row] == kHnswNoRow), for a list entry that names no row of the slab, and for a pair
+// whose raw value is NaN.  id_rank: [rows], the position of the row's external id in the bytewise order of the live ids.
+// Both launchers return hipSuccess without launching when there is nothing to scan.
+//
+// K15b: position = row, for rows [0, rows).  raw = rank = packed_hamming(compress_sign_bits(row), the query's) as f32.
+// qwords: the query's sign bits in the kernel's order, hnsw_stage_qword_count(d) words from hnsw_stage_qwords(): bit
+// e % 256 / 4 of word 4 * (e / 256) + e % 4 is set iff q[e] >= 0.0f, every other bit clear.
+struct HnswStageBitsArgs {
+  const float *X;          // the slab: `stride` floats a row (a multiple of 4, >= d), 16-byte aligned; the pad is not looked at
+  size_t stride;
+  uint32_t d, rows;
+  const uint32_t *id_rank;
+  const uint64_t *qwords;
+  uint64_t *keys;          // [rows]
+  Payload *pay;            // [rows]
+};
+inline size_t hnsw_stage_qword_count(uint32_t d) { return 4 * (((size_t)d + 255) / 256); }
+void hnsw_stage_qwords(const float *q, uint32_t d, uint64_t *out);
+hipError_t launch_hnsw_stage_bits(const HnswStageBitsArgs &a, hipStream_t s);
+// K15p: vector_top_k's value on the first p coordinates, the query on the left; metric VT_L2, VT_COSINE (the f64 cosine,
+// both norms over the prefix) or VT_INNER_PRODUCT.  Position i is row list[i], or row i when list is null (n <= rows).
+struct HnswStageScoreArgs {
+  const float *X;
+  size_t stride;
+  uint32_t d, rows;        // the slab's dimension and its used rows
+  uint32_t p;              // 1 .. d
+  const float *q;          // at least round_up(p, 4) floats, 16-byte aligned (device)
+  double qq;               // cosine: f64_dot(q, q) over the prefix (distances.rs:179-185)
+  const uint32_t *id_rank;
+  const uint32_t *list;
+  uint32_t n;              // positions
+  int metric, order;
+  uint64_t *keys;          // [n]
+  Payload *pay;            // [n]
+  int *status;             // raised to VT_ERR_OVERFLOW by a NaN raw value
+  uint32_t tt, ld;         // (the launcher's: rows of the LDS tile, 0 when nothing is staged, and floats between them)
+};
+hipError_t launch_hnsw_stage_score(const HnswStageScoreArgs &a, hipStream_t s);
+
 // ---- K12 (vt_mmr.hip): MMR reranking (vettore_distance.ex:416-519), one step kernel queued once per round ------------
 // A call solves `nprob` problems over one row matrix.  Problem p owns entries [off, off + n) of the per-candidate arrays;
 // candidate i of it is row rows[off + i] of X with the f64 relevance rel[off + i].  launch_mmr_step(a, t, ...) is queued

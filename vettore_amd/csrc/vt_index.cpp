@@ -44,6 +44,7 @@
 #include "host/vt_mvbatch.h"
 #include "host/vt_hnswgraph.h"
 #include "host/vt_hnswplan.h"
+#include "host/vt_hnswrank.h"
 #include "host/vt_mmrplan.h"
 #include "host/vt_fdeplan.h"
 #include "host/vt_concurrency.h"
@@ -64,6 +65,7 @@
 #include "host/vt_muvera.h"
 #include "host/vt_mvsearch.h"
 #include "host/vt_hnsw.h"
+#include "host/vt_hnswstage.h"
 #include "host/vt_multi.h"
 #include "host/vt_coalesce.h"
 #include "host/vt_mmr.h"
@@ -745,6 +747,10 @@ int vt_flat_quantized_search(vt_flat *h, const float *query, size_t n, size_t ca
   return guarded([&]() -> int {
   if (!h || !out || (!query && n)) return VT_ERR_ARGUMENT;
   *out = nullptr;
+  if (vt_hnsw *g = hnsw_staged_handle(h)) {  // (VT_HNSW_STAGED: the same search on an HNSW index's rows)
+    std::lock_guard<std::mutex> lk(g->mu);
+    return hnsw_quantized(g, query, n, candidates, limit, out);
+  }
   return coalesced_quantized(h, query, n, candidates, limit, out);
   });
 }
@@ -762,6 +768,10 @@ int vt_flat_funnel_search(vt_flat *h, const float *query, size_t n, const size_t
   return guarded([&]() -> int {
   if (!h || !out || (!query && n) || (nstages && !stages)) return VT_ERR_ARGUMENT;
   *out = nullptr;
+  if (vt_hnsw *g = hnsw_staged_handle(h)) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    return hnsw_funnel(g, query, n, stages, nstages, candidates, limit, out);
+  }
   return coalesced_funnel(h, query, n, stages, nstages, candidates, limit, out);
   });
 }
@@ -779,6 +789,10 @@ int vt_flat_hybrid_search(vt_flat *h, const float *query, size_t n, const int *k
   return guarded([&]() -> int {
   if (!h || !out || (!query && n) || (ngen && (!kinds || !candidates || !stage_off))) return VT_ERR_ARGUMENT;
   *out = nullptr;
+  if (vt_hnsw *g = hnsw_staged_handle(h)) {
+    std::lock_guard<std::mutex> lk(g->mu);
+    return hnsw_hybrid(g, query, n, kinds, candidates, stage_off, stages, ngen, limit, out);
+  }
   if (h->multi()) {
     std::shared_lock<std::shared_mutex> rl(h->rw);
     if (h->poisoned) return poisoned_status();
@@ -1004,6 +1018,7 @@ int vt_hnsw_new(int metric_code, int device, size_t m, size_t m0, size_t ef_cons
   h->m0 = m0;
   h->ef_construction = ef_construction;
   h->ef_search = ef_search;
+  hnsw_staged_register(h.get());
   *out = h.release();
   return VT_OK;
   });
@@ -1013,6 +1028,7 @@ void vt_hnsw_free(vt_hnsw *h) {
   if (!h) return;
   (void)guarded([&]() -> int {
     (void)h->ctx.bind();
+    hnsw_staged_unregister(h);
     delete h;
     return VT_OK;
   });

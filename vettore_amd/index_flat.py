@@ -70,6 +70,20 @@ def _normalize_ok(res):
     return res
 
 
+class Stages:
+    """What FlatGpu's staged searches (quantized_search, funnel_search, hybrid_search) call below their option handling:
+    the native calls of one kind of handle, the default generators of hybrid_search (collection.ex:512-513) and whether
+    the "hnsw" generator exists there (collection.ex:594-600).  index_hnsw.HnswStagedGpu runs the same code over its own."""
+
+    def __init__(self, quantized, funnel, hybrid, search, default_generators, hnsw_generator):
+        self.quantized, self.funnel, self.hybrid, self.search = quantized, funnel, hybrid, search
+        self.default_generators, self.hnsw_generator = default_generators, hnsw_generator
+
+
+FLAT_STAGES = Stages(nifs.flat_quantized_search, nifs.flat_funnel_search, nifs.flat_hybrid_search, nifs.flat_search,
+                     ("funnel", "quantized"), False)
+
+
 class FlatGpu:
     """`@behaviour Vettore.Index` with callbacks new/2, put/2, put_many/2,
     delete/2, search/3 (flat.ex:15-57)."""
@@ -181,15 +195,16 @@ class FlatGpu:
         return ("ok", [_hydrate(collection, hits) for hits in res[1]])
 
     @staticmethod
-    def quantized_search(collection, query, opts=None):
+    def quantized_search(collection, query, opts=None, stages=None):
         """collection.ex:276-295 on the resident corpus."""
+        stages = stages or FLAT_STAGES
         lc = FlatGpu._limit_and_candidates({} if opts is None else opts)
         if lc[0] != "ok":
             return lc
         q = collection.prepare_query(query)
         if q[0] != "ok":
             return q
-        res = nifs.flat_quantized_search(collection.index_state, q[1], lc[2], lc[1])
+        res = stages.quantized(collection.index_state, q[1], lc[2], lc[1])
         return res if res[0] != "ok" else ("ok", _hydrate(collection, res[1]))
 
     @staticmethod
@@ -204,9 +219,10 @@ class FlatGpu:
         return res if res[0] != "ok" else ("ok", [_hydrate(collection, hits) for hits in res[1]])
 
     @staticmethod
-    def funnel_search(collection, query, opts=None):
+    def funnel_search(collection, query, opts=None, stages=None):
         """collection.ex:245-260 on the resident corpus."""
         opts = {} if opts is None else opts
+        stages = stages or FLAT_STAGES
         lc = FlatGpu._limit_and_candidates(opts)
         if lc[0] != "ok":
             return lc
@@ -216,7 +232,7 @@ class FlatGpu:
         q = collection.prepare_query(query)
         if q[0] != "ok":
             return q
-        res = nifs.flat_funnel_search(collection.index_state, q[1], st[1], lc[2], lc[1])
+        res = stages.funnel(collection.index_state, q[1], st[1], lc[2], lc[1])
         return res if res[0] != "ok" else ("ok", _hydrate(collection, res[1]))
 
     @staticmethod
@@ -235,17 +251,18 @@ class FlatGpu:
         return res if res[0] != "ok" else ("ok", [_hydrate(collection, hits) for hits in res[1]])
 
     @staticmethod
-    def hybrid_search(collection, query, opts=None):
+    def hybrid_search(collection, query, opts=None, stages=None):
         """collection.ex:325-345 with rerank: exact; generators as run_hybrid_generator takes them (collection.ex:536-556):
         "funnel" | "quantized" | "search", or (name, {options})."""
         opts = {} if opts is None else opts
+        stages = stages or FLAT_STAGES
         limit = opts.get("limit", 10)
         if not _valid_size(limit):
             return ("error", "invalid_limit")
         q = collection.prepare_query(query)
         if q[0] != "ok":
             return q
-        generators = opts.get("generators", ["funnel", "quantized"])          # collection.ex:512-513
+        generators = opts.get("generators", list(stages.default_generators))  # collection.ex:512-513
         if not isinstance(generators, list) or not generators:
             return ("error", "invalid_generators")
         spec = []
@@ -259,7 +276,7 @@ class FlatGpu:
             extra = [k for k in gopts if k not in allowed]
             if extra:
                 return ("error", ("unsupported_option", extra[0]))
-            if name == "hnsw":
+            if name == "hnsw" and not stages.hnsw_generator:
                 return ("error", "hnsw_index_required")                        # collection.ex:600
             cand = gopts.get("candidates", max(limit * 10, limit))             # collection.ex:544
             if not _valid_size(cand):
@@ -270,18 +287,18 @@ class FlatGpu:
                     return st
                 spec.append((nifs.GEN_FUNNEL, cand, st[1]))
             else:
-                spec.append((nifs.GEN_QUANTIZED if name == "quantized" else nifs.GEN_SEARCH, cand, []))
+                spec.append((nifs.GEN_QUANTIZED if name == "quantized" else nifs.GEN_SEARCH, cand, []))   # ("hnsw": the index's own)
         rerank = opts.get("rerank", "exact")
         if rerank == "exact":
-            res = nifs.flat_hybrid_search(collection.index_state, q[1], spec, limit)
+            res = stages.hybrid(collection.index_state, q[1], spec, limit)
             return res if res[0] != "ok" else ("ok", _hydrate(collection, res[1]))
         if not (isinstance(rerank, tuple) and len(rerank) in (2, 3) and rerank[0] == "multi_vector"
                 and (len(rerank) == 2 or isinstance(rerank[2], dict))):
             return ("error", ("invalid_rerank", rerank))                       # collection.ex:646-647
-        return FlatGpu._multi_vector_rerank(collection, q[1], spec, rerank, limit)
+        return FlatGpu._multi_vector_rerank(collection, q[1], spec, rerank, limit, stages)
 
     @staticmethod
-    def _multi_vector_rerank(collection, query, spec, rerank, limit):
+    def _multi_vector_rerank(collection, query, spec, rerank, limit, stages=None):
         """hybrid_rerank {:multi_vector, qv[, opts]} (collection.ex:633-658): MaxSim over the candidates' stored vectors.
         The candidate union comes first.  The exact rerank of a generator's candidates keeps ALL of them when its limit
         is the candidate count, and reranking reorders a set without changing it: so the set a generator feeds the
@@ -298,14 +315,15 @@ class FlatGpu:
         qv = collection._prepare_vectors(rerank[1])
         if qv[0] != "ok":
             return qv
+        stages = stages or FLAT_STAGES
         seen, candidates = set(), []
-        for kind, cand, stages in spec:
+        for kind, cand, prefixes in spec:
             if kind == nifs.GEN_FUNNEL:
-                res = nifs.flat_funnel_search(collection.index_state, query, stages, cand, cand)
+                res = stages.funnel(collection.index_state, query, prefixes, cand, cand)
             elif kind == nifs.GEN_QUANTIZED:
-                res = nifs.flat_quantized_search(collection.index_state, query, cand, cand)
+                res = stages.quantized(collection.index_state, query, cand, cand)
             else:
-                res = nifs.flat_search(collection.index_state, query, cand)
+                res = stages.search(collection.index_state, query, cand)
             if res[0] != "ok":
                 return res
             for id_, _ in res[1]:

@@ -9,7 +9,7 @@ from __future__ import annotations
 from typing import List
 
 from . import nifs
-from .index_flat import MAX_NIF_USIZE, Result, _normalize_ok, _to_result
+from .index_flat import MAX_NIF_USIZE, FlatGpu, Result, Stages, _normalize_ok, _to_result
 
 DEFAULT_OPTIONS = {"m": 16, "m0": 32, "ef_construction": 100, "ef_search": 64, "max_level": 12}  # hnsw.ex:13-19
 MAX_M, MAX_M0, MAX_EF, MAX_LEVEL = 1_024, 2_048, 1_000_000, 64                                    # hnsw.ex:22-25
@@ -109,3 +109,27 @@ class HnswGpu:
         for id_, raw in res[1]:
             out.extend(_to_result(collection, id_, raw))          # hnsw.ex:70-90
         return ("ok", out)
+
+
+HNSW_STAGES = Stages(nifs.hnsw_quantized_search, nifs.hnsw_funnel_search, nifs.hnsw_hybrid_search, nifs.hnsw_search,
+                     ("hnsw", "quantized"), True)   # collection.ex:513: default_hybrid_generators of an :hnsw collection
+
+
+class HnswStagedGpu(HnswGpu):
+    """HnswGpu with the collection's staged searches (collection.ex:232-348) answered from the index's own rows
+    (nifs.hnsw_quantized_search, hnsw_funnel_search, hnsw_hybrid_search): option handling and error atoms are
+    FlatGpu's -- the same code --, the generators "hnsw" and "search" are both the index's own traversal, and
+    hybrid_search defaults to ["hnsw", "quantized"].  Selected with index_options={"staged_searches": True}
+    (collection.py); Vettore.Index.HnswGpu itself exports the three functions unconditionally."""
+
+    @staticmethod
+    def quantized_search(collection, query, opts=None):
+        return FlatGpu.quantized_search(collection, query, opts, HNSW_STAGES)
+
+    @staticmethod
+    def funnel_search(collection, query, opts=None):
+        return FlatGpu.funnel_search(collection, query, opts, HNSW_STAGES)
+
+    @staticmethod
+    def hybrid_search(collection, query, opts=None):
+        return FlatGpu.hybrid_search(collection, query, opts, HNSW_STAGES)

@@ -1042,6 +1042,42 @@ def flat_hybrid_search(index: FlatRef, query, generators, limit: int):
     return ("ok", _take_hits(h)) if rc == 0 else _err(rc)
 
 
+def hnsw_quantized_search(index: HnswRef, query, candidates: int, limit: int, with_keys: bool = False):
+    """collection.ex:276-295 on the HNSW index's rows: flat_quantized_search's answer over the same (id, vector) pairs.
+    (The library's three staged entry points take either kind of handle: include/vettore_flat.h, VT_HNSW_STAGED.)"""
+    q = _f32_list(query)
+    h = C.c_void_p()
+    st = _lib.load().vt_flat_quantized_search(index.handle, _fp(q), q.size, candidates, limit, C.byref(h))
+    return ("ok", _export_hits(h, with_keys)) if st == 0 else _err(st)
+
+
+def hnsw_funnel_search(index: HnswRef, query, stages: Sequence[int], candidates: int, limit: int, with_keys: bool = False):
+    """collection.ex:245-260 on the HNSW index's rows: flat_funnel_search's answer over the same (id, vector) pairs."""
+    q = _f32_list(query)
+    st = np.ascontiguousarray(np.asarray(list(stages), dtype=np.uintp))
+    h = C.c_void_p()
+    rc = _lib.load().vt_flat_funnel_search(index.handle, _fp(q), q.size, _szp(st), st.size, candidates, limit, C.byref(h))
+    return ("ok", _export_hits(h, with_keys)) if rc == 0 else _err(rc)
+
+
+def hnsw_hybrid_search(index: HnswRef, query, generators, limit: int, with_keys: bool = False):
+    """hybrid_search(rerank: :exact) on the HNSW index's rows.  `generators` as flat_hybrid_search takes them; GEN_SEARCH is
+    the index's own traversal with limit = candidates (hnsw_candidates, collection.ex:594-600)."""
+    q = _f32_list(query)
+    kinds = (C.c_int * len(generators))(*[g[0] for g in generators])
+    cands = np.ascontiguousarray([g[1] for g in generators], dtype=np.uintp)
+    flat_stages, off = [], [0]
+    for g in generators:
+        flat_stages.extend(g[2] if g[0] == GEN_FUNNEL else [])
+        off.append(len(flat_stages))
+    st = np.ascontiguousarray(flat_stages if flat_stages else [0], dtype=np.uintp)
+    so = np.ascontiguousarray(off, dtype=np.uintp)
+    h = C.c_void_p()
+    rc = _lib.load().vt_flat_hybrid_search(index.handle, _fp(q), q.size, kinds, _szp(cands), _szp(so), _szp(st),
+                                           len(generators), limit, C.byref(h))
+    return ("ok", _export_hits(h, with_keys)) if rc == 0 else _err(rc)
+
+
 def rank_ids(ids_packed: Tuple[bytes, np.ndarray]) -> np.ndarray:
     """Position of every id in the bytewise order of all of them (vt_rank_ids)."""
     blob, off = ids_packed
